@@ -133,3 +133,24 @@ def test_config_4_job_digest_does_not_depend_on_the_sharding():
         assert r.returncode == 0, r.stderr[-2000:]
         dig.append(_json_line(r.stdout)["shard_check"]["ids_digest_job"])
     assert dig[0] == dig[1]
+
+
+def test_bench_dump_outputs_is_float32_and_repeatable(tmp_path):
+    """`--dump-outputs DIR` writes the ids and waveforms of the last timed step as float32 .npy files; the same arguments give the
+    same files, and `--steps` is the number of timed steps the line reports.  Stub engine, no GPU."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    dumps = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--rows", "4", "--frames", "10",
+                            "--stub", "--dump-outputs", str(tmp_path / run)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = _json_line(r.stdout)
+        assert j["steps"] == 3 and j["ms_per_step"] > 0
+        assert j["roofline"] is None and j["cpu_baseline"] is None and j["parity"] is None        # a plain run times the headline only
+        dumps.append({n: np.load(tmp_path / run / (n + ".npy")) for n in ("codes", "audio", "rows")})
+    assert all(a.dtype == np.float32 for a in dumps[0].values())
+    assert dumps[0]["codes"].shape == (4, 10, 8) and dumps[0]["audio"].shape == (4, 3200)
+    assert dumps[0]["rows"].tolist() == [0, 1, 2, 3]
+    for n in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][n], dumps[1][n])

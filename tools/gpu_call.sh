@@ -11,7 +11,7 @@
 #   golden [ENV=V ...]             the golden parity subset (parity, full-length, batch-32, long-context, trained-like) under env switches
 #   switches                       `golden` under every runtime switch of the library, one by one, then the C client and smoke()
 #   smoke                          __graft_entry__.smoke()
-#   bench LABEL [bench.py args]    one bench.py line -> <tag>_bench_LABEL.json (+ .err)
+#   bench LABEL [bench.py args]    one `bench.py --full` line -> <tag>_bench_LABEL.json (+ .err)
 #   cbench LABEL [ENV=V ...] -- [c_bench args]      one run of the torch-free C client (examples/c_bench.c) -> <tag>_cbench.jsonl
 #   env_ab VAR ROUNDS [c_bench args]                the C client with VAR=0 / VAR=1 alternating (ONE library, a runtime switch)
 #   lib_ab base,v1,v2 ROUNDS [c_bench args]         the C client on complete library variants (tools/devx_<name>/, _build.py --variant)
@@ -64,7 +64,7 @@ step_switches() {
 }
 step_smoke() { timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee -a gpurun_out/${TAG}_smoke.log; }
 step_bench() {
-  local label="$1"; shift
+  local label="$1"; shift; set -- --full "$@"
   timeout 900 python bench.py "$@" > gpurun_out/${TAG}_bench_${label}.json 2> gpurun_out/${TAG}_bench_${label}.err; echo "bench $label rc=$?"
   python3 - <<PY
 import json

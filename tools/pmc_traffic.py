@@ -4,7 +4,7 @@
 
     cd /tmp && export TMPDIR=/tmp
     timeout 900 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $REPO/gpurun_out/prof_pmc -o pmc -- \
-        python $REPO/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-profile
+        python $REPO/bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --no-profile
     python $REPO/tools/rocpd_pmc_summary.py $(find $REPO/gpurun_out/prof_pmc -name '*.db' | head -1) > $REPO/gpurun_out/pmc_fetch.csv
     python $REPO/tools/pmc_traffic.py $REPO/gpurun_out/pmc_fetch.csv 02          # writes profiles/r02_pmc_*.json
 
