@@ -32,7 +32,7 @@ typedef struct vx_ctx vx_ctx;
 /* ABI guard.  Every descriptor struct starts with `struct_size` = sizeof(that struct) as the CALLER compiled it; the library
  * rejects a mismatch with VX_EINVAL instead of reading past the end of a shorter (older) struct.  vx_abi_version() returns
  * VX_ABI_VERSION of the library that was actually loaded, so a binding can check it before the first call. */
-#define VX_ABI_VERSION 5
+#define VX_ABI_VERSION 6      /* 6: best_of > 1 with batch > 1 (vx_sampling layout unchanged since 5) */
 int32_t vx_abi_version(void);
 
 /* Model/arena geometry.  d_model=1024, 16 heads, FFN 4096, 8 codebooks are fixed by the kernels
@@ -98,17 +98,21 @@ typedef struct vx_sampling {
   uint32_t struct_size;         /* = sizeof(vx_sampling) */
   int32_t top_k;                /* <= 0: no filtering (API default -100); 1: greedy */
   float temperature;            /* > 0 */
-  const float* uniforms;        /* optional [uniforms_steps][batch] in [0,1): inverse-CDF draws replacing
-                                   torch.multinomial (models/vallex.py:850); NULL -> counter-based RNG from `seed` */
+  const float* uniforms;        /* optional [uniforms_steps][batch x max(1, best_of)] in [0,1): inverse-CDF draws replacing
+                                   torch.multinomial (models/vallex.py:850); column r*best_of + j feeds beam j of row r (without
+                                   best_of: column r feeds row r).  NULL -> counter-based RNG from `seed` */
   int32_t uniforms_steps;
   uint64_t seed;
   int32_t force_eos_at;         /* >= 0: the (n+1)-th sample is forced to EOS (benchmark stand-in for a trained
                                    model's termination; -1 = off) */
   int32_t sync_every;           /* host polls the device EOS flags every n steps (reference: every step,
                                    models/vallex.py:574-578); <= 0 -> 8 */
-  int32_t best_of;              /* <= 1: off.  N > 1 (batch must be 1): N beams of the one utterance sampled independently,
-                                   the beam with the best sum(logp)/len^length_penalty goes on to the NAR stages
-                                   (models/vallex.py:525-527,572,583-594); uniforms, if given, are [steps][best_of] */
+  int32_t best_of;              /* <= 1: off.  N > 1: every row of the batch is decoded as N beams sampled independently, and per
+                                   row the beam with the best sum(logp)/len^length_penalty goes on to the NAR stages
+                                   (models/vallex.py:525-527,572,583-594).  Row r returns what a batch-1 call on row r alone
+                                   returns with the same draws.  N must not exceed min(max_batch, 32); the engine decodes
+                                   floor(min(max_batch, 32) / N) rows x N beams at a time.  top_k, temperature, best_of,
+                                   length_penalty, return_worst, force_eos_at and seed apply to every row. */
   float length_penalty;         /* models/vallex.py:584 */
   int32_t return_worst;         /* models/vallex.py:590-591 */
 } vx_sampling;

@@ -57,7 +57,7 @@ class vx_sampling(C.Structure):
 
 
 # every symbol include/vallex_hip.h declares (tests/test_abi.py checks the library exports exactly these)
-ABI_VERSION = 5       # VX_ABI_VERSION of include/vallex_hip.h this binding was written against
+ABI_VERSION = 6       # VX_ABI_VERSION of include/vallex_hip.h this binding was written against
 
 SYMBOLS = ["vx_abi_version", "vx_create", "vx_destroy", "vx_last_error", "vx_synchronize", "vx_load_tensor", "vx_finalize_weights",
            "vx_infer", "vx_vocos_decode", "vx_encodec_decode", "vx_encodec_encode", "vx_ar_prefill", "vx_ar_logits", "vx_ar_step",
@@ -229,13 +229,12 @@ class Engine:
         u = None
         s = vx_sampling(C.sizeof(vx_sampling), int(top_k), float(temperature), None, 0, int(seed), -1 if force_eos_at is None else int(force_eos_at),
                         int(sync_every), int(best_of), float(length_penalty), int(bool(return_worst)))
-        if best_of > 1:
-            n = int(best_of)
+        cols = n * max(1, int(best_of))       # column r * best_of + j: beam j of row r
         if uniforms is not None:
             u = np.ascontiguousarray(uniforms, np.float32)
             if u.ndim == 1:
                 u = u[:, None]
-            assert u.shape[1] == n, "uniforms must be [steps][batch]"
+            assert u.shape[1] == cols, f"uniforms must be [steps][batch x best_of] = [steps][{n} x {max(1, int(best_of))}], got {u.shape}"
             s.uniforms = _ptr(u, C.c_float)
             s.uniforms_steps = u.shape[0]
         return s, u

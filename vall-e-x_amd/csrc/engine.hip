@@ -298,12 +298,12 @@ int check_batch(vx_ctx* c, const vx_batch* b, int max_rows) {
 }
 
 // ---- AR prefill (models/vallex.py:497-562, first ar_decoder.infer call) ------------------------------------
-// beams > 1 (nb must be 1): best_of.  The reference repeats the prompt N times and runs N identical prefills
-// (models/vallex.py:525-527); here the ONE row is prefilled once and its KV cache, residual row and logits are copied to
-// N decode rows, which then sample independently.
+// beams > 1: best_of.  The reference repeats the prompt N times and runs N identical prefills (models/vallex.py:525-527); here
+// every one of the nb rows is prefilled once and decode row i*beams + j (j < beams) continues from prefill row i: its KV cache
+// and residual row are fanned out to the beams (beams.hip), which then sample independently.
 int ar_prefill(vx_ctx* c, const vx_batch* b, int r0, int nb, int beams = 1) {
   const int NL = c->NL;
-  const int nrows = beams > 1 ? beams : nb;          // decode rows after this call
+  const int nrows = nb * beams;                      // decode rows after this call
   std::vector<int> seq_off(nb), seq_len(nb), S_(nb), dst_t, id_t, lang_t, pos_t, dst_a, id_a, pos_a, row_b, row_t;
   long M = 0;
   int max_len = 0;
@@ -326,7 +326,9 @@ int ar_prefill(vx_ctx* c, const vx_batch* b, int r0, int nb, int beams = 1) {
     M += seq_len[i];
   }
   if (M > c->Mmax) FAIL(VX_EINVAL, "prefill rows %ld exceed arena %ld", M, c->Mmax);
-  c->h_L = seq_len;
+  if (nrows > c->mbr) FAIL(VX_EINVAL, "%d decode rows exceed the micro-batch (%d)", nrows, c->mbr);
+  c->h_L.resize(nrows);
+  for (int i = 0; i < nrows; ++i) c->h_L[i] = seq_len[i / beams];
   MetaBuilder mb(c);
   const long o_off = mb.add(seq_off), o_len = mb.add(seq_len), o_S = mb.add(S_), o_dt = mb.add(dst_t), o_it = mb.add(id_t),
              o_lt = mb.add(lang_t), o_pt = mb.add(pos_t), o_da = mb.add(dst_a), o_ia = mb.add(id_a), o_pa = mb.add(pos_a),
@@ -334,12 +336,13 @@ int ar_prefill(vx_ctx* c, const vx_batch* b, int r0, int nb, int beams = 1) {
   // decode state
   std::vector<int> st_pos(nrows), st_ctx(nrows), st_zero(nrows, 0), st_one(nrows, 1), st_S(nrows);
   for (int i = 0; i < nrows; ++i) {
-    const int j = beams > 1 ? 0 : i;
+    const int j = i / beams;                                      // the prefill row decode row i continues from
     st_pos[i] = b->prompt_lens[r0 + j]; st_ctx[i] = seq_len[j]; st_S[i] = S_[j];
   }
   // dec_attn launch order (decode.hip): rows by context length, the longest ceil(nb/2) first (descending), then the rest
   // ascending, so launch slots y and y + nb/2 -- which share a CU or a workgroup -- hold a long and a short context.  The
-  // order of the contexts never changes during generation (every active row grows by one per step).
+  // order of the contexts never changes during generation (every active row grows by one per step).  A row's beams have equal
+  // contexts: the stable sort keeps them adjacent (nothing below relies on it: the fan-out reads every beam's slot from st_slot).
   std::vector<int> by_len(nrows), st_ord(nrows);
   for (int i = 0; i < nrows; ++i) by_len[i] = i;
   // (<= SB_ROWS rows: batch order -- the fused small-batch attention relies on slot == row, and there is nothing to balance)
@@ -358,9 +361,9 @@ int ar_prefill(vx_ctx* c, const vx_batch* b, int r0, int nb, int beams = 1) {
   }
   // The KV arena is indexed by LAUNCH SLOT, not by batch row: dec_attn knows the address of its K / V stream from its block id
   // alone and requests the first tile before the slot record (row, context, active) has arrived (decode.hip).  The prefill
-  // scatters every sequence's K / V into the arena row of its slot; best_of: the one prefilled row has slot 0 (equal contexts
-  // keep batch order) and beam_kv_broadcast copies arena row 0 to the arena rows 1 .. beams-1 = the other beams' slots.
-  for (int& rb : row_b) rb = st_slot[rb];
+  // scatters every sequence's K / V into the arena row of its slot; best_of: prefill row i into the slot of decode row i*beams,
+  // and the fan-out (beams.hip) copies it to the slots of decode rows i*beams + 1 .. i*beams + beams-1.
+  for (int& rb : row_b) rb = st_slot[rb * beams];
   const long o_rb = mb.add(row_b);
   const long o_sp = mb.add(st_pos), o_sc = mb.add(st_ctx), o_z = mb.add(st_zero), o_1 = mb.add(st_one), o_sS = mb.add(st_S),
              o_meta = mb.add(st_meta), o_slot = mb.add(st_slot);
@@ -374,6 +377,20 @@ int ar_prefill(vx_ctx* c, const vx_batch* b, int r0, int nb, int beams = 1) {
     trim_flops += 4.0 * seq_len[i] * D_MODEL;
   }
   const long o_tq = mb.add(tq_first), o_tc = mb.add(tc_off), o_tr = mb.add(t_rows);
+  const bool trim_h2 = c->gemm_mode == 0 && c->attn_x3 && c->attn_h2, trim_f32 = c->gemm_mode == 2 && !c->attn_x3;
+  const bool trim = c->nar_trim && (trim_h2 || trim_f32) && !c->cfg.debug_taps;      // the same switch as the NAR stages (VX_NAR_TRIM)
+  // best_of fan-out tables (beams.hip): (slot of decode row i*beams, slot of decode row i*beams + j, seq_len[i]) per copy, and the
+  // row of the prefill's last-row buffer every decode row's residual comes from (trimmed: compacted row i, else packed row)
+  long o_fp = 0, o_fr = 0;
+  if (beams > 1) {
+    std::vector<int> fpairs, frow(nrows);
+    for (int i = 0; i < nb; ++i) {
+      if (seq_len[i] > c->Tmax) FAIL(VX_EINVAL, "row %d: %d cached rows exceed the arena (%d)", r0 + i, seq_len[i], c->Tmax);
+      for (int j = 1; j < beams; ++j) fpairs.insert(fpairs.end(), {st_slot[i * beams], st_slot[i * beams + j], seq_len[i]});
+      for (int j = 0; j < beams; ++j) frow[i * beams + j] = trim ? i : seq_off[i] + seq_len[i] - 1;
+    }
+    o_fp = mb.add(fpairs); o_fr = mb.add(frow);
+  }
   if (int e = upload_meta(c)) return e;
   const size_t ib = nrows * sizeof(int);
   HIPCHK(hipMemcpyAsync(c->cur_pos, mb.dev(o_sp), ib, hipMemcpyDeviceToDevice, c->stream));
@@ -406,13 +423,17 @@ int ar_prefill(vx_ctx* c, const vx_batch* b, int r0, int nb, int beams = 1) {
     c->nsplit = c->att_nsplit_force;
     c->split_fused = c->fuse_out && c->fuse_split != 0 && nrows > SB_ROWS && c->nsplit >= 2 && c->nsplit <= 4;
   }
-  // the small-batch chain compiles the split counts in (decode.hip): taken only for a combination that is instantiated
+  // the small-batch chain compiles the split counts in (decode.hip): taken only for a combination that is instantiated.  Its fused
+  // attention relies on slot == row, i.e. on the identity launch order (<= SB_ROWS rows are never balanced; best_of: the beams of
+  // row i are decode rows i*beams + j in that order) -- checked here, not assumed from `balance` above
+  bool identity = true;
+  for (int y = 0; y < nrows; ++y) identity = identity && st_ord[y] == y;
   c->sb_chain = false;
-  if (c->sb_fuse && nrows <= SB_ROWS) {
+  c->sb_qkv = false;
+  if (c->sb_fuse && nrows <= SB_ROWS && identity) {
     const int ns = nrows <= 2 ? 16 : 8;
     if (sb_chain_supported(SK_L2, SK_OUT, ns, nrows)) { c->nsplit = ns; c->sb_chain = true; }
     // ... with norm1 + QKV inside the attention launch for the smallest batches (VX_SB_QKV=<max rows>; its split count is tunable)
-    c->sb_qkv = false;
     if (c->sb_chain && nrows <= c->sb_qkv_rows) {
       // the fused kernel holds one 8-wave workgroup per CU: 16 heads x rows x splits workgroups must fit the 256 CUs in ONE round,
       // and every workgroup of a head re-reads the head's q slice through L2 -- few splits win (profiles/r04_sb_qkv_ab.log)
@@ -421,10 +442,8 @@ int ar_prefill(vx_ctx* c, const vx_batch* b, int r0, int nb, int beams = 1) {
       const int fit[5] = {0, 16, 8, 4, 4};
       const int ns2 = c->sb_qkv_nsplit > 0 ? c->sb_qkv_nsplit : fit[nrows];
       // dec_attn_qkv_kernel addresses the KV arena and its partials by batch ROW and returns when slot_meta[slot].row != row
-      // (decode.hip): it is only selected while the launch order is the identity -- checked here, not assumed from `balance` above
-      bool identity = true;
-      for (int y = 0; y < nrows; ++y) identity = identity && st_ord[y] == y;
-      if (identity && sb_qkv_chain_supported(SK_L2, SK_OUT, ns2, nrows)) { c->nsplit = ns2; c->sb_qkv = true; }
+      // (decode.hip): the launch order is the identity (checked above)
+      if (sb_qkv_chain_supported(SK_L2, SK_OUT, ns2, nrows)) { c->nsplit = ns2; c->sb_qkv = true; }
     }
   }
 
@@ -438,8 +457,6 @@ int ar_prefill(vx_ctx* c, const vx_batch* b, int r0, int nb, int beams = 1) {
   double attn_flops = 0;
   for (int i = 0; i < nb; ++i) attn_flops += 4.0 * seq_len[i] * (double)seq_len[i] * D_MODEL;
   const size_t cache_layer = (size_t)c->mbr * N_HEAD * c->Tmax * D_HEAD;
-  const bool trim_h2 = c->gemm_mode == 0 && c->attn_x3 && c->attn_h2, trim_f32 = c->gemm_mode == 2 && !c->attn_x3;
-  const bool trim = c->nar_trim && (trim_h2 || trim_f32) && !c->cfg.debug_taps;      // the same switch as the NAR stages (VX_NAR_TRIM)
   const Trim tr{nb, mb.dev(o_tq), mb.dev(o_tc), mb.dev(o_tr), trim_flops};
   for (int l = 0; l < NL; ++l) {
     if (int e = full_layer(c, c->ar[l], M, mb.dev(o_off), mb.dev(o_len), mb.dev(o_S), nb, max_len, nullptr, nullptr,
@@ -454,26 +471,21 @@ int ar_prefill(vx_ctx* c, const vx_batch* b, int r0, int nb, int beams = 1) {
   }
   // last row of every sequence -> decode residual stream h[b]  (trimmed: the last layer left exactly those rows, compacted, in the
   // buffer full_layer uses for the compacted residual stream: fxn in f16x2 mode, the QKV buffer in fp32 mode)
-  if (trim)
-    HIPCHK(hipMemcpyAsync(c->dh, trim_h2 ? c->fxn : c->fqkv, (size_t)nb * D_MODEL * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  const float* hsrc = trim ? (trim_h2 ? c->fxn : c->fqkv) : c->fx;
+  if (beams > 1)      // best_of: every decode row's residual row + the other beams' K / V, one launch
+    launch_beam_fanout(c->kc, c->vc, (long)cache_layer, NL, c->Tmax, mb.dev(o_fp), nb * (beams - 1), hsrc, mb.dev(o_fr), c->dh, nrows,
+                       c->stream);
+  else if (trim)
+    HIPCHK(hipMemcpyAsync(c->dh, hsrc, (size_t)nb * D_MODEL * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
   else
     for (int i = 0; i < nb; ++i)
       HIPCHK(hipMemcpyAsync(c->dh + (size_t)i * D_MODEL, c->fx + ((size_t)seq_off[i] + seq_len[i] - 1) * D_MODEL,
                             D_MODEL * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-  // final norm + ar_predict_layer on those rows (models/vallex.py:568)
+  // final norm + ar_predict_layer on every decode row (models/vallex.py:568; the predict GEMM's 32-column block costs the same for
+  // 1 or 32 rows, so the beams compute their logits instead of copying them)
   launch_dec_reduce_ln_pack(nullptr, 0, D_MODEL, nullptr, c->dh, nullptr, W(c, "ar_decoder.norm.weight"),
-                            W(c, "ar_decoder.norm.bias"), c->xp, nb, c->stream);
+                            W(c, "ar_decoder.norm.bias"), c->xp, nrows, c->stream);
   launch_skinny_gemm(c->pred_wp, c->xp, c->p_logits, PRED_NPAD, D_MODEL, SK_PRED, c->stream);
-  if (beams > 1) {
-    launch_beam_kv_broadcast(c->kc, c->vc, (long)cache_layer, NL, c->Tmax, seq_len[0], beams, c->stream);
-    for (int i = 1; i < beams; ++i) {
-      HIPCHK(hipMemcpyAsync(c->dh + (size_t)i * D_MODEL, c->dh, D_MODEL * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-      for (int ks = 0; ks < SK_PRED; ++ks)
-        HIPCHK(hipMemcpyAsync(c->p_logits + ((size_t)ks * MB + i) * PRED_NPAD, c->p_logits + (size_t)ks * MB * PRED_NPAD,
-                              PRED_NPAD * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-    }
-    c->h_L.assign(beams, seq_len[0]);
-  }
   return VX_OK;
 }
 
@@ -653,8 +665,10 @@ static void fb_outcome(vx_ctx* c, bool raised, int& raises, bool& sticky, int& a
 }
 
 // ---- AR generation for one micro-batch -----------------------------------------------------------------------
+// caller rows r0 .. r0+nb-1, each decoded as `beams` rows (decode row i*beams + j: beam j of row r0 + i); `seed` is the sampler's
+// seed for this micro-batch (unused with injected uniforms)
 int ar_generate(vx_ctx* c, const vx_batch* b, const vx_sampling* s, int r0, int nb, std::vector<int>& n_gen,
-                std::vector<int>& gen, int beams = 1) {
+                std::vector<int>& gen, int beams, unsigned long long seed) {
   const int nb_rows = nb;                            // rows of the caller's batch that this micro-batch prefills
   // a context whose prefills keep leaving the fp16 range runs them on the exact-fp32 kernels straight away (sticky fallback)
   const bool direct_f32 = fb_direct(c, c->sticky_prefill_f32, c->sticky_prefill_age);
@@ -664,22 +678,21 @@ int ar_generate(vx_ctx* c, const vx_batch* b, const vx_sampling* s, int r0, int 
     F32Scope f32(c);
     if (int e = ar_prefill(c, b, r0, nb_rows, beams)) return e;
   } else if (int e = ar_prefill(c, b, r0, nb_rows, beams)) return e;
-  const int ub = beams > 1 ? beams : b->batch;       // columns of the caller's uniforms: [steps][batch] or [steps][best_of]
-  if (beams > 1) nb = beams;
+  const long ub = (long)b->batch * beams;            // columns of the caller's uniforms: [steps][batch x best_of]
+  nb = nb_rows * beams;                              // decode rows from here on
   if (s->uniforms) {
-    // slice [steps][batch] -> [steps][nb] for this micro-batch
+    // slice [steps][batch x beams] -> [steps][nb] for this micro-batch: columns r0*beams .. (r0 + nb_rows)*beams
     // only the first gen_stride + 1 draws can ever be consumed (one per generated frame + the terminating sample)
     const long steps = std::min<long>(s->uniforms_steps, c->gen_stride + 1);
     if (steps * nb > c->uniforms_cap) FAIL(VX_EINVAL, "too many uniforms (%ld steps)", steps);
     std::vector<float> u((size_t)steps * nb);
     for (long t = 0; t < steps; ++t)
-      for (int i = 0; i < nb; ++i) u[t * nb + i] = s->uniforms[t * ub + r0 + i];
+      for (int i = 0; i < nb; ++i) u[t * nb + i] = s->uniforms[t * ub + (long)r0 * beams + i];
     H2D(c->d_uniforms, u.data(), u.size() * sizeof(float));
     SYNC();
   }
   // the seed of the counter-based sampler lives in a device word: a new seed per call (the reference's contract, every call
   // draws from torch's generator) does not change the captured step graph
-  const unsigned long long seed = s->seed;
   H2D(c->seed_dev, &seed, sizeof seed);
   SampleArgs sa = make_sample_args(c, s, 1, nullptr);
   std::vector<int> act(nb);
@@ -745,6 +758,17 @@ int ar_generate(vx_ctx* c, const vx_batch* b, const vx_sampling* s, int r0, int 
     c->prof[1].bytes += (double)steps * ((double)c->NL * 12.0 * D_MODEL * D_MODEL + (double)AR_LOGITS * D_MODEL) * 4.0;
   }
   return VX_OK;
+}
+
+// best_of: the sampler's seed of micro-batch k.  The counter-based sampler mixes (seed, decode row, step), so without this the beams
+// of the first row of every micro-batch would draw the same streams.  Micro-batch 0 keeps the caller's seed: a batch-1 call (one
+// micro-batch) draws exactly what it drew before batched best_of existed.
+static unsigned long long beam_seed(unsigned long long seed, int k) {
+  if (k == 0) return seed;
+  unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (unsigned long long)k;      // splitmix64 of (seed, k)
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
 }
 
 // ---- NAR: 7 stages (models/vallex.py:600-686, prefix_mode 1) ----------------------------------------------------
@@ -1083,47 +1107,67 @@ int vx_infer(vx_ctx* c, const vx_batch* b, const vx_sampling* s, int64_t* out_co
   auto cut_by_arena = [&](int n, int S) {
     return n >= c->gen_stride && c->gen_stride < 16 * S && !(s->force_eos_at >= 0 && s->force_eos_at <= c->gen_stride);
   };
+  hipEvent_t e0 = c->ev_t[0], e1 = c->ev_t[1], e2 = c->ev_t[2];      // owned by the context: nothing to leak on an early return
   if (s->best_of > 1) {
-    // best-of-N beams of ONE utterance (models/vallex.py:491,525-527): the row is replicated N times, every beam
-    // samples independently, beams that emit EOS stop; selection on sum(logp) / len^penalty (:583-594), then the NAR
-    // stages run on the chosen beam only (:600).
-    if (b->batch != 1) FAIL(VX_EINVAL, "best_of > 1 needs batch == 1 (models/vallex.py:491)");
+    // best-of-N beams of every row (models/vallex.py:491,525-527): each row is decoded as N beams that sample independently, beams
+    // that emit EOS stop; per row, selection on sum(logp) / len^penalty (:583-594), then the NAR stages run on the chosen beams only
+    // (:600).  A micro-batch holds R = mbr / N rows = R*N decode rows; row r's result is what a batch-1 call on that row alone
+    // returns with the same draws (uniforms column r*N + j = beam j of row r).
     const int N = s->best_of;
     if (N > c->mbr) FAIL(VX_EINVAL, "best_of %d exceeds the micro-batch (%d)", N, c->mbr);
-    const int Tp = b->prompt_lens[0];
-    std::vector<int> n_gen, gen, oc;
-    if (int e = ar_generate(c, b, s, 0, 1, n_gen, gen, N)) return e;     // ONE prefill, N decode rows
-    std::vector<float> slp(N);
-    D2H(slp.data(), c->sum_logp, N * sizeof(float)); SYNC();
-    int best = 0, worst = 0;
-    double bv = 0, wv = 0;
-    for (int i = 0; i < N; ++i) {
-      const double len = 1.0 + Tp + n_gen[i];                        // torch.sum(y != EOS): BOS + prompt + frames
-      const double v = (double)(float)((float)slp[i] / powf((float)len, s->length_penalty));
-      if (i == 0 || v > bv) { bv = v; best = i; }
-      if (i == 0 || v < wv) { wv = v; worst = i; }
-    }
-    const int pick = s->return_worst ? worst : best;
-    if (n_gen[pick] > out_stride) FAIL(VX_EINVAL, "out_stride %d too small for %d frames", out_stride, n_gen[pick]);
-    long sumT = 0;
-    std::vector<int> T1(1, n_gen[pick]);
-    if (int e = nar_generate(c, b, 0, 1, T1, gen.data() + (size_t)pick * c->gen_stride, c->gen_stride, oc, sumT)) return e;
-    out_lens[0] = n_gen[pick];
-    c->st_frames = n_gen[pick];
-    c->st_truncated = cut_by_arena(n_gen[pick], b->text_lens[0]) ? 1 : 0;
-    for (int t = 0; t < n_gen[pick]; ++t) {
-      int64_t* o = out_codes + (long)t * N_Q;
-      o[0] = gen[(size_t)pick * c->gen_stride + t];
-      for (int st = 0; st < N_Q - 1; ++st) o[st + 1] = oc[(size_t)st * sumT + t];
+    const int R = c->mbr / N;
+    for (int r0 = 0, k = 0; r0 < b->batch; r0 += R, ++k) {
+      const int nb = std::min(R, b->batch - r0);
+      std::vector<int> n_gen, gen, oc;
+      HIPCHK(hipEventRecord(e0, c->stream));
+      if (int e = ar_generate(c, b, s, r0, nb, n_gen, gen, N, beam_seed(s->seed, k))) return e;
+      HIPCHK(hipEventRecord(e1, c->stream));
+      std::vector<float> slp((size_t)nb * N);
+      D2H(slp.data(), c->sum_logp, slp.size() * sizeof(float)); SYNC();
+      std::vector<int> T(nb), codes0((size_t)nb * c->gen_stride);
+      for (int i = 0; i < nb; ++i) {
+        const int Tp = b->prompt_lens[r0 + i];
+        int best = 0, worst = 0;
+        double bv = 0, wv = 0;
+        for (int j = 0; j < N; ++j) {
+          const int d = i * N + j;
+          const double len = 1.0 + Tp + n_gen[d];                      // torch.sum(y != EOS): BOS + prompt + frames
+          const double v = (double)(float)((float)slp[d] / powf((float)len, s->length_penalty));
+          if (j == 0 || v > bv) { bv = v; best = j; }
+          if (j == 0 || v < wv) { wv = v; worst = j; }
+        }
+        const int pick = i * N + (s->return_worst ? worst : best);
+        T[i] = n_gen[pick];
+        if (T[i] > out_stride) FAIL(VX_EINVAL, "out_stride %d too small for %d frames", out_stride, T[i]);
+        std::copy_n(gen.begin() + (size_t)pick * c->gen_stride, c->gen_stride, codes0.begin() + (size_t)i * c->gen_stride);
+      }
+      long sumT = 0;
+      if (int e = nar_generate(c, b, r0, nb, T, codes0.data(), c->gen_stride, oc, sumT)) return e;
+      HIPCHK(hipEventRecord(e2, c->stream));
+      HIPCHK(hipEventSynchronize(e2));
+      float ms = 0;
+      HIPCHK(hipEventElapsedTime(&ms, e0, e1)); c->st_ar_ms += ms;
+      HIPCHK(hipEventElapsedTime(&ms, e1, e2)); c->st_nar_ms += ms;
+      long off = 0;
+      for (int i = 0; i < nb; ++i) {
+        out_lens[r0 + i] = T[i];
+        c->st_frames += T[i];
+        if (cut_by_arena(T[i], b->text_lens[r0 + i])) ++c->st_truncated;
+        for (int t = 0; t < T[i]; ++t) {
+          int64_t* o = out_codes + ((long)(r0 + i) * out_stride + t) * N_Q;
+          o[0] = codes0[(size_t)i * c->gen_stride + t];
+          for (int st = 0; st < N_Q - 1; ++st) o[st + 1] = oc[(size_t)st * sumT + off + t];
+        }
+        off += T[i];
+      }
     }
     return VX_OK;
   }
-  hipEvent_t e0 = c->ev_t[0], e1 = c->ev_t[1], e2 = c->ev_t[2];      // owned by the context: nothing to leak on an early return
   for (int r0 = 0; r0 < b->batch; r0 += c->mbr) {
     const int nb = std::min(c->mbr, b->batch - r0);
     std::vector<int> n_gen, gen, oc;
     HIPCHK(hipEventRecord(e0, c->stream));
-    if (int e = ar_generate(c, b, s, r0, nb, n_gen, gen)) return e;
+    if (int e = ar_generate(c, b, s, r0, nb, n_gen, gen, 1, s->seed)) return e;
     HIPCHK(hipEventRecord(e1, c->stream));
     for (int i = 0; i < nb; ++i)
       if (n_gen[i] > out_stride) FAIL(VX_EINVAL, "out_stride %d too small for %d frames", out_stride, n_gen[i]);

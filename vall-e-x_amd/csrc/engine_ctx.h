@@ -1,6 +1,6 @@
 // Internal declarations shared by the engine's translation units (engine.hip: context, AR / NAR drivers and the hot-path ABI;
 // weights.hip: ingest of the reference state-dict; vocoders.hip: Vocos head, EnCodec decoder / encoder drivers;
-// bench_harness.hip: the measurement entries of include/vallex_hip_dev.h).  Not part of the public C ABI.
+// beams.hip: the best_of fan-out; bench_harness.hip: the measurement entries of include/vallex_hip_dev.h).  Not part of the public C ABI.
 #pragma once
 
 #include <math.h>
@@ -281,6 +281,11 @@ int check_batch(vx_ctx* c, const vx_batch* b, int max_rows);
 SampleArgs make_sample_args(vx_ctx* c, const vx_sampling* s, int commit, float* logits_out);
 void ar_step_launches(vx_ctx* c, const SampleArgs* sa);
 int launch_status(vx_ctx* c);      // VX_EINVAL (+ message) if a launcher refused since the last check
+// best_of fan-out (beams.hip): one launch per prefill.  pairs [npairs][3] = {source slot, destination slot, cached rows}: that many
+// K / V rows of every (layer, head) are copied between the two arena slots; dh[d] = hsrc[hsrc_row[d]] for the nrows decode rows.
+// Every slot < mbr, every row count <= Tmax (the caller builds the table from its own slot map).
+void launch_beam_fanout(float* kc, float* vc, long cache_layer, int layers, int Tmax, const int* pairs, int npairs,
+                        const float* hsrc, const int* hsrc_row, float* dh, int nrows, hipStream_t s);
 
 struct F32Scope {            // the full-sequence path on the exact-fp32 kernels for the lifetime of the object
   vx_ctx* c;

@@ -257,7 +257,10 @@ class VALLE:
                         force_eos_at=None, seed: Optional[int] = None, sync_every: int = 8, best_of: int = 1,
                         length_penalty: float = 1.0, return_worst: bool = False) -> List[np.ndarray]:
         """rows[i] = dict(text ids (S,), prompt codes (Tp,8), enroll, prompt_language, text_language).
-        Row i equals `inference` run alone on that row.  Returns one (T_i, 8) int64 array per row."""
+        Row i equals `inference` run alone on that row.  Returns one (T_i, 8) int64 array per row.
+        `best_of` = N > 1 decodes every row as N beams (the UI's call, launch-ui.py:285-295, for a whole batch); `length_penalty`
+        and `return_worst` select per row.  Injected `uniforms` are (steps, len(rows) x max(1, N)): column i*N + j feeds beam j of
+        row i, so row i equals `inference(row i, best_of=N, uniforms=uniforms[:, i*N:(i+1)*N])`."""
         if seed is None:
             seed = fresh_seed()
         texts, langs, prompts = [], [], []

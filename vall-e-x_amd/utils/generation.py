@@ -228,7 +228,9 @@ def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent
     `texts`: strings (need the tokenizer hook) or phoneme-id arrays; `prompts`: one preset name / path / None per utterance (or
     one for all); `language`: one string or one per utterance; `text_languages`: optional per-utterance per-id language lists
     (what the tokenizer returned, `TextFrontendService`).  All utterances go through ONE `VALLE.inference_batch` call and ONE
-    Vocos call.  Returns a list of float32 waveforms."""
+    Vocos call.  `**kw` goes to `inference_batch`: `best_of`, `length_penalty` and `return_worst` apply to every utterance (best_of
+    = N: N beams per utterance), injected `uniforms` are (steps, len(texts) x max(1, N)) with column i*N + j for beam j of
+    utterance i.  Returns a list of float32 waveforms."""
     if model is None or vocos is None:
         raise RuntimeError("call preload_models() first")
     n = len(texts)
