@@ -123,6 +123,26 @@ typedef struct vx_sampling {
 int vx_infer(vx_ctx* ctx, const vx_batch* b, const vx_sampling* s, int64_t* out_codes, int32_t out_stride,
              int32_t* out_lens);
 
+/* Continuous batching (additive: VX_ABI_VERSION stays 6; a binding detects this entry point by its symbol).
+ * vx_infer decodes a batch in micro-batches of min(max_batch, 32) rows and runs each until its LONGEST row has stopped.  This entry
+ * decodes on one decode batch of min(max_batch, 32, batch) rows for the whole call: when a row stops (EOS, 16 x text length,
+ * max_new or force_eos_at), the next waiting caller row, in caller order, takes its place at the next host poll (sync_every).
+ * batch may exceed max_batch: the call holds device memory for its decode rows and one NAR group only.
+ *   - out_codes / out_lens: filled exactly as vx_infer fills them.
+ *   - on_row: may be NULL.  Otherwise it is called once per caller row, on the calling thread, from inside this call, in the order
+ *     rows complete (their NAR stages run in groups of up to 32 finished rows): codes [frames][8] is valid only during the
+ *     callback (it points into out_codes).  The callback must not call into the same context.
+ *   - injected uniforms keep vx_infer's layout [uniforms_steps][batch]: column r feeds caller row r, indexed by that row's own step.
+ *   - without uniforms, row r draws u = (splitmix64(splitmix64(splitmix64(seed) + r) + step) >> 40) x 2^-24: vx_infer's counter
+ *     formula keyed on the CALLER row r.  Rows r < min(max_batch, 32) therefore equal vx_infer's rows with the same seed; later
+ *     rows get streams of their own (in vx_infer, row r draws the stream of row r mod min(max_batch, 32)).
+ *   - best_of > 1 is refused with VX_EINVAL.
+ *   - vx_last_stats: AR steps = decode steps run, AR ms includes the admission prefills, NAR ms covers the NAR groups;
+ *     vx_last_truncated and vx_last_fallbacks report the call as they do for vx_infer. */
+typedef void (*vx_row_done_fn)(void* user, int32_t row, const int64_t* codes /* [frames][8] */, int32_t frames);
+int vx_infer_continuous(vx_ctx* ctx, const vx_batch* b, const vx_sampling* s, vx_row_done_fn on_row, void* user,
+                        int64_t* out_codes, int32_t out_stride, int32_t* out_lens);
+
 /* replaces: vocos.codes_to_features + vocos.decode(features, bandwidth_id), utils/generation.py:148-150.
  * codes [batch][codes_stride][8] int64, lens [batch] frames; audio [batch][audio_stride] fp32, 320*len samples each. */
 int vx_vocos_decode(vx_ctx* ctx, const int64_t* codes, int32_t codes_stride, const int32_t* lens, int32_t batch,

@@ -62,10 +62,13 @@ ABI_VERSION = 6       # VX_ABI_VERSION of include/vallex_hip.h this binding was 
 SYMBOLS = ["vx_abi_version", "vx_create", "vx_destroy", "vx_last_error", "vx_synchronize", "vx_load_tensor", "vx_finalize_weights",
            "vx_infer", "vx_vocos_decode", "vx_encodec_decode", "vx_encodec_encode", "vx_ar_prefill", "vx_ar_logits", "vx_ar_step",
            "vx_nar", "vx_read_tap", "vx_last_stats", "vx_last_truncated", "vx_last_fallbacks", "vx_fallback_state",
-           "vx_fallback_reset", "vx_arith_mode"]
+           "vx_fallback_reset", "vx_arith_mode", "vx_infer_continuous"]
 # ... and include/vallex_hip_dev.h: measurement / kernel development, never called by the mirrors of the reference API
 DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kernel", "vx_bench_gemm", "vx_bench_attn",
                "vx_bench_gemm_clock", "vx_bench_gemm_epilogue"]
+
+# vx_row_done_fn of vx_infer_continuous: (user, caller row, codes [frames][8] int64, frames)
+ROW_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int32)
 
 _lib = None
 
@@ -103,6 +106,8 @@ def load_library() -> C.CDLL:
     lib.vx_load_tensor.argtypes = [ctx, C.c_char_p, P(C.c_float), P(C.c_int64), C.c_int32]
     lib.vx_finalize_weights.argtypes = [ctx]
     lib.vx_infer.argtypes = [ctx, P(vx_batch), P(vx_sampling), P(C.c_int64), C.c_int32, P(C.c_int32)]
+    lib.vx_infer_continuous.argtypes = [ctx, P(vx_batch), P(vx_sampling), ROW_DONE_FN, C.c_void_p, P(C.c_int64), C.c_int32,
+                                        P(C.c_int32)]
     lib.vx_vocos_decode.argtypes = [ctx, P(C.c_int64), C.c_int32, P(C.c_int32), C.c_int32, C.c_int32, P(C.c_float),
                                     C.c_int64]
     lib.vx_encodec_decode.argtypes = [ctx, P(C.c_int64), C.c_int32, P(C.c_int32), C.c_int32, P(C.c_float), C.c_int64]
@@ -239,14 +244,46 @@ class Engine:
             s.uniforms_steps = u.shape[0]
         return s, u
 
+    @staticmethod
+    def check_continuous(best_of=1, continuous=False, on_row=None):
+        """the argument checks of infer(continuous=..., on_row=...), before any GPU work"""
+        if continuous and int(best_of) > 1:
+            raise ValueError("continuous=True does not run best_of > 1 (vx_infer_continuous); use the micro-batched schedule")
+        if on_row is not None and not continuous:
+            raise ValueError("on_row needs continuous=True: only the continuous schedule hands rows over as they complete")
+
     def infer(self, batch: Batch, top_k=-100, temperature=1.0, uniforms=None, seed=0, force_eos_at=None,
-              sync_every=8, best_of=1, length_penalty=1.0, return_worst=False):
+              sync_every=8, best_of=1, length_penalty=1.0, return_worst=False, continuous=False, on_row=None):
+        """continuous=True: vx_infer_continuous -- a finished row's decode row goes to the next waiting row at the next host poll
+        instead of riding along until the micro-batch's longest row ends.  on_row(row, codes (T, 8) int64) is then called once per
+        row, in the order rows complete, with a copy of the row's codes; an exception it raises is re-raised here once the call
+        has returned (the remaining rows are still computed)."""
+        self.check_continuous(best_of, continuous, on_row)
         s, _keep = self._sampling(batch.n, top_k, temperature, uniforms, seed, force_eos_at, sync_every, best_of,
                                   length_penalty, return_worst)
         out = np.zeros((batch.n, self.max_new, 8), np.int64)
         lens = np.zeros(batch.n, np.int32)
-        self._chk(self.lib.vx_infer(self.ctx, C.byref(batch.c), C.byref(s), _ptr(out, C.c_int64), self.max_new,
-                                    _ptr(lens, C.c_int32)))
+        if continuous:
+            raised = []
+
+            def done(_user, row, codes, frames):
+                if raised or on_row is None:
+                    return
+                try:
+                    arr = np.ctypeslib.as_array(codes, shape=(frames, 8)).copy() if frames else np.zeros((0, 8), np.int64)
+                    on_row(int(row), arr)
+                except BaseException as e:      # ctypes would print and drop it: kept and re-raised after the call
+                    raised.append(e)
+
+            cb = ROW_DONE_FN(done) if on_row is not None else ROW_DONE_FN()
+            rc = self.lib.vx_infer_continuous(self.ctx, C.byref(batch.c), C.byref(s), cb, None, _ptr(out, C.c_int64), self.max_new,
+                                              _ptr(lens, C.c_int32))
+            self._chk(rc)
+            if raised:
+                raise raised[0]
+        else:
+            self._chk(self.lib.vx_infer(self.ctx, C.byref(batch.c), C.byref(s), _ptr(out, C.c_int64), self.max_new,
+                                        _ptr(lens, C.c_int32)))
         cut = C.c_int32()
         self._chk(self.lib.vx_last_truncated(self.ctx, C.byref(cut)))
         if cut.value:

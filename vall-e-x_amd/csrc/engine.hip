@@ -298,19 +298,21 @@ int check_batch(vx_ctx* c, const vx_batch* b, int max_rows) {
 }
 
 // ---- AR prefill (models/vallex.py:497-562, first ar_decoder.infer call) ------------------------------------
-// beams > 1: best_of.  The reference repeats the prompt N times and runs N identical prefills (models/vallex.py:525-527); here
-// every one of the nb rows is prefilled once and decode row i*beams + j (j < beams) continues from prefill row i: its KV cache
-// and residual row are fanned out to the beams (beams.hip), which then sample independently.
-int ar_prefill(vx_ctx* c, const vx_batch* b, int r0, int nb, int beams = 1) {
-  const int NL = c->NL;
-  const int nrows = nb * beams;                      // decode rows after this call
-  std::vector<int> seq_off(nb), seq_len(nb), S_(nb), dst_t, id_t, lang_t, pos_t, dst_a, id_a, pos_a, row_b, row_t;
+// The full-sequence part of a prefill (tables, embeddings, the prefix-LM layers that fill the KV arena) is shared by the first fill
+// of a decode batch (ar_prefill) and by the admission of waiting rows into a running one (continuous schedule, admit_rows below).
+// prefill_tables builds the sequence tables of caller rows r0 .. r0+nb-1 into `mb`; row_b (the arena slot of every packed row) is
+// left as PREFILL row indices: the caller maps them to slots and adds them (o_rb) before upload_meta.
+int prefill_tables(vx_ctx* c, const vx_batch* b, int r0, int nb, PrefillPlan& p, MetaBuilder& mb) {
+  p.nb = nb;
+  p.seq_off.assign(nb, 0); p.seq_len.assign(nb, 0); p.S_.assign(nb, 0);
+  std::vector<int> dst_t, id_t, lang_t, pos_t, dst_a, id_a, pos_a, row_t;
+  p.row_b.clear();
   long M = 0;
   int max_len = 0;
   for (int i = 0; i < nb; ++i) {
     const int r = r0 + i, S = b->text_lens[r], Tp = b->prompt_lens[r];
-    seq_off[i] = (int)M; seq_len[i] = S + 1 + Tp; S_[i] = S;
-    max_len = std::max(max_len, seq_len[i]);
+    p.seq_off[i] = (int)M; p.seq_len[i] = S + 1 + Tp; p.S_[i] = S;
+    max_len = std::max(max_len, p.seq_len[i]);
     for (int s = 0; s < S; ++s) {
       dst_t.push_back((int)M + s);
       id_t.push_back(b->text_ids[(long)r * b->text_stride + s]);
@@ -322,17 +324,79 @@ int ar_prefill(vx_ctx* c, const vx_batch* b, int r0, int nb, int beams = 1) {
       id_a.push_back(t == 0 ? BOS_ID : b->prompt_codes[((long)r * b->prompt_stride + (t - 1)) * N_Q]);
       pos_a.push_back(t);
     }
-    for (int t = 0; t < seq_len[i]; ++t) { row_b.push_back(i); row_t.push_back(t); }
-    M += seq_len[i];
+    for (int t = 0; t < p.seq_len[i]; ++t) { p.row_b.push_back(i); row_t.push_back(t); }
+    M += p.seq_len[i];
   }
   if (M > c->Mmax) FAIL(VX_EINVAL, "prefill rows %ld exceed arena %ld", M, c->Mmax);
+  p.M = M; p.max_len = max_len;
+  p.n_t = (int)dst_t.size(); p.n_a = (int)dst_a.size();
+  p.o_off = mb.add(p.seq_off); p.o_len = mb.add(p.seq_len); p.o_S = mb.add(p.S_); p.o_dt = mb.add(dst_t); p.o_it = mb.add(id_t);
+  p.o_lt = mb.add(lang_t); p.o_pt = mb.add(pos_t); p.o_da = mb.add(dst_a); p.o_ia = mb.add(id_a); p.o_pa = mb.add(pos_a);
+  p.o_rt = mb.add(row_t);
+  // Row trimming of the LAST prefill layer (round 6; struct Trim): the decode only continues from the last row of every sequence
+  // (models/vallex.py:568: the logits of the newest position), so behind the K / V projection -- the cache needs every row -- the last
+  // layer runs its attention queries, out_proj and FFN on nb rows instead of M.
+  std::vector<int> tq_first(nb), tc_off(nb), t_rows(nb);
+  p.trim_flops = 0;
+  for (int i = 0; i < nb; ++i) {
+    tq_first[i] = p.seq_len[i] - 1; tc_off[i] = i; t_rows[i] = p.seq_off[i] + p.seq_len[i] - 1;
+    p.trim_flops += 4.0 * p.seq_len[i] * D_MODEL;
+  }
+  p.o_tq = mb.add(tq_first); p.o_tc = mb.add(tc_off); p.o_tr = mb.add(t_rows);
+  p.trim_h2 = c->gemm_mode == 0 && c->attn_x3 && c->attn_h2;
+  const bool trim_f32 = c->gemm_mode == 2 && !c->attn_x3;
+  p.trim = c->nar_trim && (p.trim_h2 || trim_f32) && !c->cfg.debug_taps;      // the same switch as the NAR stages (VX_NAR_TRIM)
+  return VX_OK;
+}
+
+// embeddings + the prefix-LM layers (K / V into the arena slots of p.row_b); the last row of every sequence is then row
+// p.hrow(i) of prefill_hsrc(c, p)
+int prefill_layers(vx_ctx* c, const PrefillPlan& p, const MetaBuilder& mb) {
+  const int NL = c->NL, nb = p.nb;
+  launch_embed_rows(c->fx, mb.dev(p.o_dt), W(c, "ar_text_embedding.word_embeddings.weight"), mb.dev(p.o_it),
+                    W(c, "ar_language_embedding.word_embeddings.weight"), mb.dev(p.o_lt), W(c, "ar_text_position.alpha"),
+                    c->pe, mb.dev(p.o_pt), p.n_t, c->stream);
+  launch_embed_rows(c->fx, mb.dev(p.o_da), W(c, "ar_audio_embedding.word_embeddings.weight"), mb.dev(p.o_ia), nullptr,
+                    nullptr, W(c, "ar_audio_position.alpha"), c->pe, mb.dev(p.o_pa), p.n_a, c->stream);
+  if (int e = tap_store(c, "ar_prefill_in", c->fx, (size_t)p.M * D_MODEL)) return e;
+
+  double attn_flops = 0;
+  for (int i = 0; i < nb; ++i) attn_flops += 4.0 * p.seq_len[i] * (double)p.seq_len[i] * D_MODEL;
+  const size_t cache_layer = (size_t)c->mbr * N_HEAD * c->Tmax * D_HEAD;
+  const Trim tr{nb, mb.dev(p.o_tq), mb.dev(p.o_tc), mb.dev(p.o_tr), p.trim_flops};
+  for (int l = 0; l < NL; ++l) {
+    if (int e = full_layer(c, c->ar[l], p.M, mb.dev(p.o_off), mb.dev(p.o_len), mb.dev(p.o_S), nb, p.max_len, nullptr, nullptr,
+                           c->kc + l * cache_layer, c->vc + l * cache_layer, mb.dev(p.o_rb), mb.dev(p.o_rt), attn_flops,
+                           (p.trim && l == NL - 1) ? &tr : nullptr))
+      return e;
+    if (c->cfg.debug_taps) {
+      char nm[64];
+      snprintf(nm, sizeof nm, "ar_layer_out.%d", l);
+      if (int e = tap_store(c, nm, c->fx, (size_t)p.M * D_MODEL)) return e;
+    }
+  }
+  return VX_OK;
+}
+
+// the buffer that holds the last row of every sequence behind prefill_layers (trimmed: the last layer left exactly those rows,
+// compacted, in the buffer full_layer uses for the compacted residual stream: fxn in f16x2 mode, the QKV buffer in fp32 mode)
+const float* prefill_hsrc(const vx_ctx* c, const PrefillPlan& p) { return p.trim ? (p.trim_h2 ? c->fxn : c->fqkv) : c->fx; }
+
+// First fill of a decode batch: the prefill of caller rows r0 .. r0+nb-1 plus the decode state and geometry that only the first
+// fill sets up (slot order, context splits, chain choice, cur_batch).
+// beams > 1: best_of.  The reference repeats the prompt N times and runs N identical prefills (models/vallex.py:525-527); here
+// every one of the nb rows is prefilled once and decode row i*beams + j (j < beams) continues from prefill row i: its KV cache
+// and residual row are fanned out to the beams (beams.hip), which then sample independently.
+int ar_prefill(vx_ctx* c, const vx_batch* b, int r0, int nb, int beams = 1) {
+  const int NL = c->NL;
+  const int nrows = nb * beams;                      // decode rows after this call
+  PrefillPlan p;
+  MetaBuilder mb(c);
+  if (int e = prefill_tables(c, b, r0, nb, p, mb)) return e;
+  const std::vector<int>&seq_off = p.seq_off, &seq_len = p.seq_len, &S_ = p.S_;
   if (nrows > c->mbr) FAIL(VX_EINVAL, "%d decode rows exceed the micro-batch (%d)", nrows, c->mbr);
   c->h_L.resize(nrows);
   for (int i = 0; i < nrows; ++i) c->h_L[i] = seq_len[i / beams];
-  MetaBuilder mb(c);
-  const long o_off = mb.add(seq_off), o_len = mb.add(seq_len), o_S = mb.add(S_), o_dt = mb.add(dst_t), o_it = mb.add(id_t),
-             o_lt = mb.add(lang_t), o_pt = mb.add(pos_t), o_da = mb.add(dst_a), o_ia = mb.add(id_a), o_pa = mb.add(pos_a),
-             o_rt = mb.add(row_t);
   // decode state
   std::vector<int> st_pos(nrows), st_ctx(nrows), st_zero(nrows, 0), st_one(nrows, 1), st_S(nrows);
   for (int i = 0; i < nrows; ++i) {
@@ -343,6 +407,7 @@ int ar_prefill(vx_ctx* c, const vx_batch* b, int r0, int nb, int beams = 1) {
   // ascending, so launch slots y and y + nb/2 -- which share a CU or a workgroup -- hold a long and a short context.  The
   // order of the contexts never changes during generation (every active row grows by one per step).  A row's beams have equal
   // contexts: the stable sort keeps them adjacent (nothing below relies on it: the fan-out reads every beam's slot from st_slot).
+  // (The continuous schedule admits new rows into the slots of finished ones: there the pairing holds only for the first fill.)
   std::vector<int> by_len(nrows), st_ord(nrows);
   for (int i = 0; i < nrows; ++i) by_len[i] = i;
   // (<= SB_ROWS rows: batch order -- the fused small-batch attention relies on slot == row, and there is nothing to balance)
@@ -363,22 +428,11 @@ int ar_prefill(vx_ctx* c, const vx_batch* b, int r0, int nb, int beams = 1) {
   // alone and requests the first tile before the slot record (row, context, active) has arrived (decode.hip).  The prefill
   // scatters every sequence's K / V into the arena row of its slot; best_of: prefill row i into the slot of decode row i*beams,
   // and the fan-out (beams.hip) copies it to the slots of decode rows i*beams + 1 .. i*beams + beams-1.
-  for (int& rb : row_b) rb = st_slot[rb * beams];
-  const long o_rb = mb.add(row_b);
+  for (int& rb : p.row_b) rb = st_slot[rb * beams];
+  p.o_rb = mb.add(p.row_b);
   const long o_sp = mb.add(st_pos), o_sc = mb.add(st_ctx), o_z = mb.add(st_zero), o_1 = mb.add(st_one), o_sS = mb.add(st_S),
              o_meta = mb.add(st_meta), o_slot = mb.add(st_slot);
-  // Row trimming of the LAST prefill layer (round 6; struct Trim): the decode only continues from the last row of every sequence
-  // (models/vallex.py:568: the logits of the newest position), so behind the K / V projection -- the cache needs every row -- the last
-  // layer runs its attention queries, out_proj and FFN on nb rows instead of M.
-  std::vector<int> tq_first(nb), tc_off(nb), t_rows(nb);
-  double trim_flops = 0;
-  for (int i = 0; i < nb; ++i) {
-    tq_first[i] = seq_len[i] - 1; tc_off[i] = i; t_rows[i] = seq_off[i] + seq_len[i] - 1;
-    trim_flops += 4.0 * seq_len[i] * D_MODEL;
-  }
-  const long o_tq = mb.add(tq_first), o_tc = mb.add(tc_off), o_tr = mb.add(t_rows);
-  const bool trim_h2 = c->gemm_mode == 0 && c->attn_x3 && c->attn_h2, trim_f32 = c->gemm_mode == 2 && !c->attn_x3;
-  const bool trim = c->nar_trim && (trim_h2 || trim_f32) && !c->cfg.debug_taps;      // the same switch as the NAR stages (VX_NAR_TRIM)
+  const bool trim = p.trim;
   // best_of fan-out tables (beams.hip): (slot of decode row i*beams, slot of decode row i*beams + j, seq_len[i]) per copy, and the
   // row of the prefill's last-row buffer every decode row's residual comes from (trimmed: compacted row i, else packed row)
   long o_fp = 0, o_fr = 0;
@@ -387,7 +441,7 @@ int ar_prefill(vx_ctx* c, const vx_batch* b, int r0, int nb, int beams = 1) {
     for (int i = 0; i < nb; ++i) {
       if (seq_len[i] > c->Tmax) FAIL(VX_EINVAL, "row %d: %d cached rows exceed the arena (%d)", r0 + i, seq_len[i], c->Tmax);
       for (int j = 1; j < beams; ++j) fpairs.insert(fpairs.end(), {st_slot[i * beams], st_slot[i * beams + j], seq_len[i]});
-      for (int j = 0; j < beams; ++j) frow[i * beams + j] = trim ? i : seq_off[i] + seq_len[i] - 1;
+      for (int j = 0; j < beams; ++j) frow[i * beams + j] = p.hrow(i);
     }
     o_fp = mb.add(fpairs); o_fr = mb.add(frow);
   }
@@ -447,31 +501,10 @@ int ar_prefill(vx_ctx* c, const vx_batch* b, int r0, int nb, int beams = 1) {
     }
   }
 
-  launch_embed_rows(c->fx, mb.dev(o_dt), W(c, "ar_text_embedding.word_embeddings.weight"), mb.dev(o_it),
-                    W(c, "ar_language_embedding.word_embeddings.weight"), mb.dev(o_lt), W(c, "ar_text_position.alpha"),
-                    c->pe, mb.dev(o_pt), (int)dst_t.size(), c->stream);
-  launch_embed_rows(c->fx, mb.dev(o_da), W(c, "ar_audio_embedding.word_embeddings.weight"), mb.dev(o_ia), nullptr,
-                    nullptr, W(c, "ar_audio_position.alpha"), c->pe, mb.dev(o_pa), (int)dst_a.size(), c->stream);
-  if (int e = tap_store(c, "ar_prefill_in", c->fx, (size_t)M * D_MODEL)) return e;
-
-  double attn_flops = 0;
-  for (int i = 0; i < nb; ++i) attn_flops += 4.0 * seq_len[i] * (double)seq_len[i] * D_MODEL;
+  if (int e = prefill_layers(c, p, mb)) return e;
+  // last row of every sequence -> decode residual stream h[b]
+  const float* hsrc = prefill_hsrc(c, p);
   const size_t cache_layer = (size_t)c->mbr * N_HEAD * c->Tmax * D_HEAD;
-  const Trim tr{nb, mb.dev(o_tq), mb.dev(o_tc), mb.dev(o_tr), trim_flops};
-  for (int l = 0; l < NL; ++l) {
-    if (int e = full_layer(c, c->ar[l], M, mb.dev(o_off), mb.dev(o_len), mb.dev(o_S), nb, max_len, nullptr, nullptr,
-                           c->kc + l * cache_layer, c->vc + l * cache_layer, mb.dev(o_rb), mb.dev(o_rt), attn_flops,
-                           (trim && l == NL - 1) ? &tr : nullptr))
-      return e;
-    if (c->cfg.debug_taps) {
-      char nm[64];
-      snprintf(nm, sizeof nm, "ar_layer_out.%d", l);
-      if (int e = tap_store(c, nm, c->fx, (size_t)M * D_MODEL)) return e;
-    }
-  }
-  // last row of every sequence -> decode residual stream h[b]  (trimmed: the last layer left exactly those rows, compacted, in the
-  // buffer full_layer uses for the compacted residual stream: fxn in f16x2 mode, the QKV buffer in fp32 mode)
-  const float* hsrc = trim ? (trim_h2 ? c->fxn : c->fqkv) : c->fx;
   if (beams > 1)      // best_of: every decode row's residual row + the other beams' K / V, one launch
     launch_beam_fanout(c->kc, c->vc, (long)cache_layer, NL, c->Tmax, mb.dev(o_fp), nb * (beams - 1), hsrc, mb.dev(o_fr), c->dh, nrows,
                        c->stream);
@@ -927,6 +960,254 @@ int nar_generate(vx_ctx* c, const vx_batch* b, int r0, int nb, const std::vector
   return nar_generate_once(c, b, r0, nb, T, codes0, codes0_stride, out_codes, sumT_out);
 }
 
+// ---- continuous schedule (vx_infer_continuous) ---------------------------------------------------------------
+// One decode batch of nd = min(mbr, batch) rows for the whole call: the first fill is ar_prefill of caller rows 0 .. nd-1 (it sets
+// the geometry: slot order, context splits, chain choice -- fixed from then on, so the captured step graph never changes); at every
+// host poll (every sync_every steps, and at the step where a row reaches its cap) the rows that stopped are harvested (n_gen + gen row to the host) and waiting caller rows, first come first served, are
+// admitted into the freed decode rows: one prefill per admission round into the freed rows' KV slots, then the first sample of
+// the admitted rows alone.  Harvested rows go through the NAR stages in groups of mbr (the rest once nothing is left to decode),
+// between two decode steps: nar_generate only touches the full-sequence buffers.
+
+// caller rows `rows` of b gathered into a batch of their own (prefill / NAR of a non-contiguous row set)
+struct SubBatch {
+  std::vector<int32_t> ids, lang, tl, pc, pl;
+  vx_batch b{};
+  SubBatch(const vx_batch* src, const std::vector<int>& rows) {
+    const int n = (int)rows.size(), ts = src->text_stride, ps = src->prompt_stride;
+    ids.resize((size_t)n * ts); lang.resize((size_t)n * ts); pc.resize((size_t)n * ps * N_Q); tl.resize(n); pl.resize(n);
+    for (int i = 0; i < n; ++i) {
+      const int r = rows[i];
+      std::copy_n(src->text_ids + (long)r * ts, ts, ids.begin() + (size_t)i * ts);
+      std::copy_n(src->text_lang + (long)r * ts, ts, lang.begin() + (size_t)i * ts);
+      std::copy_n(src->prompt_codes + (long)r * ps * N_Q, (size_t)ps * N_Q, pc.begin() + (size_t)i * ps * N_Q);
+      tl[i] = src->text_lens[r]; pl[i] = src->prompt_lens[r];
+    }
+    b = *src;
+    b.batch = n; b.text_ids = ids.data(); b.text_lang = lang.data(); b.text_lens = tl.data();
+    b.prompt_codes = pc.data(); b.prompt_lens = pl.data();
+  }
+};
+
+// the sampler's draws of caller rows crow[i] into decode columns drow[i] of d_uniforms (launch_admit_uniforms); the tables go into
+// the MetaBuilder of the phase, before its upload
+struct UniformCols { long o_pairs = 0, o_staged = -1; int n = 0, steps = 0; };
+static int uniform_cols(vx_ctx* c, const vx_batch* b, const vx_sampling* s, const std::vector<int>& drow, const std::vector<int>& crow,
+                        MetaBuilder& mb, UniformCols& u) {
+  // only the first gen_stride + 1 draws of a row can ever be consumed (one per generated frame + the terminating sample)
+  u.n = (int)drow.size();
+  u.steps = s->uniforms ? (int)std::min<long>(s->uniforms_steps, c->gen_stride + 1) : c->gen_stride + 1;
+  if ((long)u.steps * c->cur_batch > c->uniforms_cap) FAIL(VX_EINVAL, "too many uniforms (%d steps)", u.steps);
+  std::vector<int> pairs(2 * u.n);
+  for (int i = 0; i < u.n; ++i) { pairs[2 * i] = drow[i]; pairs[2 * i + 1] = crow[i]; }
+  u.o_pairs = mb.add(pairs);
+  if (s->uniforms) {       // column r of the caller's [uniforms_steps][batch], staged as [n][steps] (float bits in the int tables)
+    std::vector<int> st((size_t)u.n * u.steps);
+    for (int i = 0; i < u.n; ++i)
+      for (int t = 0; t < u.steps; ++t) memcpy(&st[(size_t)i * u.steps + t], &s->uniforms[(long)t * b->batch + crow[i]], sizeof(float));
+    u.o_staged = mb.add(st);
+  }
+  return VX_OK;
+}
+static void uniform_cols_launch(vx_ctx* c, const vx_sampling* s, const UniformCols& u, const MetaBuilder& mb) {
+  const float* staged = u.o_staged >= 0 ? reinterpret_cast<const float*>(mb.dev(u.o_staged)) : nullptr;
+  launch_admit_uniforms(mb.dev(u.o_pairs), u.n, staged, u.steps, s->seed, c->d_uniforms, c->cur_batch, c->stream);
+}
+
+// admission of caller rows crow[i] (sub-batch sb, row i) into the free decode rows drow[i] of the running decode batch, up to and
+// including their first sample.  The rows still decoding keep every piece of their state: the prefill scatters K / V into the
+// admitted rows' slots only, its final norm + predict layer run on scratch copies (dh2 / xp_att: the step recomputes both before
+// it reads them; the logits of rows that are not admitted are never read), and the sampler commits the admitted rows only.
+static int admit_rows(vx_ctx* c, const vx_batch* b, const vx_sampling* s, const SampleArgs& sa, const std::vector<int>& drow,
+                      const std::vector<int>& crow, const std::vector<int>& slot_of) {
+  const int k = (int)drow.size(), nd = c->cur_batch;
+  SubBatch sb(b, crow);
+  PrefillPlan p;
+  MetaBuilder mb(c);
+  if (int e = prefill_tables(c, &sb.b, 0, k, p, mb)) return e;
+  for (int& rb : p.row_b) rb = slot_of[drow[rb]];
+  p.o_rb = mb.add(p.row_b);
+  std::vector<int> tab(5 * k), adm(nd, 0), saved(nd, 0);
+  for (int i = 0; i < k; ++i) {
+    tab[5 * i] = drow[i]; tab[5 * i + 1] = sb.pl[i]; tab[5 * i + 2] = p.seq_len[i]; tab[5 * i + 3] = p.S_[i]; tab[5 * i + 4] = p.hrow(i);
+    adm[drow[i]] = 1;
+  }
+  const long o_tab = mb.add(tab), o_adm = mb.add(adm), o_saved = mb.add(saved);
+  UniformCols uc;
+  if (int e = uniform_cols(c, b, s, drow, crow, mb, uc)) return e;
+  if (int e = upload_meta(c)) return e;
+  uniform_cols_launch(c, s, uc, mb);
+  if (int e = prefill_layers(c, p, mb)) return e;
+  launch_admit_rows(mb.dev(o_tab), k, prefill_hsrc(c, p), c->dh2, c->cur_tok, c->cur_pos, c->ctx_len, c->n_gen, c->text_len,
+                    c->slot_meta, c->slot_of, c->stream);
+  launch_dec_reduce_ln_pack(nullptr, 0, D_MODEL, nullptr, c->dh2, nullptr, W(c, "ar_decoder.norm.weight"),
+                            W(c, "ar_decoder.norm.bias"), c->xp_att, nd, c->stream);
+  launch_skinny_gemm(c->pred_wp, c->xp_att, c->p_logits, PRED_NPAD, D_MODEL, SK_PRED, c->stream);
+  int* sv = c->imeta + o_saved;
+  launch_admit_mask(0, mb.dev(o_adm), sv, nd, c->active, c->slot_meta, c->slot_of, c->n_active, c->stream);
+  LAUNCH(launch_dec_sample(sa, c->stream));
+  launch_admit_mask(1, mb.dev(o_adm), sv, nd, c->active, c->slot_meta, c->slot_of, c->n_active, c->stream);
+  return launch_status(c);
+}
+
+int infer_continuous(vx_ctx* c, const vx_batch* b, const vx_sampling* s, vx_row_done_fn on_row, void* user, int64_t* out_codes,
+                     int32_t out_stride, int32_t* out_lens) {
+  const int B = b->batch, nd = std::min(c->mbr, B);
+  hipEvent_t e0 = c->ev_t[0], e1 = c->ev_t[1], e2 = c->ev_t[2];
+  HIPCHK(hipEventRecord(e0, c->stream));
+  // per decode row: the caller row in it (-1: free), the step count at its admission and the step by which it has stopped at the
+  // latest (the sampler stops a row at n_gen = min(16 S, gen_stride, force_eos_at))
+  std::vector<int> occ(nd, -1), done_by(nd, 0), act(nd, 0), ng(nd, 0), slot_of(nd);
+  std::vector<std::vector<int>> rowgen(B);           // first-codebook ids of every harvested row (D2H target: never reallocated)
+  std::vector<int> pend;                             // harvested rows waiting for their NAR stages, in the order they completed
+  int next = 0;                                      // first caller row not admitted yet
+  long steps = 0;
+  const int first_cap = s->force_eos_at >= 0 ? std::min(c->gen_stride, s->force_eos_at) : c->gen_stride;
+  auto row_cap = [&](int r) { return std::min(first_cap, 16 * b->text_lens[r]); };
+  auto cut_by_arena = [&](int n, int S) {
+    return n >= c->gen_stride && c->gen_stride < 16 * S && !(s->force_eos_at >= 0 && s->force_eos_at <= c->gen_stride);
+  };
+  SampleArgs sa{};
+  // one admission round (first fill or admission) with the f16x2 range guard of ar_generate: a raised flag re-runs the round,
+  // prefill and first sample, on the exact-fp32 kernels; it counts in vx_last_fallbacks and towards sticky mode
+  auto round = [&](const std::vector<int>& drow, const std::vector<int>& crow) -> int {
+    const bool first = occ[0] < 0 && next == 0;
+    bool raised = false;
+    auto attempt = [&](bool read_flag) -> int {
+      if (first) {
+        if (int e = ar_prefill(c, b, 0, nd)) return e;
+        sa = make_sample_args(c, s, 1, nullptr);
+        sa.uniforms = c->d_uniforms;                 // every row draws from its own column, injected or counter-based
+        MetaBuilder mb(c);
+        UniformCols uc;
+        if (int e = uniform_cols(c, b, s, drow, crow, mb, uc)) return e;
+        if (int e = upload_meta(c)) return e;
+        uniform_cols_launch(c, s, uc, mb);
+        LAUNCH(launch_dec_sample(sa, c->stream));
+        if (int e = launch_status(c)) return e;
+        D2H(slot_of.data(), c->slot_of, nd * sizeof(int));
+      } else if (int e = admit_rows(c, b, s, sa, drow, crow, slot_of)) return e;
+      int flag = 0;
+      D2H(act.data(), c->active, nd * sizeof(int));
+      D2H(ng.data(), c->n_gen, nd * sizeof(int));
+      if (read_flag) D2H(&flag, c->range_flag, sizeof(int));
+      SYNC();
+      raised = flag != 0;
+      return VX_OK;
+    };
+    const bool direct_f32 = fb_direct(c, c->sticky_prefill_f32, c->sticky_prefill_age);
+    if (direct_f32) {
+      ++c->st_fb_prefill; ++c->fb_total;
+      if (int e = ensure_f32_buffers(c)) return e;
+      F32Scope f32(c);
+      if (int e = attempt(false)) return e;
+    } else {
+      if (int e = attempt(range_guarded(c))) return e;
+      fb_outcome(c, raised, c->fb_prefill_raises, c->sticky_prefill_f32, c->sticky_prefill_age);
+      if (raised) {
+        HIPCHK(hipMemsetAsync(c->range_flag, 0, sizeof(int), c->stream));
+        ++c->st_fb_prefill; ++c->fb_total;
+        if (int e = ensure_f32_buffers(c)) return e;
+        F32Scope f32(c);
+        if (int e = attempt(false)) return e;
+      }
+    }
+    for (size_t i = 0; i < drow.size(); ++i) { occ[drow[i]] = crow[i]; done_by[drow[i]] = (int)steps + row_cap(crow[i]); }
+    next += (int)crow.size();
+    return VX_OK;
+  };
+  // NAR stages of the first n pending rows, then their codes to the caller
+  auto nar_group = [&](int n) -> int {
+    std::vector<int> rows(pend.begin(), pend.begin() + n), T(n), codes0((size_t)n * c->gen_stride, 0), oc;
+    pend.erase(pend.begin(), pend.begin() + n);
+    SYNC();                                          // the harvested gen rows have arrived
+    for (int i = 0; i < n; ++i) {
+      T[i] = (int)rowgen[rows[i]].size();
+      std::copy(rowgen[rows[i]].begin(), rowgen[rows[i]].end(), codes0.begin() + (size_t)i * c->gen_stride);
+    }
+    SubBatch sb(b, rows);
+    long sumT = 0;
+    HIPCHK(hipEventRecord(e1, c->stream));
+    if (int e = nar_generate(c, &sb.b, 0, n, T, codes0.data(), c->gen_stride, oc, sumT)) return e;
+    HIPCHK(hipEventRecord(e2, c->stream));
+    HIPCHK(hipEventSynchronize(e2));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, e1, e2)); c->st_nar_ms += ms;
+    long off = 0;
+    for (int i = 0; i < n; ++i) {
+      const int r = rows[i];
+      out_lens[r] = T[i];
+      c->st_frames += T[i];
+      if (cut_by_arena(T[i], b->text_lens[r])) ++c->st_truncated;
+      int64_t* o0 = out_codes + (long)r * out_stride * N_Q;
+      for (int t = 0; t < T[i]; ++t) {
+        int64_t* o = o0 + (long)t * N_Q;
+        o[0] = codes0[(size_t)i * c->gen_stride + t];
+        for (int st = 0; st < N_Q - 1; ++st) o[st + 1] = oc[(size_t)st * sumT + off + t];
+      }
+      off += T[i];
+      if (on_row) on_row(user, r, o0, T[i]);
+    }
+    return VX_OK;
+  };
+
+  {
+    std::vector<int> first(nd);
+    for (int i = 0; i < nd; ++i) first[i] = i;
+    if (int e = round(first, first)) return e;
+  }
+  char sig[160];
+  snprintf(sig, sizeof sig, "b%d ns%d c%d%d%d k%d t%a u%d f%d l%d", nd, c->nsplit, (int)c->sb_chain, (int)c->sb_qkv, (int)c->split_fused, sa.top_k,
+           sa.temperature, sa.uniforms != nullptr, sa.force_eos_at, sa.sum_logp != nullptr);
+  const int sync_every = s->sync_every > 0 ? s->sync_every : 8;
+  const int gs = (c->graph_multi && sync_every % GRAPH_STEPS == 0) ? GRAPH_STEPS : 1;
+  for (;;) {
+    // harvest: the rows that stopped hand their ids to the host (delivered at the next sync) and free their decode rows
+    std::vector<int> freed;
+    for (int d = 0; d < nd; ++d) {
+      if (occ[d] < 0 || act[d]) continue;
+      const int r = occ[d];
+      if (ng[d] > out_stride) FAIL(VX_EINVAL, "out_stride %d too small for %d frames", out_stride, ng[d]);
+      rowgen[r].assign(ng[d], 0);
+      if (ng[d]) D2H(rowgen[r].data(), c->gen + (size_t)d * c->gen_stride, ng[d] * sizeof(int));
+      pend.push_back(r);
+      occ[d] = -1;
+    }
+    for (int d = 0; d < nd; ++d) if (occ[d] < 0) freed.push_back(d);
+    // admission (policy: whenever a poll finds a free row), FIFO over the waiting caller rows
+    if (next < B && !freed.empty()) {
+      const int k = std::min<int>((int)freed.size(), B - next);
+      std::vector<int> drow(freed.begin(), freed.begin() + k), crow(k);
+      for (int i = 0; i < k; ++i) crow[i] = next + i;
+      if (int e = round(drow, crow)) return e;
+      continue;                                      // an admitted row may have stopped at its first sample
+    }
+    const bool live = std::any_of(occ.begin(), occ.end(), [](int r) { return r >= 0; });
+    while ((int)pend.size() >= c->mbr || (!live && !pend.empty()))
+      if (int e = nar_group(std::min<int>(c->mbr, (int)pend.size()))) return e;
+    if (!live) break;
+    // decode steps up to the next host poll, or up to the step by which a live row has stopped at the latest (its cap: that poll
+    // is sure to free a row -- without it a row capped between two polls would leave its decode row idle until the next one)
+    long soonest = (steps / sync_every + 1) * sync_every;
+    for (int d = 0; d < nd; ++d) if (occ[d] >= 0) soonest = std::min<long>(soonest, done_by[d]);
+    const long target = std::max(soonest, steps + 1);
+    while (steps < target) {
+      const int n = (steps % gs == 0 && steps + gs <= target) ? gs : 1;
+      if (int e = ar_step_run(c, &sa, sig, n)) return e;
+      steps += n;
+    }
+    D2H(act.data(), c->active, nd * sizeof(int));
+    D2H(ng.data(), c->n_gen, nd * sizeof(int));
+    SYNC();
+  }
+  HIPCHK(hipEventRecord(e1, c->stream));
+  HIPCHK(hipEventSynchronize(e1));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+  c->st_ar_ms = ms - c->st_nar_ms;
+  c->st_steps = steps;
+  return VX_OK;
+}
+
 }  // namespace vxe
 
 // =================================================================================================================
@@ -1192,6 +1473,21 @@ int vx_infer(vx_ctx* c, const vx_batch* b, const vx_sampling* s, int64_t* out_co
     }
   }
   return VX_OK;
+}
+
+int vx_infer_continuous(vx_ctx* c, const vx_batch* b, const vx_sampling* s, vx_row_done_fn on_row, void* user, int64_t* out_codes,
+                        int32_t out_stride, int32_t* out_lens) {
+  if (!c || !s || !out_codes || !out_lens) return VX_EINVAL;
+  HIPCHK(hipSetDevice(c->dev));
+  if (s->struct_size != sizeof(vx_sampling))
+    FAIL(VX_EINVAL, "vx_sampling.struct_size is %u, this library expects %zu (ABI version %d)", s->struct_size, sizeof(vx_sampling), VX_ABI_VERSION);
+  // any number of rows: the call holds device memory for its min(max_batch, 32) decode rows and one NAR group only
+  if (int e = check_batch(c, b, 0x7fffffff)) return e;
+  if (!(s->temperature > 0.f)) FAIL(VX_EINVAL, "temperature must be > 0");
+  if (s->best_of > 1) FAIL(VX_EINVAL, "vx_infer_continuous does not run best_of > 1 (use vx_infer)");
+  c->st_steps = 0; c->st_frames = 0; c->st_ar_ms = 0; c->st_nar_ms = 0; c->st_truncated = 0;
+  c->st_fb_prefill = c->st_fb_nar = 0;
+  return infer_continuous(c, b, s, on_row, user, out_codes, out_stride, out_lens);
 }
 
 int64_t vx_read_tap(vx_ctx* c, const char* name, float* dst, int64_t max_floats) {

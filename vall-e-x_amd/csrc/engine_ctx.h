@@ -287,6 +287,35 @@ int launch_status(vx_ctx* c);      // VX_EINVAL (+ message) if a launcher refuse
 void launch_beam_fanout(float* kc, float* vc, long cache_layer, int layers, int Tmax, const int* pairs, int npairs,
                         const float* hsrc, const int* hsrc_row, float* dh, int nrows, hipStream_t s);
 
+// sequence tables of one full-sequence AR prefill (engine.hip prefill_tables: ar_prefill's first fill and the continuous schedule's
+// admissions); offsets into the MetaBuilder of the prefill
+struct PrefillPlan {
+  int nb = 0, max_len = 0, n_t = 0, n_a = 0;
+  long M = 0;
+  std::vector<int> seq_off, seq_len, S_;
+  std::vector<int> row_b;          // [M] prefill row of every packed row; the caller maps it to an arena slot and adds it as o_rb
+  long o_off = 0, o_len = 0, o_S = 0, o_dt = 0, o_it = 0, o_lt = 0, o_pt = 0, o_da = 0, o_ia = 0, o_pa = 0, o_rt = 0, o_rb = 0,
+       o_tq = 0, o_tc = 0, o_tr = 0;
+  double trim_flops = 0;
+  bool trim = false, trim_h2 = false;
+  int hrow(int i) const { return trim ? i : seq_off[i] + seq_len[i] - 1; }   // row of sequence i's last position in prefill_hsrc
+};
+
+// continuous schedule (admit.hip).  Admission of waiting caller rows into free decode rows of a running decode batch:
+//   tab [n][5] = {decode row d, prompt frames Tp, context S + 1 + Tp, text length S, row of hsrc}: the decode state of row d as
+//   ar_prefill sets it (slot_meta context included; the active flag is set by launch_admit_mask) and hres[d] = hsrc[row];
+void launch_admit_rows(const int* tab, int n, const float* hsrc, float* hres, int* cur_tok, int* cur_pos, int* ctx_len, int* n_gen,
+                       int* text_len, int* slot_meta, const int* slot_of, hipStream_t s);
+//   phase 0: saved[d] = admitted[d] ? 0 : active[d], active[d] = admitted[d] (the sampler then commits the admitted rows only);
+//   phase 1: active[d] |= saved[d], slot_meta[4 slot_of[d] + 2] = active[d], *n_active = number of active rows.  nrows <= 64.
+void launch_admit_mask(int phase, const int* admitted, int* saved, int nrows, int* active, int* slot_meta, const int* slot_of,
+                       int* n_active, hipStream_t s);
+//   the sampler's draws of decode column d for steps 0 .. steps-1, u[t * ncols + d]: pairs [n][2] = {d, caller row r};
+//   staged != null: staged[i * steps + t] (injected uniforms, column r of the caller's [steps][batch]); else the counter-based
+//   draw of caller row r, splitmix64(splitmix64(splitmix64(seed) + r) + t) >> 40 x 2^-24 (dec_sample_kernel's formula)
+void launch_admit_uniforms(const int* pairs, int n, const float* staged, int steps, unsigned long long seed, float* u, int ncols,
+                           hipStream_t s);
+
 struct F32Scope {            // the full-sequence path on the exact-fp32 kernels for the lifetime of the object
   vx_ctx* c;
   int gm;

@@ -255,12 +255,17 @@ class VALLE:
 
     def inference_batch(self, rows: Sequence[dict], top_k: int = -100, temperature: float = 1.0, uniforms=None,
                         force_eos_at=None, seed: Optional[int] = None, sync_every: int = 8, best_of: int = 1,
-                        length_penalty: float = 1.0, return_worst: bool = False) -> List[np.ndarray]:
+                        length_penalty: float = 1.0, return_worst: bool = False, continuous: bool = False,
+                        on_row=None) -> List[np.ndarray]:
         """rows[i] = dict(text ids (S,), prompt codes (Tp,8), enroll, prompt_language, text_language).
         Row i equals `inference` run alone on that row.  Returns one (T_i, 8) int64 array per row.
         `best_of` = N > 1 decodes every row as N beams (the UI's call, launch-ui.py:285-295, for a whole batch); `length_penalty`
         and `return_worst` select per row.  Injected `uniforms` are (steps, len(rows) x max(1, N)): column i*N + j feeds beam j of
-        row i, so row i equals `inference(row i, best_of=N, uniforms=uniforms[:, i*N:(i+1)*N])`."""
+        row i, so row i equals `inference(row i, best_of=N, uniforms=uniforms[:, i*N:(i+1)*N])`.
+        `continuous=True` runs the continuous schedule (vx_infer_continuous): a finished row's decode row is refilled with the next
+        waiting row at the next host poll; `on_row(i, codes)` (continuous only) receives every row as soon as its NAR stages are
+        done.  Without injected uniforms row i >= 32 then draws a stream of its own (include/vallex_hip.h)."""
+        Engine.check_continuous(best_of, continuous, on_row)
         if seed is None:
             seed = fresh_seed()
         texts, langs, prompts = [], [], []
@@ -272,7 +277,8 @@ class VALLE:
             langs.append(self._lang_row(len(t), int(r["enroll"]), r["prompt_language"], r["text_language"]))
         return self.engine.infer(Batch(texts, langs, prompts), top_k=top_k, temperature=temperature, uniforms=uniforms,
                                  seed=seed, force_eos_at=force_eos_at, sync_every=sync_every, best_of=best_of,
-                                 length_penalty=length_penalty, return_worst=return_worst)
+                                 length_penalty=length_penalty, return_worst=return_worst, continuous=continuous,
+                                 on_row=on_row)
 
     def make_batch(self, rows: Sequence[dict]) -> Batch:
         texts = [_np(r["text"], np.int32).reshape(-1) for r in rows]
