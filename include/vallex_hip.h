@@ -143,6 +143,53 @@ typedef void (*vx_row_done_fn)(void* user, int32_t row, const int64_t* codes /* 
 int vx_infer_continuous(vx_ctx* ctx, const vx_batch* b, const vx_sampling* s, vx_row_done_fn on_row, void* user,
                         int64_t* out_codes, int32_t out_stride, int32_t* out_lens);
 
+/* Serving session (additive: VX_ABI_VERSION stays 6).  vx_infer and vx_infer_continuous take a closed batch; a session takes
+ * requests at any time and admits each into the running decode batch as soon as enough decode rows are free.  Contract: a request
+ * returns exactly what a batch-1 vx_infer call on it returns (same seed or same draws, same best_of / length_penalty /
+ * return_worst), whatever else is in the session.
+ *   - vx_serve_open reads the session-wide fields of vx_sampling only: top_k, temperature, force_eos_at, sync_every.  best_of (<= 1),
+ *     seed (0), uniforms (NULL), length_penalty (0 or 1) and return_worst (0) must keep their defaults: they are per request.  The
+ *     decode batch is nd = min(max_batch, 32) rows, all free.  One session per context: while it is open, vx_infer,
+ *     vx_infer_continuous, vx_ar_prefill, vx_ar_step and vx_nar return VX_EINVAL (they would overwrite the decode state);
+ *     vx_vocos_decode and vx_encodec_* stay allowed.
+ *   - vx_serve_submit copies everything it needs (the caller's buffers may be freed on return), does no GPU work and writes
+ *     increasing request ids.  Every row is checked as vx_infer checks it, plus best_of <= nd and, with injected uniforms,
+ *     uniforms_steps >= min(16 x text length, max_new, force_eos_at) + 1.  On any failure nothing of the call is enqueued.
+ *   - vx_serve_run admits waiting requests first come first served: the head request waits until best_of decode rows are free, a
+ *     later request does not overtake it.  It runs up to max_steps decode steps (<= 0: until no request is decoding or waiting), with
+ *     host polls every sync_every steps and at the step where a row reaches its cap; requests whose beams have all stopped go through
+ *     the NAR stages in groups of up to 32, and before it returns every request that finished during the call has been delivered:
+ *     on_done (may be NULL) is called once per request on the calling thread, codes [frames][8] valid during the callback only; the
+ *     callback must not call into the same context.  live / waiting (may be NULL): requests decoding / not admitted yet.
+ *     vx_last_stats, vx_last_truncated and vx_last_fallbacks describe the last vx_serve_run.
+ *   - vx_serve_close drops waiting requests and requests still decoding; the context is usable for vx_infer again.  vx_destroy closes
+ *     an open session.
+ *   - Beams.  A request with best_of = N is prefilled once and decoded as N beams on N free decode rows (any slots).  It is harvested
+ *     when all N have stopped (EOS, 16 x text length, max_new or force_eos_at: models/vallex.py:572-578) and its winner is selected
+ *     as vx_infer selects it: sum(logp) / (1 + Tp + frames)^length_penalty, first index wins ties, or the worst with return_worst.
+ *   - RNG.  Beam j of a request with seed s draws u_t = (splitmix64(splitmix64(splitmix64(s) + j) + t) >> 40) x 2^-24 at its own step
+ *     t: vx_infer's formula for decode row j of a batch-1 call.  Injected uniforms are [uniforms_steps][max(1, best_of)]: column j
+ *     feeds beam j.
+ *   - Arithmetic.  The f16x2 range guard works per admission round: a raised flag re-runs the round (prefill, beam fan-out, first
+ *     sample) on the fp32 kernels and counts in vx_last_fallbacks and towards sticky mode. */
+typedef struct vx_serve vx_serve;
+typedef struct vx_request {
+  uint32_t struct_size;         /* = sizeof(vx_request) */
+  int32_t best_of;              /* <= 1: one beam; N: N beams, N <= min(max_batch, 32) */
+  float length_penalty;
+  int32_t return_worst;
+  uint64_t seed;                /* counter RNG key of this request (ignored with uniforms) */
+  const float* uniforms;        /* optional [uniforms_steps][max(1, best_of)]: column j feeds beam j */
+  int32_t uniforms_steps;
+} vx_request;
+typedef void (*vx_serve_done_fn)(void* user, int64_t request_id, const int64_t* codes /* [frames][8] */, int32_t frames);
+int vx_serve_open(vx_ctx* ctx, const vx_sampling* s, vx_serve** out);
+/* rows->batch requests, req [rows->batch]; ids_out [rows->batch] (may be NULL) */
+int vx_serve_submit(vx_serve* srv, const vx_batch* rows, const vx_request* req, int64_t* ids_out);
+int vx_serve_run(vx_serve* srv, int32_t max_steps, vx_serve_done_fn on_done, void* user, int32_t* live_requests,
+                 int32_t* waiting_requests);
+int vx_serve_close(vx_serve* srv);
+
 /* replaces: vocos.codes_to_features + vocos.decode(features, bandwidth_id), utils/generation.py:148-150.
  * codes [batch][codes_stride][8] int64, lens [batch] frames; audio [batch][audio_stride] fp32, 320*len samples each. */
 int vx_vocos_decode(vx_ctx* ctx, const int64_t* codes, int32_t codes_stride, const int32_t* lens, int32_t batch,

@@ -56,19 +56,28 @@ class vx_sampling(C.Structure):
                 ("return_worst", C.c_int32)]
 
 
+class vx_request(C.Structure):
+    """one request of a serving session (vx_serve_submit): its own best_of, selection, seed or injected draws"""
+    _fields_ = [("struct_size", C.c_uint32), ("best_of", C.c_int32), ("length_penalty", C.c_float), ("return_worst", C.c_int32),
+                ("seed", C.c_uint64), ("uniforms", C.POINTER(C.c_float)), ("uniforms_steps", C.c_int32)]
+
+
 # every symbol include/vallex_hip.h declares (tests/test_abi.py checks the library exports exactly these)
 ABI_VERSION = 6       # VX_ABI_VERSION of include/vallex_hip.h this binding was written against
 
 SYMBOLS = ["vx_abi_version", "vx_create", "vx_destroy", "vx_last_error", "vx_synchronize", "vx_load_tensor", "vx_finalize_weights",
            "vx_infer", "vx_vocos_decode", "vx_encodec_decode", "vx_encodec_encode", "vx_ar_prefill", "vx_ar_logits", "vx_ar_step",
            "vx_nar", "vx_read_tap", "vx_last_stats", "vx_last_truncated", "vx_last_fallbacks", "vx_fallback_state",
-           "vx_fallback_reset", "vx_arith_mode", "vx_infer_continuous"]
+           "vx_fallback_reset", "vx_arith_mode", "vx_infer_continuous", "vx_serve_open", "vx_serve_submit", "vx_serve_run",
+           "vx_serve_close"]
 # ... and include/vallex_hip_dev.h: measurement / kernel development, never called by the mirrors of the reference API
 DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kernel", "vx_bench_gemm", "vx_bench_attn",
                "vx_bench_gemm_clock", "vx_bench_gemm_epilogue"]
 
 # vx_row_done_fn of vx_infer_continuous: (user, caller row, codes [frames][8] int64, frames)
 ROW_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int32)
+# vx_serve_done_fn of vx_serve_run: (user, request id, codes [frames][8] int64, frames)
+SERVE_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int32)
 
 _lib = None
 
@@ -108,6 +117,10 @@ def load_library() -> C.CDLL:
     lib.vx_infer.argtypes = [ctx, P(vx_batch), P(vx_sampling), P(C.c_int64), C.c_int32, P(C.c_int32)]
     lib.vx_infer_continuous.argtypes = [ctx, P(vx_batch), P(vx_sampling), ROW_DONE_FN, C.c_void_p, P(C.c_int64), C.c_int32,
                                         P(C.c_int32)]
+    lib.vx_serve_open.argtypes = [ctx, P(vx_sampling), P(C.c_void_p)]
+    lib.vx_serve_submit.argtypes = [C.c_void_p, P(vx_batch), P(vx_request), P(C.c_int64)]
+    lib.vx_serve_run.argtypes = [C.c_void_p, C.c_int32, SERVE_DONE_FN, C.c_void_p, P(C.c_int32), P(C.c_int32)]
+    lib.vx_serve_close.argtypes = [C.c_void_p]
     lib.vx_vocos_decode.argtypes = [ctx, P(C.c_int64), C.c_int32, P(C.c_int32), C.c_int32, C.c_int32, P(C.c_float),
                                     C.c_int64]
     lib.vx_encodec_decode.argtypes = [ctx, P(C.c_int64), C.c_int32, P(C.c_int32), C.c_int32, P(C.c_float), C.c_int64]
@@ -251,6 +264,12 @@ class Engine:
             raise ValueError("continuous=True does not run best_of > 1 (vx_infer_continuous); use the micro-batched schedule")
         if on_row is not None and not continuous:
             raise ValueError("on_row needs continuous=True: only the continuous schedule hands rows over as they complete")
+
+    def serve(self, top_k=-100, temperature=1.0, sync_every=8, force_eos_at=None) -> "ServeSession":
+        """open a serving session on this context (vx_serve_open): requests are submitted at any time and join the running decode
+        batch as soon as enough decode rows are free.  top_k, temperature, sync_every and force_eos_at apply to the whole session;
+        best_of, length_penalty, return_worst, seed and injected uniforms are per request (ServeSession.submit)."""
+        return ServeSession(self, top_k, temperature, sync_every, force_eos_at)
 
     def infer(self, batch: Batch, top_k=-100, temperature=1.0, uniforms=None, seed=0, force_eos_at=None,
               sync_every=8, best_of=1, length_penalty=1.0, return_worst=False, continuous=False, on_row=None):
@@ -458,3 +477,103 @@ class Engine:
         a, f, am, nm = C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
         self._chk(self.lib.vx_last_stats(self.ctx, C.byref(a), C.byref(f), C.byref(am), C.byref(nm)))
         return dict(ar_steps=a.value, frames=f.value, ar_ms=am.value, nar_ms=nm.value)
+
+
+def _done_codes(codes, frames):
+    return np.ctypeslib.as_array(codes, shape=(frames, 8)).copy() if frames else np.zeros((0, 8), np.int64)
+
+
+class ServeSession:
+    """A serving session of one Engine (vx_serve_open .. vx_serve_close).  Not thread-safe: every call from the thread that owns the
+    engine (VALLE.serve wraps it in a worker thread).  While it is open, Engine.infer / nar / the step-level entries on the same
+    engine fail; vocos_decode / encodec_* stay available.  A request returns exactly what Engine.infer on it alone (batch 1, same
+    seed or draws, same best_of / length_penalty / return_worst) returns."""
+
+    def __init__(self, engine: Engine, top_k=-100, temperature=1.0, sync_every=8, force_eos_at=None):
+        self.engine = engine
+        self.lib = engine.lib
+        s, _ = Engine._sampling(1, top_k, temperature, None, 0, force_eos_at, sync_every)
+        s.length_penalty = 1.0
+        h = C.c_void_p()
+        engine._chk(self.lib.vx_serve_open(engine.ctx, C.byref(s), C.byref(h)))
+        self.h = h
+        self.rows = min(engine.max_batch, 32)           # decode rows of the session: the largest best_of it takes
+
+    @staticmethod
+    def check_request(best_of=1, uniforms=None, rows: Optional[int] = None):
+        """argument checks of one request, before any GPU work: best_of >= 1 (<= the session's decode rows), uniforms
+        (steps, best_of) or (steps,) for best_of 1.  Returns the uniforms as a C-contiguous float32 array (or None)."""
+        if isinstance(best_of, bool) or int(best_of) != best_of or int(best_of) < 1:
+            raise ValueError(f"best_of must be an integer >= 1, got {best_of!r}")
+        n = int(best_of)
+        if rows is not None and n > rows:
+            raise ValueError(f"best_of {n} exceeds the session's {rows} decode rows")
+        if uniforms is None:
+            return None
+        u = np.ascontiguousarray(uniforms, np.float32)
+        if u.ndim == 1 and n == 1:
+            u = u[:, None]
+        if u.ndim != 2 or u.shape[1] != n:
+            raise ValueError(f"uniforms must be (steps, best_of) = (steps, {n}), got {tuple(np.shape(uniforms))}")
+        return u
+
+    def submit(self, batch: Batch, requests: Sequence[dict]):
+        """enqueue batch.n requests (row i of `batch` with requests[i] = dict(best_of=1, seed=0, uniforms=None, length_penalty=1.0,
+        return_worst=False)); host copies only.  Returns their request ids."""
+        if len(requests) != batch.n:
+            raise ValueError(f"{len(requests)} requests for {batch.n} rows")
+        arr = (vx_request * batch.n)()
+        keep = []
+        for i, q in enumerate(requests):
+            u = self.check_request(q.get("best_of", 1), q.get("uniforms"), self.rows)
+            r = arr[i]
+            r.struct_size = C.sizeof(vx_request)
+            r.best_of = int(q.get("best_of", 1))
+            r.length_penalty = float(q.get("length_penalty", 1.0))
+            r.return_worst = int(bool(q.get("return_worst", False)))
+            r.seed = int(q.get("seed", 0)) & ((1 << 64) - 1)
+            if u is not None:
+                keep.append(u)
+                r.uniforms = _ptr(u, C.c_float)
+                r.uniforms_steps = u.shape[0]
+        ids = np.zeros(batch.n, np.int64)
+        self.engine._chk(self.lib.vx_serve_submit(self._handle(), C.byref(batch.c), arr, _ptr(ids, C.c_int64)))
+        return [int(i) for i in ids]
+
+    def run(self, max_steps: int = 0, on_done=None):
+        """vx_serve_run: admit, decode up to max_steps steps (<= 0: until nothing is decoding or waiting), deliver every request
+        that finished.  on_done(request id, codes (T, 8) int64) is called once per request; an exception it raises is re-raised
+        here once the call has returned (the other requests are still delivered).  Returns (requests decoding, requests waiting)."""
+        raised = []
+
+        def done(_user, rid, codes, frames):
+            if raised or on_done is None:
+                return
+            try:
+                on_done(int(rid), _done_codes(codes, frames))
+            except BaseException as e:      # ctypes would print and drop it: kept and re-raised after the call
+                raised.append(e)
+
+        cb = SERVE_DONE_FN(done) if on_done is not None else SERVE_DONE_FN()
+        live, waiting = C.c_int32(), C.c_int32()
+        self.engine._chk(self.lib.vx_serve_run(self._handle(), int(max_steps), cb, None, C.byref(live), C.byref(waiting)))
+        if raised:
+            raise raised[0]
+        return live.value, waiting.value
+
+    def _handle(self):
+        if not self.h:
+            raise RuntimeError("the serving session is closed")
+        return self.h
+
+    def close(self):
+        """vx_serve_close: drops what has not been delivered; the engine is usable for infer again"""
+        if self.h and getattr(self.engine, "ctx", None):
+            self.engine._chk(self.lib.vx_serve_close(self.h))
+        self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

@@ -3,6 +3,9 @@
 // utils/generation.py:148-150; every hot op is a hand-written gfx950 kernel from the sibling .hip files.
 #include "engine_ctx.h"
 
+#include <deque>
+#include <memory>
+
 namespace {
 // the message of a failed vx_create (no context to hang it on): per thread, contexts are created from several host threads
 // (bench.py --contexts) and vx_last_error(NULL) must not read a string another thread is assigning
@@ -382,6 +385,54 @@ int prefill_layers(vx_ctx* c, const PrefillPlan& p, const MetaBuilder& mb) {
 // compacted, in the buffer full_layer uses for the compacted residual stream: fxn in f16x2 mode, the QKV buffer in fp32 mode)
 const float* prefill_hsrc(const vx_ctx* c, const PrefillPlan& p) { return p.trim ? (p.trim_h2 ? c->fxn : c->fqkv) : c->fx; }
 
+// Decode geometry of a decode batch of nrows rows: context splits of dec_attn, chain choice (host state only; the first fill of a
+// decode batch sets it through ar_prefill, a serving session once for its nd free rows, serve_setup).  `identity`: the launch slot
+// order is the identity (slot == row).
+static void decode_geometry(vx_ctx* c, int nrows, bool identity) {
+  // enough (row, head, split) 8-wave workgroups to put >= 2 on every CU; one split (no combine launch) from 32 rows up
+  c->nsplit = std::max(1, std::min(16, 512 / (nrows * N_HEAD)));
+  // 5 .. 16 rows: ONE 8-wave workgroup per CU (256 / (rows x 16) splits, at least 2) -- round 6 sweep at 5 / 8 / 12 / 16 rows x contexts
+  // ~500 / ~1300 (profiles/r06_sb_sweep2.txt): 5 rows 6 -> 3 splits -3.5 %, 8 rows 4 -> 2 splits -3 % / -0.6 % of the AR phase, 12 and 16 rows
+  // stay at 2; one split (the fused out_proj) only pays from 17 rows up
+  if (nrows > SB_ROWS && nrows <= 16) c->nsplit = std::max(2, 256 / (nrows * N_HEAD));
+  // 8 .. 16 rows (round 6, profiles/r06_fuse_split_sweep.txt): out_proj folded into dec_attn WITH context splits -- the combine moves behind the
+  // head's W_o slice (decode.hip dec_attn_kernel<true, *, true>, dec_reduce_ln_split_kernel), two launches per layer fewer.  The fused
+  // kernel runs two rows per 16-wave workgroup: as many splits (<= 4) as keep 16 heads x row pairs x splits inside ONE round of the 256 CUs
+  // (8 rows: 4, 9 .. 10: 3, 11 .. 16: 2; AR phase -2.7 % at 8 rows / context ~1000, -7 % at 10 rows, -5.5 % at 12, -4.6 % at 16).  5 .. 7 rows:
+  // too few workgroups either way, the unfused chain stays (5 rows: 297 vs 299 ms, 6 rows: 302 vs 302).
+  c->split_fused = false;
+  if (c->fuse_out && c->fuse_split == 1 && nrows >= 8 && nrows <= 16) {
+    const int ns = std::min(4, 256 / (N_HEAD * ((nrows + 1) / 2)));
+    if (ns >= 2) { c->nsplit = ns; c->split_fused = true; }
+  }
+  if (c->att_nsplit_force > 0) {                                      // measurement switches (tools/gpu_call.sh sb_sweep, tools/fuse_split_sweep.sh)
+    c->nsplit = c->att_nsplit_force;
+    c->split_fused = c->fuse_out && c->fuse_split != 0 && nrows > SB_ROWS && c->nsplit >= 2 && c->nsplit <= 4;
+  }
+  // the small-batch chain compiles the split counts in (decode.hip): taken only for a combination that is instantiated.  Its fused
+  // attention relies on slot == row, i.e. on the identity launch order (<= SB_ROWS rows are never balanced; best_of: the beams of
+  // row i are decode rows i*beams + j in that order) -- passed by the caller (ar_prefill checks its slot order, it does not assume it
+  // from its `balance` rule)
+  c->sb_chain = false;
+  c->sb_qkv = false;
+  if (c->sb_fuse && nrows <= SB_ROWS && identity) {
+    const int ns = nrows <= 2 ? 16 : 8;
+    if (sb_chain_supported(SK_L2, SK_OUT, ns, nrows)) { c->nsplit = ns; c->sb_chain = true; }
+    // ... with norm1 + QKV inside the attention launch for the smallest batches (VX_SB_QKV=<max rows>; its split count is tunable)
+    if (c->sb_chain && nrows <= c->sb_qkv_rows) {
+      // the fused kernel holds one 8-wave workgroup per CU: 16 heads x rows x splits workgroups must fit the 256 CUs in ONE round,
+      // and every workgroup of a head re-reads the head's q slice through L2 -- few splits win (profiles/r04_sb_qkv_ab.log)
+      // one row: 16 splits = 256 workgroups (round 6 sweep, profiles/r06_sb_sweep.txt: equal to 8 at contexts ~400 / ~800, -2 % of the AR
+      // phase at ~1300 -- the context share of a workgroup halves while the q slice it re-reads through L2 stays)
+      const int fit[5] = {0, 16, 8, 4, 4};
+      const int ns2 = c->sb_qkv_nsplit > 0 ? c->sb_qkv_nsplit : fit[nrows];
+      // dec_attn_qkv_kernel addresses the KV arena and its partials by batch ROW and returns when slot_meta[slot].row != row
+      // (decode.hip): the launch order is the identity (`identity`, above)
+      if (sb_qkv_chain_supported(SK_L2, SK_OUT, ns2, nrows)) { c->nsplit = ns2; c->sb_qkv = true; }
+    }
+  }
+}
+
 // First fill of a decode batch: the prefill of caller rows r0 .. r0+nb-1 plus the decode state and geometry that only the first
 // fill sets up (slot order, context splits, chain choice, cur_batch).
 // beams > 1: best_of.  The reference repeats the prompt N times and runs N identical prefills (models/vallex.py:525-527); here
@@ -457,49 +508,9 @@ int ar_prefill(vx_ctx* c, const vx_batch* b, int r0, int nb, int beams = 1) {
   HIPCHK(hipMemcpyAsync(c->slot_of, mb.dev(o_slot), ib, hipMemcpyDeviceToDevice, c->stream));
   H2D(c->n_active, &nrows, sizeof(int));
   c->cur_batch = nrows;
-  // enough (row, head, split) 8-wave workgroups to put >= 2 on every CU; one split (no combine launch) from 32 rows up
-  c->nsplit = std::max(1, std::min(16, 512 / (nrows * N_HEAD)));
-  // 5 .. 16 rows: ONE 8-wave workgroup per CU (256 / (rows x 16) splits, at least 2) -- round 6 sweep at 5 / 8 / 12 / 16 rows x contexts
-  // ~500 / ~1300 (profiles/r06_sb_sweep2.txt): 5 rows 6 -> 3 splits -3.5 %, 8 rows 4 -> 2 splits -3 % / -0.6 % of the AR phase, 12 and 16 rows
-  // stay at 2; one split (the fused out_proj) only pays from 17 rows up
-  if (nrows > SB_ROWS && nrows <= 16) c->nsplit = std::max(2, 256 / (nrows * N_HEAD));
-  // 8 .. 16 rows (round 6, profiles/r06_fuse_split_sweep.txt): out_proj folded into dec_attn WITH context splits -- the combine moves behind the
-  // head's W_o slice (decode.hip dec_attn_kernel<true, *, true>, dec_reduce_ln_split_kernel), two launches per layer fewer.  The fused
-  // kernel runs two rows per 16-wave workgroup: as many splits (<= 4) as keep 16 heads x row pairs x splits inside ONE round of the 256 CUs
-  // (8 rows: 4, 9 .. 10: 3, 11 .. 16: 2; AR phase -2.7 % at 8 rows / context ~1000, -7 % at 10 rows, -5.5 % at 12, -4.6 % at 16).  5 .. 7 rows:
-  // too few workgroups either way, the unfused chain stays (5 rows: 297 vs 299 ms, 6 rows: 302 vs 302).
-  c->split_fused = false;
-  if (c->fuse_out && c->fuse_split == 1 && nrows >= 8 && nrows <= 16) {
-    const int ns = std::min(4, 256 / (N_HEAD * ((nrows + 1) / 2)));
-    if (ns >= 2) { c->nsplit = ns; c->split_fused = true; }
-  }
-  if (c->att_nsplit_force > 0) {                                      // measurement switches (tools/gpu_call.sh sb_sweep, tools/fuse_split_sweep.sh)
-    c->nsplit = c->att_nsplit_force;
-    c->split_fused = c->fuse_out && c->fuse_split != 0 && nrows > SB_ROWS && c->nsplit >= 2 && c->nsplit <= 4;
-  }
-  // the small-batch chain compiles the split counts in (decode.hip): taken only for a combination that is instantiated.  Its fused
-  // attention relies on slot == row, i.e. on the identity launch order (<= SB_ROWS rows are never balanced; best_of: the beams of
-  // row i are decode rows i*beams + j in that order) -- checked here, not assumed from `balance` above
   bool identity = true;
   for (int y = 0; y < nrows; ++y) identity = identity && st_ord[y] == y;
-  c->sb_chain = false;
-  c->sb_qkv = false;
-  if (c->sb_fuse && nrows <= SB_ROWS && identity) {
-    const int ns = nrows <= 2 ? 16 : 8;
-    if (sb_chain_supported(SK_L2, SK_OUT, ns, nrows)) { c->nsplit = ns; c->sb_chain = true; }
-    // ... with norm1 + QKV inside the attention launch for the smallest batches (VX_SB_QKV=<max rows>; its split count is tunable)
-    if (c->sb_chain && nrows <= c->sb_qkv_rows) {
-      // the fused kernel holds one 8-wave workgroup per CU: 16 heads x rows x splits workgroups must fit the 256 CUs in ONE round,
-      // and every workgroup of a head re-reads the head's q slice through L2 -- few splits win (profiles/r04_sb_qkv_ab.log)
-      // one row: 16 splits = 256 workgroups (round 6 sweep, profiles/r06_sb_sweep.txt: equal to 8 at contexts ~400 / ~800, -2 % of the AR
-      // phase at ~1300 -- the context share of a workgroup halves while the q slice it re-reads through L2 stays)
-      const int fit[5] = {0, 16, 8, 4, 4};
-      const int ns2 = c->sb_qkv_nsplit > 0 ? c->sb_qkv_nsplit : fit[nrows];
-      // dec_attn_qkv_kernel addresses the KV arena and its partials by batch ROW and returns when slot_meta[slot].row != row
-      // (decode.hip): the launch order is the identity (checked above)
-      if (sb_qkv_chain_supported(SK_L2, SK_OUT, ns2, nrows)) { c->nsplit = ns2; c->sb_qkv = true; }
-    }
-  }
+  decode_geometry(c, nrows, identity);
 
   if (int e = prefill_layers(c, p, mb)) return e;
   // last row of every sequence -> decode residual stream h[b]
@@ -791,6 +802,20 @@ int ar_generate(vx_ctx* c, const vx_batch* b, const vx_sampling* s, int r0, int 
     c->prof[1].bytes += (double)steps * ((double)c->NL * 12.0 * D_MODEL * D_MODEL + (double)AR_LOGITS * D_MODEL) * 4.0;
   }
   return VX_OK;
+}
+
+// best_of selection of one row's N beams (models/vallex.py:583-594): sum(logp) / len^length_penalty with len = torch.sum(y != EOS) =
+// BOS + prompt + frames; the first index wins ties; return_worst picks the lowest.  vx_infer and the serving session both call it.
+static int select_beam(const float* slp, const int* n_gen, int N, int Tp, float length_penalty, bool return_worst) {
+  int best = 0, worst = 0;
+  double bv = 0, wv = 0;
+  for (int j = 0; j < N; ++j) {
+    const double len = 1.0 + Tp + n_gen[j];
+    const double v = (double)(float)((float)slp[j] / powf((float)len, length_penalty));
+    if (j == 0 || v > bv) { bv = v; best = j; }
+    if (j == 0 || v < wv) { wv = v; worst = j; }
+  }
+  return return_worst ? worst : best;
 }
 
 // best_of: the sampler's seed of micro-batch k.  The counter-based sampler mixes (seed, decode row, step), so without this the beams
@@ -1208,6 +1233,330 @@ int infer_continuous(vx_ctx* c, const vx_batch* b, const vx_sampling* s, vx_row_
   return VX_OK;
 }
 
+// ---- serving session (vx_serve_*) ----------------------------------------------------------------------------------
+// A decode batch of nd = min(max_batch, 32) rows that outlives any single call.  Requests are submitted at any time (host copies
+// only); vx_serve_run admits them first come first served into free decode rows, decodes, harvests requests whose beams have all
+// stopped, selects one beam per request and runs the NAR stages in groups.  Geometry (slot order, context splits, chain) is fixed
+// at vx_serve_open for nd free rows (serve_setup), so the captured step graph never changes; every admission, the first included,
+// goes through serve_admit.  DESIGN.md section 10.
+struct ServeReq {
+  int64_t id = 0;
+  int N = 1;                                   // beams
+  float length_penalty = 1.f;
+  bool worst = false;
+  unsigned long long seed = 0;
+  int usteps = 0;                              // injected draws per beam (0: counter-based)
+  std::vector<float> u;                        // [N][usteps]
+  std::vector<int32_t> ids, lang, pc;          // text ids / language ids [S], prompt codes [Tp][8]
+  int S = 0, Tp = 0;
+  std::vector<int> rows;                       // decode row of every beam
+  std::vector<std::vector<int>> gen;           // first-codebook ids of every harvested beam (D2H targets: never reallocated)
+  std::vector<int> ng;                         // frames of every harvested beam
+  std::vector<float> slp;                      // sum(logp) of every harvested beam
+  int harvested = 0;
+};
+
+// requests gathered into one vx_batch (prefill / NAR of a request group)
+struct ReqBatch {
+  std::vector<int32_t> ids, lang, tl, pc, pl;
+  vx_batch b{};
+  explicit ReqBatch(const std::vector<ServeReq*>& rq) {
+    const int n = (int)rq.size();
+    int ts = 1, ps = 1;
+    for (const ServeReq* r : rq) { ts = std::max(ts, r->S); ps = std::max(ps, r->Tp); }
+    ids.assign((size_t)n * ts, 0); lang.assign((size_t)n * ts, 0); pc.assign((size_t)n * ps * N_Q, 0); tl.resize(n); pl.resize(n);
+    for (int i = 0; i < n; ++i) {
+      const ServeReq* r = rq[i];
+      std::copy(r->ids.begin(), r->ids.end(), ids.begin() + (size_t)i * ts);
+      std::copy(r->lang.begin(), r->lang.end(), lang.begin() + (size_t)i * ts);
+      std::copy(r->pc.begin(), r->pc.end(), pc.begin() + (size_t)i * ps * N_Q);
+      tl[i] = r->S; pl[i] = r->Tp;
+    }
+    b.struct_size = sizeof(vx_batch); b.batch = n;
+    b.text_ids = ids.data(); b.text_lang = lang.data(); b.text_stride = ts; b.text_lens = tl.data();
+    b.prompt_codes = pc.data(); b.prompt_stride = ps; b.prompt_lens = pl.data();
+  }
+};
+
+}  // namespace vxe
+
+struct vx_serve {
+  vx_ctx* c = nullptr;
+  vx_sampling s{};                             // session-wide: top_k, temperature, force_eos_at, sync_every
+  int nd = 0;
+  int64_t next_id = 0;
+  std::deque<std::unique_ptr<ServeReq>> waiting;
+  std::vector<std::unique_ptr<ServeReq>> live;     // admitted, some beam still decoding
+  std::vector<std::unique_ptr<ServeReq>> pend;     // every beam harvested, NAR stages pending (in the order they completed)
+  std::vector<ServeReq*> occ;                  // per decode row: its request (null: free)
+  std::vector<int> beam, done_by, act, ng, slot_of;
+  long steps = 0;                              // decode steps since vx_serve_open
+  SampleArgs sa{};
+  std::string sig;
+};
+
+namespace vxe {
+
+// nd free decode rows: identity slot order, every row inactive (slot record {d, 1, 0}), n_active = 0, and the geometry of nd rows
+static int serve_setup(vx_ctx* c, int nd) {
+  std::vector<int> zero(nd, 0), one(nd, 1), meta(4 * nd, 0), slot(nd);
+  for (int d = 0; d < nd; ++d) { meta[4 * d] = d; meta[4 * d + 1] = 1; slot[d] = d; }
+  MetaBuilder mb(c);
+  const long o_z = mb.add(zero), o_1 = mb.add(one), o_meta = mb.add(meta), o_slot = mb.add(slot);
+  if (int e = upload_meta(c)) return e;
+  const size_t ib = nd * sizeof(int);
+  HIPCHK(hipMemcpyAsync(c->cur_pos, mb.dev(o_z), ib, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->ctx_len, mb.dev(o_1), ib, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->n_gen, mb.dev(o_z), ib, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->cur_tok, mb.dev(o_z), ib, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->active, mb.dev(o_z), ib, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->text_len, mb.dev(o_1), ib, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->slot_meta, mb.dev(o_meta), 4 * ib, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->slot_of, mb.dev(o_slot), ib, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipMemsetAsync(c->n_active, 0, sizeof(int), c->stream));
+  c->cur_batch = nd;
+  c->h_L.assign(nd, 0);
+  decode_geometry(c, nd, true);
+  SYNC();                                      // the staged tables are consumed before the next MetaBuilder reuses imeta
+  return VX_OK;
+}
+
+// admission of requests rq (their beam rows assigned, rq[i]->rows) into free decode rows, up to and including their first sample.
+// Each request is prefilled once, into the arena slot of its first beam row; the fan-out (beams.hip, pairs only) copies its K / V to
+// the other beams' slots; every beam row gets its own admit_rows entry pointing at the request's prefill row, its own draws (keyed
+// on (request seed, beam) or the request's injected column) and a zero sum_logp.  The rows still decoding keep every piece of their
+// state, as in admit_rows.
+static int serve_admit(vx_serve* v, const std::vector<ServeReq*>& rq) {
+  vx_ctx* c = v->c;
+  const int k = (int)rq.size(), nd = v->nd;
+  ReqBatch rb(rq);
+  PrefillPlan p;
+  MetaBuilder mb(c);
+  if (int e = prefill_tables(c, &rb.b, 0, k, p, mb)) return e;
+  for (int& r : p.row_b) r = v->slot_of[rq[r]->rows[0]];
+  p.o_rb = mb.add(p.row_b);
+  std::vector<int> tab, adm(nd, 0), saved(nd, 0), pairs, staged, utab;
+  const int cap_steps = c->gen_stride + 1;         // draws a row can ever consume: one per generated frame + the terminating one
+  int max_steps = 1;
+  for (int i = 0; i < k; ++i) {
+    const ServeReq* r = rq[i];
+    if (p.seq_len[i] > c->Tmax) FAIL(VX_EINVAL, "request %lld: %d cached rows exceed the arena (%d)", (long long)r->id, p.seq_len[i], c->Tmax);
+    for (int j = 0; j < r->N; ++j) {
+      const int d = r->rows[j];
+      tab.insert(tab.end(), {d, r->Tp, p.seq_len[i], p.S_[i], p.hrow(i)});
+      adm[d] = 1;
+      if (j) pairs.insert(pairs.end(), {v->slot_of[r->rows[0]], v->slot_of[d], p.seq_len[i]});
+    }
+  }
+  // injected draws first (their offsets go into the draw table), as float bits in the int tables
+  std::vector<int> soff(k, -1);
+  for (int i = 0; i < k; ++i) {
+    const ServeReq* r = rq[i];
+    if (!r->usteps) continue;
+    soff[i] = (int)staged.size();
+    const int st = std::min(r->usteps, cap_steps);
+    for (int j = 0; j < r->N; ++j) {
+      const size_t o = staged.size();
+      staged.resize(o + st);
+      memcpy(&staged[o], &r->u[(size_t)j * r->usteps], st * sizeof(float));
+    }
+  }
+  const long o_st = staged.empty() ? 0 : mb.add(staged);
+  for (int i = 0; i < k; ++i) {
+    const ServeReq* r = rq[i];
+    const int st = r->usteps ? std::min(r->usteps, cap_steps) : cap_steps;
+    max_steps = std::max(max_steps, st);
+    for (int j = 0; j < r->N; ++j)
+      utab.insert(utab.end(), {r->rows[j], j, r->usteps ? (int)(o_st + soff[i] + (long)j * st) : -1, st, (int)(uint32_t)r->seed,
+                               (int)(uint32_t)(r->seed >> 32)});
+  }
+  const int nbeam = (int)tab.size() / 5;
+  if ((long)max_steps * nd > c->uniforms_cap) FAIL(VX_EINVAL, "too many uniforms (%d steps)", max_steps);
+  const long o_tab = mb.add(tab), o_adm = mb.add(adm), o_saved = mb.add(saved), o_ut = mb.add(utab),
+             o_fp = pairs.empty() ? 0 : mb.add(pairs);
+  if (int e = upload_meta(c)) return e;
+  launch_serve_uniforms(mb.dev(o_ut), nbeam, max_steps, reinterpret_cast<const float*>(c->imeta), c->d_uniforms, nd, c->sum_logp,
+                        c->stream);
+  if (int e = prefill_layers(c, p, mb)) return e;
+  const float* hsrc = prefill_hsrc(c, p);
+  if (!pairs.empty())
+    launch_beam_fanout(c->kc, c->vc, (long)((size_t)c->mbr * N_HEAD * c->Tmax * D_HEAD), c->NL, c->Tmax, mb.dev(o_fp),
+                       (int)pairs.size() / 3, hsrc, nullptr, c->dh, 0, c->stream);
+  launch_admit_rows(mb.dev(o_tab), nbeam, hsrc, c->dh2, c->cur_tok, c->cur_pos, c->ctx_len, c->n_gen, c->text_len, c->slot_meta,
+                    c->slot_of, c->stream);
+  launch_dec_reduce_ln_pack(nullptr, 0, D_MODEL, nullptr, c->dh2, nullptr, W(c, "ar_decoder.norm.weight"),
+                            W(c, "ar_decoder.norm.bias"), c->xp_att, nd, c->stream);
+  launch_skinny_gemm(c->pred_wp, c->xp_att, c->p_logits, PRED_NPAD, D_MODEL, SK_PRED, c->stream);
+  int* sv = c->imeta + o_saved;
+  launch_admit_mask(0, mb.dev(o_adm), sv, nd, c->active, c->slot_meta, c->slot_of, c->n_active, c->stream);
+  LAUNCH(launch_dec_sample(v->sa, c->stream));
+  launch_admit_mask(1, mb.dev(o_adm), sv, nd, c->active, c->slot_meta, c->slot_of, c->n_active, c->stream);
+  return launch_status(c);
+}
+
+// one admission round with the f16x2 range guard of infer_continuous: a raised flag re-runs the round (prefill, fan-out, first
+// sample) on the exact-fp32 kernels; it counts in vx_last_fallbacks and towards sticky mode
+static int serve_round(vx_serve* v, const std::vector<ServeReq*>& rq) {
+  vx_ctx* c = v->c;
+  const int nd = v->nd;
+  bool raised = false;
+  auto attempt = [&](bool read_flag) -> int {
+    if (int e = serve_admit(v, rq)) return e;
+    int flag = 0;
+    D2H(v->act.data(), c->active, nd * sizeof(int));
+    D2H(v->ng.data(), c->n_gen, nd * sizeof(int));
+    if (read_flag) D2H(&flag, c->range_flag, sizeof(int));
+    SYNC();
+    raised = flag != 0;
+    return VX_OK;
+  };
+  if (fb_direct(c, c->sticky_prefill_f32, c->sticky_prefill_age)) {
+    ++c->st_fb_prefill; ++c->fb_total;
+    if (int e = ensure_f32_buffers(c)) return e;
+    F32Scope f32(c);
+    if (int e = attempt(false)) return e;
+  } else {
+    if (int e = attempt(range_guarded(c))) return e;
+    fb_outcome(c, raised, c->fb_prefill_raises, c->sticky_prefill_f32, c->sticky_prefill_age);
+    if (raised) {
+      HIPCHK(hipMemsetAsync(c->range_flag, 0, sizeof(int), c->stream));
+      ++c->st_fb_prefill; ++c->fb_total;
+      if (int e = ensure_f32_buffers(c)) return e;
+      F32Scope f32(c);
+      if (int e = attempt(false)) return e;
+    }
+  }
+  const int first_cap = v->s.force_eos_at >= 0 ? std::min(c->gen_stride, v->s.force_eos_at) : c->gen_stride;
+  for (ServeReq* r : rq)
+    for (int j = 0; j < r->N; ++j) {
+      const int d = r->rows[j];
+      v->occ[d] = r; v->beam[d] = j; v->done_by[d] = (int)v->steps + std::min(first_cap, 16 * r->S);
+    }
+  return VX_OK;
+}
+
+// NAR stages of the first n pending requests (each reduced to its selected beam), then their codes to the caller
+static int serve_nar_group(vx_serve* v, int n, vx_serve_done_fn on_done, void* user) {
+  vx_ctx* c = v->c;
+  std::vector<std::unique_ptr<ServeReq>> grp;
+  for (int i = 0; i < n; ++i) grp.push_back(std::move(v->pend[i]));
+  v->pend.erase(v->pend.begin(), v->pend.begin() + n);
+  SYNC();                                            // the harvested gen rows and sums have arrived
+  std::vector<ServeReq*> rq(n);
+  std::vector<int> T(n), codes0((size_t)n * c->gen_stride, 0), oc;
+  for (int i = 0; i < n; ++i) {
+    ServeReq* r = rq[i] = grp[i].get();
+    const int pick = select_beam(r->slp.data(), r->ng.data(), r->N, r->Tp, r->length_penalty, r->worst);
+    T[i] = r->ng[pick];
+    std::copy(r->gen[pick].begin(), r->gen[pick].begin() + T[i], codes0.begin() + (size_t)i * c->gen_stride);
+  }
+  ReqBatch rb(rq);
+  long sumT = 0;
+  hipEvent_t e1 = c->ev_t[1], e2 = c->ev_t[2];
+  HIPCHK(hipEventRecord(e1, c->stream));
+  if (int e = nar_generate(c, &rb.b, 0, n, T, codes0.data(), c->gen_stride, oc, sumT)) return e;
+  HIPCHK(hipEventRecord(e2, c->stream));
+  HIPCHK(hipEventSynchronize(e2));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, e1, e2)); c->st_nar_ms += ms;
+  const bool forced = v->s.force_eos_at >= 0 && v->s.force_eos_at <= c->gen_stride;
+  long off = 0;
+  std::vector<int64_t> out;
+  for (int i = 0; i < n; ++i) {
+    c->st_frames += T[i];
+    if (T[i] >= c->gen_stride && c->gen_stride < 16 * rq[i]->S && !forced) ++c->st_truncated;
+    out.assign((size_t)std::max(1, T[i]) * N_Q, 0);
+    for (int t = 0; t < T[i]; ++t) {
+      int64_t* o = out.data() + (size_t)t * N_Q;
+      o[0] = codes0[(size_t)i * c->gen_stride + t];
+      for (int st = 0; st < N_Q - 1; ++st) o[st + 1] = oc[(size_t)st * sumT + off + t];
+    }
+    off += T[i];
+    if (on_done) on_done(user, rq[i]->id, out.data(), T[i]);
+  }
+  return VX_OK;
+}
+
+static int serve_run(vx_serve* v, int max_steps, vx_serve_done_fn on_done, void* user) {
+  vx_ctx* c = v->c;
+  const int nd = v->nd;
+  hipEvent_t e0 = c->ev_t[0], e1 = c->ev_t[1];
+  HIPCHK(hipEventRecord(e0, c->stream));
+  const long start = v->steps;
+  const int sync_every = v->s.sync_every > 0 ? v->s.sync_every : 8;
+  const int gs = (c->graph_multi && sync_every % GRAPH_STEPS == 0) ? GRAPH_STEPS : 1;
+  for (;;) {
+    // harvest: the beam rows that stopped hand their ids and sums to the host (delivered at the next sync) and free their rows
+    for (int d = 0; d < nd; ++d) {
+      ServeReq* r = v->occ[d];
+      if (!r || v->act[d]) continue;
+      const int j = v->beam[d];
+      r->ng[j] = v->ng[d];
+      r->gen[j].assign(std::max(1, v->ng[d]), 0);
+      if (v->ng[d]) D2H(r->gen[j].data(), c->gen + (size_t)d * c->gen_stride, v->ng[d] * sizeof(int));
+      D2H(&r->slp[j], c->sum_logp + d, sizeof(float));
+      v->occ[d] = nullptr;
+      if (++r->harvested == r->N) {
+        auto it = std::find_if(v->live.begin(), v->live.end(), [&](const std::unique_ptr<ServeReq>& q) { return q.get() == r; });
+        v->pend.push_back(std::move(*it));
+        v->live.erase(it);
+      }
+    }
+    // admission, first come first served: the head waits for best_of free rows, a later request does not overtake it
+    std::vector<int> freed;
+    for (int d = 0; d < nd; ++d) if (!v->occ[d]) freed.push_back(d);
+    std::vector<ServeReq*> rq;
+    size_t used = 0;
+    while (!v->waiting.empty() && (size_t)v->waiting.front()->N <= freed.size() - used) {
+      std::unique_ptr<ServeReq> r = std::move(v->waiting.front());
+      v->waiting.pop_front();
+      r->rows.assign(freed.begin() + used, freed.begin() + used + r->N);
+      used += r->N;
+      r->gen.assign(r->N, {}); r->ng.assign(r->N, 0); r->slp.assign(r->N, 0.f); r->harvested = 0;
+      rq.push_back(r.get());
+      v->live.push_back(std::move(r));
+    }
+    if (!rq.empty()) {
+      if (int e = serve_round(v, rq)) return e;
+      continue;                                      // an admitted beam may have stopped at its first sample
+    }
+    const bool live = std::any_of(v->occ.begin(), v->occ.end(), [](const ServeReq* r) { return r != nullptr; });
+    while ((int)v->pend.size() >= c->mbr)
+      if (int e = serve_nar_group(v, c->mbr, on_done, user)) return e;
+    if (!live || (max_steps > 0 && v->steps - start >= max_steps)) break;
+    // decode steps up to the next host poll, or up to the step by which a live row has stopped at the latest (its cap)
+    long soonest = (v->steps / sync_every + 1) * sync_every;
+    for (int d = 0; d < nd; ++d) if (v->occ[d]) soonest = std::min<long>(soonest, v->done_by[d]);
+    long target = std::max(soonest, v->steps + 1);
+    if (max_steps > 0) target = std::min(target, start + max_steps);
+    while (v->steps < target) {
+      const int n = (v->steps % gs == 0 && v->steps + gs <= target) ? gs : 1;
+      if (int e = ar_step_run(c, &v->sa, v->sig, n)) return e;
+      v->steps += n;
+    }
+    D2H(v->act.data(), c->active, nd * sizeof(int));
+    D2H(v->ng.data(), c->n_gen, nd * sizeof(int));
+    SYNC();
+  }
+  // every request harvested during this call goes through its NAR stages before the call returns
+  while (!v->pend.empty())
+    if (int e = serve_nar_group(v, std::min<int>(c->mbr, (int)v->pend.size()), on_done, user)) return e;
+  HIPCHK(hipEventRecord(e1, c->stream));
+  HIPCHK(hipEventSynchronize(e1));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+  c->st_ar_ms = ms - c->st_nar_ms;
+  c->st_steps = v->steps - start;
+  SYNC();                                            // beams harvested at the last poll of a request still decoding: delivered now
+  return VX_OK;
+}
+
+// entry points that overwrite the decode state refuse to run while a serving session owns it
+static int serve_busy(vx_ctx* c, const char* what) {
+  if (!c->serve) return VX_OK;
+  FAIL(VX_EINVAL, "%s: a serving session is open on this context (vx_serve_close it first)", what);
+}
+
 }  // namespace vxe
 
 // =================================================================================================================
@@ -1278,6 +1627,8 @@ int vx_create(int device_id, const vx_config* cfg, vx_ctx** out) {
 
 void vx_destroy(vx_ctx* c) {
   if (!c) return;
+  delete c->serve;                 // an open session goes with its context
+  c->serve = nullptr;
   (void)hipSetDevice(c->dev);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->graph_exec) (void)hipGraphExecDestroy(c->graph_exec);
@@ -1300,6 +1651,7 @@ int vx_synchronize(vx_ctx* c) {
 
 int vx_ar_prefill(vx_ctx* c, const vx_batch* b) {
   if (!c) return VX_EINVAL;
+  if (int e = serve_busy(c, "vx_ar_prefill")) return e;
   HIPCHK(hipSetDevice(c->dev));
   if (int e = check_batch(c, b, c->mbr)) return e;
   c->st_fb_prefill = c->st_fb_nar = 0;
@@ -1334,6 +1686,7 @@ int vx_ar_logits(vx_ctx* c, float* out) {
 
 int vx_ar_step(vx_ctx* c, const int32_t* tokens) {
   if (!c || !tokens) return VX_EINVAL;
+  if (int e = serve_busy(c, "vx_ar_step")) return e;
   if (c->cur_batch <= 0) FAIL(VX_ESTATE, "no prefill has run");
   HIPCHK(hipSetDevice(c->dev));
   H2D(c->force_tok, tokens, c->cur_batch * sizeof(int));
@@ -1348,6 +1701,7 @@ int vx_ar_step(vx_ctx* c, const int32_t* tokens) {
 int vx_nar(vx_ctx* c, const vx_batch* b, const int32_t* codes0, int32_t codes0_stride, const int32_t* lens,
            int64_t* out_codes, int32_t out_stride) {
   if (!c || !codes0 || !lens || !out_codes) return VX_EINVAL;
+  if (int e = serve_busy(c, "vx_nar")) return e;
   HIPCHK(hipSetDevice(c->dev));
   if (int e = check_batch(c, b, c->mbr)) return e;
   std::vector<int> T(lens, lens + b->batch);
@@ -1377,6 +1731,7 @@ int vx_nar(vx_ctx* c, const vx_batch* b, const int32_t* codes0, int32_t codes0_s
 int vx_infer(vx_ctx* c, const vx_batch* b, const vx_sampling* s, int64_t* out_codes, int32_t out_stride,
              int32_t* out_lens) {
   if (!c || !s || !out_codes || !out_lens) return VX_EINVAL;
+  if (int e = serve_busy(c, "vx_infer")) return e;
   HIPCHK(hipSetDevice(c->dev));
   if (s->struct_size != sizeof(vx_sampling))
     FAIL(VX_EINVAL, "vx_sampling.struct_size is %u, this library expects %zu (ABI version %d)", s->struct_size, sizeof(vx_sampling), VX_ABI_VERSION);
@@ -1407,17 +1762,8 @@ int vx_infer(vx_ctx* c, const vx_batch* b, const vx_sampling* s, int64_t* out_co
       D2H(slp.data(), c->sum_logp, slp.size() * sizeof(float)); SYNC();
       std::vector<int> T(nb), codes0((size_t)nb * c->gen_stride);
       for (int i = 0; i < nb; ++i) {
-        const int Tp = b->prompt_lens[r0 + i];
-        int best = 0, worst = 0;
-        double bv = 0, wv = 0;
-        for (int j = 0; j < N; ++j) {
-          const int d = i * N + j;
-          const double len = 1.0 + Tp + n_gen[d];                      // torch.sum(y != EOS): BOS + prompt + frames
-          const double v = (double)(float)((float)slp[d] / powf((float)len, s->length_penalty));
-          if (j == 0 || v > bv) { bv = v; best = j; }
-          if (j == 0 || v < wv) { wv = v; worst = j; }
-        }
-        const int pick = i * N + (s->return_worst ? worst : best);
+        const int pick = i * N + select_beam(&slp[(size_t)i * N], &n_gen[(size_t)i * N], N, b->prompt_lens[r0 + i], s->length_penalty,
+                                             s->return_worst != 0);
         T[i] = n_gen[pick];
         if (T[i] > out_stride) FAIL(VX_EINVAL, "out_stride %d too small for %d frames", out_stride, T[i]);
         std::copy_n(gen.begin() + (size_t)pick * c->gen_stride, c->gen_stride, codes0.begin() + (size_t)i * c->gen_stride);
@@ -1478,6 +1824,7 @@ int vx_infer(vx_ctx* c, const vx_batch* b, const vx_sampling* s, int64_t* out_co
 int vx_infer_continuous(vx_ctx* c, const vx_batch* b, const vx_sampling* s, vx_row_done_fn on_row, void* user, int64_t* out_codes,
                         int32_t out_stride, int32_t* out_lens) {
   if (!c || !s || !out_codes || !out_lens) return VX_EINVAL;
+  if (int e = serve_busy(c, "vx_infer_continuous")) return e;
   HIPCHK(hipSetDevice(c->dev));
   if (s->struct_size != sizeof(vx_sampling))
     FAIL(VX_EINVAL, "vx_sampling.struct_size is %u, this library expects %zu (ABI version %d)", s->struct_size, sizeof(vx_sampling), VX_ABI_VERSION);
@@ -1488,6 +1835,108 @@ int vx_infer_continuous(vx_ctx* c, const vx_batch* b, const vx_sampling* s, vx_r
   c->st_steps = 0; c->st_frames = 0; c->st_ar_ms = 0; c->st_nar_ms = 0; c->st_truncated = 0;
   c->st_fb_prefill = c->st_fb_nar = 0;
   return infer_continuous(c, b, s, on_row, user, out_codes, out_stride, out_lens);
+}
+
+int vx_serve_open(vx_ctx* c, const vx_sampling* s, vx_serve** out) {
+  if (!c || !s || !out) return VX_EINVAL;
+  HIPCHK(hipSetDevice(c->dev));
+  if (!c->finalized) FAIL(VX_ESTATE, "weights not finalized");
+  if (s->struct_size != sizeof(vx_sampling))
+    FAIL(VX_EINVAL, "vx_sampling.struct_size is %u, this library expects %zu (ABI version %d)", s->struct_size, sizeof(vx_sampling), VX_ABI_VERSION);
+  if (c->serve) FAIL(VX_EINVAL, "a serving session is already open on this context");
+  if (!(s->temperature > 0.f)) FAIL(VX_EINVAL, "temperature must be > 0");
+  if (s->best_of > 1 || s->seed != 0 || s->uniforms || (s->length_penalty != 0.f && s->length_penalty != 1.f) || s->return_worst)
+    FAIL(VX_EINVAL, "vx_serve_open: best_of, seed, uniforms, length_penalty and return_worst are per request (vx_request)");
+  auto* v = new vx_serve();
+  v->c = c;
+  v->s = *s;
+  v->s.best_of = 1; v->s.length_penalty = 1.f;
+  v->nd = c->mbr;
+  v->occ.assign(v->nd, nullptr);
+  v->beam.assign(v->nd, 0); v->done_by.assign(v->nd, 0); v->act.assign(v->nd, 0); v->ng.assign(v->nd, 0);
+  v->slot_of.resize(v->nd);
+  for (int d = 0; d < v->nd; ++d) v->slot_of[d] = d;
+  if (int e = serve_setup(c, v->nd)) { delete v; return e; }
+  v->sa = make_sample_args(c, &v->s, 1, nullptr);
+  v->sa.uniforms = c->d_uniforms;                  // every beam row draws from its own column, injected or counter-based
+  v->sa.sum_logp = c->sum_logp;                    // always on: best_of is per request
+  char sig[160];
+  snprintf(sig, sizeof sig, "b%d ns%d c%d%d%d k%d t%a u%d f%d l%d", v->nd, c->nsplit, (int)c->sb_chain, (int)c->sb_qkv, (int)c->split_fused,
+           v->sa.top_k, v->sa.temperature, 1, v->sa.force_eos_at, 1);
+  v->sig = sig;
+  c->serve = v;
+  *out = v;
+  return VX_OK;
+}
+
+int vx_serve_submit(vx_serve* v, const vx_batch* b, const vx_request* req, int64_t* ids_out) {
+  if (!v || !req) return VX_EINVAL;
+  vx_ctx* c = v->c;
+  if (int e = check_batch(c, b, 0x7fffffff)) return e;
+  const int first_cap = v->s.force_eos_at >= 0 ? std::min(c->gen_stride, v->s.force_eos_at) : c->gen_stride;
+  for (int i = 0; i < b->batch; ++i) {
+    const vx_request& q = req[i];
+    if (q.struct_size != sizeof(vx_request))
+      FAIL(VX_EINVAL, "vx_request.struct_size is %u, this library expects %zu (ABI version %d)", q.struct_size, sizeof(vx_request), VX_ABI_VERSION);
+    const int N = std::max(1, q.best_of);
+    if (N > v->nd) FAIL(VX_EINVAL, "request %d: best_of %d exceeds the session's %d decode rows", i, N, v->nd);
+    if (b->text_lens[i] + 1 + b->prompt_lens[i] > c->Tmax) FAIL(VX_EINVAL, "request %d: the prompt does not fit the arena", i);
+    if (q.uniforms) {
+      // every draw the request can consume: one per generated frame + the terminating one
+      const int need = std::min(first_cap, 16 * b->text_lens[i]) + 1;
+      if (q.uniforms_steps < need) FAIL(VX_EINVAL, "request %d: %d uniforms steps, it can draw %d", i, q.uniforms_steps, need);
+    }
+  }
+  std::vector<std::unique_ptr<ServeReq>> add;
+  for (int i = 0; i < b->batch; ++i) {
+    const vx_request& q = req[i];
+    auto r = std::make_unique<ServeReq>();
+    r->N = std::max(1, q.best_of);
+    r->length_penalty = q.length_penalty;
+    r->worst = q.return_worst != 0;
+    r->seed = q.seed;
+    r->S = b->text_lens[i]; r->Tp = b->prompt_lens[i];
+    r->ids.assign(b->text_ids + (long)i * b->text_stride, b->text_ids + (long)i * b->text_stride + r->S);
+    r->lang.assign(b->text_lang + (long)i * b->text_stride, b->text_lang + (long)i * b->text_stride + r->S);
+    r->pc.assign(b->prompt_codes + (long)i * b->prompt_stride * N_Q, b->prompt_codes + ((long)i * b->prompt_stride + r->Tp) * N_Q);
+    if (q.uniforms) {       // [uniforms_steps][N] -> [N][steps], only the draws that can be consumed
+      r->usteps = std::min(q.uniforms_steps, c->gen_stride + 1);
+      r->u.resize((size_t)r->N * r->usteps);
+      for (int j = 0; j < r->N; ++j)
+        for (int t = 0; t < r->usteps; ++t) r->u[(size_t)j * r->usteps + t] = q.uniforms[(long)t * r->N + j];
+    }
+    add.push_back(std::move(r));
+  }
+  for (int i = 0; i < b->batch; ++i) {
+    add[i]->id = v->next_id++;
+    if (ids_out) ids_out[i] = add[i]->id;
+    v->waiting.push_back(std::move(add[i]));
+  }
+  return VX_OK;
+}
+
+int vx_serve_run(vx_serve* v, int32_t max_steps, vx_serve_done_fn on_done, void* user, int32_t* live_requests,
+                 int32_t* waiting_requests) {
+  if (!v) return VX_EINVAL;
+  vx_ctx* c = v->c;
+  HIPCHK(hipSetDevice(c->dev));
+  c->st_steps = 0; c->st_frames = 0; c->st_ar_ms = 0; c->st_nar_ms = 0; c->st_truncated = 0;
+  c->st_fb_prefill = c->st_fb_nar = 0;
+  if (int e = serve_run(v, max_steps, on_done, user)) return e;
+  if (live_requests) *live_requests = (int32_t)v->live.size();
+  if (waiting_requests) *waiting_requests = (int32_t)v->waiting.size();
+  return VX_OK;
+}
+
+int vx_serve_close(vx_serve* v) {
+  if (!v) return VX_EINVAL;
+  vx_ctx* c = v->c;
+  HIPCHK(hipSetDevice(c->dev));
+  SYNC();                                           // no copy in flight may target a request that is about to go
+  c->serve = nullptr;
+  delete v;
+  // the next vx_infer sets its own geometry (ar_prefill); nothing of the session's decode state is read again
+  return VX_OK;
 }
 
 int64_t vx_read_tap(vx_ctx* c, const char* name, float* dst, int64_t max_floats) {

@@ -1,6 +1,7 @@
 // Internal declarations shared by the engine's translation units (engine.hip: context, AR / NAR drivers and the hot-path ABI;
 // weights.hip: ingest of the reference state-dict; vocoders.hip: Vocos head, EnCodec decoder / encoder drivers;
-// beams.hip: the best_of fan-out; bench_harness.hip: the measurement entries of include/vallex_hip_dev.h).  Not part of the public C ABI.
+// beams.hip: the best_of fan-out; admit.hip / serve.hip: admission kernels of the continuous schedule / the serving session;
+// bench_harness.hip: the measurement entries of include/vallex_hip_dev.h).  Not part of the public C ABI.
 #pragma once
 
 #include <math.h>
@@ -147,6 +148,7 @@ struct vx_ctx {
   int nsplit = 1;
   int att_nsplit_force = 0;        // VX_ATT_NSPLIT=n: context splits of dec_attn on the general chain (0 = 512 / (rows x 16) workgroups rule)
   std::vector<int> h_L;            // prefill lengths of the current micro-batch
+  vx_serve* serve = nullptr;       // the open serving session (vx_serve_open); it owns the decode state while it is open
 
   // graph
   hipGraphExec_t graph_exec = nullptr, graph_exec_n = nullptr;   // one decode step / GRAPH_STEPS steps per launch
@@ -314,6 +316,11 @@ void launch_admit_mask(int phase, const int* admitted, int* saved, int nrows, in
 //   staged != null: staged[i * steps + t] (injected uniforms, column r of the caller's [steps][batch]); else the counter-based
 //   draw of caller row r, splitmix64(splitmix64(splitmix64(seed) + r) + t) >> 40 x 2^-24 (dec_sample_kernel's formula)
 void launch_admit_uniforms(const int* pairs, int n, const float* staged, int steps, unsigned long long seed, float* u, int ncols,
+                           hipStream_t s);
+
+// serving session (serve.hip): draws + sum_logp reset of admitted beam rows.  tab [n][6] = {decode row d, beam j, offset of the
+// request's staged draws of beam j in `staged` (-1: counter-based, keyed on (seed, j)), draws to write, seed low, seed high word}
+void launch_serve_uniforms(const int* tab, int n, int max_steps, const float* staged, float* u, int ncols, float* sum_logp,
                            hipStream_t s);
 
 struct F32Scope {            // the full-sequence path on the exact-fp32 kernels for the lifetime of the object

@@ -12,12 +12,14 @@ Differences a caller can observe (all documented in DESIGN.md):
 from __future__ import annotations
 
 import math
+import threading
+from concurrent.futures import Future
 from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
 
 from .. import macros
-from .._capi import ARITH, Batch, Engine
+from .._capi import ARITH, VX_EINVAL, Batch, Engine, ServeSession, VallexHipError
 
 try:  # torch is plumbing only: the reference API hands tensors in and out
     import torch
@@ -280,9 +282,149 @@ class VALLE:
                                  length_penalty=length_penalty, return_worst=return_worst, continuous=continuous,
                                  on_row=on_row)
 
+    def serve(self, top_k: int = -100, temperature: float = 1.0, sync_every: int = 8, force_eos_at=None, max_steps: int = 32,
+              post=None, **kw) -> "Server":
+        """A threaded serving front end (include/vallex_hip.h vx_serve_*): `Server.submit(row, best_of=..., seed=...)` may be called
+        from any thread at any time and returns a Future of the row's (T, 8) int64 codes -- exactly what `inference_batch([row],
+        best_of=..., seed=...)` returns.  top_k / temperature / sync_every / force_eos_at apply to the whole session; best_of,
+        length_penalty, return_worst, seed and uniforms are per request (Server.submit).  `max_steps`: decode steps per
+        vx_serve_run, i.e. how long a new submission waits at most for the worker to pick it up.  `post(codes list) -> results`
+        (optional) runs on the worker thread for every group of completed requests (AudioServer: Vocos)."""
+        if kw:
+            bad = sorted(kw)
+            raise ValueError(f"{', '.join(bad)}: per request in a serving session (Server.submit), not session-wide"
+                             if set(bad) <= {"best_of", "length_penalty", "return_worst", "seed", "uniforms"}
+                             else f"unexpected arguments {bad}")
+        return Server(self, top_k=top_k, temperature=temperature, sync_every=sync_every, force_eos_at=force_eos_at,
+                      max_steps=max_steps, post=post)
+
     def make_batch(self, rows: Sequence[dict]) -> Batch:
         texts = [_np(r["text"], np.int32).reshape(-1) for r in rows]
         prompts = [_np(r["prompt"], np.int32).reshape(-1, 8) for r in rows]
         langs = [self._lang_row(len(t), int(r["enroll"]), r["prompt_language"], r["text_language"])
                  for t, r in zip(texts, rows)]
         return Batch(texts, langs, prompts)
+
+
+class Server:
+    """Threaded front end of a serving session (VALLE.serve).  One worker thread owns every C call on the model's engine: it opens the
+    session, moves queued submissions into it between two vx_serve_run calls, runs the session while anything is decoding or
+    waiting, and resolves every request's Future as soon as its NAR stages are done.  submit() is thread-safe and does the host
+    work of a row (ids, languages, prompt) on the submitting thread.  close() (or leaving a `with` block) finishes everything that
+    was submitted, then closes the session.  A C error fails every outstanding Future with the VallexHipError and closes the session;
+    a request the library refuses (VX_EINVAL at submit: oversized row, too few uniforms) fails its own Future only."""
+
+    def __init__(self, model: "VALLE", top_k=-100, temperature=1.0, sync_every=8, force_eos_at=None, max_steps=32, post=None):
+        self._model = model
+        self._opts = dict(top_k=top_k, temperature=temperature, sync_every=sync_every, force_eos_at=force_eos_at)
+        self._max_steps = int(max_steps)
+        self._post = post
+        self._cv = threading.Condition()
+        self._queue: List[tuple] = []           # (Batch, request dict, Future) not yet handed to the library
+        self._futs: Dict[int, Future] = {}     # request id -> Future (worker thread only)
+        self._closing = False
+        self._error: Optional[BaseException] = None
+        engine = model.engine                   # built here: a weight error surfaces on the caller's thread
+        self.rows = min(engine.max_batch, 32)
+        self._ready = threading.Event()
+        self._thread = threading.Thread(target=self._loop, name="vallex-serve", daemon=True)
+        self._thread.start()
+        self._ready.wait()
+        if self._error is not None:
+            raise self._error
+
+    def submit(self, row: dict, best_of: int = 1, seed: Optional[int] = None, uniforms=None, length_penalty: float = 1.0,
+               return_worst: bool = False) -> Future:
+        """row: the dict of inference_batch (text, prompt, enroll, prompt_language, text_language).  Returns a Future of the
+        (T, 8) int64 codes (or of post's result).  seed=None draws a fresh seed, like inference."""
+        u = ServeSession.check_request(best_of, uniforms, self.rows)
+        if seed is None:
+            seed = fresh_seed()
+        batch = self._model.make_batch([row])
+        req = dict(best_of=int(best_of), seed=int(seed), uniforms=u, length_penalty=float(length_penalty),
+                   return_worst=bool(return_worst))
+        fut: Future = Future()
+        with self._cv:
+            if self._closing or self._error is not None:
+                raise RuntimeError("the server is closed" if self._error is None else f"the server failed: {self._error}")
+            self._queue.append((batch, req, fut))
+            self._cv.notify()
+        return fut
+
+    def close(self):
+        """finish every submitted request, then close the session (idempotent)"""
+        with self._cv:
+            self._closing = True
+            self._cv.notify()
+        if self._thread.is_alive() and threading.current_thread() is not self._thread:
+            self._thread.join()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    # ---- worker thread ----
+    def _loop(self):
+        try:
+            session = self._model.engine.serve(**self._opts)
+        except BaseException as e:
+            self._error = e
+            self._ready.set()
+            return
+        self._ready.set()
+        try:
+            while True:
+                with self._cv:
+                    while not self._queue and not self._futs and not self._closing:
+                        self._cv.wait()
+                    items, self._queue = self._queue, []
+                    if not items and not self._futs and self._closing:
+                        break
+                for batch, req, fut in items:
+                    if not fut.set_running_or_notify_cancel():
+                        continue
+                    try:
+                        rid = session.submit(batch, [req])[0]
+                    except VallexHipError as e:
+                        if e.code != VX_EINVAL:
+                            raise
+                        fut.set_exception(e)             # refused: this request only, the session goes on
+                        continue
+                    self._futs[rid] = fut
+                if self._futs:
+                    done = []
+                    session.run(self._max_steps, lambda rid, codes: done.append((rid, codes)))
+                    self._deliver(done)
+        except BaseException as e:
+            self._fail(e)
+        finally:
+            try:
+                session.close()
+            except BaseException:
+                pass
+
+    def _deliver(self, done):
+        if not done:
+            return
+        futs = [self._futs.pop(rid) for rid, _ in done]
+        codes = [c for _, c in done]
+        try:
+            res = self._post(codes) if self._post is not None else codes
+        except BaseException as e:
+            for f in futs:
+                f.set_exception(e)
+            return
+        for f, r in zip(futs, res):
+            f.set_result(r)
+
+    def _fail(self, e: BaseException):
+        with self._cv:
+            self._error = e
+            self._closing = True
+            items, self._queue = self._queue, []
+        for f in list(self._futs.values()) + [it[2] for it in items]:
+            if not f.done():
+                f.set_exception(e)
+        self._futs.clear()

@@ -237,32 +237,65 @@ def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent
     prompts = list(prompts) if isinstance(prompts, (list, tuple)) else [prompts] * n
     langs_in = list(language) if isinstance(language, (list, tuple)) else [language] * n
     text_languages = list(text_languages) if text_languages is not None else [None] * n
-    rows = []
-    for text, prompt, lang_in, tl in zip(texts, prompts, langs_in, text_languages):
-        if isinstance(text, str):
-            text = text.replace("\n", "").strip(" ")
-        lang_in = _detect(text, lang_in)
-        if prompt is not None:
-            audio_prompts, text_prompts, lang_pr = _load_prompt(prompt)
-        else:
-            audio_prompts = np.zeros([1, 0, NUM_QUANTIZERS], np.int32)
-            text_prompts = np.zeros([1, 0], np.int32)
-            lang_pr = None
-        lang_token = lang2token[lang_in]
-        lang = token2lang[lang_token]
-        phone_tokens, langs = _tokenize(text, lang_token)
-        if tl is not None:
-            langs = list(tl)
-        if lang_pr is None:
-            lang_pr = lang if lang != "mix" else "en"
-        lang_eff = lang if accent == "no-accent" else token2lang[langdropdown2token[accent]]
-        text_language = (langs if langs is not None else lang_eff) if accent == "no-accent" else lang_eff
-        if text_language == "mix":
-            raise KeyError("mix")
-        rows.append(dict(text=np.concatenate([text_prompts.reshape(-1), phone_tokens]), prompt=audio_prompts[0],
-                         enroll=text_prompts.shape[-1], prompt_language=lang_pr, text_language=text_language))
+    rows = [_utterance_row(text, prompt, lang_in, accent, tl)
+            for text, prompt, lang_in, tl in zip(texts, prompts, langs_in, text_languages)]
     codes = model.inference_batch(rows, top_k=-100, temperature=1, **kw)
     return model.engine.vocos_decode(codes, 2)
+
+
+def _utterance_row(text, prompt, lang_in, accent, tl=None) -> dict:
+    """the inference_batch row of one utterance of generate_audio_batch / AudioServer (front-end work on the calling thread)"""
+    if isinstance(text, str):
+        text = text.replace("\n", "").strip(" ")
+    lang_in = _detect(text, lang_in)
+    if prompt is not None:
+        audio_prompts, text_prompts, lang_pr = _load_prompt(prompt)
+    else:
+        audio_prompts = np.zeros([1, 0, NUM_QUANTIZERS], np.int32)
+        text_prompts = np.zeros([1, 0], np.int32)
+        lang_pr = None
+    lang_token = lang2token[lang_in]
+    lang = token2lang[lang_token]
+    phone_tokens, langs = _tokenize(text, lang_token)
+    if tl is not None:
+        langs = list(tl)
+    if lang_pr is None:
+        lang_pr = lang if lang != "mix" else "en"
+    lang_eff = lang if accent == "no-accent" else token2lang[langdropdown2token[accent]]
+    text_language = (langs if langs is not None else lang_eff) if accent == "no-accent" else lang_eff
+    if text_language == "mix":
+        raise KeyError("mix")
+    return dict(text=np.concatenate([text_prompts.reshape(-1), phone_tokens]), prompt=audio_prompts[0],
+                enroll=text_prompts.shape[-1], prompt_language=lang_pr, text_language=text_language)
+
+
+class AudioServer:
+    """Audio-level counterpart of `generate_audio` / `generate_audio_batch` on a serving session (VALLE.serve): `submit` may be
+    called from any thread at any time -- a UI can hand in its best_of=5 calls (launch-ui.py) concurrently -- and returns a
+    Future of the float32 waveform.  Front-end work (tokenizer, prompt lookup, language detection) runs on the submitting thread;
+    the codes of every group of completed requests go through Vocos on the server's worker thread.  Utterance i equals
+    `generate_audio_batch([text], [prompt], language, accent, best_of=..., seed=...)[0]`.  `**serve_kw` goes to VALLE.serve
+    (sync_every, force_eos_at, max_steps)."""
+
+    def __init__(self, **serve_kw):
+        if model is None or vocos is None:
+            raise RuntimeError("call preload_models() first")
+        self._server = model.serve(top_k=-100, temperature=1.0, post=lambda codes: model.engine.vocos_decode(codes, 2), **serve_kw)
+
+    def submit(self, text, prompt=None, language="auto", accent="no-accent", best_of=1, seed=None, uniforms=None,
+               length_penalty=1.0, return_worst=False, text_language=None):
+        row = _utterance_row(text, prompt, language, accent, text_language)
+        return self._server.submit(row, best_of=best_of, seed=seed, uniforms=uniforms, length_penalty=length_penalty,
+                                   return_worst=return_worst)
+
+    def close(self):
+        self._server.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def generate_audio_from_long_text(text, prompt=None, language="auto", accent="no-accent", mode="sliding-window", **kw):
