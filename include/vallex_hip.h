@@ -146,22 +146,33 @@ int vx_infer_continuous(vx_ctx* ctx, const vx_batch* b, const vx_sampling* s, vx
 /* Serving session (additive: VX_ABI_VERSION stays 6).  vx_infer and vx_infer_continuous take a closed batch; a session takes
  * requests at any time and admits each into the running decode batch as soon as enough decode rows are free.  Contract: a request
  * returns exactly what a batch-1 vx_infer call on it returns (same seed or same draws, same best_of / length_penalty /
- * return_worst), whatever else is in the session.
- *   - vx_serve_open reads the session-wide fields of vx_sampling only: top_k, temperature, force_eos_at, sync_every.  best_of (<= 1),
+ * return_worst, same top_k / temperature / force_eos_at), whatever else is in the session.
+ *   - Per request: best_of, length_penalty, return_worst, seed or injected uniforms (vx_request), and top_k, temperature and
+ *     force_eos_at (vx_request_sampling, vx_serve_submit_ex).  Session-wide: sync_every only.  The session samples every decode row
+ *     with its own request's top_k / temperature / force_eos_at; vx_serve_open's values are the defaults of vx_serve_submit.
+ *   - vx_serve_open reads the session-wide fields of vx_sampling only: top_k, temperature, force_eos_at (the defaults), sync_every.  best_of (<= 1),
  *     seed (0), uniforms (NULL), length_penalty (0 or 1) and return_worst (0) must keep their defaults: they are per request.  The
  *     decode batch is nd = min(max_batch, 32) rows, all free.  One session per context: while it is open, vx_infer,
  *     vx_infer_continuous, vx_ar_prefill, vx_ar_step and vx_nar return VX_EINVAL (they would overwrite the decode state);
  *     vx_vocos_decode and vx_encodec_* stay allowed.
  *   - vx_serve_submit copies everything it needs (the caller's buffers may be freed on return), does no GPU work and writes
  *     increasing request ids.  Every row is checked as vx_infer checks it, plus best_of <= nd and, with injected uniforms,
- *     uniforms_steps >= min(16 x text length, max_new, force_eos_at) + 1.  On any failure nothing of the call is enqueued.
+ *     uniforms_steps >= min(16 x text length, max_new, the request's force_eos_at) + 1.  On any failure nothing of the call is
+ *     enqueued.  vx_serve_submit_ex takes one vx_request_sampling per request as well (smp NULL: the session's values, exactly
+ *     vx_serve_submit); it checks struct_size, temperature > 0 and finite, force_eos_at >= -1.
  *   - vx_serve_run admits waiting requests first come first served: the head request waits until best_of decode rows are free, a
  *     later request does not overtake it.  It runs up to max_steps decode steps (<= 0: until no request is decoding or waiting), with
  *     host polls every sync_every steps and at the step where a row reaches its cap; requests whose beams have all stopped go through
  *     the NAR stages in groups of up to 32, and before it returns every request that finished during the call has been delivered:
  *     on_done (may be NULL) is called once per request on the calling thread, codes [frames][8] valid during the callback only; the
  *     callback must not call into the same context.  live / waiting (may be NULL): requests decoding / not admitted yet.
- *     vx_last_stats, vx_last_truncated and vx_last_fallbacks describe the last vx_serve_run.
+ *     vx_last_stats, vx_last_truncated and vx_last_fallbacks describe the last vx_serve_run; vx_last_truncated judges every request
+ *     by its own force_eos_at.
+ *   - vx_serve_cancel, between two vx_serve_run calls, drops a request; state (may be NULL) = 0: unknown id, already delivered or
+ *     already cancelled (not an error); 1: it was waiting and is removed; 2: it was decoding (some of its beams may have stopped
+ *     already): its beam rows stop before the next decode step and are free for the next admission.  A cancelled request never
+ *     reaches on_done, and cancelling never changes what another request returns.  Called from inside vx_serve_run (on_done) it
+ *     returns VX_EINVAL and changes nothing.
  *   - vx_serve_close drops waiting requests and requests still decoding; the context is usable for vx_infer again.  vx_destroy closes
  *     an open session.
  *   - Beams.  A request with best_of = N is prefilled once and decoded as N beams on N free decode rows (any slots).  It is harvested
@@ -189,6 +200,16 @@ int vx_serve_submit(vx_serve* srv, const vx_batch* rows, const vx_request* req, 
 int vx_serve_run(vx_serve* srv, int32_t max_steps, vx_serve_done_fn on_done, void* user, int32_t* live_requests,
                  int32_t* waiting_requests);
 int vx_serve_close(vx_serve* srv);
+/* per-request topk_sampling arguments (models/vallex.py:836-853) of a serving session */
+typedef struct vx_request_sampling {
+  uint32_t struct_size;         /* = sizeof(vx_request_sampling) */
+  int32_t top_k;                /* as vx_sampling.top_k */
+  float temperature;            /* > 0, finite */
+  int32_t force_eos_at;         /* as vx_sampling.force_eos_at: -1 off, n >= 0: the (n+1)-th sample is EOS (at most n frames) */
+} vx_request_sampling;
+int vx_serve_submit_ex(vx_serve* srv, const vx_batch* rows, const vx_request* req,
+                       const vx_request_sampling* smp /* [rows->batch] or NULL */, int64_t* ids_out);
+int vx_serve_cancel(vx_serve* srv, int64_t request_id, int32_t* state /* may be NULL */);
 
 /* replaces: vocos.codes_to_features + vocos.decode(features, bandwidth_id), utils/generation.py:148-150.
  * codes [batch][codes_stride][8] int64, lens [batch] frames; audio [batch][audio_stride] fp32, 320*len samples each. */

@@ -13,7 +13,12 @@ return the same ids; the tool checks that.
 Both legs are warmed up once (graph capture), then they alternate for --reps rounds.  Prints one JSON object: per leg the median
 requests/s (K / (last completion - first arrival)), mean and p95 latency from arrival to codes, AR steps, AR / NAR ms and the
 fraction of beam rows live per decode step (5 x frames / (steps x 32): every beam of a request runs to the same cap).
-   python tools/serve_bench.py [--requests 24] [--gap-ms 60] [--reps 2] [--out profiles/r09_serve.json]"""
+--cancel-frac F adds a third leg, session_cancel: a seeded share F of the requests are cancel candidates, and each candidate that
+is still undelivered at the first point between two vx_serve_run calls lying --cancel-after-ms after its arrival is cancelled
+(vx_serve_cancel).  Which candidates that catches depends on wall-clock timing, so every repeat records how many it cancelled
+("cancelled"), and ids are compared only for requests delivered in both runs.  The JSON then also compares the latency of the
+requests that are not candidates with and without the cancellations ("cancel").
+   python tools/serve_bench.py [--requests 24] [--gap-ms 60] [--reps 2] [--cancel-frac 0.25] [--out profiles/r09_serve.json]"""
 import argparse
 import json
 import os
@@ -53,6 +58,8 @@ def main():
     ap.add_argument("--run-steps", type=int, default=8)
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--cancel-frac", type=float, default=0.0)
+    ap.add_argument("--cancel-after-ms", type=float, default=100.0)
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -69,8 +76,11 @@ def main():
     gaps = np.random.default_rng(2026).exponential(args.gap_ms / 1000.0, size=K)
     arrive = np.concatenate([[0.0], np.cumsum(gaps[1:])])
     eng = m.engine
+    n_cancel = int(round(args.cancel_frac * K))
+    to_cancel = set(np.random.default_rng(7).choice(K, size=n_cancel, replace=False).tolist()) if n_cancel else set()
+    keep = [i for i in range(K) if i not in to_cancel]
 
-    def session():
+    def session(cancel=frozenset()):
         done_t, codes = [None] * K, [None] * K
         st = dict(ar_steps=0, ar_ms=0.0, nar_ms=0.0, frames=0)
         with eng.serve(top_k=-100, temperature=1.0, sync_every=8) as sess:
@@ -82,9 +92,13 @@ def main():
                 done_t[i] = time.perf_counter() - t0
                 codes[i] = c
 
-            live = 0
+            live, i2rid, cancelled = 0, {}, set()
             while nxt < K or live:
                 now = time.perf_counter() - t0
+                for i in sorted(cancel - cancelled):
+                    if i in i2rid and done_t[i] is None and now - arrive[i] >= args.cancel_after_ms / 1000.0:
+                        sess.cancel(i2rid[i])
+                        cancelled.add(i)
                 if nxt < K and arrive[nxt] > now and not live:
                     time.sleep(arrive[nxt] - now)
                     now = time.perf_counter() - t0
@@ -94,6 +108,7 @@ def main():
                 if nxt > k0:
                     ids = sess.submit(m.make_batch(rows[k0:nxt]), [dict(best_of=N, uniforms=us[i]) for i in range(k0, nxt)])
                     rid2i.update({rid: i for rid, i in zip(ids, range(k0, nxt))})
+                    i2rid.update({i: rid for rid, i in zip(ids, range(k0, nxt))})
                 live, waiting = sess.run(args.run_steps, on_done)
                 live += waiting
                 s = eng.last_stats()
@@ -125,27 +140,46 @@ def main():
         return done_t, codes, st
 
     legs = {"session": session, "batched": batched}
+    if to_cancel:
+        legs["session_cancel"] = lambda: session(frozenset(to_cancel))
     ref = {k: f()[1] for k, f in legs.items()}                       # warm-up: graph capture of both legs
     ids_equal = all(a.shape == b.shape and np.array_equal(a, b) for a, b in zip(ref["session"], ref["batched"]))
-    res = {k: dict(req_per_s=[], lat_mean_ms=[], lat_p95_ms=[], ar_steps=[], ar_ms=[], nar_ms=[], live_frac=[]) for k in legs}
+    if to_cancel:       # the requests that were not cancelled return what they return without the cancellations
+        ids_equal = ids_equal and all(np.array_equal(ref["session_cancel"][i], ref["session"][i]) for i in keep)
+        ids_equal = ids_equal and all(np.array_equal(a, b) for a, b in zip(ref["session_cancel"], ref["session"]) if a is not None)
+    res = {k: dict(req_per_s=[], lat_mean_ms=[], lat_p95_ms=[], ar_steps=[], ar_ms=[], nar_ms=[], live_frac=[], kept_lat_mean_ms=[],
+                   kept_lat_p95_ms=[], cancelled=[]) for k in legs}
     for _ in range(args.reps):
         for k, f in legs.items():
             done_t, codes, st = f()
-            ids_equal = ids_equal and all(np.array_equal(a, b) for a, b in zip(codes, ref[k]))
-            lat = (np.array(done_t) - arrive) * 1000.0
+            ids_equal = ids_equal and all(np.array_equal(a, b) for a, b in zip(codes, ref[k]) if a is not None and b is not None)
+            got = [i for i in range(K) if done_t[i] is not None]
+            lat = (np.array([done_t[i] for i in got]) - arrive[got]) * 1000.0
+            kl = (np.array([done_t[i] for i in keep]) - arrive[keep]) * 1000.0
             r = res[k]
-            r["req_per_s"].append(K / (max(done_t) - arrive[0]))
+            r["req_per_s"].append(len(got) / (max(done_t[i] for i in got) - arrive[0]))
             r["lat_mean_ms"].append(float(lat.mean()))
             r["lat_p95_ms"].append(float(np.percentile(lat, 95)))
+            r["kept_lat_mean_ms"].append(float(kl.mean()))
+            r["kept_lat_p95_ms"].append(float(np.percentile(kl, 95)))
+            r["cancelled"].append(K - len(got))
             r["ar_steps"].append(st["ar_steps"]); r["ar_ms"].append(st["ar_ms"]); r["nar_ms"].append(st["nar_ms"])
             r["live_frac"].append(N * st["frames"] / max(1, st["ar_steps"] * MBR))
     out = dict(tool="tools/serve_bench.py", device=torch.cuda.get_device_name(0), layers=12, requests=K, best_of=N,
                gap_ms=args.gap_ms, arrival_span_s=float(arrive[-1]), text_len=[args.s_lo, args.s_hi], run_steps=args.run_steps,
                reps=args.reps, frames_per_request=[int(len(o)) for o in ref["session"]], ids_equal=bool(ids_equal),
-               legs={k: {m_: round(float(statistics.median(v)), 3) for m_, v in r.items()} for k, r in res.items()})
+               legs={k: {m_: round(float(statistics.median(v)), 3) for m_, v in r.items()} for k, r in res.items()},
+               spread={k: {m_: [round(float(min(v)), 3), round(float(max(v)), 3)] for m_, v in r.items()} for k, r in res.items()})
     s_, b_ = out["legs"]["session"], out["legs"]["batched"]
     out["session_over_batched"] = dict(req_per_s=round(s_["req_per_s"] / b_["req_per_s"], 3),
                                        lat_mean=round(s_["lat_mean_ms"] / b_["lat_mean_ms"], 3))
+    if to_cancel:
+        c_ = out["legs"]["session_cancel"]
+        out["cancel"] = dict(frac=args.cancel_frac, after_ms=args.cancel_after_ms, candidates=sorted(to_cancel),
+                             cancelled_per_rep=res["session_cancel"]["cancelled"],
+                             kept_lat_mean_ms=[s_["kept_lat_mean_ms"], c_["kept_lat_mean_ms"]],
+                             kept_lat_p95_ms=[s_["kept_lat_p95_ms"], c_["kept_lat_p95_ms"]],
+                             note="[without cancellation, with cancellation], latency of the requests that are not cancelled")
     line = json.dumps(out)
     print(line)
     if args.out:

@@ -62,6 +62,11 @@ class vx_request(C.Structure):
                 ("seed", C.c_uint64), ("uniforms", C.POINTER(C.c_float)), ("uniforms_steps", C.c_int32)]
 
 
+class vx_request_sampling(C.Structure):
+    """per-request topk_sampling arguments of a serving session (vx_serve_submit_ex)"""
+    _fields_ = [("struct_size", C.c_uint32), ("top_k", C.c_int32), ("temperature", C.c_float), ("force_eos_at", C.c_int32)]
+
+
 # every symbol include/vallex_hip.h declares (tests/test_abi.py checks the library exports exactly these)
 ABI_VERSION = 6       # VX_ABI_VERSION of include/vallex_hip.h this binding was written against
 
@@ -69,7 +74,7 @@ SYMBOLS = ["vx_abi_version", "vx_create", "vx_destroy", "vx_last_error", "vx_syn
            "vx_infer", "vx_vocos_decode", "vx_encodec_decode", "vx_encodec_encode", "vx_ar_prefill", "vx_ar_logits", "vx_ar_step",
            "vx_nar", "vx_read_tap", "vx_last_stats", "vx_last_truncated", "vx_last_fallbacks", "vx_fallback_state",
            "vx_fallback_reset", "vx_arith_mode", "vx_infer_continuous", "vx_serve_open", "vx_serve_submit", "vx_serve_run",
-           "vx_serve_close"]
+           "vx_serve_close", "vx_serve_submit_ex", "vx_serve_cancel"]
 # ... and include/vallex_hip_dev.h: measurement / kernel development, never called by the mirrors of the reference API
 DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kernel", "vx_bench_gemm", "vx_bench_attn",
                "vx_bench_gemm_clock", "vx_bench_gemm_epilogue"]
@@ -121,6 +126,8 @@ def load_library() -> C.CDLL:
     lib.vx_serve_submit.argtypes = [C.c_void_p, P(vx_batch), P(vx_request), P(C.c_int64)]
     lib.vx_serve_run.argtypes = [C.c_void_p, C.c_int32, SERVE_DONE_FN, C.c_void_p, P(C.c_int32), P(C.c_int32)]
     lib.vx_serve_close.argtypes = [C.c_void_p]
+    lib.vx_serve_submit_ex.argtypes = [C.c_void_p, P(vx_batch), P(vx_request), P(vx_request_sampling), P(C.c_int64)]
+    lib.vx_serve_cancel.argtypes = [C.c_void_p, C.c_int64, P(C.c_int32)]
     lib.vx_vocos_decode.argtypes = [ctx, P(C.c_int64), C.c_int32, P(C.c_int32), C.c_int32, C.c_int32, P(C.c_float),
                                     C.c_int64]
     lib.vx_encodec_decode.argtypes = [ctx, P(C.c_int64), C.c_int32, P(C.c_int32), C.c_int32, P(C.c_float), C.c_int64]
@@ -267,8 +274,9 @@ class Engine:
 
     def serve(self, top_k=-100, temperature=1.0, sync_every=8, force_eos_at=None) -> "ServeSession":
         """open a serving session on this context (vx_serve_open): requests are submitted at any time and join the running decode
-        batch as soon as enough decode rows are free.  top_k, temperature, sync_every and force_eos_at apply to the whole session;
-        best_of, length_penalty, return_worst, seed and injected uniforms are per request (ServeSession.submit)."""
+        batch as soon as enough decode rows are free.  sync_every applies to the whole session; top_k, temperature and force_eos_at
+        given here are the defaults of a request that does not set its own; best_of, length_penalty, return_worst, seed, injected
+        uniforms, top_k, temperature and force_eos_at are per request (ServeSession.submit)."""
         return ServeSession(self, top_k, temperature, sync_every, force_eos_at)
 
     def infer(self, batch: Batch, top_k=-100, temperature=1.0, uniforms=None, seed=0, force_eos_at=None,
@@ -487,27 +495,44 @@ class ServeSession:
     """A serving session of one Engine (vx_serve_open .. vx_serve_close).  Not thread-safe: every call from the thread that owns the
     engine (VALLE.serve wraps it in a worker thread).  While it is open, Engine.infer / nar / the step-level entries on the same
     engine fail; vocos_decode / encodec_* stay available.  A request returns exactly what Engine.infer on it alone (batch 1, same
-    seed or draws, same best_of / length_penalty / return_worst) returns."""
+    seed or draws, same best_of / length_penalty / return_worst, same top_k / temperature / force_eos_at) returns."""
+
+    CANCEL_STATES = {0: None, 1: "waiting", 2: "decoding"}      # vx_serve_cancel's state
 
     def __init__(self, engine: Engine, top_k=-100, temperature=1.0, sync_every=8, force_eos_at=None):
         self.engine = engine
         self.lib = engine.lib
         s, _ = Engine._sampling(1, top_k, temperature, None, 0, force_eos_at, sync_every)
         s.length_penalty = 1.0
+        self.defaults = dict(top_k=s.top_k, temperature=s.temperature, force_eos_at=s.force_eos_at)   # as the library holds them
         h = C.c_void_p()
         engine._chk(self.lib.vx_serve_open(engine.ctx, C.byref(s), C.byref(h)))
         self.h = h
         self.rows = min(engine.max_batch, 32)           # decode rows of the session: the largest best_of it takes
 
     @staticmethod
-    def check_request(best_of=1, uniforms=None, rows: Optional[int] = None):
+    def check_request(best_of=1, uniforms=None, rows: Optional[int] = None, top_k=None, temperature=None, force_eos_at=None,
+                      text_len: Optional[int] = None, max_new: Optional[int] = None):
         """argument checks of one request, before any GPU work: best_of >= 1 (<= the session's decode rows), uniforms
-        (steps, best_of) or (steps,) for best_of 1.  Returns the uniforms as a C-contiguous float32 array (or None)."""
+        (steps, best_of) or (steps,) for best_of 1; top_k an integer, temperature > 0 and finite, force_eos_at an integer >= -1 (each
+        None: the session's value).  With text_len (and max_new), uniforms must also cover every draw the request can take,
+        min(16 x text_len, max_new, force_eos_at) + 1 steps: a standalone pre-check for callers that want it early --
+        submit() and Server.submit() do not pass text_len, the library checks the draws at vx_serve_submit(_ex) (VX_EINVAL, which
+        Server turns into a failed Future of that request only).  Returns the uniforms as a C-contiguous float32 array (or None)."""
         if isinstance(best_of, bool) or int(best_of) != best_of or int(best_of) < 1:
             raise ValueError(f"best_of must be an integer >= 1, got {best_of!r}")
         n = int(best_of)
         if rows is not None and n > rows:
             raise ValueError(f"best_of {n} exceeds the session's {rows} decode rows")
+        if top_k is not None and (isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer))):
+            raise ValueError(f"top_k must be an integer, got {top_k!r}")
+        if temperature is not None:
+            t = float(temperature)
+            if not (t > 0.0) or not np.isfinite(t) or t > float(np.finfo(np.float32).max):
+                raise ValueError(f"temperature must be > 0 and finite, got {temperature!r}")
+        if force_eos_at is not None:
+            if isinstance(force_eos_at, bool) or not isinstance(force_eos_at, (int, np.integer)) or int(force_eos_at) < -1:
+                raise ValueError(f"force_eos_at must be an integer >= -1 (or None), got {force_eos_at!r}")
         if uniforms is None:
             return None
         u = np.ascontiguousarray(uniforms, np.float32)
@@ -515,17 +540,37 @@ class ServeSession:
             u = u[:, None]
         if u.ndim != 2 or u.shape[1] != n:
             raise ValueError(f"uniforms must be (steps, best_of) = (steps, {n}), got {tuple(np.shape(uniforms))}")
+        if text_len is not None:
+            cap = 16 * int(text_len)
+            if max_new is not None:
+                cap = min(cap, int(max_new))
+            if force_eos_at is not None and int(force_eos_at) >= 0:
+                cap = min(cap, int(force_eos_at))
+            if u.shape[0] < cap + 1:
+                raise ValueError(f"uniforms has {u.shape[0]} steps, the request can draw {cap + 1} "
+                                 "(min(16 x text length, max_new, force_eos_at) + 1)")
         return u
 
     def submit(self, batch: Batch, requests: Sequence[dict]):
         """enqueue batch.n requests (row i of `batch` with requests[i] = dict(best_of=1, seed=0, uniforms=None, length_penalty=1.0,
-        return_worst=False)); host copies only.  Returns their request ids."""
+        return_worst=False, top_k=None, temperature=None, force_eos_at=None)); host copies only.  top_k / temperature /
+        force_eos_at None: the session's value; when any request of the call sets one, the call goes through vx_serve_submit_ex.
+        Returns their request ids."""
         if len(requests) != batch.n:
             raise ValueError(f"{len(requests)} requests for {batch.n} rows")
         arr = (vx_request * batch.n)()
         keep = []
+        per = any(q.get(k) is not None for q in requests for k in ("top_k", "temperature", "force_eos_at"))
+        smp = (vx_request_sampling * batch.n)() if per else None
         for i, q in enumerate(requests):
-            u = self.check_request(q.get("best_of", 1), q.get("uniforms"), self.rows)
+            u = self.check_request(q.get("best_of", 1), q.get("uniforms"), self.rows, q.get("top_k"), q.get("temperature"),
+                                   q.get("force_eos_at"))
+            if per:
+                m = smp[i]
+                m.struct_size = C.sizeof(vx_request_sampling)
+                m.top_k = int(q["top_k"]) if q.get("top_k") is not None else self.defaults["top_k"]
+                m.temperature = float(q["temperature"]) if q.get("temperature") is not None else self.defaults["temperature"]
+                m.force_eos_at = int(q["force_eos_at"]) if q.get("force_eos_at") is not None else self.defaults["force_eos_at"]
             r = arr[i]
             r.struct_size = C.sizeof(vx_request)
             r.best_of = int(q.get("best_of", 1))
@@ -537,8 +582,19 @@ class ServeSession:
                 r.uniforms = _ptr(u, C.c_float)
                 r.uniforms_steps = u.shape[0]
         ids = np.zeros(batch.n, np.int64)
-        self.engine._chk(self.lib.vx_serve_submit(self._handle(), C.byref(batch.c), arr, _ptr(ids, C.c_int64)))
+        if per:
+            self.engine._chk(self.lib.vx_serve_submit_ex(self._handle(), C.byref(batch.c), arr, smp, _ptr(ids, C.c_int64)))
+        else:
+            self.engine._chk(self.lib.vx_serve_submit(self._handle(), C.byref(batch.c), arr, _ptr(ids, C.c_int64)))
         return [int(i) for i in ids]
+
+    def cancel(self, rid: int):
+        """vx_serve_cancel, between two run() calls: "waiting" (removed before admission), "decoding" (its decode rows stop before
+        the next step and go to the next admission) or None (unknown, already delivered or already cancelled).  A cancelled request
+        is never passed to on_done.  Called from inside an on_done callback it raises VallexHipError (VX_EINVAL)."""
+        st = C.c_int32()
+        self.engine._chk(self.lib.vx_serve_cancel(self._handle(), int(rid), C.byref(st)))
+        return self.CANCEL_STATES[st.value]
 
     def run(self, max_steps: int = 0, on_done=None):
         """vx_serve_run: admit, decode up to max_steps steps (<= 0: until nothing is decoding or waiting), deliver every request

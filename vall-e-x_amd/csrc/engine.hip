@@ -557,13 +557,13 @@ SampleArgs make_sample_args(vx_ctx* c, const vx_sampling* s, int commit, float* 
 }
 
 // ---- one cached decode step (models/vallex.py:552-571 with kv_cache set) --------------------------------------
-void ar_step_launches(vx_ctx* c, const SampleArgs* sa) {
+void ar_step_launches(vx_ctx* c, const SampleArgs* sa, const ServeSampleArgs* rsa) {
   const int nb = c->cur_batch, NL = c->NL;
   hipStream_t st = c->stream;
   const size_t cache_layer = (size_t)c->mbr * N_HEAD * c->Tmax * D_HEAD;
   // sampling mode: the previous dec_sample already embedded the token and applied norm1 of layer 0; the teacher-forced
-  // mode (sa == null, vx_ar_step) has to do it here
-  if (!sa)
+  // mode (sa == null, rsa == null: vx_ar_step) has to do it here
+  if (!sa && !rsa)
     launch_dec_embed_ln_pack(c->cur_tok, c->cur_pos, W(c, "ar_audio_embedding.word_embeddings.weight"),
                              W(c, "ar_audio_position.alpha"), c->pe, c->dh, c->ar[0].n1_w, c->ar[0].n1_b, c->xp, nb, st);
   if (c->sb_chain) {
@@ -615,7 +615,8 @@ void ar_step_launches(vx_ctx* c, const SampleArgs* sa) {
       LAUNCH(launch_skinny_gemm_sb_ln(c->pred_wp, c->p_logits, PRED_NPAD, SK_PRED, c->p_o, SK_L2, c->ar[NL - 1].l2_b, hr, nullptr,
                                W(c, "ar_decoder.norm.weight"), W(c, "ar_decoder.norm.bias"), nb, st));
     }
-    if (sa) LAUNCH(launch_dec_sample(*sa, st));
+    if (rsa) LAUNCH(launch_serve_sample(*rsa, st));
+    else if (sa) LAUNCH(launch_dec_sample(*sa, st));
     return;
   }
   for (int l = 0; l < NL; ++l) {
@@ -648,7 +649,8 @@ void ar_step_launches(vx_ctx* c, const SampleArgs* sa) {
     launch_dec_reduce_ln_pack(c->p_o, SK_L2, D_MODEL, L.l2_b, c->dh, c->dh, ng, nbp, c->xp, nb, st);
   }
   { ProfScope ps(c, 1); launch_skinny_gemm(c->pred_wp, c->xp, c->p_logits, PRED_NPAD, D_MODEL, SK_PRED, st, true); }
-  if (sa) LAUNCH(launch_dec_sample(*sa, st));
+  if (rsa) LAUNCH(launch_serve_sample(*rsa, st));
+  else if (sa) LAUNCH(launch_dec_sample(*sa, st));
 }
 
 // the decode kernels compile these split counts in (decode.hip); retuning one without instantiating it must not reach a GPU
@@ -669,9 +671,9 @@ int launch_status(vx_ctx* c) {
 // dec_sample launch), which a multi-step graph pays once per GRAPH_STEPS steps.  All step state (positions, lengths, flags, the
 // sampler's counters) lives on the device, so a replay is position independent.
 constexpr int GRAPH_STEPS = 4;
-int ar_step_run(vx_ctx* c, const SampleArgs* sa, const std::string& sig, int nsteps = 1) {
-  if (!c->cfg.use_graph || c->prof_on == 1 || !sa) {
-    for (int i = 0; i < nsteps; ++i) ar_step_launches(c, sa);
+int ar_step_run(vx_ctx* c, const SampleArgs* sa, const std::string& sig, int nsteps = 1, const ServeSampleArgs* rsa = nullptr) {
+  if (!c->cfg.use_graph || c->prof_on == 1 || (!sa && !rsa)) {
+    for (int i = 0; i < nsteps; ++i) ar_step_launches(c, sa, rsa);
     HIPCHK(hipGetLastError());
     return launch_status(c);
   }
@@ -684,7 +686,7 @@ int ar_step_run(vx_ctx* c, const SampleArgs* sa, const std::string& sig, int nst
   if (!ge) {
     hipGraph_t g = nullptr;
     HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    for (int i = 0; i < nsteps; ++i) ar_step_launches(c, sa);
+    for (int i = 0; i < nsteps; ++i) ar_step_launches(c, sa, rsa);
     HIPCHK(hipStreamEndCapture(c->stream, &g));
     if (int e = launch_status(c)) { (void)hipGraphDestroy(g); return e; }      // an incomplete step must never be replayed
     HIPCHK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
@@ -1246,6 +1248,9 @@ struct ServeReq {
   bool worst = false;
   unsigned long long seed = 0;
   int usteps = 0;                              // injected draws per beam (0: counter-based)
+  int top_k = 1;                               // topk_sampling arguments of this request (vx_request_sampling, or the session's)
+  float temperature = 1.f;
+  int force_eos_at = -1;
   std::vector<float> u;                        // [N][usteps]
   std::vector<int32_t> ids, lang, pc;          // text ids / language ids [S], prompt codes [Tp][8]
   int S = 0, Tp = 0;
@@ -1254,6 +1259,8 @@ struct ServeReq {
   std::vector<int> ng;                         // frames of every harvested beam
   std::vector<float> slp;                      // sum(logp) of every harvested beam
   int harvested = 0;
+  // the step count at which the sampler has stopped every beam at the latest: min(16 S, gen_stride, force_eos_at)
+  int cap(int gen_stride) const { return std::min(force_eos_at >= 0 ? std::min(gen_stride, force_eos_at) : gen_stride, 16 * S); }
 };
 
 // requests gathered into one vx_batch (prefill / NAR of a request group)
@@ -1291,8 +1298,9 @@ struct vx_serve {
   std::vector<ServeReq*> occ;                  // per decode row: its request (null: free)
   std::vector<int> beam, done_by, act, ng, slot_of;
   long steps = 0;                              // decode steps since vx_serve_open
-  SampleArgs sa{};
+  ServeSampleArgs rsa{};                       // the per-row sampler of every step and admission (serve_sample.hip)
   std::string sig;
+  bool running = false;                        // inside vx_serve_run (on_done): vx_serve_cancel refuses
 };
 
 namespace vxe {
@@ -1368,7 +1376,7 @@ static int serve_admit(vx_serve* v, const std::vector<ServeReq*>& rq) {
     max_steps = std::max(max_steps, st);
     for (int j = 0; j < r->N; ++j)
       utab.insert(utab.end(), {r->rows[j], j, r->usteps ? (int)(o_st + soff[i] + (long)j * st) : -1, st, (int)(uint32_t)r->seed,
-                               (int)(uint32_t)(r->seed >> 32)});
+                               (int)(uint32_t)(r->seed >> 32), r->top_k, __builtin_bit_cast(int, r->temperature), r->force_eos_at});
   }
   const int nbeam = (int)tab.size() / 5;
   if ((long)max_steps * nd > c->uniforms_cap) FAIL(VX_EINVAL, "too many uniforms (%d steps)", max_steps);
@@ -1376,7 +1384,7 @@ static int serve_admit(vx_serve* v, const std::vector<ServeReq*>& rq) {
              o_fp = pairs.empty() ? 0 : mb.add(pairs);
   if (int e = upload_meta(c)) return e;
   launch_serve_uniforms(mb.dev(o_ut), nbeam, max_steps, reinterpret_cast<const float*>(c->imeta), c->d_uniforms, nd, c->sum_logp,
-                        c->stream);
+                        c->row_smp, c->stream);
   if (int e = prefill_layers(c, p, mb)) return e;
   const float* hsrc = prefill_hsrc(c, p);
   if (!pairs.empty())
@@ -1389,7 +1397,7 @@ static int serve_admit(vx_serve* v, const std::vector<ServeReq*>& rq) {
   launch_skinny_gemm(c->pred_wp, c->xp_att, c->p_logits, PRED_NPAD, D_MODEL, SK_PRED, c->stream);
   int* sv = c->imeta + o_saved;
   launch_admit_mask(0, mb.dev(o_adm), sv, nd, c->active, c->slot_meta, c->slot_of, c->n_active, c->stream);
-  LAUNCH(launch_dec_sample(v->sa, c->stream));
+  LAUNCH(launch_serve_sample(v->rsa, c->stream));
   launch_admit_mask(1, mb.dev(o_adm), sv, nd, c->active, c->slot_meta, c->slot_of, c->n_active, c->stream);
   return launch_status(c);
 }
@@ -1426,11 +1434,10 @@ static int serve_round(vx_serve* v, const std::vector<ServeReq*>& rq) {
       if (int e = attempt(false)) return e;
     }
   }
-  const int first_cap = v->s.force_eos_at >= 0 ? std::min(c->gen_stride, v->s.force_eos_at) : c->gen_stride;
   for (ServeReq* r : rq)
     for (int j = 0; j < r->N; ++j) {
       const int d = r->rows[j];
-      v->occ[d] = r; v->beam[d] = j; v->done_by[d] = (int)v->steps + std::min(first_cap, 16 * r->S);
+      v->occ[d] = r; v->beam[d] = j; v->done_by[d] = (int)v->steps + r->cap(c->gen_stride);
     }
   return VX_OK;
 }
@@ -1459,11 +1466,11 @@ static int serve_nar_group(vx_serve* v, int n, vx_serve_done_fn on_done, void* u
   HIPCHK(hipEventSynchronize(e2));
   float ms = 0;
   HIPCHK(hipEventElapsedTime(&ms, e1, e2)); c->st_nar_ms += ms;
-  const bool forced = v->s.force_eos_at >= 0 && v->s.force_eos_at <= c->gen_stride;
   long off = 0;
   std::vector<int64_t> out;
   for (int i = 0; i < n; ++i) {
     c->st_frames += T[i];
+    const bool forced = rq[i]->force_eos_at >= 0 && rq[i]->force_eos_at <= c->gen_stride;     // the request's own cap
     if (T[i] >= c->gen_stride && c->gen_stride < 16 * rq[i]->S && !forced) ++c->st_truncated;
     out.assign((size_t)std::max(1, T[i]) * N_Q, 0);
     for (int t = 0; t < T[i]; ++t) {
@@ -1531,7 +1538,7 @@ static int serve_run(vx_serve* v, int max_steps, vx_serve_done_fn on_done, void*
     if (max_steps > 0) target = std::min(target, start + max_steps);
     while (v->steps < target) {
       const int n = (v->steps % gs == 0 && v->steps + gs <= target) ? gs : 1;
-      if (int e = ar_step_run(c, &v->sa, v->sig, n)) return e;
+      if (int e = ar_step_run(c, nullptr, v->sig, n, &v->rsa)) return e;
       v->steps += n;
     }
     D2H(v->act.data(), c->active, nd * sizeof(int));
@@ -1555,6 +1562,90 @@ static int serve_run(vx_serve* v, int max_steps, vx_serve_done_fn on_done, void*
 static int serve_busy(vx_ctx* c, const char* what) {
   if (!c->serve) return VX_OK;
   FAIL(VX_EINVAL, "%s: a serving session is open on this context (vx_serve_close it first)", what);
+}
+
+// vx_serve_submit / vx_serve_submit_ex: smp null = the session's top_k / temperature / force_eos_at for every request
+static int serve_submit(vx_serve* v, const vx_batch* b, const vx_request* req, const vx_request_sampling* smp, int64_t* ids_out) {
+  vx_ctx* c = v->c;
+  if (int e = check_batch(c, b, 0x7fffffff)) return e;
+  std::vector<vx_request_sampling> rs(b->batch, vx_request_sampling{sizeof(vx_request_sampling), v->s.top_k, v->s.temperature,
+                                                                    v->s.force_eos_at});
+  for (int i = 0; i < b->batch; ++i) {
+    const vx_request& q = req[i];
+    if (q.struct_size != sizeof(vx_request))
+      FAIL(VX_EINVAL, "vx_request.struct_size is %u, this library expects %zu (ABI version %d)", q.struct_size, sizeof(vx_request), VX_ABI_VERSION);
+    if (smp) {
+      const vx_request_sampling& m = smp[i];
+      if (m.struct_size != sizeof(vx_request_sampling))
+        FAIL(VX_EINVAL, "vx_request_sampling.struct_size is %u, this library expects %zu (ABI version %d)", m.struct_size,
+             sizeof(vx_request_sampling), VX_ABI_VERSION);
+      if (!(m.temperature > 0.f) || !std::isfinite(m.temperature))
+        FAIL(VX_EINVAL, "request %d: temperature must be > 0 and finite (got %g)", i, (double)m.temperature);
+      if (m.force_eos_at < -1) FAIL(VX_EINVAL, "request %d: force_eos_at must be >= -1 (got %d)", i, m.force_eos_at);
+      rs[i] = m;
+    }
+    const int N = std::max(1, q.best_of);
+    if (N > v->nd) FAIL(VX_EINVAL, "request %d: best_of %d exceeds the session's %d decode rows", i, N, v->nd);
+    if (b->text_lens[i] + 1 + b->prompt_lens[i] > c->Tmax) FAIL(VX_EINVAL, "request %d: the prompt does not fit the arena", i);
+    if (q.uniforms) {
+      // every draw the request can consume: one per generated frame + the terminating one (its own force_eos_at)
+      const int f = rs[i].force_eos_at;
+      const int need = std::min(f >= 0 ? std::min(c->gen_stride, f) : c->gen_stride, 16 * b->text_lens[i]) + 1;
+      if (q.uniforms_steps < need) FAIL(VX_EINVAL, "request %d: %d uniforms steps, it can draw %d", i, q.uniforms_steps, need);
+    }
+  }
+  std::vector<std::unique_ptr<ServeReq>> add;
+  for (int i = 0; i < b->batch; ++i) {
+    const vx_request& q = req[i];
+    auto r = std::make_unique<ServeReq>();
+    r->top_k = rs[i].top_k; r->temperature = rs[i].temperature; r->force_eos_at = rs[i].force_eos_at;
+    r->N = std::max(1, q.best_of);
+    r->length_penalty = q.length_penalty;
+    r->worst = q.return_worst != 0;
+    r->seed = q.seed;
+    r->S = b->text_lens[i]; r->Tp = b->prompt_lens[i];
+    r->ids.assign(b->text_ids + (long)i * b->text_stride, b->text_ids + (long)i * b->text_stride + r->S);
+    r->lang.assign(b->text_lang + (long)i * b->text_stride, b->text_lang + (long)i * b->text_stride + r->S);
+    r->pc.assign(b->prompt_codes + (long)i * b->prompt_stride * N_Q, b->prompt_codes + ((long)i * b->prompt_stride + r->Tp) * N_Q);
+    if (q.uniforms) {       // [uniforms_steps][N] -> [N][steps], only the draws that can be consumed
+      r->usteps = std::min(q.uniforms_steps, c->gen_stride + 1);
+      r->u.resize((size_t)r->N * r->usteps);
+      for (int j = 0; j < r->N; ++j)
+        for (int t = 0; t < r->usteps; ++t) r->u[(size_t)j * r->usteps + t] = q.uniforms[(long)t * r->N + j];
+    }
+    add.push_back(std::move(r));
+  }
+  for (int i = 0; i < b->batch; ++i) {
+    add[i]->id = v->next_id++;
+    if (ids_out) ids_out[i] = add[i]->id;
+    v->waiting.push_back(std::move(add[i]));
+  }
+  return VX_OK;
+}
+
+// vx_serve_cancel: 0 unknown / delivered / cancelled, 1 waiting (removed), 2 decoding (its rows stop and are free)
+static int serve_cancel(vx_serve* v, int64_t id, int* state) {
+  vx_ctx* c = v->c;
+  *state = 0;
+  auto wi = std::find_if(v->waiting.begin(), v->waiting.end(), [&](const std::unique_ptr<ServeReq>& q) { return q->id == id; });
+  if (wi != v->waiting.end()) {
+    v->waiting.erase(wi);
+    *state = 1;
+    return VX_OK;
+  }
+  auto li = std::find_if(v->live.begin(), v->live.end(), [&](const std::unique_ptr<ServeReq>& q) { return q->id == id; });
+  if (li == v->live.end()) return VX_OK;
+  // its beam rows that are still occupied (a beam harvested earlier has freed its row already): inactive before the next step,
+  // slot records and n_active corrected on the stream, free on the host; the harvest never looks at them again
+  unsigned rows = 0;
+  for (int d = 0; d < v->nd; ++d)
+    if (v->occ[d] == li->get()) { rows |= 1u << d; v->occ[d] = nullptr; }
+  if (rows) launch_serve_cancel(rows, v->nd, c->active, c->slot_meta, c->slot_of, c->n_active, c->stream);
+  HIPCHK(hipGetLastError());
+  SYNC();                                           // the rows are stopped before the call returns (cancel is rare: one sync)
+  v->live.erase(li);
+  *state = 2;
+  return VX_OK;
 }
 
 }  // namespace vxe
@@ -1856,13 +1947,26 @@ int vx_serve_open(vx_ctx* c, const vx_sampling* s, vx_serve** out) {
   v->beam.assign(v->nd, 0); v->done_by.assign(v->nd, 0); v->act.assign(v->nd, 0); v->ng.assign(v->nd, 0);
   v->slot_of.resize(v->nd);
   for (int d = 0; d < v->nd; ++d) v->slot_of[d] = d;
+  // the per-row sampling records (allocated once per context, before any step graph of a session is captured)
+  if (!c->row_smp) {
+    if (int e = dev_alloc(c, &c->row_smp, 4 * MB)) { delete v; return e; }
+  }
   if (int e = serve_setup(c, v->nd)) { delete v; return e; }
-  v->sa = make_sample_args(c, &v->s, 1, nullptr);
-  v->sa.uniforms = c->d_uniforms;                  // every beam row draws from its own column, injected or counter-based
-  v->sa.sum_logp = c->sum_logp;                    // always on: best_of is per request
+  // the per-row sampler (serve_sample.hip) with dec_sample's buffers: every beam row draws from its own column of d_uniforms
+  // (injected or counter-based) and accumulates sum_logp (best_of is per request); top_k / temperature / force_eos_at come from
+  // row_smp, so they are not part of the graph signature
+  const SampleArgs sa = make_sample_args(c, &v->s, 1, nullptr);
+  ServeSampleArgs& r = v->rsa;
+  r.partial = sa.partial; r.splitk = sa.splitk; r.npad = sa.npad;
+  r.row_smp = c->row_smp;
+  r.uniforms = c->d_uniforms; r.uniforms_stride = sa.uniforms_stride;
+  r.cur_tok = sa.cur_tok; r.cur_pos = sa.cur_pos; r.ctx_len = sa.ctx_len; r.n_gen = sa.n_gen; r.active = sa.active;
+  r.n_active = sa.n_active; r.text_len = sa.text_len; r.slot_meta = sa.slot_meta; r.slot_of = sa.slot_of;
+  r.gen = sa.gen; r.gen_stride = sa.gen_stride; r.sum_logp = c->sum_logp; r.batch = sa.batch;
+  r.emb_tab = sa.emb_tab; r.emb_alpha = sa.emb_alpha; r.pe = sa.pe; r.ln_g = sa.ln_g; r.ln_b = sa.ln_b; r.emb_h = sa.emb_h;
+  r.emb_xp = sa.emb_xp; r.wt = sa.wt;
   char sig[160];
-  snprintf(sig, sizeof sig, "b%d ns%d c%d%d%d k%d t%a u%d f%d l%d", v->nd, c->nsplit, (int)c->sb_chain, (int)c->sb_qkv, (int)c->split_fused,
-           v->sa.top_k, v->sa.temperature, 1, v->sa.force_eos_at, 1);
+  snprintf(sig, sizeof sig, "b%d ns%d c%d%d%d serve-rows u1 l1", v->nd, c->nsplit, (int)c->sb_chain, (int)c->sb_qkv, (int)c->split_fused);
   v->sig = sig;
   c->serve = v;
   *out = v;
@@ -1871,47 +1975,22 @@ int vx_serve_open(vx_ctx* c, const vx_sampling* s, vx_serve** out) {
 
 int vx_serve_submit(vx_serve* v, const vx_batch* b, const vx_request* req, int64_t* ids_out) {
   if (!v || !req) return VX_EINVAL;
+  return serve_submit(v, b, req, nullptr, ids_out);
+}
+
+int vx_serve_submit_ex(vx_serve* v, const vx_batch* b, const vx_request* req, const vx_request_sampling* smp, int64_t* ids_out) {
+  if (!v || !req) return VX_EINVAL;
+  return serve_submit(v, b, req, smp, ids_out);
+}
+
+int vx_serve_cancel(vx_serve* v, int64_t request_id, int32_t* state) {
+  if (!v) return VX_EINVAL;
   vx_ctx* c = v->c;
-  if (int e = check_batch(c, b, 0x7fffffff)) return e;
-  const int first_cap = v->s.force_eos_at >= 0 ? std::min(c->gen_stride, v->s.force_eos_at) : c->gen_stride;
-  for (int i = 0; i < b->batch; ++i) {
-    const vx_request& q = req[i];
-    if (q.struct_size != sizeof(vx_request))
-      FAIL(VX_EINVAL, "vx_request.struct_size is %u, this library expects %zu (ABI version %d)", q.struct_size, sizeof(vx_request), VX_ABI_VERSION);
-    const int N = std::max(1, q.best_of);
-    if (N > v->nd) FAIL(VX_EINVAL, "request %d: best_of %d exceeds the session's %d decode rows", i, N, v->nd);
-    if (b->text_lens[i] + 1 + b->prompt_lens[i] > c->Tmax) FAIL(VX_EINVAL, "request %d: the prompt does not fit the arena", i);
-    if (q.uniforms) {
-      // every draw the request can consume: one per generated frame + the terminating one
-      const int need = std::min(first_cap, 16 * b->text_lens[i]) + 1;
-      if (q.uniforms_steps < need) FAIL(VX_EINVAL, "request %d: %d uniforms steps, it can draw %d", i, q.uniforms_steps, need);
-    }
-  }
-  std::vector<std::unique_ptr<ServeReq>> add;
-  for (int i = 0; i < b->batch; ++i) {
-    const vx_request& q = req[i];
-    auto r = std::make_unique<ServeReq>();
-    r->N = std::max(1, q.best_of);
-    r->length_penalty = q.length_penalty;
-    r->worst = q.return_worst != 0;
-    r->seed = q.seed;
-    r->S = b->text_lens[i]; r->Tp = b->prompt_lens[i];
-    r->ids.assign(b->text_ids + (long)i * b->text_stride, b->text_ids + (long)i * b->text_stride + r->S);
-    r->lang.assign(b->text_lang + (long)i * b->text_stride, b->text_lang + (long)i * b->text_stride + r->S);
-    r->pc.assign(b->prompt_codes + (long)i * b->prompt_stride * N_Q, b->prompt_codes + ((long)i * b->prompt_stride + r->Tp) * N_Q);
-    if (q.uniforms) {       // [uniforms_steps][N] -> [N][steps], only the draws that can be consumed
-      r->usteps = std::min(q.uniforms_steps, c->gen_stride + 1);
-      r->u.resize((size_t)r->N * r->usteps);
-      for (int j = 0; j < r->N; ++j)
-        for (int t = 0; t < r->usteps; ++t) r->u[(size_t)j * r->usteps + t] = q.uniforms[(long)t * r->N + j];
-    }
-    add.push_back(std::move(r));
-  }
-  for (int i = 0; i < b->batch; ++i) {
-    add[i]->id = v->next_id++;
-    if (ids_out) ids_out[i] = add[i]->id;
-    v->waiting.push_back(std::move(add[i]));
-  }
+  if (v->running) FAIL(VX_EINVAL, "vx_serve_cancel: called from inside vx_serve_run (on_done); cancel between two vx_serve_run calls");
+  HIPCHK(hipSetDevice(c->dev));
+  int st = 0;
+  if (int e = serve_cancel(v, request_id, &st)) return e;
+  if (state) *state = st;
   return VX_OK;
 }
 
@@ -1919,10 +1998,14 @@ int vx_serve_run(vx_serve* v, int32_t max_steps, vx_serve_done_fn on_done, void*
                  int32_t* waiting_requests) {
   if (!v) return VX_EINVAL;
   vx_ctx* c = v->c;
+  if (v->running) FAIL(VX_EINVAL, "vx_serve_run: called from inside vx_serve_run (on_done)");
   HIPCHK(hipSetDevice(c->dev));
   c->st_steps = 0; c->st_frames = 0; c->st_ar_ms = 0; c->st_nar_ms = 0; c->st_truncated = 0;
   c->st_fb_prefill = c->st_fb_nar = 0;
-  if (int e = serve_run(v, max_steps, on_done, user)) return e;
+  v->running = true;
+  const int rc = serve_run(v, max_steps, on_done, user);
+  v->running = false;
+  if (rc) return rc;
   if (live_requests) *live_requests = (int32_t)v->live.size();
   if (waiting_requests) *waiting_requests = (int32_t)v->waiting.size();
   return VX_OK;

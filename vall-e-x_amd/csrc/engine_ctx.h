@@ -1,6 +1,7 @@
 // Internal declarations shared by the engine's translation units (engine.hip: context, AR / NAR drivers and the hot-path ABI;
 // weights.hip: ingest of the reference state-dict; vocoders.hip: Vocos head, EnCodec decoder / encoder drivers;
 // beams.hip: the best_of fan-out; admit.hip / serve.hip: admission kernels of the continuous schedule / the serving session;
+// serve_sample.hip: the serving session's per-row sampler;
 // bench_harness.hip: the measurement entries of include/vallex_hip_dev.h).  Not part of the public C ABI.
 #pragma once
 
@@ -149,6 +150,7 @@ struct vx_ctx {
   int att_nsplit_force = 0;        // VX_ATT_NSPLIT=n: context splits of dec_attn on the general chain (0 = 512 / (rows x 16) workgroups rule)
   std::vector<int> h_L;            // prefill lengths of the current micro-batch
   vx_serve* serve = nullptr;       // the open serving session (vx_serve_open); it owns the decode state while it is open
+  int* row_smp = nullptr;          // [MB][4] per-row sampling record of the session's sampler (first vx_serve_open allocates it)
 
   // graph
   hipGraphExec_t graph_exec = nullptr, graph_exec_n = nullptr;   // one decode step / GRAPH_STEPS steps per launch
@@ -281,7 +283,9 @@ int ensure_f32_buffers(vx_ctx* c);
 int take_range_flag(vx_ctx* c, bool* raised);
 int check_batch(vx_ctx* c, const vx_batch* b, int max_rows);
 SampleArgs make_sample_args(vx_ctx* c, const vx_sampling* s, int commit, float* logits_out);
-void ar_step_launches(vx_ctx* c, const SampleArgs* sa);
+struct ServeSampleArgs;
+// rsa != null (serving session): the step ends in the per-row sampler (serve_sample.hip) instead of dec_sample
+void ar_step_launches(vx_ctx* c, const SampleArgs* sa, const ServeSampleArgs* rsa = nullptr);
 int launch_status(vx_ctx* c);      // VX_EINVAL (+ message) if a launcher refused since the last check
 // best_of fan-out (beams.hip): one launch per prefill.  pairs [npairs][3] = {source slot, destination slot, cached rows}: that many
 // K / V rows of every (layer, head) are copied between the two arena slots; dh[d] = hsrc[hsrc_row[d]] for the nrows decode rows.
@@ -320,8 +324,33 @@ void launch_admit_uniforms(const int* pairs, int n, const float* staged, int ste
 
 // serving session (serve.hip): draws + sum_logp reset of admitted beam rows.  tab [n][6] = {decode row d, beam j, offset of the
 // request's staged draws of beam j in `staged` (-1: counter-based, keyed on (seed, j)), draws to write, seed low, seed high word}
+// ... it also writes the admitted rows' sampling record row_smp[4 d .. 4 d + 3] = {top_k, temperature bits, force_eos_at, 0}:
+// tab [n][9] = the six words above + {top_k, temperature bits, force_eos_at}
+constexpr int SERVE_UTAB = 9;
 void launch_serve_uniforms(const int* tab, int n, int max_steps, const float* staged, float* u, int ncols, float* sum_logp,
-                           hipStream_t s);
+                           int* row_smp, hipStream_t s);
+// cancellation of decoding requests (serve.hip): active[d] = 0 for every bit d of `rows`, then, for d < nrows,
+// slot_meta[4 slot_of[d] + 2] = active[d] and *n_active = number of active rows (recounted from the flags).  nrows <= 32.
+void launch_serve_cancel(unsigned rows, int nrows, int* active, int* slot_meta, const int* slot_of, int* n_active, hipStream_t s);
+
+// the serving session's sampler (serve_sample.hip): dec_sample_kernel's computation with top_k, temperature and force_eos_at read
+// per decode row from row_smp (written at admission by launch_serve_uniforms) instead of launch constants.  Always commits, always
+// draws from `uniforms` (the session writes every admitted row's column), always accumulates sum_logp.
+struct ServeSampleArgs {
+  const float* partial; int splitk; int npad;     // logits partials [splitk][MB][npad]
+  const int* row_smp;                              // [MB][4] = {top_k, temperature bits, force_eos_at, 0}
+  const float* uniforms; int uniforms_stride;     // [steps][uniforms_stride]
+  int* cur_tok; int* cur_pos; int* ctx_len; int* n_gen; int* active; int* n_active; const int* text_len;
+  int* slot_meta; const int* slot_of;
+  int* gen; int gen_stride;
+  float* sum_logp;
+  int batch;
+  // the fused start of the next step, as SampleArgs (emb_tab == null: off)
+  const float* emb_tab; const float* emb_alpha; const float* pe; const float* ln_g; const float* ln_b;
+  float* emb_h; float* emb_xp;
+  int wt;
+};
+bool launch_serve_sample(const ServeSampleArgs& a, hipStream_t s);
 
 struct F32Scope {            // the full-sequence path on the exact-fp32 kernels for the lifetime of the object
   vx_ctx* c;

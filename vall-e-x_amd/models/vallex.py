@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import math
 import threading
-from concurrent.futures import Future
+from concurrent.futures import Future, InvalidStateError
 from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
@@ -286,8 +286,9 @@ class VALLE:
               post=None, **kw) -> "Server":
         """A threaded serving front end (include/vallex_hip.h vx_serve_*): `Server.submit(row, best_of=..., seed=...)` may be called
         from any thread at any time and returns a Future of the row's (T, 8) int64 codes -- exactly what `inference_batch([row],
-        best_of=..., seed=...)` returns.  top_k / temperature / sync_every / force_eos_at apply to the whole session; best_of,
-        length_penalty, return_worst, seed and uniforms are per request (Server.submit).  `max_steps`: decode steps per
+        best_of=..., seed=...)` returns.  sync_every applies to the whole session; top_k / temperature / force_eos_at given here
+        are the defaults of the requests that do not set their own; best_of, length_penalty, return_worst, seed, uniforms, top_k,
+        temperature and force_eos_at are per request (Server.submit).  A request's Future can be cancelled until it is delivered.  `max_steps`: decode steps per
         vx_serve_run, i.e. how long a new submission waits at most for the worker to pick it up.  `post(codes list) -> results`
         (optional) runs on the worker thread for every group of completed requests (AudioServer: Vocos)."""
         if kw:
@@ -312,7 +313,10 @@ class Server:
     waiting, and resolves every request's Future as soon as its NAR stages are done.  submit() is thread-safe and does the host
     work of a row (ids, languages, prompt) on the submitting thread.  close() (or leaving a `with` block) finishes everything that
     was submitted, then closes the session.  A C error fails every outstanding Future with the VallexHipError and closes the session;
-    a request the library refuses (VX_EINVAL at submit: oversized row, too few uniforms) fails its own Future only."""
+    a request the library refuses (VX_EINVAL at submit: oversized row, too few uniforms) fails its own Future only.  A Future stays
+    PENDING until it is delivered, so `fut.cancel()` succeeds while its request waits or decodes: a done-callback wakes the worker,
+    which cancels the request in the session (vx_serve_cancel) before its next vx_serve_run -- the request's decode rows go to the
+    next admission -- and a cancelled Future never receives a result."""
 
     def __init__(self, model: "VALLE", top_k=-100, temperature=1.0, sync_every=8, force_eos_at=None, max_steps=32, post=None):
         self._model = model
@@ -334,22 +338,34 @@ class Server:
             raise self._error
 
     def submit(self, row: dict, best_of: int = 1, seed: Optional[int] = None, uniforms=None, length_penalty: float = 1.0,
-               return_worst: bool = False) -> Future:
+               return_worst: bool = False, top_k: Optional[int] = None, temperature: Optional[float] = None,
+               force_eos_at: Optional[int] = None) -> Future:
         """row: the dict of inference_batch (text, prompt, enroll, prompt_language, text_language).  Returns a Future of the
-        (T, 8) int64 codes (or of post's result).  seed=None draws a fresh seed, like inference."""
-        u = ServeSession.check_request(best_of, uniforms, self.rows)
+        (T, 8) int64 codes (or of post's result).  seed=None draws a fresh seed, like inference; top_k / temperature /
+        force_eos_at None: the session's value."""
+        u = ServeSession.check_request(best_of, uniforms, self.rows, top_k, temperature, force_eos_at)
         if seed is None:
             seed = fresh_seed()
         batch = self._model.make_batch([row])
         req = dict(best_of=int(best_of), seed=int(seed), uniforms=u, length_penalty=float(length_penalty),
                    return_worst=bool(return_worst))
+        for k, v in (("top_k", top_k), ("temperature", temperature), ("force_eos_at", force_eos_at)):
+            if v is not None:
+                req[k] = v
         fut: Future = Future()
         with self._cv:
             if self._closing or self._error is not None:
                 raise RuntimeError("the server is closed" if self._error is None else f"the server failed: {self._error}")
             self._queue.append((batch, req, fut))
             self._cv.notify()
+        fut.add_done_callback(self._wake)
         return fut
+
+    def _wake(self, fut: Future):
+        """done-callback of every Future: a cancellation wakes the worker (it cancels the request before its next run)"""
+        if fut.cancelled():
+            with self._cv:
+                self._cv.notify()
 
     def close(self):
         """finish every submitted request, then close the session (idempotent)"""
@@ -376,21 +392,26 @@ class Server:
         self._ready.set()
         try:
             while True:
+                # Futures cancelled since the last run: out of the session before the next one
+                for rid in [r for r, f in self._futs.items() if f.cancelled()]:
+                    session.cancel(rid)
+                    del self._futs[rid]
                 with self._cv:
                     while not self._queue and not self._futs and not self._closing:
                         self._cv.wait()
-                    items, self._queue = self._queue, []
-                    if not items and not self._futs and self._closing:
+                    # the exit test reads the live queue under the lock: a submit() that got in before close() is served
+                    if not self._queue and not self._futs and self._closing:
                         break
+                    items, self._queue = self._queue, []
                 for batch, req, fut in items:
-                    if not fut.set_running_or_notify_cancel():
+                    if fut.cancelled():
                         continue
                     try:
                         rid = session.submit(batch, [req])[0]
                     except VallexHipError as e:
                         if e.code != VX_EINVAL:
                             raise
-                        fut.set_exception(e)             # refused: this request only, the session goes on
+                        self._settle(fut, exc=e)         # refused: this request only, the session goes on
                         continue
                     self._futs[rid] = fut
                 if self._futs:
@@ -414,10 +435,21 @@ class Server:
             res = self._post(codes) if self._post is not None else codes
         except BaseException as e:
             for f in futs:
-                f.set_exception(e)
+                self._settle(f, exc=e)
             return
         for f, r in zip(futs, res):
-            f.set_result(r)
+            self._settle(f, res=r)
+
+    @staticmethod
+    def _settle(f: Future, res=None, exc=None):
+        """a Future cancelled after its request was delivered (between run() and here) keeps its cancellation"""
+        try:
+            if exc is not None:
+                f.set_exception(exc)
+            else:
+                f.set_result(res)
+        except InvalidStateError:
+            pass
 
     def _fail(self, e: BaseException):
         with self._cv:
@@ -426,5 +458,5 @@ class Server:
             items, self._queue = self._queue, []
         for f in list(self._futs.values()) + [it[2] for it in items]:
             if not f.done():
-                f.set_exception(e)
+                self._settle(f, exc=e)
         self._futs.clear()
