@@ -47,6 +47,38 @@ int vx_bench_gemm_clock(vx_ctx* ctx, int32_t M, int32_t N, int32_t K, int32_t ke
  * 32-bit words of C (16-bit words of the planes in mode 0).  N % 256 == 0. */
 int vx_bench_gemm_epilogue(vx_ctx* ctx, int32_t M, int32_t N, int32_t K, int32_t mode, int64_t* differing, int64_t* compared);
 
+/* ---- correctness entries: product kernels on caller-chosen operands -------------------------------------------
+ * Not timed.  Host pointers in and out, staged through the context's pinned ring, launched on the context's stream through the
+ * product launchers.  Every output buffer is pre-filled with a sentinel, so the caller sees what a kernel did not write. */
+#define VX_DEV_SENTINEL_I (-123456789)
+#define VX_DEV_SENTINEL_F (-1.0e30f)
+#define VX_DEV_SENTINEL_H 0xFBFF /* half-word fill of plane outputs (fp16 -65504); reported as VX_DEV_SENTINEL_F */
+#define VX_DEV_SAMPLE_CFG 10
+#define VX_DEV_SAMPLE_STATE 12
+/* The decode sampler (kernel 0: dec_sample_kernel, 1: serve_sample_kernel) on n chosen cases; case i runs in decode row i % 32 of
+ * launch i / 32, launch slot (7 row + 3) % 32.  Rows of a launch without a case are inactive.
+ *   cfg   [n][10] = {kernel, splitk (1 | 2 | 4), top_k, force_eos_at, active, n_gen, cur_pos, ctx_len, text_len, gen_stride}
+ *   fcfg  [n][3]  = {temperature, the draw u in [0, 1), incoming sum_logp}
+ *   partial [n][4][1025]: the split-K addends of the logit row (the first `splitk` are read)
+ * kernel, splitk and gen_stride are launch constants, and for kernel 0 so are top_k, temperature and force_eos_at: the cases of
+ * one launch must agree on them (VX_EINVAL otherwise).
+ *   logits [n][1025]: the reduced logits (kernel 0 writes them; kernel 1 leaves the sentinel)
+ *   state  [n][12] = {active, n_gen, cur_tok, cur_pos, ctx_len, slot_meta[4 slot .. 4 slot + 3], gen[row][old n_gen], the launch's
+ *                     n_active, slot}.  Before the launch cur_tok, gen and slot_meta word 3 hold the sentinel, slot_meta words 0 .. 2
+ *                     = {row, ctx_len, active} and n_active = the number of active cases of the launch.
+ *   sum_logp [n]; emb_h [n][1024]; emb_xp [n][1024] = the row's part of the packed-x image, un-packed.
+ * The fused next-step embedding reads the context's finalized AR audio embedding, position alpha, positional table and norm1 of
+ * layer 0. */
+int vx_dev_sample(vx_ctx* ctx, int32_t n, const int32_t* cfg, const float* fcfg, const float* partial, float* logits, int32_t* state,
+                  float* sum_logp, float* emb_h, float* emb_xp);
+/* One launch of a full-sequence attention kernel: variant 0 fp32, 10 bf16x3, 20 f16x2; planes 1 (variants 10, 20): the output leaves
+ * as the fp16 head / tail planes of out_proj, read back and returned as (head + tail) / 2^5.  qkv [sum seq_len][3072]; prefix_len
+ * NULL: no mask; q_first (variant 0 with fp32 rows, variant 20 with planes) or NULL: only rows [q_first[b], seq_len[b]) of every
+ * sequence are computed and stored compacted.  out [out_rows][1024], out_rows >= the rows stored (a few more rows show that
+ * nothing is written behind them).  *range_flag = the f16x2 range flag after the launch (0 for the other variants). */
+int vx_dev_attn(vx_ctx* ctx, int32_t variant, int32_t planes, int32_t batch, const float* qkv, const int32_t* seq_len,
+                const int32_t* prefix_len, const int32_t* q_first, float* out, int64_t out_rows, int32_t* range_flag);
+
 #ifdef __cplusplus
 }
 #endif

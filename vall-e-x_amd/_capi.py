@@ -77,7 +77,11 @@ SYMBOLS = ["vx_abi_version", "vx_create", "vx_destroy", "vx_last_error", "vx_syn
            "vx_serve_close", "vx_serve_submit_ex", "vx_serve_cancel"]
 # ... and include/vallex_hip_dev.h: measurement / kernel development, never called by the mirrors of the reference API
 DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kernel", "vx_bench_gemm", "vx_bench_attn",
-               "vx_bench_gemm_clock", "vx_bench_gemm_epilogue"]
+               "vx_bench_gemm_clock", "vx_bench_gemm_epilogue", "vx_dev_sample", "vx_dev_attn"]
+# sentinels the correctness entries pre-fill their outputs with (include/vallex_hip_dev.h)
+DEV_SENTINEL_I = -123456789
+DEV_SENTINEL_F = np.float32(-1.0e30)
+DEV_SAMPLE_CFG = ("kernel", "splitk", "top_k", "force_eos_at", "active", "n_gen", "cur_pos", "ctx_len", "text_len", "gen_stride")
 
 # vx_row_done_fn of vx_infer_continuous: (user, caller row, codes [frames][8] int64, frames)
 ROW_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int32)
@@ -148,6 +152,10 @@ def load_library() -> C.CDLL:
     lib.vx_bench_gemm_epilogue.argtypes = [ctx, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_int64), P(C.c_int64)]
     lib.vx_bench_gemm_clock.argtypes = [ctx, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_double), P(C.c_double),
                                         P(C.c_double)]
+    lib.vx_dev_sample.argtypes = [ctx, C.c_int32, P(C.c_int32), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_int32), P(C.c_float),
+                                  P(C.c_float), P(C.c_float)]
+    lib.vx_dev_attn.argtypes = [ctx, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), P(C.c_int32), P(C.c_int32), P(C.c_int32),
+                                P(C.c_float), C.c_int64, P(C.c_int32)]
     lib.vx_last_stats.argtypes = [ctx, P(C.c_int64), P(C.c_int64), P(C.c_double), P(C.c_double)]
     lib.vx_last_truncated.argtypes = [ctx, P(C.c_int32)]
     lib.vx_last_fallbacks.argtypes = [ctx, P(C.c_int32), P(C.c_int32), P(C.c_int64)]
@@ -457,6 +465,55 @@ class Engine:
         us, md = C.c_double(), C.c_double()
         self._chk(self.lib.vx_bench_attn(self.ctx, batch, length, int(causal), variant, reps, C.byref(us), C.byref(md)))
         return us.value, md.value
+
+    def dev_sample(self, cases: Sequence[dict]):
+        """vx_dev_sample: the decode sampler on chosen cases.  Each case is a dict with the keys of DEV_SAMPLE_CFG (defaults: kernel 0,
+        splitk 1, top_k -100, force_eos_at -1, active 1, n_gen 0, cur_pos 0, ctx_len 1, text_len 1, gen_stride 16) plus temperature
+        (1.0), u (0.0), sum_logp (0.0) and partial (splitk, 1025) float32.  Case i runs in decode row i % 32 of launch i // 32.
+        Returns a dict of arrays, one row per case: logits (n, 1025), active, n_gen, cur_tok, cur_pos, ctx_len, slot_meta (n, 4), gen,
+        n_active, slot, sum_logp, emb_h (n, 1024), emb_xp (n, 1024)."""
+        dflt = dict(kernel=0, splitk=1, top_k=-100, force_eos_at=-1, active=1, n_gen=0, cur_pos=0, ctx_len=1, text_len=1, gen_stride=16)
+        n = len(cases)
+        cfg = np.array([[int(q.get(k, dflt[k])) for k in DEV_SAMPLE_CFG] for q in cases], np.int32).reshape(n, len(DEV_SAMPLE_CFG))
+        fcfg = np.array([[q.get("temperature", 1.0), q.get("u", 0.0), q.get("sum_logp", 0.0)] for q in cases], np.float32).reshape(n, 3)
+        part = np.zeros((n, 4, 1025), np.float32)
+        for i, q in enumerate(cases):
+            p = np.asarray(q["partial"], np.float32).reshape(-1, 1025)
+            if p.shape[0] != cfg[i, 1]:
+                raise ValueError(f"case {i}: partial has {p.shape[0]} addends, splitk is {cfg[i, 1]}")
+            part[i, : p.shape[0]] = p
+        logits = np.empty((n, 1025), np.float32)
+        state = np.empty((n, 12), np.int32)
+        slp = np.empty(n, np.float32)
+        emb_h = np.empty((n, 1024), np.float32)
+        emb_xp = np.empty((n, 1024), np.float32)
+        self._chk(self.lib.vx_dev_sample(self.ctx, n, _ptr(cfg, C.c_int32), _ptr(fcfg, C.c_float), _ptr(part, C.c_float),
+                                         _ptr(logits, C.c_float), _ptr(state, C.c_int32), _ptr(slp, C.c_float), _ptr(emb_h, C.c_float),
+                                         _ptr(emb_xp, C.c_float)))
+        return dict(logits=logits, active=state[:, 0], n_gen=state[:, 1], cur_tok=state[:, 2], cur_pos=state[:, 3], ctx_len=state[:, 4],
+                    slot_meta=state[:, 5:9], gen=state[:, 9], n_active=state[:, 10], slot=state[:, 11], sum_logp=slp, emb_h=emb_h,
+                    emb_xp=emb_xp)
+
+    def dev_attn(self, variant: int, planes: bool, qkv: np.ndarray, seq_len, prefix_len=None, q_first=None, extra_rows: int = 0):
+        """vx_dev_attn: one full-sequence attention launch (variant 0 fp32 / 10 bf16x3 / 20 f16x2; planes: fp16 plane output, read
+        back as fp32) on packed q|k|v rows (sum seq_len, 3072).  Returns (out (rows + extra_rows, 1024) float32 -- rows the kernel did
+        not write hold DEV_SENTINEL_F --, the f16x2 range flag)."""
+        sl = np.ascontiguousarray(seq_len, np.int32)
+        q = np.ascontiguousarray(qkv, np.float32)
+        if q.shape != (int(sl.sum()), 3072):
+            raise ValueError(f"qkv must be (sum seq_len, 3072) = ({int(sl.sum())}, 3072), got {q.shape}")
+        pre = None if prefix_len is None else np.ascontiguousarray(prefix_len, np.int32)
+        qf = None if q_first is None else np.ascontiguousarray(q_first, np.int32)
+        for a in (pre, qf):
+            if a is not None and a.shape != sl.shape:
+                raise ValueError("prefix_len / q_first must have one entry per sequence")
+        rows = int(sl.sum()) - (0 if qf is None else int(qf.sum())) + int(extra_rows)
+        out = np.empty((rows, 1024), np.float32)
+        flag = C.c_int32()
+        self._chk(self.lib.vx_dev_attn(self.ctx, int(variant), int(bool(planes)), len(sl), _ptr(q, C.c_float), _ptr(sl, C.c_int32),
+                                       None if pre is None else _ptr(pre, C.c_int32), None if qf is None else _ptr(qf, C.c_int32),
+                                       _ptr(out, C.c_float), rows, C.byref(flag)))
+        return out, flag.value
 
     def last_fallbacks(self):
         """phases of the last call that left the fp16 range of the f16x2 kernels and were re-run in fp32 (+ lifetime count)"""

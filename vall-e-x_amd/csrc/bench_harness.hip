@@ -527,4 +527,215 @@ int vx_bench_gemm_epilogue(vx_ctx* c, int32_t M, int32_t N, int32_t K, int32_t m
   return VX_OK;
 }
 
+// ---- correctness entries: the product samplers / attention kernels on caller-chosen operands (no timing) ----------------------
+// vx_dev_sample: case i runs in decode row i % 32 of launch i / 32 (the partials are laid out [splitk][32][npad], so the row matters).
+// Every launch gets private scratch state pre-filled with the sentinels; only the fused embedding reads the context (the finalized
+// AR audio embedding, position alpha, positional table and norm1 of layer 0).
+int vx_dev_sample(vx_ctx* c, int32_t n, const int32_t* cfg, const float* fcfg, const float* partial, float* logits, int32_t* state,
+                  float* sum_logp, float* emb_h, float* emb_xp) {
+  if (!c) return VX_EINVAL;
+  if (n <= 0 || !cfg || !fcfg || !partial || !logits || !state || !sum_logp || !emb_h || !emb_xp) FAIL(VX_EINVAL, "vx_dev_sample: null argument or n <= 0");
+  if (!c->finalized) FAIL(VX_ESTATE, "vx_dev_sample: weights not finalized");
+  constexpr int GS_MAX = 4096, NG_MAX = 4096, NC = VX_DEV_SAMPLE_CFG, NS = VX_DEV_SAMPLE_STATE;
+  for (int i = 0; i < n; ++i) {
+    const int32_t* k = cfg + (size_t)i * NC;
+    const float T = fcfg[3 * i], u = fcfg[3 * i + 1];
+    if ((k[0] != 0 && k[0] != 1) || (k[1] != 1 && k[1] != 2 && k[1] != 4) || (k[4] != 0 && k[4] != 1) || k[5] < 0 || k[5] > NG_MAX || k[6] < 0 ||
+        k[6] + 1 >= c->pe_rows || k[8] < 0 || k[9] < 1 || k[9] > GS_MAX || !(T > 0.0f) || !(T < 3.0e38f) || !(u >= 0.0f) || !(u < 1.0f))
+      FAIL(VX_EINVAL, "vx_dev_sample: case %d out of range (kernel 0/1, splitk 1/2/4, active 0/1, 0 <= n_gen <= %d, 0 <= cur_pos < %d, "
+           "text_len >= 0, 1 <= gen_stride <= %d, temperature > 0, 0 <= u < 1)", i, NG_MAX, c->pe_rows - 1, GS_MAX);
+    const int32_t* k0 = cfg + (size_t)(i / MB) * MB * NC;      // first case of the launch: the launch constants must agree
+    const float T0 = fcfg[3 * (i / MB) * MB];
+    if (k[0] != k0[0] || k[1] != k0[1] || k[9] != k0[9] ||
+        (k[0] == 0 && (k[2] != k0[2] || k[3] != k0[3] || memcmp(&T, &T0, 4) != 0)))
+      FAIL(VX_EINVAL, "vx_dev_sample: case %d differs from the first case of its launch in a launch constant (kernel, splitk, gen_stride; "
+           "kernel 0 also top_k, temperature, force_eos_at)", i);
+  }
+  HIPCHK(hipSetDevice(c->dev));
+  // scratch: one float block and one int block, both sized for the largest launch
+  int ng_top = 0;
+  for (int i = 0; i < n; ++i) ng_top = std::max(ng_top, cfg[(size_t)i * NC + 5]);
+  const size_t f_part = 0, f_u = f_part + (size_t)4 * MB * PRED_NPAD, f_slp = f_u + (size_t)(ng_top + 1) * MB, f_lg = f_slp + MB,
+               fh = f_lg + (size_t)MB * AR_LOGITS, fxp = fh + (size_t)MB * D_MODEL, fend = fxp + (size_t)MB * D_MODEL;
+  static_assert((MB * AR_LOGITS) % 4 == 0 && (MB * PRED_NPAD) % 4 == 0, "emb_h / emb_xp take 16-byte vector stores");
+  enum { I_ACT = 0, I_NGEN = MB, I_TOK = 2 * MB, I_POS = 3 * MB, I_CTX = 4 * MB, I_TLEN = 5 * MB, I_SLOT = 6 * MB, I_NACT = 7 * MB, I_META = 7 * MB + 4,
+         I_SMP = I_META + 4 * MB, I_GEN = I_SMP + 4 * MB };
+  const size_t i_end = I_GEN + (size_t)MB * GS_MAX;
+  float* df = nullptr;
+  int* di = nullptr;
+  auto cleanup = [&]() { if (df) (void)hipFree(df); if (di) (void)hipFree(di); };
+  hipError_t he;
+#define TRY(x) if ((he = (x)) != hipSuccess) { cleanup(); c->err = std::string(#x) + ": " + hipGetErrorString(he); return VX_EHIP; }
+#define TRYX(x) do { if (int _e = (x)) { cleanup(); return _e; } } while (0)
+  TRY(hipMalloc((void**)&df, fend * 4));
+  TRY(hipMalloc((void**)&di, i_end * 4));
+  const float* emb_tab = W(c, "ar_audio_embedding.word_embeddings.weight");
+  const float* emb_alpha = W(c, "ar_audio_position.alpha");
+  if (!emb_tab || !emb_alpha || c->ar.empty()) { cleanup(); FAIL(VX_ESTATE, "vx_dev_sample: the context has no AR embedding / layer 0"); }
+  std::vector<float> hf(fend);
+  std::vector<int> hi;
+  for (int l0 = 0; l0 < n; l0 += MB) {
+    const int nr = std::min(MB, n - l0);
+    const int32_t* k0 = cfg + (size_t)l0 * NC;
+    const int kernel = k0[0], splitk = k0[1], gs = k0[9];
+    std::fill(hf.begin(), hf.end(), VX_DEV_SENTINEL_F);
+    hi.assign(I_GEN + (size_t)MB * gs, VX_DEV_SENTINEL_I);
+    int nact = 0;
+    for (int b = 0; b < MB; ++b) {
+      const int slot = (7 * b + 3) % MB;                        // a permutation of the launch slots: slot != row
+      hi[I_SLOT + b] = slot;
+      hi[I_ACT + b] = 0;                                         // rows without a case: inactive
+      hi[I_NGEN + b] = hi[I_POS + b] = hi[I_CTX + b] = hi[I_TLEN + b] = 0;
+      hi[I_META + 4 * slot] = b; hi[I_META + 4 * slot + 1] = 0; hi[I_META + 4 * slot + 2] = 0;
+      hi[I_SMP + 4 * b] = 1; hi[I_SMP + 4 * b + 1] = 0x3F800000; hi[I_SMP + 4 * b + 2] = -1; hi[I_SMP + 4 * b + 3] = 0;
+      hf[f_slp + b] = 0.f;
+      for (int ks = 0; ks < 4; ++ks) for (int j = 0; j < PRED_NPAD; ++j) hf[f_part + ((size_t)ks * MB + b) * PRED_NPAD + j] = 0.f;
+      if (b >= nr) continue;
+      const int32_t* k = k0 + (size_t)b * NC;
+      const float* f = fcfg + 3 * (size_t)(l0 + b);
+      hi[I_ACT + b] = k[4]; hi[I_NGEN + b] = k[5]; hi[I_POS + b] = k[6]; hi[I_CTX + b] = k[7]; hi[I_TLEN + b] = k[8];
+      hi[I_META + 4 * slot + 1] = k[7]; hi[I_META + 4 * slot + 2] = k[4];
+      hi[I_SMP + 4 * b] = k[2]; memcpy(&hi[I_SMP + 4 * b + 1], &f[0], 4); hi[I_SMP + 4 * b + 2] = k[3];
+      hf[f_u + (size_t)k[5] * MB + b] = f[1];
+      hf[f_slp + b] = f[2];
+      nact += k[4];
+      for (int ks = 0; ks < splitk; ++ks)
+        memcpy(&hf[f_part + ((size_t)ks * MB + b) * PRED_NPAD], partial + ((size_t)(l0 + b) * 4 + ks) * AR_LOGITS, AR_LOGITS * 4);
+    }
+    hi[I_NACT] = nact;
+    TRYX(xfer_h2d(c, df, hf.data(), fend * 4));
+    TRYX(xfer_h2d(c, di, hi.data(), hi.size() * 4));
+    bool ok;
+    if (kernel == 0) {
+      SampleArgs a{};
+      a.partial = df + f_part; a.splitk = splitk; a.npad = PRED_NPAD;
+      a.top_k = k0[2]; a.temperature = fcfg[3 * (size_t)l0]; a.force_eos_at = k0[3];
+      a.uniforms = df + f_u; a.uniforms_stride = MB; a.seed_dev = c->seed_dev; a.commit = 1;
+      a.cur_tok = di + I_TOK; a.cur_pos = di + I_POS; a.ctx_len = di + I_CTX; a.n_gen = di + I_NGEN; a.active = di + I_ACT;
+      a.n_active = di + I_NACT; a.text_len = di + I_TLEN; a.slot_meta = di + I_META; a.slot_of = di + I_SLOT;
+      a.gen = di + I_GEN; a.gen_stride = gs; a.logits_out = df + f_lg; a.sum_logp = df + f_slp; a.batch = MB;
+      a.emb_tab = emb_tab; a.emb_alpha = emb_alpha; a.pe = c->pe; a.ln_g = c->ar[0].n1_w; a.ln_b = c->ar[0].n1_b;
+      a.emb_h = df + fh; a.emb_xp = df + fxp; a.wt = 1;
+      ok = launch_dec_sample(a, c->stream);
+    } else {
+      ServeSampleArgs a{};
+      a.partial = df + f_part; a.splitk = splitk; a.npad = PRED_NPAD; a.row_smp = di + I_SMP;
+      a.uniforms = df + f_u; a.uniforms_stride = MB;
+      a.cur_tok = di + I_TOK; a.cur_pos = di + I_POS; a.ctx_len = di + I_CTX; a.n_gen = di + I_NGEN; a.active = di + I_ACT;
+      a.n_active = di + I_NACT; a.text_len = di + I_TLEN; a.slot_meta = di + I_META; a.slot_of = di + I_SLOT;
+      a.gen = di + I_GEN; a.gen_stride = gs; a.sum_logp = df + f_slp; a.batch = MB;
+      a.emb_tab = emb_tab; a.emb_alpha = emb_alpha; a.pe = c->pe; a.ln_g = c->ar[0].n1_w; a.ln_b = c->ar[0].n1_b;
+      a.emb_h = df + fh; a.emb_xp = df + fxp; a.wt = 1;
+      ok = launch_serve_sample(a, c->stream);
+    }
+    if (!ok) { cleanup(); FAIL(VX_EINVAL, "vx_dev_sample: split-K factor not compiled in"); }
+    std::vector<float> of(fend);
+    std::vector<int> oi(hi.size());
+    TRYX(xfer_d2h(c, of.data(), df, fend * 4));
+    TRYX(xfer_d2h(c, oi.data(), di, oi.size() * 4));
+    TRYX(xfer_sync(c));
+    TRY(hipGetLastError());
+    for (int b = 0; b < nr; ++b) {
+      const size_t i = (size_t)l0 + b;
+      const int slot = (7 * b + 3) % MB, ng0 = k0[(size_t)b * NC + 5];
+      int32_t* st = state + i * NS;
+      st[0] = oi[I_ACT + b]; st[1] = oi[I_NGEN + b]; st[2] = oi[I_TOK + b]; st[3] = oi[I_POS + b]; st[4] = oi[I_CTX + b];
+      for (int w = 0; w < 4; ++w) st[5 + w] = oi[I_META + 4 * slot + w];
+      st[9] = ng0 < gs ? oi[I_GEN + (size_t)b * gs + ng0] : VX_DEV_SENTINEL_I;
+      st[10] = oi[I_NACT];
+      st[11] = slot;
+      sum_logp[i] = of[f_slp + b];
+      memcpy(logits + i * AR_LOGITS, &of[f_lg + (size_t)b * AR_LOGITS], AR_LOGITS * 4);
+      memcpy(emb_h + i * D_MODEL, &of[fh + (size_t)b * D_MODEL], D_MODEL * 4);
+      // the packed-x image (decode.hip ln_pack_row): float4 column c4 of decode row b lives at ((c4 >> 1) * 64 + b + 32 * (c4 & 1)) * 4
+      for (int c4 = 0; c4 < D_MODEL / 4; ++c4)
+        memcpy(emb_xp + i * D_MODEL + 4 * c4, &of[fxp + (((size_t)(c4 >> 1) * 64) + b + 32 * (c4 & 1)) * 4], 16);
+    }
+  }
+#undef TRY
+#undef TRYX
+  cleanup();
+  return VX_OK;
+}
+
+// vx_dev_attn: one launch of a full-sequence attention kernel on the caller's packed q|k|v rows; seq_off / c_off are derived here.
+int vx_dev_attn(vx_ctx* c, int32_t variant, int32_t planes, int32_t batch, const float* qkv, const int32_t* seq_len,
+                const int32_t* prefix_len, const int32_t* q_first, float* out, int64_t out_rows, int32_t* range_flag) {
+  if (!c) return VX_EINVAL;
+  if (!qkv || !seq_len || !out || batch <= 0 || batch > 256) FAIL(VX_EINVAL, "vx_dev_attn: null argument or batch outside 1 .. 256");
+  if ((variant != 0 && variant != 10 && variant != 20) || (planes != 0 && planes != 1) || (planes && variant == 0))
+    FAIL(VX_EINVAL, "vx_dev_attn: variant must be 0, 10 or 20; planes 0 or 1 (1: variants 10 and 20)");
+  if (q_first && !((variant == 0 && !planes) || (variant == 20 && planes)))
+    FAIL(VX_EINVAL, "vx_dev_attn: q_first goes with variant 0 (fp32 rows) or variant 20 with planes: the launchers that trim");
+  std::vector<int> meta(5 * (size_t)batch, 0);          // seq_off | seq_len | prefix_len | q_first | c_off
+  long M = 0, rows = 0;
+  int max_len = 0;
+  for (int b = 0; b < batch; ++b) {
+    const int len = seq_len[b];
+    if (len <= 0 || len > 65536 || (prefix_len && (prefix_len[b] < 0 || prefix_len[b] > len)) || (q_first && (q_first[b] < 0 || q_first[b] > len)))
+      FAIL(VX_EINVAL, "vx_dev_attn: sequence %d: 1 <= len <= 65536, 0 <= prefix_len <= len, 0 <= q_first <= len", b);
+    meta[b] = (int)M; meta[batch + b] = len;
+    meta[2 * batch + b] = prefix_len ? prefix_len[b] : 0;
+    meta[3 * batch + b] = q_first ? q_first[b] : 0;
+    meta[4 * batch + b] = (int)rows;
+    M += len; rows += len - (q_first ? q_first[b] : 0);
+    max_len = std::max(max_len, len);
+    if (M > (1 << 20)) FAIL(VX_EINVAL, "vx_dev_attn: more than 2^20 rows");
+  }
+  if (out_rows < rows || out_rows > rows + 4096) FAIL(VX_EINVAL, "vx_dev_attn: out_rows must be %ld .. %ld", rows, rows + 4096);
+  HIPCHK(hipSetDevice(c->dev));
+  const long pstride = h2_plane(out_rows, D_MODEL, H2_TILE_A);
+  float *dq = nullptr, *dout = nullptr;
+  unsigned short* dpl = nullptr;
+  int* dmeta = nullptr;
+  auto cleanup = [&]() { for (void* p : {(void*)dq, (void*)dout, (void*)dpl, (void*)dmeta}) if (p) (void)hipFree(p); };
+  hipError_t he;
+#define TRY(x) if ((he = (x)) != hipSuccess) { cleanup(); c->err = std::string(#x) + ": " + hipGetErrorString(he); return VX_EHIP; }
+#define TRYX(x) do { if (int _e = (x)) { cleanup(); return _e; } } while (0)
+  TRY(hipMalloc((void**)&dq, (size_t)M * 3 * D_MODEL * 4));
+  TRY(hipMalloc((void**)&dmeta, (meta.size() + 4) * 4));
+  meta.resize(meta.size() + 4, 0);                                 // + the range flag, zero
+  int* dflag = dmeta + 5 * (size_t)batch;
+  TRYX(xfer_h2d(c, dq, qkv, (size_t)M * 3 * D_MODEL * 4));
+  TRYX(xfer_h2d(c, dmeta, meta.data(), meta.size() * 4));
+  if (planes) {
+    TRY(hipMalloc((void**)&dpl, (size_t)2 * pstride * 2));
+    std::vector<unsigned short> fill((size_t)2 * pstride, VX_DEV_SENTINEL_H);
+    TRYX(xfer_h2d(c, dpl, fill.data(), fill.size() * 2));
+  } else {
+    TRY(hipMalloc((void**)&dout, (size_t)out_rows * D_MODEL * 4));
+    std::vector<float> fill((size_t)out_rows * D_MODEL, VX_DEV_SENTINEL_F);
+    TRYX(xfer_h2d(c, dout, fill.data(), fill.size() * 4));
+  }
+  const int *d_off = dmeta, *d_len = dmeta + batch, *d_pre = prefix_len ? dmeta + 2 * batch : nullptr,
+            *d_qf = q_first ? dmeta + 3 * batch : nullptr, *d_co = q_first ? dmeta + 4 * batch : nullptr;
+  if (variant == 0) launch_attn_full(dq, dout, d_off, d_len, d_pre, batch, max_len, c->stream, d_qf, d_co);
+  else if (variant == 10) launch_attn_full_x3(dq, dout, d_off, d_len, d_pre, batch, max_len, 0, c->stream, dpl, pstride);
+  else launch_attn_full_h2(dq, dout, d_off, d_len, d_pre, batch, max_len, c->stream, dpl, pstride, dflag, -1, d_qf, d_co);
+  int flag = 0;
+  std::vector<unsigned short> hp(planes ? (size_t)2 * pstride : 0);
+  if (!planes) TRYX(xfer_d2h(c, out, dout, (size_t)out_rows * D_MODEL * 4));
+  else TRYX(xfer_d2h(c, hp.data(), dpl, hp.size() * 2));
+  TRYX(xfer_d2h(c, &flag, dflag, 4));
+  TRYX(xfer_sync(c));
+  if (planes) {
+    // f16x2 A planes of out_proj (vx_common.h): tile-major [rows / 256][K / 32][256][32], x * 2^5 = head + tail
+    for (long r = 0; r < out_rows; ++r)
+      for (int col = 0; col < D_MODEL; ++col) {
+        const size_t idx = ((((size_t)(r >> 8) * (D_MODEL / 32)) + (col >> 5)) * 256 + (r & 255)) * 32 + (col & 31);
+        const unsigned short hh = hp[idx], tt = hp[idx + pstride];
+        _Float16 fh_, ft_;
+        memcpy(&fh_, &hh, 2); memcpy(&ft_, &tt, 2);
+        out[(size_t)r * D_MODEL + col] = (hh == VX_DEV_SENTINEL_H && tt == VX_DEV_SENTINEL_H) ? VX_DEV_SENTINEL_F
+                                                                                               : ((float)fh_ + (float)ft_) * (1.0f / H2_ACT_SCALE);
+      }
+  }
+  TRY(hipGetLastError());
+  if (range_flag) *range_flag = flag;
+#undef TRY
+#undef TRYX
+  cleanup();
+  return VX_OK;
+}
+
 }  // extern "C"

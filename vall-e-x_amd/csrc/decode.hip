@@ -816,6 +816,16 @@ bool launch_skinny16_sb_ln(const float* W16, const float* bias, float* xp_out, i
   return true;
 }
 
+// c + a * b as TWO fp32 operations, the product rounded before the add -- what torch does for `emb + alpha * pe`
+// (modules/embedding.py:93-97).  __fmul_rn / __fadd_rn are a plain `*` and `+` in this toolchain and contract into one fma under
+// hipcc's default -ffp-contract=fast (found by tests/test_gpu_kernel_sampler.py: v_pk_fma_f32 in the sampler's fused embedding);
+// the pragma keeps the two roundings.
+__device__ __forceinline__ float mul_add_unfused(float a, float b, float c) {
+#pragma clang fp contract(off)
+  const float p = a * b;
+  return c + p;
+}
+
 // Start of a step: embed the newest token of each row at its audio position (the reference re-embeds all of y and
 // keeps the last row, models/vallex.py:529-531,552-553), then norm1 of layer 0.
 __global__ __launch_bounds__(64) void dec_embed_ln_pack_kernel(const int* __restrict__ tok,
@@ -838,7 +848,7 @@ __global__ __launch_bounds__(64) void dec_embed_ln_pack_kernel(const int* __rest
     v[i] = *reinterpret_cast<const f32x4*>(tab + trow + c);
     const f32x4 p = *reinterpret_cast<const f32x4*>(pe + prow + c);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[i][e] = __fadd_rn(v[i][e], __fmul_rn(a, p[e]));
+    for (int e = 0; e < 4; ++e) v[i][e] = mul_add_unfused(a, p[e], v[i][e]);
     *reinterpret_cast<f32x4*>(h + (long)b * D_MODEL + c) = v[i];
   }
   ln_pack_row(v, b, gg, be, xp);
@@ -1740,7 +1750,7 @@ __global__ __launch_bounds__(64) void dec_sample_kernel(SampleArgs a) {
     const int cc = (lane + 64 * i) * 4;
     hv[i] = *reinterpret_cast<const f32x4*>(a.emb_tab + (long)tok * D_MODEL + cc);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) hv[i][q] = __fadd_rn(hv[i][q], __fmul_rn(alpha, pe4[i][q]));
+    for (int q = 0; q < 4; ++q) hv[i][q] = mul_add_unfused(alpha, pe4[i][q], hv[i][q]);
     store_result(a.emb_h + (long)b * D_MODEL + cc, hv[i], a.wt != 0);
   }
   ln_pack_row(hv, b, gg, be, a.emb_xp, a.wt != 0);

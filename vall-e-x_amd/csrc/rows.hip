@@ -114,6 +114,16 @@ void launch_layernorm(const float* x, int ldx, float* y, int ldy, int rows, int 
                        nullptr);
 }
 
+// c + a * b as TWO fp32 operations, the product rounded before the add -- what torch does for `emb + alpha * pe`
+// (modules/embedding.py:93-97).  __fmul_rn / __fadd_rn are a plain `*` and `+` in this toolchain and contract into one fma under
+// hipcc's default -ffp-contract=fast (found by tests/test_gpu_kernel_sampler.py: v_pk_fma_f32 in the sampler's fused embedding);
+// the pragma keeps the two roundings.
+__device__ __forceinline__ float mul_add_unfused(float a, float b, float c) {
+#pragma clang fp contract(off)
+  const float p = a * b;
+  return c + p;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Embedding rows.  TokenEmbedding (modules/embedding.py:43-47) + language embedding add
 // (models/vallex.py:504-505) + SinePositionalEmbedding (modules/embedding.py:93-97:
@@ -140,7 +150,7 @@ __global__ __launch_bounds__(256) void embed_rows_kernel(float* __restrict__ out
   const float a = alpha[0];
   const f32x4 p = *reinterpret_cast<const f32x4*>(pe + (long)pos[row] * D_MODEL + t * 4);
 #pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = __fadd_rn(v[e], __fmul_rn(a, p[e]));
+  for (int e = 0; e < 4; ++e) v[e] = mul_add_unfused(a, p[e], v[e]);
   *reinterpret_cast<f32x4*>(out + (long)(dst ? dst[row] : row) * D_MODEL + t * 4) = v;
 }
 
@@ -186,7 +196,7 @@ __global__ __launch_bounds__(256) void add_pe_scatter_kernel(float* __restrict__
   const f32x4 p = *reinterpret_cast<const f32x4*>(pe + (long)pos[row] * D_MODEL + t * 4);
   const float a = alpha[0];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = __fadd_rn(v[e], __fmul_rn(a, p[e]));
+  for (int e = 0; e < 4; ++e) v[e] = mul_add_unfused(a, p[e], v[e]);
   *reinterpret_cast<f32x4*>(out + (long)dst[row] * D_MODEL + t * 4) = v;
 }
 

@@ -72,6 +72,16 @@ __device__ __forceinline__ int sum64i(int x) {
   return __builtin_amdgcn_readlane(x, 63);
 }
 
+// c + a * b as TWO fp32 operations, the product rounded before the add -- what torch does for `emb + alpha * pe`
+// (modules/embedding.py:93-97).  __fmul_rn / __fadd_rn are a plain `*` and `+` in this toolchain and contract into one fma under
+// hipcc's default -ffp-contract=fast (found by tests/test_gpu_kernel_sampler.py: v_pk_fma_f32 in the sampler's fused embedding);
+// the pragma keeps the two roundings.
+__device__ __forceinline__ float mul_add_unfused(float a, float b, float c) {
+#pragma clang fp contract(off)
+  const float p = a * b;
+  return c + p;
+}
+
 // LayerNorm of one 1024-wide row held as lane l's float4 columns l + 64 i, written in the packed-x image (decode.hip ln_pack_row)
 __device__ __forceinline__ void ln_pack(const f32x4 (&v)[4], int b, const f32x4 (&gg)[4], const f32x4 (&be)[4], float* __restrict__ xp,
                                         bool wt) {
@@ -246,7 +256,7 @@ __global__ __launch_bounds__(64) void serve_sample_kernel(ServeSampleArgs a) {
     const int cc = (lane + 64 * i) * 4;
     hv[i] = *reinterpret_cast<const f32x4*>(a.emb_tab + (long)tok * D_MODEL + cc);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) hv[i][q] = __fadd_rn(hv[i][q], __fmul_rn(alpha, pe4[i][q]));
+    for (int q = 0; q < 4; ++q) hv[i][q] = mul_add_unfused(alpha, pe4[i][q], hv[i][q]);
     store_wt(a.emb_h + (long)b * D_MODEL + cc, hv[i], a.wt != 0);
   }
   ln_pack(hv, b, gg, be, a.emb_xp, a.wt != 0);
