@@ -146,7 +146,9 @@ int vx_infer_continuous(vx_ctx* ctx, const vx_batch* b, const vx_sampling* s, vx
 /* Serving session (additive: VX_ABI_VERSION stays 6).  vx_infer and vx_infer_continuous take a closed batch; a session takes
  * requests at any time and admits each into the running decode batch as soon as enough decode rows are free.  Contract: a request
  * returns exactly what a batch-1 vx_infer call on it returns (same seed or same draws, same best_of / length_penalty /
- * return_worst, same top_k / temperature / force_eos_at), whatever else is in the session.
+ * return_worst, same top_k / temperature / force_eos_at), whatever else is in the session.  With per-request filters
+ * (vx_request_filters, vx_serve_submit_filtered) the same holds: a request returns the same result whatever else is in the session,
+ * and with the neutral filters (top_p 1, repetition_penalty 1, min_frames 0) it returns what that batch-1 vx_infer call returns.
  *   - Per request: best_of, length_penalty, return_worst, seed or injected uniforms (vx_request), and top_k, temperature and
  *     force_eos_at (vx_request_sampling, vx_serve_submit_ex).  Session-wide: sync_every only.  The session samples every decode row
  *     with its own request's top_k / temperature / force_eos_at; vx_serve_open's values are the defaults of vx_serve_submit.
@@ -210,6 +212,27 @@ typedef struct vx_request_sampling {
 int vx_serve_submit_ex(vx_serve* srv, const vx_batch* rows, const vx_request* req,
                        const vx_request_sampling* smp /* [rows->batch] or NULL */, int64_t* ids_out);
 int vx_serve_cancel(vx_serve* srv, int64_t request_id, int32_t* state /* may be NULL */);
+/* Per-request logit filters of a serving session, applied per decode row to the row's fp32 logits in this order: repetition
+ * penalty, min_frames, temperature, top_k, top_p, then the draw.
+ *   - repetition_penalty r over the request's own generated frames (per beam; the prompt does not count), the last
+ *     repetition_window of them (0: all): every token that occurs there, once however often, gets l > 0 ? l / r : l * r.
+ *   - min_frames m: EOS cannot be sampled while fewer than m frames are generated.  The stop rules still end the request
+ *     (16 x text length, max_new, force_eos_at, which overrides the sample as before).
+ *   - top_p: nucleus sampling over the tokens top_k left (top_k_top_p_filtering, models/vallex.py:811-832): a token stays iff the
+ *     probability mass of the strictly larger logits is <= top_p.  Every token tied with the last kept value is kept (the reference's
+ *     unstable sort splits such a tie arbitrarily).  sum(logp) of best_of is taken under the filtered distribution.
+ * flt NULL: exactly vx_serve_submit_ex.  Checked (VX_EINVAL, nothing enqueued, the message names the field): struct_size; top_p finite,
+ * > 0 and <= 1; repetition_penalty finite and > 0; repetition_window >= 0; min_frames >= 0. */
+typedef struct vx_request_filters {
+  uint32_t struct_size;         /* = sizeof(vx_request_filters) */
+  float top_p;                  /* (0, 1]; 1: off */
+  float repetition_penalty;     /* > 0; 1: off */
+  int32_t repetition_window;    /* frames looked back; 0: every generated frame */
+  int32_t min_frames;           /* 0: off */
+} vx_request_filters;
+int vx_serve_submit_filtered(vx_serve* srv, const vx_batch* rows, const vx_request* req,
+                             const vx_request_sampling* smp /* [rows->batch] or NULL */,
+                             const vx_request_filters* flt /* [rows->batch] or NULL */, int64_t* ids_out);
 
 /* replaces: vocos.codes_to_features + vocos.decode(features, bandwidth_id), utils/generation.py:148-150.
  * codes [batch][codes_stride][8] int64, lens [batch] frames; audio [batch][audio_stride] fp32, 320*len samples each. */

@@ -71,6 +71,14 @@ int vx_bench_gemm_epilogue(vx_ctx* ctx, int32_t M, int32_t N, int32_t K, int32_t
  * layer 0. */
 int vx_dev_sample(vx_ctx* ctx, int32_t n, const int32_t* cfg, const float* fcfg, const float* partial, float* logits, int32_t* state,
                   float* sum_logp, float* emb_h, float* emb_xp);
+/* vx_dev_sample for kernel 1 only (cfg[i][0] must be 1), with the per-row filter record of the serving session's sampler:
+ *   ffilt [n][2] = {top_p, repetition_penalty};  ifilt [n][2] = {repetition_window, min_frames}
+ *   hist  [n][hist_stride] int32: the case's first min(n_gen, gen_stride) generated tokens, copied into its gen row before the
+ *                                 launch (hist_stride >= that count for every case; hist may be NULL when all counts are 0)
+ * Same sentinels and outputs (gen[row][old n_gen] is still reported from the slot the sample writes). */
+int vx_dev_sample_filtered(vx_ctx* ctx, int32_t n, const int32_t* cfg, const float* fcfg, const float* ffilt, const int32_t* ifilt,
+                           const int32_t* hist, int32_t hist_stride, const float* partial, float* logits, int32_t* state,
+                           float* sum_logp, float* emb_h, float* emb_xp);
 /* One launch of a full-sequence attention kernel: variant 0 fp32, 10 bf16x3, 20 f16x2; planes 1 (variants 10, 20): the output leaves
  * as the fp16 head / tail planes of out_proj, read back and returned as (head + tail) / 2^5.  qkv [sum seq_len][3072]; prefix_len
  * NULL: no mask; q_first (variant 0 with fp32 rows, variant 20 with planes) or NULL: only rows [q_first[b], seq_len[b]) of every

@@ -18,6 +18,10 @@ is still undelivered at the first point between two vx_serve_run calls lying --c
 (vx_serve_cancel).  Which candidates that catches depends on wall-clock timing, so every repeat records how many it cancelled
 ("cancelled"), and ids are compared only for requests delivered in both runs.  The JSON then also compares the latency of the
 requests that are not candidates with and without the cancellations ("cancel").
+--top-p / --repetition-penalty / --repetition-window / --min-frames give every session request those logit filters
+(vx_serve_submit_filtered).  With the defaults (1, 1, 0, 0) the session submits exactly as without them.  vx_infer has no filters, so
+with any of them set the batched leg still runs unfiltered, for the timing only, and ids are compared between the repeats of the
+session legs alone; the JSON records the values under "filters".
    python tools/serve_bench.py [--requests 24] [--gap-ms 60] [--reps 2] [--cancel-frac 0.25] [--out profiles/r09_serve.json]"""
 import argparse
 import json
@@ -60,7 +64,20 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--cancel-frac", type=float, default=0.0)
     ap.add_argument("--cancel-after-ms", type=float, default=100.0)
+    ap.add_argument("--top-p", type=float, default=1.0)
+    ap.add_argument("--repetition-penalty", type=float, default=1.0)
+    ap.add_argument("--repetition-window", type=int, default=0)
+    ap.add_argument("--min-frames", type=int, default=0)
     args = ap.parse_args()
+    flt = {}                                          # only what differs from the neutral values: the default run submits as before
+    if args.top_p != 1.0:
+        flt["top_p"] = args.top_p
+    if args.repetition_penalty != 1.0:
+        flt["repetition_penalty"] = args.repetition_penalty
+    if args.repetition_window != 0:
+        flt["repetition_window"] = args.repetition_window
+    if args.min_frames != 0:
+        flt["min_frames"] = args.min_frames
     import torch
     if not torch.cuda.is_available():
         sys.exit("serve_bench: no GPU (this tool measures the MI355X; it prints no numbers without one)")
@@ -106,7 +123,7 @@ def main():
                 while nxt < K and arrive[nxt] <= now:
                     nxt += 1
                 if nxt > k0:
-                    ids = sess.submit(m.make_batch(rows[k0:nxt]), [dict(best_of=N, uniforms=us[i]) for i in range(k0, nxt)])
+                    ids = sess.submit(m.make_batch(rows[k0:nxt]), [dict(best_of=N, uniforms=us[i], **flt) for i in range(k0, nxt)])
                     rid2i.update({rid: i for rid, i in zip(ids, range(k0, nxt))})
                     i2rid.update({i: rid for rid, i in zip(ids, range(k0, nxt))})
                 live, waiting = sess.run(args.run_steps, on_done)
@@ -143,7 +160,7 @@ def main():
     if to_cancel:
         legs["session_cancel"] = lambda: session(frozenset(to_cancel))
     ref = {k: f()[1] for k, f in legs.items()}                       # warm-up: graph capture of both legs
-    ids_equal = all(a.shape == b.shape and np.array_equal(a, b) for a, b in zip(ref["session"], ref["batched"]))
+    ids_equal = bool(flt) or all(a.shape == b.shape and np.array_equal(a, b) for a, b in zip(ref["session"], ref["batched"]))
     if to_cancel:       # the requests that were not cancelled return what they return without the cancellations
         ids_equal = ids_equal and all(np.array_equal(ref["session_cancel"][i], ref["session"][i]) for i in keep)
         ids_equal = ids_equal and all(np.array_equal(a, b) for a, b in zip(ref["session_cancel"], ref["session"]) if a is not None)
@@ -167,7 +184,7 @@ def main():
             r["live_frac"].append(N * st["frames"] / max(1, st["ar_steps"] * MBR))
     out = dict(tool="tools/serve_bench.py", device=torch.cuda.get_device_name(0), layers=12, requests=K, best_of=N,
                gap_ms=args.gap_ms, arrival_span_s=float(arrive[-1]), text_len=[args.s_lo, args.s_hi], run_steps=args.run_steps,
-               reps=args.reps, frames_per_request=[int(len(o)) for o in ref["session"]], ids_equal=bool(ids_equal),
+               reps=args.reps, filters=flt, frames_per_request=[int(len(o)) for o in ref["session"]], ids_equal=bool(ids_equal),
                legs={k: {m_: round(float(statistics.median(v)), 3) for m_, v in r.items()} for k, r in res.items()},
                spread={k: {m_: [round(float(min(v)), 3), round(float(max(v)), 3)] for m_, v in r.items()} for k, r in res.items()})
     s_, b_ = out["legs"]["session"], out["legs"]["batched"]

@@ -67,6 +67,12 @@ class vx_request_sampling(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("top_k", C.c_int32), ("temperature", C.c_float), ("force_eos_at", C.c_int32)]
 
 
+class vx_request_filters(C.Structure):
+    """per-request logit filters of a serving session (vx_serve_submit_filtered); neutral: top_p 1, repetition_penalty 1, 0, 0"""
+    _fields_ = [("struct_size", C.c_uint32), ("top_p", C.c_float), ("repetition_penalty", C.c_float),
+                ("repetition_window", C.c_int32), ("min_frames", C.c_int32)]
+
+
 # every symbol include/vallex_hip.h declares (tests/test_abi.py checks the library exports exactly these)
 ABI_VERSION = 6       # VX_ABI_VERSION of include/vallex_hip.h this binding was written against
 
@@ -74,10 +80,10 @@ SYMBOLS = ["vx_abi_version", "vx_create", "vx_destroy", "vx_last_error", "vx_syn
            "vx_infer", "vx_vocos_decode", "vx_encodec_decode", "vx_encodec_encode", "vx_ar_prefill", "vx_ar_logits", "vx_ar_step",
            "vx_nar", "vx_read_tap", "vx_last_stats", "vx_last_truncated", "vx_last_fallbacks", "vx_fallback_state",
            "vx_fallback_reset", "vx_arith_mode", "vx_infer_continuous", "vx_serve_open", "vx_serve_submit", "vx_serve_run",
-           "vx_serve_close", "vx_serve_submit_ex", "vx_serve_cancel"]
+           "vx_serve_close", "vx_serve_submit_ex", "vx_serve_cancel", "vx_serve_submit_filtered"]
 # ... and include/vallex_hip_dev.h: measurement / kernel development, never called by the mirrors of the reference API
 DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kernel", "vx_bench_gemm", "vx_bench_attn",
-               "vx_bench_gemm_clock", "vx_bench_gemm_epilogue", "vx_dev_sample", "vx_dev_attn"]
+               "vx_bench_gemm_clock", "vx_bench_gemm_epilogue", "vx_dev_sample", "vx_dev_attn", "vx_dev_sample_filtered"]
 # sentinels the correctness entries pre-fill their outputs with (include/vallex_hip_dev.h)
 DEV_SENTINEL_I = -123456789
 DEV_SENTINEL_F = np.float32(-1.0e30)
@@ -132,6 +138,8 @@ def load_library() -> C.CDLL:
     lib.vx_serve_close.argtypes = [C.c_void_p]
     lib.vx_serve_submit_ex.argtypes = [C.c_void_p, P(vx_batch), P(vx_request), P(vx_request_sampling), P(C.c_int64)]
     lib.vx_serve_cancel.argtypes = [C.c_void_p, C.c_int64, P(C.c_int32)]
+    lib.vx_serve_submit_filtered.argtypes = [C.c_void_p, P(vx_batch), P(vx_request), P(vx_request_sampling), P(vx_request_filters),
+                                             P(C.c_int64)]
     lib.vx_vocos_decode.argtypes = [ctx, P(C.c_int64), C.c_int32, P(C.c_int32), C.c_int32, C.c_int32, P(C.c_float),
                                     C.c_int64]
     lib.vx_encodec_decode.argtypes = [ctx, P(C.c_int64), C.c_int32, P(C.c_int32), C.c_int32, P(C.c_float), C.c_int64]
@@ -154,6 +162,9 @@ def load_library() -> C.CDLL:
                                         P(C.c_double)]
     lib.vx_dev_sample.argtypes = [ctx, C.c_int32, P(C.c_int32), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_int32), P(C.c_float),
                                   P(C.c_float), P(C.c_float)]
+    lib.vx_dev_sample_filtered.argtypes = [ctx, C.c_int32, P(C.c_int32), P(C.c_float), P(C.c_float), P(C.c_int32), P(C.c_int32),
+                                           C.c_int32, P(C.c_float), P(C.c_float), P(C.c_int32), P(C.c_float), P(C.c_float),
+                                           P(C.c_float)]
     lib.vx_dev_attn.argtypes = [ctx, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), P(C.c_int32), P(C.c_int32), P(C.c_int32),
                                 P(C.c_float), C.c_int64, P(C.c_int32)]
     lib.vx_last_stats.argtypes = [ctx, P(C.c_int64), P(C.c_int64), P(C.c_double), P(C.c_double)]
@@ -467,12 +478,24 @@ class Engine:
         return us.value, md.value
 
     def dev_sample(self, cases: Sequence[dict]):
+        """vx_dev_sample: the decode sampler on chosen cases (keys, defaults and outputs: _dev_sample)"""
+        return self._dev_sample(cases, False)
+
+    def dev_sample_filtered(self, cases: Sequence[dict]):
+        """vx_dev_sample_filtered: dev_sample for kernel 1 (serve_sample_kernel, the default here) with the per-row filter record.
+        Every case takes dev_sample's keys plus top_p (1.0), repetition_penalty (1.0), repetition_window (0), min_frames (0) and
+        hist: the row's first n_gen generated tokens (int sequence, at least min(n_gen, gen_stride) long; it may be left out when
+        repetition_penalty is 1, which reads no history).  Same
+        outputs as dev_sample."""
+        return self._dev_sample(cases, True)
+
+    def _dev_sample(self, cases: Sequence[dict], filtered: bool):
         """vx_dev_sample: the decode sampler on chosen cases.  Each case is a dict with the keys of DEV_SAMPLE_CFG (defaults: kernel 0,
         splitk 1, top_k -100, force_eos_at -1, active 1, n_gen 0, cur_pos 0, ctx_len 1, text_len 1, gen_stride 16) plus temperature
         (1.0), u (0.0), sum_logp (0.0) and partial (splitk, 1025) float32.  Case i runs in decode row i % 32 of launch i // 32.
         Returns a dict of arrays, one row per case: logits (n, 1025), active, n_gen, cur_tok, cur_pos, ctx_len, slot_meta (n, 4), gen,
         n_active, slot, sum_logp, emb_h (n, 1024), emb_xp (n, 1024)."""
-        dflt = dict(kernel=0, splitk=1, top_k=-100, force_eos_at=-1, active=1, n_gen=0, cur_pos=0, ctx_len=1, text_len=1, gen_stride=16)
+        dflt = dict(kernel=1 if filtered else 0, splitk=1, top_k=-100, force_eos_at=-1, active=1, n_gen=0, cur_pos=0, ctx_len=1, text_len=1, gen_stride=16)
         n = len(cases)
         cfg = np.array([[int(q.get(k, dflt[k])) for k in DEV_SAMPLE_CFG] for q in cases], np.int32).reshape(n, len(DEV_SAMPLE_CFG))
         fcfg = np.array([[q.get("temperature", 1.0), q.get("u", 0.0), q.get("sum_logp", 0.0)] for q in cases], np.float32).reshape(n, 3)
@@ -487,9 +510,24 @@ class Engine:
         slp = np.empty(n, np.float32)
         emb_h = np.empty((n, 1024), np.float32)
         emb_xp = np.empty((n, 1024), np.float32)
-        self._chk(self.lib.vx_dev_sample(self.ctx, n, _ptr(cfg, C.c_int32), _ptr(fcfg, C.c_float), _ptr(part, C.c_float),
-                                         _ptr(logits, C.c_float), _ptr(state, C.c_int32), _ptr(slp, C.c_float), _ptr(emb_h, C.c_float),
-                                         _ptr(emb_xp, C.c_float)))
+        if filtered:
+            ffilt = np.array([[q.get("top_p", 1.0), q.get("repetition_penalty", 1.0)] for q in cases], np.float32).reshape(n, 2)
+            ifilt = np.array([[int(q.get("repetition_window", 0)), int(q.get("min_frames", 0))] for q in cases], np.int32).reshape(n, 2)
+            need = [min(int(cfg[i, 5]), int(cfg[i, 9])) for i in range(n)]
+            hist = np.zeros((n, max(1, max(need))), np.int32)
+            for i, q in enumerate(cases):
+                h = np.asarray(q.get("hist", ()), np.int64).reshape(-1)
+                if len(h) < need[i] and ("hist" in q or ffilt[i, 1] != 1.0):
+                    raise ValueError(f"case {i}: hist has {len(h)} tokens, n_gen is {need[i]}")
+                hist[i, : min(need[i], len(h))] = h[: need[i]]     # no hist and no penalty: the history is never read, zeros
+            self._chk(self.lib.vx_dev_sample_filtered(self.ctx, n, _ptr(cfg, C.c_int32), _ptr(fcfg, C.c_float), _ptr(ffilt, C.c_float),
+                                                      _ptr(ifilt, C.c_int32), _ptr(hist, C.c_int32), hist.shape[1],
+                                                      _ptr(part, C.c_float), _ptr(logits, C.c_float), _ptr(state, C.c_int32),
+                                                      _ptr(slp, C.c_float), _ptr(emb_h, C.c_float), _ptr(emb_xp, C.c_float)))
+        else:
+            self._chk(self.lib.vx_dev_sample(self.ctx, n, _ptr(cfg, C.c_int32), _ptr(fcfg, C.c_float), _ptr(part, C.c_float),
+                                             _ptr(logits, C.c_float), _ptr(state, C.c_int32), _ptr(slp, C.c_float),
+                                             _ptr(emb_h, C.c_float), _ptr(emb_xp, C.c_float)))
         return dict(logits=logits, active=state[:, 0], n_gen=state[:, 1], cur_tok=state[:, 2], cur_pos=state[:, 3], ctx_len=state[:, 4],
                     slot_meta=state[:, 5:9], gen=state[:, 9], n_active=state[:, 10], slot=state[:, 11], sum_logp=slp, emb_h=emb_h,
                     emb_xp=emb_xp)
@@ -555,6 +593,7 @@ class ServeSession:
     seed or draws, same best_of / length_penalty / return_worst, same top_k / temperature / force_eos_at) returns."""
 
     CANCEL_STATES = {0: None, 1: "waiting", 2: "decoding"}      # vx_serve_cancel's state
+    FILTERS = ("top_p", "repetition_penalty", "repetition_window", "min_frames")      # vx_request_filters, per request
 
     def __init__(self, engine: Engine, top_k=-100, temperature=1.0, sync_every=8, force_eos_at=None):
         self.engine = engine
@@ -569,13 +608,28 @@ class ServeSession:
 
     @staticmethod
     def check_request(best_of=1, uniforms=None, rows: Optional[int] = None, top_k=None, temperature=None, force_eos_at=None,
-                      text_len: Optional[int] = None, max_new: Optional[int] = None):
+                      text_len: Optional[int] = None, max_new: Optional[int] = None, top_p=None, repetition_penalty=None,
+                      repetition_window=None, min_frames=None):
         """argument checks of one request, before any GPU work: best_of >= 1 (<= the session's decode rows), uniforms
         (steps, best_of) or (steps,) for best_of 1; top_k an integer, temperature > 0 and finite, force_eos_at an integer >= -1 (each
         None: the session's value).  With text_len (and max_new), uniforms must also cover every draw the request can take,
         min(16 x text_len, max_new, force_eos_at) + 1 steps: a standalone pre-check for callers that want it early --
         submit() and Server.submit() do not pass text_len, the library checks the draws at vx_serve_submit(_ex) (VX_EINVAL, which
-        Server turns into a failed Future of that request only).  Returns the uniforms as a C-contiguous float32 array (or None)."""
+        Server turns into a failed Future of that request only).  The filters (each None: neutral): top_p finite in (0, 1],
+        repetition_penalty finite and > 0, repetition_window and min_frames integers >= 0.  Returns the uniforms as a C-contiguous
+        float32 array (or None)."""
+        if top_p is not None:
+            t = float(top_p)
+            if not np.isfinite(t) or not (0.0 < t <= 1.0) or not (np.float32(t) > 0):
+                raise ValueError(f"top_p must be in (0, 1], got {top_p!r}")
+        if repetition_penalty is not None:
+            t = float(repetition_penalty)
+            if not np.isfinite(t) or not (t > 0.0) or t > float(np.finfo(np.float32).max) or not (np.float32(t) > 0):
+                raise ValueError(f"repetition_penalty must be > 0 and finite, got {repetition_penalty!r}")
+        for name, val in (("repetition_window", repetition_window), ("min_frames", min_frames)):
+            if val is not None and (isinstance(val, bool) or not isinstance(val, (int, np.integer)) or int(val) < 0
+                                    or int(val) > 0x7fffffff):
+                raise ValueError(f"{name} must be an integer >= 0, got {val!r}")
         if isinstance(best_of, bool) or int(best_of) != best_of or int(best_of) < 1:
             raise ValueError(f"best_of must be an integer >= 1, got {best_of!r}")
         n = int(best_of)
@@ -612,16 +666,27 @@ class ServeSession:
         """enqueue batch.n requests (row i of `batch` with requests[i] = dict(best_of=1, seed=0, uniforms=None, length_penalty=1.0,
         return_worst=False, top_k=None, temperature=None, force_eos_at=None)); host copies only.  top_k / temperature /
         force_eos_at None: the session's value; when any request of the call sets one, the call goes through vx_serve_submit_ex.
-        Returns their request ids."""
+        top_p / repetition_penalty / repetition_window / min_frames (each None: neutral = 1.0, 1.0, 0, 0): when any request of the
+        call sets one, the call goes through vx_serve_submit_filtered.  Returns their request ids."""
         if len(requests) != batch.n:
             raise ValueError(f"{len(requests)} requests for {batch.n} rows")
         arr = (vx_request * batch.n)()
         keep = []
         per = any(q.get(k) is not None for q in requests for k in ("top_k", "temperature", "force_eos_at"))
         smp = (vx_request_sampling * batch.n)() if per else None
+        filt = any(q.get(k) is not None for q in requests for k in self.FILTERS)
+        flt = (vx_request_filters * batch.n)() if filt else None
         for i, q in enumerate(requests):
             u = self.check_request(q.get("best_of", 1), q.get("uniforms"), self.rows, q.get("top_k"), q.get("temperature"),
-                                   q.get("force_eos_at"))
+                                   q.get("force_eos_at"), top_p=q.get("top_p"), repetition_penalty=q.get("repetition_penalty"),
+                                   repetition_window=q.get("repetition_window"), min_frames=q.get("min_frames"))
+            if filt:
+                f = flt[i]
+                f.struct_size = C.sizeof(vx_request_filters)
+                f.top_p = float(q["top_p"]) if q.get("top_p") is not None else 1.0
+                f.repetition_penalty = float(q["repetition_penalty"]) if q.get("repetition_penalty") is not None else 1.0
+                f.repetition_window = int(q["repetition_window"]) if q.get("repetition_window") is not None else 0
+                f.min_frames = int(q["min_frames"]) if q.get("min_frames") is not None else 0
             if per:
                 m = smp[i]
                 m.struct_size = C.sizeof(vx_request_sampling)
@@ -639,7 +704,9 @@ class ServeSession:
                 r.uniforms = _ptr(u, C.c_float)
                 r.uniforms_steps = u.shape[0]
         ids = np.zeros(batch.n, np.int64)
-        if per:
+        if filt:
+            self.engine._chk(self.lib.vx_serve_submit_filtered(self._handle(), C.byref(batch.c), arr, smp, flt, _ptr(ids, C.c_int64)))
+        elif per:
             self.engine._chk(self.lib.vx_serve_submit_ex(self._handle(), C.byref(batch.c), arr, smp, _ptr(ids, C.c_int64)))
         else:
             self.engine._chk(self.lib.vx_serve_submit(self._handle(), C.byref(batch.c), arr, _ptr(ids, C.c_int64)))

@@ -531,8 +531,11 @@ int vx_bench_gemm_epilogue(vx_ctx* c, int32_t M, int32_t N, int32_t K, int32_t m
 // vx_dev_sample: case i runs in decode row i % 32 of launch i / 32 (the partials are laid out [splitk][32][npad], so the row matters).
 // Every launch gets private scratch state pre-filled with the sentinels; only the fused embedding reads the context (the finalized
 // AR audio embedding, position alpha, positional table and norm1 of layer 0).
-int vx_dev_sample(vx_ctx* c, int32_t n, const int32_t* cfg, const float* fcfg, const float* partial, float* logits, int32_t* state,
-                  float* sum_logp, float* emb_h, float* emb_xp) {
+// ffilt / ifilt / hist null: vx_dev_sample; else vx_dev_sample_filtered (kernel 1 only: the launch gets a row_flt record per row and
+// every case's generated tokens in its gen row)
+static int dev_sample_run(vx_ctx* c, int32_t n, const int32_t* cfg, const float* fcfg, const float* ffilt, const int32_t* ifilt,
+                          const int32_t* hist, int32_t hist_stride, const float* partial, float* logits, int32_t* state,
+                          float* sum_logp, float* emb_h, float* emb_xp) {
   if (!c) return VX_EINVAL;
   if (n <= 0 || !cfg || !fcfg || !partial || !logits || !state || !sum_logp || !emb_h || !emb_xp) FAIL(VX_EINVAL, "vx_dev_sample: null argument or n <= 0");
   if (!c->finalized) FAIL(VX_ESTATE, "vx_dev_sample: weights not finalized");
@@ -559,7 +562,7 @@ int vx_dev_sample(vx_ctx* c, int32_t n, const int32_t* cfg, const float* fcfg, c
                fh = f_lg + (size_t)MB * AR_LOGITS, fxp = fh + (size_t)MB * D_MODEL, fend = fxp + (size_t)MB * D_MODEL;
   static_assert((MB * AR_LOGITS) % 4 == 0 && (MB * PRED_NPAD) % 4 == 0, "emb_h / emb_xp take 16-byte vector stores");
   enum { I_ACT = 0, I_NGEN = MB, I_TOK = 2 * MB, I_POS = 3 * MB, I_CTX = 4 * MB, I_TLEN = 5 * MB, I_SLOT = 6 * MB, I_NACT = 7 * MB, I_META = 7 * MB + 4,
-         I_SMP = I_META + 4 * MB, I_GEN = I_SMP + 4 * MB };
+         I_SMP = I_META + 4 * MB, I_FLT = I_SMP + 4 * MB, I_GEN = I_FLT + 4 * MB };
   const size_t i_end = I_GEN + (size_t)MB * GS_MAX;
   float* df = nullptr;
   int* di = nullptr;
@@ -588,6 +591,7 @@ int vx_dev_sample(vx_ctx* c, int32_t n, const int32_t* cfg, const float* fcfg, c
       hi[I_NGEN + b] = hi[I_POS + b] = hi[I_CTX + b] = hi[I_TLEN + b] = 0;
       hi[I_META + 4 * slot] = b; hi[I_META + 4 * slot + 1] = 0; hi[I_META + 4 * slot + 2] = 0;
       hi[I_SMP + 4 * b] = 1; hi[I_SMP + 4 * b + 1] = 0x3F800000; hi[I_SMP + 4 * b + 2] = -1; hi[I_SMP + 4 * b + 3] = 0;
+      hi[I_FLT + 4 * b] = hi[I_FLT + 4 * b + 1] = 0x3F800000; hi[I_FLT + 4 * b + 2] = hi[I_FLT + 4 * b + 3] = 0;
       hf[f_slp + b] = 0.f;
       for (int ks = 0; ks < 4; ++ks) for (int j = 0; j < PRED_NPAD; ++j) hf[f_part + ((size_t)ks * MB + b) * PRED_NPAD + j] = 0.f;
       if (b >= nr) continue;
@@ -596,6 +600,12 @@ int vx_dev_sample(vx_ctx* c, int32_t n, const int32_t* cfg, const float* fcfg, c
       hi[I_ACT + b] = k[4]; hi[I_NGEN + b] = k[5]; hi[I_POS + b] = k[6]; hi[I_CTX + b] = k[7]; hi[I_TLEN + b] = k[8];
       hi[I_META + 4 * slot + 1] = k[7]; hi[I_META + 4 * slot + 2] = k[4];
       hi[I_SMP + 4 * b] = k[2]; memcpy(&hi[I_SMP + 4 * b + 1], &f[0], 4); hi[I_SMP + 4 * b + 2] = k[3];
+      if (ffilt) {
+        memcpy(&hi[I_FLT + 4 * b], ffilt + 2 * (size_t)(l0 + b), 8);
+        hi[I_FLT + 4 * b + 2] = ifilt[2 * (size_t)(l0 + b)]; hi[I_FLT + 4 * b + 3] = ifilt[2 * (size_t)(l0 + b) + 1];
+        const int nh = std::min(k[5], gs);
+        if (nh) memcpy(&hi[I_GEN + (size_t)b * gs], hist + (size_t)(l0 + b) * hist_stride, (size_t)nh * 4);
+      }
       hf[f_u + (size_t)k[5] * MB + b] = f[1];
       hf[f_slp + b] = f[2];
       nact += k[4];
@@ -620,6 +630,7 @@ int vx_dev_sample(vx_ctx* c, int32_t n, const int32_t* cfg, const float* fcfg, c
     } else {
       ServeSampleArgs a{};
       a.partial = df + f_part; a.splitk = splitk; a.npad = PRED_NPAD; a.row_smp = di + I_SMP;
+      a.row_flt = ffilt ? di + I_FLT : nullptr;
       a.uniforms = df + f_u; a.uniforms_stride = MB;
       a.cur_tok = di + I_TOK; a.cur_pos = di + I_POS; a.ctx_len = di + I_CTX; a.n_gen = di + I_NGEN; a.active = di + I_ACT;
       a.n_active = di + I_NACT; a.text_len = di + I_TLEN; a.slot_meta = di + I_META; a.slot_of = di + I_SLOT;
@@ -656,6 +667,30 @@ int vx_dev_sample(vx_ctx* c, int32_t n, const int32_t* cfg, const float* fcfg, c
 #undef TRYX
   cleanup();
   return VX_OK;
+}
+
+int vx_dev_sample(vx_ctx* c, int32_t n, const int32_t* cfg, const float* fcfg, const float* partial, float* logits, int32_t* state,
+                  float* sum_logp, float* emb_h, float* emb_xp) {
+  return dev_sample_run(c, n, cfg, fcfg, nullptr, nullptr, nullptr, 0, partial, logits, state, sum_logp, emb_h, emb_xp);
+}
+
+int vx_dev_sample_filtered(vx_ctx* c, int32_t n, const int32_t* cfg, const float* fcfg, const float* ffilt, const int32_t* ifilt,
+                           const int32_t* hist, int32_t hist_stride, const float* partial, float* logits, int32_t* state,
+                           float* sum_logp, float* emb_h, float* emb_xp) {
+  if (!c) return VX_EINVAL;
+  if (n <= 0 || !cfg || !ffilt || !ifilt || hist_stride < 0) FAIL(VX_EINVAL, "vx_dev_sample_filtered: null argument, n <= 0 or hist_stride < 0");
+  for (int i = 0; i < n; ++i) {
+    const int32_t* k = cfg + (size_t)i * VX_DEV_SAMPLE_CFG;
+    const float tp = ffilt[2 * i], rp = ffilt[2 * i + 1];
+    if (k[0] != 1) FAIL(VX_EINVAL, "vx_dev_sample_filtered: case %d: kernel must be 1 (serve_sample_kernel)", i);
+    if (!(tp > 0.0f) || !(tp <= 1.0f) || !(rp > 0.0f) || !(rp < 3.0e38f) || ifilt[2 * i] < 0 || ifilt[2 * i + 1] < 0)
+      FAIL(VX_EINVAL, "vx_dev_sample_filtered: case %d out of range (0 < top_p <= 1, repetition_penalty > 0 and finite, "
+           "repetition_window >= 0, min_frames >= 0)", i);
+    const int nh = k[5] < k[9] ? k[5] : k[9];
+    if (nh > 0 && (!hist || nh > hist_stride))
+      FAIL(VX_EINVAL, "vx_dev_sample_filtered: case %d has %d generated tokens, hist holds %d per case", i, nh, hist_stride);
+  }
+  return dev_sample_run(c, n, cfg, fcfg, ffilt, ifilt, hist, hist_stride, partial, logits, state, sum_logp, emb_h, emb_xp);
 }
 
 // vx_dev_attn: one launch of a full-sequence attention kernel on the caller's packed q|k|v rows; seq_off / c_off are derived here.

@@ -1251,6 +1251,8 @@ struct ServeReq {
   int top_k = 1;                               // topk_sampling arguments of this request (vx_request_sampling, or the session's)
   float temperature = 1.f;
   int force_eos_at = -1;
+  float top_p = 1.f, rep_penalty = 1.f;        // vx_request_filters (neutral: 1, 1, 0, 0)
+  int rep_window = 0, min_frames = 0;
   std::vector<float> u;                        // [N][usteps]
   std::vector<int32_t> ids, lang, pc;          // text ids / language ids [S], prompt codes [Tp][8]
   int S = 0, Tp = 0;
@@ -1376,7 +1378,9 @@ static int serve_admit(vx_serve* v, const std::vector<ServeReq*>& rq) {
     max_steps = std::max(max_steps, st);
     for (int j = 0; j < r->N; ++j)
       utab.insert(utab.end(), {r->rows[j], j, r->usteps ? (int)(o_st + soff[i] + (long)j * st) : -1, st, (int)(uint32_t)r->seed,
-                               (int)(uint32_t)(r->seed >> 32), r->top_k, __builtin_bit_cast(int, r->temperature), r->force_eos_at});
+                               (int)(uint32_t)(r->seed >> 32), r->top_k, __builtin_bit_cast(int, r->temperature), r->force_eos_at,
+                               __builtin_bit_cast(int, r->top_p), __builtin_bit_cast(int, r->rep_penalty), r->rep_window,
+                               r->min_frames});
   }
   const int nbeam = (int)tab.size() / 5;
   if ((long)max_steps * nd > c->uniforms_cap) FAIL(VX_EINVAL, "too many uniforms (%d steps)", max_steps);
@@ -1384,7 +1388,7 @@ static int serve_admit(vx_serve* v, const std::vector<ServeReq*>& rq) {
              o_fp = pairs.empty() ? 0 : mb.add(pairs);
   if (int e = upload_meta(c)) return e;
   launch_serve_uniforms(mb.dev(o_ut), nbeam, max_steps, reinterpret_cast<const float*>(c->imeta), c->d_uniforms, nd, c->sum_logp,
-                        c->row_smp, c->stream);
+                        c->row_smp, c->row_flt, c->stream);
   if (int e = prefill_layers(c, p, mb)) return e;
   const float* hsrc = prefill_hsrc(c, p);
   if (!pairs.empty())
@@ -1564,8 +1568,10 @@ static int serve_busy(vx_ctx* c, const char* what) {
   FAIL(VX_EINVAL, "%s: a serving session is open on this context (vx_serve_close it first)", what);
 }
 
-// vx_serve_submit / vx_serve_submit_ex: smp null = the session's top_k / temperature / force_eos_at for every request
-static int serve_submit(vx_serve* v, const vx_batch* b, const vx_request* req, const vx_request_sampling* smp, int64_t* ids_out) {
+// vx_serve_submit / vx_serve_submit_ex / vx_serve_submit_filtered: smp null = the session's top_k / temperature / force_eos_at for
+// every request; flt null = the neutral filters (top_p 1, repetition penalty 1, min_frames 0)
+static int serve_submit(vx_serve* v, const vx_batch* b, const vx_request* req, const vx_request_sampling* smp,
+                        const vx_request_filters* flt, int64_t* ids_out) {
   vx_ctx* c = v->c;
   if (int e = check_batch(c, b, 0x7fffffff)) return e;
   std::vector<vx_request_sampling> rs(b->batch, vx_request_sampling{sizeof(vx_request_sampling), v->s.top_k, v->s.temperature,
@@ -1584,6 +1590,18 @@ static int serve_submit(vx_serve* v, const vx_batch* b, const vx_request* req, c
       if (m.force_eos_at < -1) FAIL(VX_EINVAL, "request %d: force_eos_at must be >= -1 (got %d)", i, m.force_eos_at);
       rs[i] = m;
     }
+    if (flt) {
+      const vx_request_filters& f = flt[i];
+      if (f.struct_size != sizeof(vx_request_filters))
+        FAIL(VX_EINVAL, "vx_request_filters.struct_size is %u, this library expects %zu (ABI version %d)", f.struct_size,
+             sizeof(vx_request_filters), VX_ABI_VERSION);
+      if (!std::isfinite(f.top_p) || !(f.top_p > 0.f) || !(f.top_p <= 1.f))
+        FAIL(VX_EINVAL, "request %d: top_p must be in (0, 1] (got %g)", i, (double)f.top_p);
+      if (!std::isfinite(f.repetition_penalty) || !(f.repetition_penalty > 0.f))
+        FAIL(VX_EINVAL, "request %d: repetition_penalty must be > 0 and finite (got %g)", i, (double)f.repetition_penalty);
+      if (f.repetition_window < 0) FAIL(VX_EINVAL, "request %d: repetition_window must be >= 0 (got %d)", i, f.repetition_window);
+      if (f.min_frames < 0) FAIL(VX_EINVAL, "request %d: min_frames must be >= 0 (got %d)", i, f.min_frames);
+    }
     const int N = std::max(1, q.best_of);
     if (N > v->nd) FAIL(VX_EINVAL, "request %d: best_of %d exceeds the session's %d decode rows", i, N, v->nd);
     if (b->text_lens[i] + 1 + b->prompt_lens[i] > c->Tmax) FAIL(VX_EINVAL, "request %d: the prompt does not fit the arena", i);
@@ -1599,6 +1617,10 @@ static int serve_submit(vx_serve* v, const vx_batch* b, const vx_request* req, c
     const vx_request& q = req[i];
     auto r = std::make_unique<ServeReq>();
     r->top_k = rs[i].top_k; r->temperature = rs[i].temperature; r->force_eos_at = rs[i].force_eos_at;
+    if (flt) {
+      r->top_p = flt[i].top_p; r->rep_penalty = flt[i].repetition_penalty;
+      r->rep_window = flt[i].repetition_window; r->min_frames = flt[i].min_frames;
+    }
     r->N = std::max(1, q.best_of);
     r->length_penalty = q.length_penalty;
     r->worst = q.return_worst != 0;
@@ -1951,6 +1973,9 @@ int vx_serve_open(vx_ctx* c, const vx_sampling* s, vx_serve** out) {
   if (!c->row_smp) {
     if (int e = dev_alloc(c, &c->row_smp, 4 * MB)) { delete v; return e; }
   }
+  if (!c->row_flt) {
+    if (int e = dev_alloc(c, &c->row_flt, 4 * MB)) { delete v; return e; }
+  }
   if (int e = serve_setup(c, v->nd)) { delete v; return e; }
   // the per-row sampler (serve_sample.hip) with dec_sample's buffers: every beam row draws from its own column of d_uniforms
   // (injected or counter-based) and accumulates sum_logp (best_of is per request); top_k / temperature / force_eos_at come from
@@ -1959,6 +1984,7 @@ int vx_serve_open(vx_ctx* c, const vx_sampling* s, vx_serve** out) {
   ServeSampleArgs& r = v->rsa;
   r.partial = sa.partial; r.splitk = sa.splitk; r.npad = sa.npad;
   r.row_smp = c->row_smp;
+  r.row_flt = c->row_flt;           // every admission writes its rows' records; no sample runs on a row before its admission
   r.uniforms = c->d_uniforms; r.uniforms_stride = sa.uniforms_stride;
   r.cur_tok = sa.cur_tok; r.cur_pos = sa.cur_pos; r.ctx_len = sa.ctx_len; r.n_gen = sa.n_gen; r.active = sa.active;
   r.n_active = sa.n_active; r.text_len = sa.text_len; r.slot_meta = sa.slot_meta; r.slot_of = sa.slot_of;
@@ -1975,12 +2001,18 @@ int vx_serve_open(vx_ctx* c, const vx_sampling* s, vx_serve** out) {
 
 int vx_serve_submit(vx_serve* v, const vx_batch* b, const vx_request* req, int64_t* ids_out) {
   if (!v || !req) return VX_EINVAL;
-  return serve_submit(v, b, req, nullptr, ids_out);
+  return serve_submit(v, b, req, nullptr, nullptr, ids_out);
 }
 
 int vx_serve_submit_ex(vx_serve* v, const vx_batch* b, const vx_request* req, const vx_request_sampling* smp, int64_t* ids_out) {
   if (!v || !req) return VX_EINVAL;
-  return serve_submit(v, b, req, smp, ids_out);
+  return serve_submit(v, b, req, smp, nullptr, ids_out);
+}
+
+int vx_serve_submit_filtered(vx_serve* v, const vx_batch* b, const vx_request* req, const vx_request_sampling* smp,
+                             const vx_request_filters* flt, int64_t* ids_out) {
+  if (!v || !req) return VX_EINVAL;
+  return serve_submit(v, b, req, smp, flt, ids_out);
 }
 
 int vx_serve_cancel(vx_serve* v, int64_t request_id, int32_t* state) {

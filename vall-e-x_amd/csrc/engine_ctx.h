@@ -151,6 +151,7 @@ struct vx_ctx {
   std::vector<int> h_L;            // prefill lengths of the current micro-batch
   vx_serve* serve = nullptr;       // the open serving session (vx_serve_open); it owns the decode state while it is open
   int* row_smp = nullptr;          // [MB][4] per-row sampling record of the session's sampler (first vx_serve_open allocates it)
+  int* row_flt = nullptr;          // [MB][4] per-row filter record {top_p bits, penalty bits, window, min_frames}, allocated with row_smp
 
   // graph
   hipGraphExec_t graph_exec = nullptr, graph_exec_n = nullptr;   // one decode step / GRAPH_STEPS steps per launch
@@ -326,19 +327,23 @@ void launch_admit_uniforms(const int* pairs, int n, const float* staged, int ste
 // request's staged draws of beam j in `staged` (-1: counter-based, keyed on (seed, j)), draws to write, seed low, seed high word}
 // ... it also writes the admitted rows' sampling record row_smp[4 d .. 4 d + 3] = {top_k, temperature bits, force_eos_at, 0}:
 // tab [n][9] = the six words above + {top_k, temperature bits, force_eos_at}
-constexpr int SERVE_UTAB = 9;
+// ... and their filter record row_flt[4 d .. 4 d + 3] = {top_p bits, repetition penalty bits, repetition window, min_frames}:
+// tab [n][13] = the nine words above + those four
+constexpr int SERVE_UTAB = 13;
 void launch_serve_uniforms(const int* tab, int n, int max_steps, const float* staged, float* u, int ncols, float* sum_logp,
-                           int* row_smp, hipStream_t s);
+                           int* row_smp, int* row_flt, hipStream_t s);
 // cancellation of decoding requests (serve.hip): active[d] = 0 for every bit d of `rows`, then, for d < nrows,
 // slot_meta[4 slot_of[d] + 2] = active[d] and *n_active = number of active rows (recounted from the flags).  nrows <= 32.
 void launch_serve_cancel(unsigned rows, int nrows, int* active, int* slot_meta, const int* slot_of, int* n_active, hipStream_t s);
 
 // the serving session's sampler (serve_sample.hip): dec_sample_kernel's computation with top_k, temperature and force_eos_at read
 // per decode row from row_smp (written at admission by launch_serve_uniforms) instead of launch constants.  Always commits, always
-// draws from `uniforms` (the session writes every admitted row's column), always accumulates sum_logp.
+// draws from `uniforms` (the session writes every admitted row's column), always accumulates sum_logp.  row_flt (may be null: every
+// row neutral) adds the per-row top_p, repetition penalty over the row's generated frames and min_frames.
 struct ServeSampleArgs {
   const float* partial; int splitk; int npad;     // logits partials [splitk][MB][npad]
   const int* row_smp;                              // [MB][4] = {top_k, temperature bits, force_eos_at, 0}
+  const int* row_flt;                              // [MB][4] = {top_p bits, penalty bits, window, min_frames}; null: neutral
   const float* uniforms; int uniforms_stride;     // [steps][uniforms_stride]
   int* cur_tok; int* cur_pos; int* ctx_len; int* n_gen; int* active; int* n_active; const int* text_len;
   int* slot_meta; const int* slot_of;

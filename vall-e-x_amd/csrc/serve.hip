@@ -8,7 +8,8 @@
 // row; here every admitted beam row has its own request seed and is keyed on its beam index j, so beam j of a request with seed s
 // draws exactly what decode row j of a batch-1 vx_infer call with seed s draws (dec_sample_kernel's counter formula).  It also
 // zeroes sum_logp of the admitted rows (the rows still decoding keep theirs) and writes their sampling record row_smp[4 d ..] =
-// {top_k, temperature bits, force_eos_at, 0}, which the session's sampler (serve_sample.hip) reads per decode row.
+// {top_k, temperature bits, force_eos_at, 0} and their filter record row_flt[4 d ..] = {top_p bits, repetition penalty bits,
+// repetition window, min_frames}, which the session's sampler (serve_sample.hip) reads per decode row.
 //
 // serve_cancel_kernel stops the beam rows of cancelled requests between two vx_serve_run calls: their active flags and slot records
 // go to 0 and n_active is recounted from the flags, as admit_mask_kernel's phase 1 recounts it.  A later admission into those rows
@@ -25,18 +26,19 @@ __device__ __forceinline__ unsigned long long mix64(unsigned long long x) {     
   return x ^ (x >> 31);
 }
 
-// grid (ceil(max steps / 256), n), 256 threads.  tab[9 i .. 9 i + 8] = {decode row d, beam j, offset of the staged draws in
-// `staged` (-1: counter-based), draws to write, seed low word, seed high word, top_k, temperature bits, force_eos_at}.  Column d of
-// u gets steps 0 .. draws-1.
+// grid (ceil(max steps / 256), n), 256 threads.  tab[13 i .. 13 i + 12] = {decode row d, beam j, offset of the staged draws in
+// `staged` (-1: counter-based), draws to write, seed low word, seed high word, top_k, temperature bits, force_eos_at, top_p bits,
+// repetition penalty bits, repetition window, min_frames}.  Column d of u gets steps 0 .. draws-1.
 __global__ __launch_bounds__(256) void serve_uniforms_kernel(const int* __restrict__ tab, const float* __restrict__ staged,
                                                              float* __restrict__ u, int ncols, float* __restrict__ sum_logp,
-                                                             int* __restrict__ row_smp) {
+                                                             int* __restrict__ row_smp, int* __restrict__ row_flt) {
   const int* e = tab + SERVE_UTAB * blockIdx.y;
   const int d = e[0], j = e[1], off = e[2], steps = e[3];
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     sum_logp[d] = 0.f;
     *reinterpret_cast<int4*>(row_smp + 4 * d) = make_int4(e[6], e[7], e[8], 0);
+    *reinterpret_cast<int4*>(row_flt + 4 * d) = make_int4(e[9], e[10], e[11], e[12]);
   }
   if (t >= steps) return;
   float x;
@@ -65,10 +67,10 @@ __global__ __launch_bounds__(64) void serve_cancel_kernel(unsigned rows, int nro
 }  // namespace
 
 void launch_serve_uniforms(const int* tab, int n, int max_steps, const float* staged, float* u, int ncols, float* sum_logp,
-                           int* row_smp, hipStream_t s) {
+                           int* row_smp, int* row_flt, hipStream_t s) {
   if (n <= 0) return;
   const int gx = std::max(1, (max_steps + 255) / 256);
-  hipLaunchKernelGGL(serve_uniforms_kernel, dim3(gx, n), dim3(256), 0, s, tab, staged, u, ncols, sum_logp, row_smp);
+  hipLaunchKernelGGL(serve_uniforms_kernel, dim3(gx, n), dim3(256), 0, s, tab, staged, u, ncols, sum_logp, row_smp, row_flt);
 }
 
 void launch_serve_cancel(unsigned rows, int nrows, int* active, int* slot_meta, const int* slot_of, int* n_active, hipStream_t s) {

@@ -10,6 +10,24 @@
 // this file's own copies of decode.hip's: the DPP wave reductions, ln_pack_row's packed-x layout and store_result's write-through
 // vector store.  The draws need no splitmix64 here: the session always reads them from the row's d_uniforms column, which
 // serve_uniforms_kernel fills at admission with dec_sample_kernel's counter formula (or the request's injected draws).
+//
+// Per-request filters (vx_request_filters, vx_serve_submit_filtered): a second row record row_flt[4 d ..] = {top_p bits, repetition
+// penalty bits, repetition window, min_frames}.  A row with the neutral record (top_p >= 1, penalty == 1, min_frames <= n_gen), or a
+// launch without row_flt, takes wave-uniform branches around all of it and runs the sequence above on the same values.  Otherwise, in
+// this order, all fp32:
+//   1. repetition penalty r over the row's own generated frames gen[max(0, n_gen - w) .. n_gen) (w = 0: all of them; the prompt does
+//      not count): every token of that window, once however often it occurs, gets l > 0 ? l / r : l * r.  The window is marked in a
+//      1025-bit LDS bitmap (every token range-checked before it indexes the bitmap) and applied to the LDS logit row.
+//   2. min_frames m: while n_gen < m, l[EOS] = -inf (no finite logit left: the non-finite guard below samples EOS).
+//   3. temperature and 4. top_k as before.
+//   5. top_p: with e_i = exp(l_i - max) over the survivors of top_k, total = sum e_i and G(x) = sum of e_j over l_j > x, token i is
+//      kept iff G(l_i) <= top_p * total.  On tie-free logits this is top_k_top_p_filtering's rule (models/vallex.py:811-832: sort
+//      descending, drop a token when the cumulative probability of the tokens before it exceeds top_p).  DIFFERENCE: the reference's
+//      unstable torch.sort splits a tie at the cut arbitrarily; here every token tied with the last kept value is kept -- the rule
+//      the reference's own top-k has (`logits < kth`, :808).  The cut is found without a sort: the kept set is {l_i >= x*} for the
+//      smallest x* with G(x*) <= top_p * total, and G is monotone, so 32 rounds of bisection over the order-preserving unsigned
+//      image of the fp32 values find x* (one 17-value masked sum and one wave sum per round).
+// Every new loop has a bound known before it starts (32 rounds; the window is at most gen_stride frames).
 #include "engine_ctx.h"
 
 namespace vxe {
@@ -72,6 +90,15 @@ __device__ __forceinline__ int sum64i(int x) {
   return __builtin_amdgcn_readlane(x, 63);
 }
 
+// order-preserving unsigned image of an fp32 value: a < b  <=>  okey(a) < okey(b) (-0 below +0; NaNs at the ends)
+__device__ __forceinline__ unsigned okey(float x) {
+  const unsigned u = __builtin_bit_cast(unsigned, x);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float okey_inv(unsigned k) {
+  return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
 // c + a * b as TWO fp32 operations, the product rounded before the add -- what torch does for `emb + alpha * pe`
 // (modules/embedding.py:93-97).  __fmul_rn / __fadd_rn are a plain `*` and `+` in this toolchain and contract into one fma under
 // hipcc's default -ffp-contract=fast (found by tests/test_gpu_kernel_sampler.py: v_pk_fma_f32 in the sampler's fused embedding);
@@ -110,6 +137,7 @@ __device__ __forceinline__ void ln_pack(const f32x4 (&v)[4], int b, const f32x4 
 template <int SK>
 __global__ __launch_bounds__(64) void serve_sample_kernel(ServeSampleArgs a) {
   __shared__ float lg[64 * SPL];
+  __shared__ unsigned seen[(AR_LOGITS + 31) / 32];                 // tokens of the repetition window, one bit each
   const int b = blockIdx.x, lane = threadIdx.x;
   // row state: every scalar the kernel needs, requested up front (independent loads)
   if (a.active[b] == 0) return;
@@ -117,6 +145,10 @@ __global__ __launch_bounds__(64) void serve_sample_kernel(ServeSampleArgs a) {
   const int4 smp = *reinterpret_cast<const int4*>(a.row_smp + 4 * b);
   const int top_k = smp.x, force_eos_at = smp.z;
   const float temperature = __builtin_bit_cast(float, smp.y);
+  int4 flt = make_int4(0x3F800000, 0x3F800000, 0, 0);              // neutral: top_p 1, penalty 1, window 0, min_frames 0
+  if (a.row_flt) flt = *reinterpret_cast<const int4*>(a.row_flt + 4 * b);
+  const float top_p = __builtin_bit_cast(float, flt.x), penalty = __builtin_bit_cast(float, flt.y);
+  const int rep_window = flt.z, min_frames = flt.w;
   {
     float pp[SPL][SK];
 #pragma unroll
@@ -136,6 +168,31 @@ __global__ __launch_bounds__(64) void serve_sample_kernel(ServeSampleArgs a) {
     }
   }
   __syncthreads();
+
+  if (penalty != 1.0f) {                                           // wave-uniform: a neutral row reads no history
+    if (lane < (AR_LOGITS + 31) / 32) seen[lane] = 0u;
+    __syncthreads();
+    const int hi = ngen < a.gen_stride ? ngen : a.gen_stride;      // frames this row has written: never past its gen row
+    const int lo = (rep_window > 0 && rep_window < hi) ? hi - rep_window : 0;
+    for (int i = lo + lane; i < hi; i += 64) {
+      const int t = a.gen[(long)b * a.gen_stride + i];
+      if ((unsigned)t < (unsigned)AR_LOGITS) atomicOr(&seen[t >> 5], 1u << (t & 31));
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < SPL; ++i) {
+      const int n = lane + 64 * i;
+      if (n < AR_LOGITS && ((seen[n >> 5] >> (n & 31)) & 1u)) {
+        const float x = lg[n];
+        lg[n] = x > 0.f ? x / penalty : x * penalty;
+      }
+    }
+    __syncthreads();
+  }
+  if (ngen < min_frames) {                                         // wave-uniform
+    if (lane == 0) lg[EOS_ID] = -INFINITY;
+    __syncthreads();
+  }
 
   // the draw and the fixed operands of the fused embedding do not depend on the logits: request them now
   const float u = a.uniforms[(long)ngen * a.uniforms_stride + b];
@@ -195,6 +252,28 @@ __global__ __launch_bounds__(64) void serve_sample_kernel(ServeSampleArgs a) {
     }
 #pragma unroll
     for (int j = 0; j < SPL; ++j) if (v[j] < thr) v[j] = -INFINITY;
+  }
+  if (top_p < 1.0f) {                                              // wave-uniform; :811-832 without the sort (header comment)
+    float ep[SPL], part = 0.f;
+#pragma unroll
+    for (int j = 0; j < SPL; ++j) { ep[j] = expf(v[j] - mx); part += ep[j]; }
+    const float budget = top_p * sum64f(part);
+    // invariant: G(klo) > budget or klo is the image of -inf; G(khi) <= budget (G(max) = 0).  khi - klo < 2^32 and every round
+    // halves it (rounding up), so after 32 rounds khi - klo <= 1 and khi is the image of the smallest kept value.  Every mid lies
+    // between the images of -inf and of the maximum: it is the image of a number, never of a NaN.
+    unsigned klo = okey(-INFINITY), khi = okey(mx);
+    for (int it = 0; it < 32; ++it) {
+      const unsigned mid = klo + ((khi - klo) >> 1);
+      const float x = okey_inv(mid);
+      float g = 0.f;
+#pragma unroll
+      for (int j = 0; j < SPL; ++j) g += v[j] > x ? ep[j] : 0.f;
+      g = sum64f(g);
+      if (g <= budget) khi = mid; else klo = mid;
+    }
+    const float cut = okey_inv(khi);
+#pragma unroll
+    for (int j = 0; j < SPL; ++j) if (v[j] < cut) v[j] = -INFINITY;
   }
   // softmax numerators (the common 1 / sum cancels in the inverse CDF)
   float e[SPL], loc = 0.f;

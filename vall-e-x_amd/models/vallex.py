@@ -339,17 +339,23 @@ class Server:
 
     def submit(self, row: dict, best_of: int = 1, seed: Optional[int] = None, uniforms=None, length_penalty: float = 1.0,
                return_worst: bool = False, top_k: Optional[int] = None, temperature: Optional[float] = None,
-               force_eos_at: Optional[int] = None) -> Future:
+               force_eos_at: Optional[int] = None, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
+               repetition_window: Optional[int] = None, min_frames: Optional[int] = None) -> Future:
         """row: the dict of inference_batch (text, prompt, enroll, prompt_language, text_language).  Returns a Future of the
         (T, 8) int64 codes (or of post's result).  seed=None draws a fresh seed, like inference; top_k / temperature /
-        force_eos_at None: the session's value."""
-        u = ServeSession.check_request(best_of, uniforms, self.rows, top_k, temperature, force_eos_at)
+        force_eos_at None: the session's value.  top_p (nucleus sampling after top_k), repetition_penalty over the last
+        repetition_window generated frames (0: all of them) and min_frames (no EOS before that many frames); None: off."""
+        u = ServeSession.check_request(best_of, uniforms, self.rows, top_k, temperature, force_eos_at, top_p=top_p,
+                                       repetition_penalty=repetition_penalty, repetition_window=repetition_window,
+                                       min_frames=min_frames)
         if seed is None:
             seed = fresh_seed()
         batch = self._model.make_batch([row])
         req = dict(best_of=int(best_of), seed=int(seed), uniforms=u, length_penalty=float(length_penalty),
                    return_worst=bool(return_worst))
-        for k, v in (("top_k", top_k), ("temperature", temperature), ("force_eos_at", force_eos_at)):
+        for k, v in (("top_k", top_k), ("temperature", temperature), ("force_eos_at", force_eos_at), ("top_p", top_p),
+                     ("repetition_penalty", repetition_penalty), ("repetition_window", repetition_window),
+                     ("min_frames", min_frames)):
             if v is not None:
                 req[k] = v
         fut: Future = Future()

@@ -283,11 +283,15 @@ class AudioServer:
         self._server = model.serve(top_k=-100, temperature=1.0, post=lambda codes: model.engine.vocos_decode(codes, 2), **serve_kw)
 
     def submit(self, text, prompt=None, language="auto", accent="no-accent", best_of=1, seed=None, uniforms=None,
-               length_penalty=1.0, return_worst=False, text_language=None, top_k=-100, temperature=1.0):
-        """top_k / temperature: generate_audio's defaults, per request.  The Future can be cancelled until it is delivered."""
+               length_penalty=1.0, return_worst=False, text_language=None, top_k=-100, temperature=1.0, top_p=1.0,
+               repetition_penalty=1.0, repetition_window=0, min_frames=0):
+        """top_k / temperature: generate_audio's defaults, per request.  top_p / repetition_penalty / repetition_window / min_frames:
+        the request's logit filters (Server.submit); the defaults are neutral.  The Future can be cancelled until it is delivered."""
         row = _utterance_row(text, prompt, language, accent, text_language)
         return self._server.submit(row, best_of=best_of, seed=seed, uniforms=uniforms, length_penalty=length_penalty,
-                                   return_worst=return_worst, top_k=top_k, temperature=temperature)
+                                   return_worst=return_worst, top_k=top_k, temperature=temperature, top_p=top_p,
+                                   repetition_penalty=repetition_penalty, repetition_window=repetition_window,
+                                   min_frames=min_frames)
 
     def close(self):
         self._server.close()
