@@ -86,6 +86,34 @@ int vx_dev_sample_filtered(vx_ctx* ctx, int32_t n, const int32_t* cfg, const flo
  * nothing is written behind them).  *range_flag = the f16x2 range flag after the launch (0 for the other variants). */
 int vx_dev_attn(vx_ctx* ctx, int32_t variant, int32_t planes, int32_t batch, const float* qkv, const int32_t* seq_len,
                 const int32_t* prefix_len, const int32_t* q_first, float* out, int64_t out_rows, int32_t* range_flag);
+/* The attention block of ONE decode step on nrows (1 .. 32) chosen rows: the launches of the engine's step from the attention launch
+ * to the launch behind which the out_proj result exists, with the chain and the context splits the engine's own rule picks for nrows
+ * rows (reported in geom[3] = {nsplit, sb_qkv, split_fused}):
+ *   1 .. 4 rows        dec_attn_qkv (norm1 + in_proj + split attention) | out_proj GEMM with the combine as prologue
+ *   5 .. 7 rows        dec_attn | dec_attn_combine | out_proj GEMM | reduce + LayerNorm
+ *   8 .. 16 rows       dec_attn with out_proj folded in, context splits | reduce (weighs the slabs by e^(m_s - M) / L) + LayerNorm
+ *   17 .. 32 rows      dec_attn with out_proj folded in, one split | reduce + LayerNorm
+ * The weights are the context's layer 0 (in_proj, out_proj, norm1, norm2, and linear2's bias for skp 8); everything else is private
+ * scratch of the call, pre-filled with the sentinel -- the K / V arena too, which has nrows slots of [16][Tmax][64] for a Tmax of the
+ * caller's (128 .. 4096).  The context's decode state is not touched.
+ *   ctx_len [nrows]: cached rows INCLUDING the new token (1 .. Tmax);  active [nrows]: 0 = a finished row
+ *   slot_order [nrows]: slot_order[y] = the row in launch slot y, a permutation (the identity for nrows <= 4)
+ *   kc, vc [nrows][16][Tmax][64], in and out, indexed by ROW (the entry moves row r's stream into its slot and back): the cached rows
+ *       0 .. ctx - 2 and whatever the caller wants a reused slot to hold behind them; out: the whole stream after the launch
+ *   qkv (the dec_attn chains): the in_proj split-K slabs [4][nrows][3072], or for qkv_balanced != 0 [8][nrows][3072] with q in all
+ *       eight and k, v in the first four (columns 1024 .. 3071 of slabs 4 .. 7 are not read)
+ *   x_in (the 1 .. 4-row chain): skp 0: [nrows][1024], norm1(h) as the sampler leaves it (packed by the entry); skp 8: [9][nrows][1024],
+ *       eight linear2 slabs and the residual row: x = norm1(resid + sum of the slabs + linear2 bias)
+ *   resid [nrows][1024] (the dec_attn chains): the residual rows the closing reduce + LayerNorm adds
+ *   out [4][nrows][1024]: the 1 .. 4-row chain: the four split-K slabs of out_proj (bias not added); the other chains: out[0] = h =
+ *       resid + out_proj(attention) (every row: the reduce kernels do not look at the active flag), out[1 .. 3] keep the sentinel
+ *   xp_att [nrows][1024]: the attention output in front of out_proj where a chain stores it (5 .. 7 rows), un-packed
+ *   part_ml [nrows][16][17][2]: (m, l) of partial s < nsplit of every (row, head) where the chain has context splits; the 1 .. 4-row
+ *       chain's partial `nsplit` (the new token's) has no (m, l): the consumer forms it
+ * VX_ESTATE while a serving session is open; VX_EINVAL for Tmax < 128, a context beyond Tmax, a slot order that is no permutation. */
+int vx_dev_dec_attn(vx_ctx* ctx, int32_t nrows, int32_t Tmax, int32_t qkv_balanced, int32_t skp, const int32_t* ctx_len,
+                    const int32_t* active, const int32_t* slot_order, float* kc, float* vc, const float* qkv, const float* x_in,
+                    const float* resid, float* out, float* xp_att, float* part_ml, int32_t* geom);
 
 #ifdef __cplusplus
 }

@@ -201,3 +201,243 @@ def attention_operands(kind, seed=5):
     else:
         raise ValueError(kind)
     return x.astype(np.float32)
+
+
+# ---- the attention block of one decode step (dec_attn chains, csrc/decode.hip) -----------------------------------------------------
+DEC_TILE = 128                # rows of one dec_attn tile
+DEC_TMAX = 384                # arena rows per (slot, head) the tests ask vx_dev_dec_attn for: three tiles
+DEC_ROWS = (1, 2, 3, 4, 5, 7, 8, 9, 11, 16, 17, 32)
+# contexts INCLUDING the new token, long and short alternating
+DEC_CTX = (300, 1, 257, 2, 130, 16, 129, 17, 128, 18, 127, 33)
+DEC_KINDS = ("uniform", "model", "sharp", "new_heavy", "new_light")
+
+
+def dec_geometry(nrows):
+    """(chain, context splits) the engine's rule picks with its default switches (engine.hip decode_geometry)"""
+    if nrows <= 4:
+        return "sb_qkv", (16, 8, 4, 4)[nrows - 1]
+    if nrows <= 7:
+        return "unfused", max(2, 256 // (nrows * 16))
+    if nrows <= 16:
+        return "split_fused", min(4, 256 // (16 * ((nrows + 1) // 2)))
+    return "fused", 1
+
+
+def dec_split_bounds(npast, nsplit):
+    """[t0, t1) of every context split over the npast cached rows: chunk = (ceil(npast / nsplit) + 15) & ~15 (decode.hip)"""
+    chunk = ((npast + nsplit - 1) // nsplit + 15) & ~15
+    return [(min(s * chunk, npast), min(s * chunk + chunk, npast)) for s in range(nsplit)]
+
+
+def dec_launch_contexts(nrows):
+    """the context lengths of the launches one row count is tested with: every context of DEC_CTX appears; from 8 rows up (two rows
+    per workgroup, launch slots y and y + ceil(nrows / 2)) the pairs hold long + short, short + long and, for an even row count, one
+    pair of equal contexts"""
+    n12 = len(DEC_CTX)
+    if nrows < 8:
+        return [[DEC_CTX[(j * nrows + i) % n12] for i in range(nrows)] for j in range(-(-n12 // nrows))]
+    gy = (nrows + 1) // 2
+    out = []
+    for j in range(-(-n12 // gy)):
+        c = [DEC_CTX[(j * gy + i) % n12] for i in range(gy)] + [DEC_CTX[(j * gy + i + 1) % n12] for i in range(nrows - gy)]
+        if nrows % 2 == 0:
+            c[nrows - 1] = c[gy - 1]
+        out.append(c)
+    return out
+
+
+def balance_order(ctx):
+    """the engine's launch order (engine.hip ar_prefill): rows by context, the longest ceil(n / 2) first (descending, stable), then
+    the rest ascending; order[y] = the row in launch slot y"""
+    n = len(ctx)
+    by_len = sorted(range(n), key=lambda i: -int(ctx[i]))
+    first = (n + 1) // 2
+    return np.array(by_len[:first] + [by_len[n - 1 - (y - first)] for y in range(first, n)], np.int32)
+
+
+def dec_layer0_weights(sd):
+    p = "ar_decoder.layers.0."
+    return dict(in_w=sd[p + "self_attn.in_proj_weight"], in_b=sd[p + "self_attn.in_proj_bias"], out_w=sd[p + "self_attn.out_proj.weight"],
+                out_b=sd[p + "self_attn.out_proj.bias"], n1_w=sd[p + "norm1.weight"], n1_b=sd[p + "norm1.bias"], l2_b=sd[p + "linear2.bias"])
+
+
+def _stale(tmax=DEC_TMAX):
+    """what a reused arena slot holds behind a shorter request: finite values of order 1e4, both signs"""
+    if tmax not in _STALE:
+        rng = np.random.default_rng(77)
+        _STALE[tmax] = tuple((rng.uniform(0.5, 1.5, (16, tmax, 64)) * 1.0e4 * rng.choice([-1.0, 1.0], (16, tmax, 64))).astype(np.float32)
+                             for _ in range(2))
+    return _STALE[tmax]
+
+
+_STALE = {}
+
+
+def dec_case(kind, ctx, w, chain, seed, skp=0, balanced=False, stale=True, tmax=DEC_TMAX):
+    """operands of one launch for vx_dev_dec_attn (keyword arguments of Engine.dev_dec_attn, + `kind`, `chain`).
+    dec_attn chains: the q | k_new | v_new rows are chosen, then split into in_proj slabs (4, or 8 + 4 + 4 `balanced`);
+    sb_qkv chain: x (skp 0) or eight linear2 slabs + the residual row (skp 8) are chosen, q / k_new / v_new follow from in_proj; there
+    'uniform' is a uniform x in [-2, 2) and 'model' a normal x with per-channel gains from {0.1, 1, 4} (the sets below describe the
+    cached K / V of that chain, and q | k_new | v_new of the others).
+      uniform    uniform [-1, 1), q x 4          model      normal q, k; v normal with per-channel gains from {0.01, 1, 30}
+      sharp      scores spread over a few hundred (q, k x 10; sb_qkv: cached keys x 300): the running-max rescale matters
+      new_heavy  the new token's score ~ 16 above the cached keys' (almost all of the mass), new_light: ~ 16 below (almost none)"""
+    rng = np.random.default_rng(seed)
+    n = len(ctx)
+    sb = chain == "sb_qkv"
+    case = dict(ctx_len=np.array(ctx, np.int32), tmax=tmax, kind=kind, chain=chain, skp=skp, qkv_balanced=balanced)
+    if sb:
+        # the chosen row: uniform [-2, 2) for 'uniform', normal with per-channel gains from {0.1, 1, 4} for 'model', normal otherwise
+        row = rng.uniform(-2.0, 2.0, (n, 1024)) if kind == "uniform" else rng.normal(0.0, 1.0, (n, 1024))
+        if kind == "model":
+            row = row * rng.choice([0.1, 1.0, 4.0], 1024)
+        if skp:                              # ... is the residual row; the eight linear2 slabs follow its distribution at 0.4 x
+            slabs = rng.uniform(-0.8, 0.8, (8, n, 1024)) if kind == "uniform" else rng.normal(0.0, 0.4, (8, n, 1024))
+            x_in = np.concatenate([slabs, row[None]]).astype(np.float32)
+            x = layer_norm_ref(x_in.astype(np.float64).sum(0) + w["l2_b"].astype(np.float64), w["n1_w"], w["n1_b"])
+        else:
+            x_in = row.astype(np.float32)
+            x = x_in.astype(np.float64)
+        case["x_in"] = x_in
+        q = (x @ w["in_w"][:1024].astype(np.float64).T + w["in_b"][:1024]).reshape(n, 16, 64)
+    else:
+        if kind == "uniform":
+            t = rng.uniform(-1.0, 1.0, (n, 3072))
+            t[:, :1024] *= 4.0
+        else:
+            t = rng.normal(0.0, 1.0, (n, 3072))
+        if kind == "model":
+            t[:, 2048:] *= rng.choice([0.01, 1.0, 30.0], 1024)
+        if kind == "sharp":
+            t[:, :2048] *= 10.0
+        q = t[:, :1024].reshape(n, 16, 64)
+        if kind in ("new_heavy", "new_light"):
+            t[:, 1024:2048] = (2.0 if kind == "new_heavy" else -2.0) * t[:, :1024]      # q . k_new / 8 = +-|q|^2 / 4 ~ +-16
+        pre = t - w["in_b"].astype(np.float64)
+        slabs = rng.normal(0.0, 0.5, (4, n, 3072)) * np.abs(pre).mean()
+        slabs[3] = pre - slabs[:3].sum(0)
+        slabs = slabs.astype(np.float32)
+        if balanced:                          # q: every slab in two exact halves (eight slabs, the same sums); k, v: the same four
+            b8 = np.zeros((8, n, 3072), np.float32)
+            b8[:4] = slabs
+            b8[:, :, :1024] = np.repeat(slabs[:, :, :1024] * np.float32(0.5), 2, axis=0)
+            slabs = b8
+        case["qkv"] = slabs
+        case["resid"] = rng.normal(0.0, 1.0, (n, 1024)).astype(np.float32)
+    k_rows, v_rows = [], []
+    for r in range(n):
+        p = int(ctx[r]) - 1
+        if kind == "uniform":
+            k, v = rng.uniform(-1.0, 1.0, (p, 16, 64)), rng.uniform(-1.0, 1.0, (p, 16, 64))
+        else:
+            k, v = rng.normal(0.0, 1.0, (p, 16, 64)), rng.normal(0.0, 1.0, (p, 16, 64))
+        if kind == "model":
+            v = v * rng.choice([0.01, 1.0, 30.0], (16, 64))
+        if kind == "sharp":
+            k = k * (300.0 if sb else 10.0)
+        if kind in ("new_heavy", "new_light") and sb:          # k_new follows from x here: move the cached keys' scores instead
+            qq = q[r] / (q[r] ** 2).sum(-1, keepdims=True)
+            k = 0.1 * k + (-128.0 if kind == "new_heavy" else 128.0) * qq[None]
+        k_rows.append(k.astype(np.float32))
+        v_rows.append(v.astype(np.float32))
+    case["k_rows"], case["v_rows"] = k_rows, v_rows
+    if stale:
+        sk, sv = _stale(tmax)
+        case["k_fill"] = [sk[:, int(c) - 1:] for c in ctx]
+        case["v_fill"] = [sv[:, int(c) - 1:] for c in ctx]
+    return case
+
+
+def dec_attn_block_ref(case, w, nsplit):
+    """float64 reference of the block on the fp32 operands of `case`: q / k_new / v_new = sum of the slabs + bias (sb_qkv: norm1 and
+    in_proj in front), softmax(q K^T / 8) over the cached rows plus the new token, out_proj.  Returns a dict of float64 arrays: qkv
+    (n, 3072), attn (n, 1024), proj = W_o attn (n, 1024), h = resid + out_b + proj (dec_attn chains), and per (row, head, split)
+    m (the split's largest score) and l = sum exp(score - m) over dec_split_bounds -- the last split of a dec_attn chain holds the new
+    token too, the sb_qkv chain keeps it apart; empty splits: (-1e30, 0)."""
+    f8 = np.float64
+    ctx = case["ctx_len"]
+    n = len(ctx)
+    sb = case["chain"] == "sb_qkv"
+    if sb:
+        xi = case["x_in"].astype(f8)
+        x = layer_norm_ref(xi.sum(0) + w["l2_b"].astype(f8), w["n1_w"], w["n1_b"]) if case["skp"] else xi
+        qkv = x @ w["in_w"].astype(f8).T + w["in_b"].astype(f8)
+    else:
+        s = case["qkv"].astype(f8)
+        qkv = np.concatenate([s[:, :, :1024].sum(0), s[:4, :, 1024:].sum(0)], -1) + w["in_b"].astype(f8)
+    attn = np.zeros((n, 1024))
+    m = np.full((n, 16, nsplit), -1.0e30)
+    l = np.zeros((n, 16, nsplit))
+    for r in range(n):
+        q, kn, vn = (qkv[r, i * 1024:(i + 1) * 1024].reshape(16, 64) for i in range(3))
+        K = np.concatenate([case["k_rows"][r].astype(f8).transpose(1, 0, 2), kn[:, None]], 1)         # (16, ctx, 64)
+        V = np.concatenate([case["v_rows"][r].astype(f8).transpose(1, 0, 2), vn[:, None]], 1)
+        sc = np.einsum("hd,htd->ht", q, K) / 8.0
+        e = np.exp(sc - sc.max(-1, keepdims=True))
+        attn[r] = np.einsum("ht,htd->hd", e / e.sum(-1, keepdims=True), V).reshape(1024)
+        npast = int(ctx[r]) - 1
+        for si, (t0, t1) in enumerate(dec_split_bounds(npast, nsplit)):
+            part = sc[:, t0:t1]
+            if si == nsplit - 1 and not sb:
+                part = np.concatenate([part, sc[:, npast:]], 1)
+            if part.shape[1]:
+                m[r, :, si] = part.max(-1)
+                l[r, :, si] = np.exp(part - part.max(-1, keepdims=True)).sum(-1)
+    proj = attn @ w["out_w"].astype(f8).T
+    out = dict(qkv=qkv, attn=attn, proj=proj, m=m, l=l)
+    if not sb:
+        out["h"] = case["resid"].astype(f8) + w["out_b"].astype(f8) + proj
+    return out
+
+
+def dec_attn_block_fp32(case, w, nsplit):
+    """the yardstick: the same block in torch-CPU fp32 on the same fp32 operands, in the reference's formulation (F.layer_norm,
+    F.linear, F.softmax and matmuls; modules/activation.py:142-167) -- the same keys as dec_attn_block_ref"""
+    import torch
+    import torch.nn.functional as F
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32))
+    ctx = case["ctx_len"]
+    n = len(ctx)
+    sb = case["chain"] == "sb_qkv"
+    if sb:
+        xi = T(case["x_in"])
+        x = F.layer_norm(xi.sum(0) + T(w["l2_b"]), (1024,), T(w["n1_w"]), T(w["n1_b"]), 1e-5) if case["skp"] else xi
+        qkv = F.linear(x, T(w["in_w"]), T(w["in_b"]))
+    else:
+        s = T(case["qkv"])
+        qkv = torch.cat([s[:, :, :1024].sum(0), s[:4, :, 1024:].sum(0)], -1) + T(w["in_b"])
+    attn = torch.zeros(n, 1024)
+    m = torch.full((n, 16, nsplit), -1.0e30)
+    l = torch.zeros(n, 16, nsplit)
+    for r in range(n):
+        q, kn, vn = (qkv[r, i * 1024:(i + 1) * 1024].reshape(16, 1, 64) for i in range(3))
+        K = torch.cat([T(case["k_rows"][r]).transpose(0, 1), kn], 1)
+        V = torch.cat([T(case["v_rows"][r]).transpose(0, 1), vn], 1)
+        sc = (q @ K.transpose(-2, -1)) * 0.125                                                        # (16, 1, ctx)
+        attn[r] = (F.softmax(sc, dim=-1) @ V).reshape(1024)
+        sc = sc[:, 0]
+        npast = int(ctx[r]) - 1
+        for si, (t0, t1) in enumerate(dec_split_bounds(npast, nsplit)):
+            part = sc[:, t0:t1]
+            if si == nsplit - 1 and not sb:
+                part = torch.cat([part, sc[:, npast:]], 1)
+            if part.shape[1]:
+                m[r, :, si] = part.max(-1).values
+                l[r, :, si] = torch.exp(part - part.max(-1, keepdim=True).values).sum(-1)
+    proj = F.linear(attn, T(w["out_w"]))
+    out = dict(qkv=qkv.numpy(), attn=attn.numpy(), proj=proj.numpy(), m=m.numpy(), l=l.numpy())
+    if not sb:
+        out["h"] = (T(case["resid"]) + F.linear(attn, T(w["out_w"]), T(w["out_b"]))).numpy()
+    return out
+
+
+def dec_append_expected(case, w):
+    """K[ctx - 1], V[ctx - 1] of every row as dec_attn_kernel appends them: the fp32 slab sum ((p0 + p1) + p2) + p3, then + bias (k and
+    v have four slabs in both layouts); (n, 16, 64) each"""
+    s = case["qkv"][:4]
+    t = s[0].copy()
+    for ks in range(1, 4):
+        t = (t + s[ks]).astype(np.float32)
+    t = (t + w["in_b"].astype(np.float32)).astype(np.float32)
+    n = t.shape[0]
+    return t[:, 1024:2048].reshape(n, 16, 64), t[:, 2048:].reshape(n, 16, 64)

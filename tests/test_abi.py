@@ -115,3 +115,20 @@ def test_library_sources_never_abort_the_host_process():
                 continue
             bad.append((os.path.basename(f), m.group(0)))
     assert not bad, bad
+
+
+def test_dev_dec_attn_prototype_matches_binding(lib):
+    """the header's prototype of vx_dev_dec_attn and the ctypes signature agree argument by argument (17 of them)"""
+    import ctypes as C
+    hdr = open(os.path.join(ROOT, "include", "vallex_hip_dev.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    proto = re.search(r"\bint vx_dev_dec_attn\((.*?)\);", hdr, re.S).group(1)
+    args = [" ".join(a.split()) for a in proto.split(",")]
+    assert args == ["vx_ctx* ctx", "int32_t nrows", "int32_t Tmax", "int32_t qkv_balanced", "int32_t skp", "const int32_t* ctx_len",
+                    "const int32_t* active", "const int32_t* slot_order", "float* kc", "float* vc", "const float* qkv", "const float* x_in",
+                    "const float* resid", "float* out", "float* xp_att", "float* part_ml", "int32_t* geom"], args
+    kinds = {"vx_ctx*": C.c_void_p, "int32_t": C.c_int32, "const int32_t*": C.POINTER(C.c_int32), "int32_t*": C.POINTER(C.c_int32),
+             "float*": C.POINTER(C.c_float), "const float*": C.POINTER(C.c_float)}
+    want = [kinds[a.rsplit(" ", 1)[0]] for a in args]
+    assert lib.vx_dev_dec_attn.restype is C.c_int and len(lib.vx_dev_dec_attn.argtypes) == 17
+    assert list(lib.vx_dev_dec_attn.argtypes) == want

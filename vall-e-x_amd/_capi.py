@@ -83,7 +83,8 @@ SYMBOLS = ["vx_abi_version", "vx_create", "vx_destroy", "vx_last_error", "vx_syn
            "vx_serve_close", "vx_serve_submit_ex", "vx_serve_cancel", "vx_serve_submit_filtered"]
 # ... and include/vallex_hip_dev.h: measurement / kernel development, never called by the mirrors of the reference API
 DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kernel", "vx_bench_gemm", "vx_bench_attn",
-               "vx_bench_gemm_clock", "vx_bench_gemm_epilogue", "vx_dev_sample", "vx_dev_attn", "vx_dev_sample_filtered"]
+               "vx_bench_gemm_clock", "vx_bench_gemm_epilogue", "vx_dev_sample", "vx_dev_attn", "vx_dev_sample_filtered",
+               "vx_dev_dec_attn"]
 # sentinels the correctness entries pre-fill their outputs with (include/vallex_hip_dev.h)
 DEV_SENTINEL_I = -123456789
 DEV_SENTINEL_F = np.float32(-1.0e30)
@@ -167,6 +168,9 @@ def load_library() -> C.CDLL:
                                            P(C.c_float)]
     lib.vx_dev_attn.argtypes = [ctx, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), P(C.c_int32), P(C.c_int32), P(C.c_int32),
                                 P(C.c_float), C.c_int64, P(C.c_int32)]
+    lib.vx_dev_dec_attn.argtypes = [ctx, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_float),
+                                    P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
+                                    P(C.c_int32)]
     lib.vx_last_stats.argtypes = [ctx, P(C.c_int64), P(C.c_int64), P(C.c_double), P(C.c_double)]
     lib.vx_last_truncated.argtypes = [ctx, P(C.c_int32)]
     lib.vx_last_fallbacks.argtypes = [ctx, P(C.c_int32), P(C.c_int32), P(C.c_int64)]
@@ -552,6 +556,55 @@ class Engine:
                                        None if pre is None else _ptr(pre, C.c_int32), None if qf is None else _ptr(qf, C.c_int32),
                                        _ptr(out, C.c_float), rows, C.byref(flag)))
         return out, flag.value
+
+    def dev_dec_attn(self, ctx_len, k_rows, v_rows, tmax: int, qkv=None, x_in=None, resid=None, active=None, slot_order=None,
+                     qkv_balanced: bool = False, skp: int = 0, k_fill=0.0, v_fill=0.0):
+        """vx_dev_dec_attn: the attention block of one decode step of layer 0 on chosen rows (include/vallex_hip_dev.h).
+        ctx_len (n,): cached rows including the new token; k_rows / v_rows: per row the cached rows (ctx - 1, 16, 64) float32;
+        k_fill / v_fill: what the rest of the row's arena stream, rows ctx - 1 .. tmax - 1, holds before the launch -- a scalar or per
+        row an array that broadcasts to (16, tmax - ctx + 1, 64).  qkv (4 | 8, n, 3072) for the dec_attn chains, x_in (n, 1024) or
+        (9, n, 1024) for the 1 .. 4-row chain, resid (n, 1024).  Returns a dict: nsplit, sb_qkv, split_fused, out (4, n, 1024), xp_att
+        (n, 1024), part_ml (n, 16, 17, 2), k / v (n, 16, tmax, 64) after the launch and k0 / v0, the same streams before it."""
+        cl = np.ascontiguousarray(ctx_len, np.int32)
+        n = len(cl)
+        act = np.ones(n, np.int32) if active is None else np.ascontiguousarray(active, np.int32)
+        order = np.arange(n, dtype=np.int32) if slot_order is None else np.ascontiguousarray(slot_order, np.int32)
+        if act.shape != (n,) or order.shape != (n,):
+            raise ValueError("active / slot_order must have one entry per row")
+        arena = []
+        for rows, fill in ((k_rows, k_fill), (v_rows, v_fill)):
+            a = np.empty((n, 16, int(tmax), 64), np.float32)
+            for r in range(n):
+                p = min(max(int(cl[r]) - 1, 0), int(tmax))             # (an out-of-range context is the entry's to refuse)
+                a[r, :, p:] = fill if np.isscalar(fill) else fill[r]
+                if p:
+                    kr = np.asarray(rows[r], np.float32)
+                    if kr.shape != (int(cl[r]) - 1, 16, 64):
+                        raise ValueError(f"row {r}: cached rows must be ({int(cl[r]) - 1}, 16, 64), got {kr.shape}")
+                    a[r, :, :p] = kr[:p].transpose(1, 0, 2)
+            arena.append(a)
+        k0, v0 = arena
+        k, v = k0.copy(), v0.copy()
+
+        def opt(a, shapes, what):
+            if a is None:
+                return None, None
+            a = np.ascontiguousarray(a, np.float32)
+            if a.shape not in shapes:
+                raise ValueError(f"{what} must be one of {shapes}, got {a.shape}")
+            return a, _ptr(a, C.c_float)
+        qkv, pq = opt(qkv, [((8 if qkv_balanced else 4), n, 3072)], "qkv")
+        x_in, px = opt(x_in, [(9, n, 1024)] if skp else [(n, 1024)], "x_in")
+        resid, pr = opt(resid, [(n, 1024)], "resid")
+        out = np.empty((4, n, 1024), np.float32)
+        xp_att = np.empty((n, 1024), np.float32)
+        part_ml = np.empty((n, 16, 17, 2), np.float32)
+        geom = np.zeros(3, np.int32)
+        self._chk(self.lib.vx_dev_dec_attn(self.ctx, n, int(tmax), int(bool(qkv_balanced)), int(skp), _ptr(cl, C.c_int32), _ptr(act, C.c_int32),
+                                           _ptr(order, C.c_int32), _ptr(k, C.c_float), _ptr(v, C.c_float), pq, px, pr, _ptr(out, C.c_float),
+                                           _ptr(xp_att, C.c_float), _ptr(part_ml, C.c_float), _ptr(geom, C.c_int32)))
+        return dict(nsplit=int(geom[0]), sb_qkv=bool(geom[1]), split_fused=bool(geom[2]), out=out, xp_att=xp_att, part_ml=part_ml,
+                    k=k, v=v, k0=k0, v0=v0)
 
     def last_fallbacks(self):
         """phases of the last call that left the fp16 range of the f16x2 kernels and were re-run in fp32 (+ lifetime count)"""

@@ -773,4 +773,151 @@ int vx_dev_attn(vx_ctx* c, int32_t variant, int32_t planes, int32_t batch, const
   return VX_OK;
 }
 
+// vx_dev_dec_attn: the attention block of ONE decode step of layer 0 on caller-chosen operands -- the launch sequence of ar_step_launches
+// from the attention launch to the launch behind which the out_proj result exists, with the geometry decode_geometry picks for `nrows`.
+// Everything the launches touch is private scratch pre-filled with the sentinels (the K / V arena included: [nrows slots][16][Tmax][64]);
+// the context only lends its layer-0 weights and its geometry switches, and the four geometry fields decode_geometry sets are put
+// back, so the decode state of the context is not touched.
+int vx_dev_dec_attn(vx_ctx* c, int32_t nrows, int32_t Tmax, int32_t qkv_balanced, int32_t skp, const int32_t* ctx_len,
+                    const int32_t* active, const int32_t* slot_order, float* kc, float* vc, const float* qkv, const float* x_in,
+                    const float* resid, float* out, float* xp_att, float* part_ml, int32_t* geom) {
+  if (!c) return VX_EINVAL;
+  if (!ctx_len || !active || !slot_order || !kc || !vc || !out || !xp_att || !part_ml || !geom)
+    FAIL(VX_EINVAL, "vx_dev_dec_attn: null argument");
+  if (c->serve) FAIL(VX_ESTATE, "vx_dev_dec_attn: a serving session is open on this context (vx_serve_close it first)");
+  if (!c->finalized || c->ar.empty()) FAIL(VX_ESTATE, "vx_dev_dec_attn: weights not finalized");
+  if (nrows < 1 || nrows > MB) FAIL(VX_EINVAL, "vx_dev_dec_attn: nrows must be 1 .. %d", MB);
+  if (Tmax < DEC_ATTN_TILE || Tmax > 4096) FAIL(VX_EINVAL, "vx_dev_dec_attn: Tmax must be %d .. 4096", DEC_ATTN_TILE);
+  if (skp != 0 && skp != SK_L2) FAIL(VX_EINVAL, "vx_dev_dec_attn: skp must be 0 or %d", SK_L2);
+  bool identity = true;
+  {
+    unsigned seen = 0;
+    for (int y = 0; y < nrows; ++y) {
+      const int r = slot_order[y];
+      if (r < 0 || r >= nrows || (seen >> r & 1u)) FAIL(VX_EINVAL, "vx_dev_dec_attn: slot_order is not a permutation of 0 .. %d", nrows - 1);
+      seen |= 1u << r;
+      identity = identity && r == y;
+    }
+  }
+  if (nrows <= SB_ROWS && !identity) FAIL(VX_EINVAL, "vx_dev_dec_attn: up to %d rows the slot order must be the identity", SB_ROWS);
+  for (int r = 0; r < nrows; ++r) {
+    if (ctx_len[r] < 1 || ctx_len[r] > Tmax) FAIL(VX_EINVAL, "vx_dev_dec_attn: row %d: the context (%d) must be 1 .. Tmax = %d", r, ctx_len[r], Tmax);
+    if (active[r] != 0 && active[r] != 1) FAIL(VX_EINVAL, "vx_dev_dec_attn: row %d: active must be 0 or 1", r);
+  }
+  // the product's own rule; the context's geometry fields are put back below (a later ar_prefill / vx_serve_open sets its own anyway)
+  const int k_nsplit = c->nsplit;
+  const bool k_sf = c->split_fused, k_sbc = c->sb_chain, k_sbq = c->sb_qkv;
+  decode_geometry(c, nrows, identity);
+  const int nsplit = c->nsplit;
+  const bool split_fused = c->split_fused, sb_chain = c->sb_chain, sb_qkv = c->sb_qkv;
+  c->nsplit = k_nsplit; c->split_fused = k_sf; c->sb_chain = k_sbc; c->sb_qkv = k_sbq;
+  geom[0] = nsplit; geom[1] = sb_qkv; geom[2] = split_fused;
+  if (sb_chain && !sb_qkv) FAIL(VX_ESTATE, "vx_dev_dec_attn: the small-batch chain without the fused QKV (VX_SB_QKV) is not covered by this entry");
+  const bool fused = !sb_chain && c->fuse_out && (nsplit == 1 || split_fused);
+  if (sb_qkv ? !x_in : (!qkv || !resid)) FAIL(VX_EINVAL, "vx_dev_dec_attn: %s", sb_qkv ? "this chain reads x_in" : "this chain reads qkv and resid");
+  const LayerW& L = c->ar[0];
+  if (fused && !L.out_wh) FAIL(VX_ESTATE, "vx_dev_dec_attn: the context has no head-major W_o");
+  if ((split_fused && nsplit > 4) || nsplit > 16) FAIL(VX_ESTATE, "vx_dev_dec_attn: %d context splits exceed the scratch slabs", nsplit);
+  HIPCHK(hipSetDevice(c->dev));
+
+  constexpr int d = D_MODEL, NP = 3 * D_MODEL, NPART = 17;                 // NPART: partials per (row, head) of the scratch, >= nsplit + 1
+  const size_t stream_w = (size_t)N_HEAD * Tmax * D_HEAD, arena = (size_t)nrows * stream_w;
+  const size_t f_qkv = 0, f_xp = f_qkv + (size_t)SK_QKV_BAL_Q * MB * NP, f_xpa = f_xp + (size_t)MB * d, f_po = f_xpa + (size_t)MB * d,
+               f_poh = f_po + (size_t)SK_L2 * MB * d, f_pto = f_poh + (size_t)4 * N_HEAD * MB * d, f_pml = f_pto + (size_t)MB * N_HEAD * NPART * D_HEAD,
+               f_qkn = f_pml + (size_t)MB * N_HEAD * NPART * 2, f_dh = f_qkn + (size_t)MB * N_HEAD * 2 * D_HEAD, f_dh2 = f_dh + (size_t)MB * d,
+               fend = f_dh2 + (size_t)MB * d;
+  static_assert(SK_OUT <= SK_L2 && SK_QKV <= SK_QKV_BAL_Q, "p_o / p_qkv scratch is sized by the larger slab count");
+  float *dk = nullptr, *dv = nullptr, *df = nullptr;
+  int* di = nullptr;                                                       // slot_meta [MB][4] | active [MB]
+  auto cleanup = [&]() { for (void* p : {(void*)dk, (void*)dv, (void*)df, (void*)di}) if (p) (void)hipFree(p); };
+  hipError_t he;
+#define TRY(x) if ((he = (x)) != hipSuccess) { cleanup(); c->err = std::string(#x) + ": " + hipGetErrorString(he); return VX_EHIP; }
+#define TRYX(x) do { if (int _e = (x)) { cleanup(); return _e; } } while (0)
+  TRY(hipMalloc((void**)&dk, arena * 4));
+  TRY(hipMalloc((void**)&dv, arena * 4));
+  TRY(hipMalloc((void**)&df, fend * 4));
+  TRY(hipMalloc((void**)&di, (size_t)5 * MB * 4));
+  std::vector<int> slot_of(nrows);
+  for (int y = 0; y < nrows; ++y) slot_of[slot_order[y]] = y;
+  {
+    std::vector<float> hf(fend, VX_DEV_SENTINEL_F);
+    for (int r = 0; r < nrows; ++r) {
+      if (!sb_qkv) {
+        const int slabs = qkv_balanced ? SK_QKV_BAL_Q : SK_QKV;
+        for (int ks = 0; ks < slabs; ++ks) memcpy(&hf[f_qkv + ((size_t)ks * MB + r) * NP], qkv + ((size_t)ks * nrows + r) * NP, NP * 4);
+        memcpy(&hf[f_dh + (size_t)r * d], resid + (size_t)r * d, d * 4);
+      } else if (skp == 0) {
+        // the packed-x image (decode.hip ln_pack_row): float4 column c4 of row r at ((c4 >> 1) * 64 + r + 32 * (c4 & 1)) * 4
+        for (int c4 = 0; c4 < d / 4; ++c4) memcpy(&hf[f_xp + (((size_t)(c4 >> 1) * 64) + r + 32 * (c4 & 1)) * 4], x_in + (size_t)r * d + 4 * c4, 16);
+      } else {
+        for (int ks = 0; ks < SK_L2; ++ks) memcpy(&hf[f_po + ((size_t)ks * MB + r) * d], x_in + ((size_t)ks * nrows + r) * d, d * 4);
+        memcpy(&hf[f_dh + (size_t)r * d], x_in + ((size_t)SK_L2 * nrows + r) * d, d * 4);
+      }
+    }
+    std::vector<int> hi(5 * MB, 0);
+    for (int y = 0; y < nrows; ++y) {
+      const int r = slot_order[y];
+      hi[4 * y] = r; hi[4 * y + 1] = ctx_len[r]; hi[4 * y + 2] = active[r];
+      hi[4 * MB + r] = active[r];
+    }
+    TRYX(xfer_h2d(c, df, hf.data(), fend * 4));
+    TRYX(xfer_h2d(c, di, hi.data(), hi.size() * 4));
+    for (int r = 0; r < nrows; ++r) {
+      TRYX(xfer_h2d(c, dk + (size_t)slot_of[r] * stream_w, kc + (size_t)r * stream_w, stream_w * 4));
+      TRYX(xfer_h2d(c, dv + (size_t)slot_of[r] * stream_w, vc + (size_t)r * stream_w, stream_w * 4));
+    }
+  }
+  const int* d_meta = di;
+  const int* d_active = di + 4 * MB;
+  float *p_qkv = df + f_qkv, *xp = df + f_xp, *xpa = df + f_xpa, *p_o = df + f_po, *p_oh = df + f_poh, *pt_o = df + f_pto, *pt_ml = df + f_pml,
+        *qk_new = df + f_qkn, *dh = df + f_dh, *dh2 = df + f_dh2;
+  hipStream_t st = c->stream;
+  bool ok = true;
+  if (sb_qkv) {
+    ok = launch_dec_attn_qkv(L.in_w, L.in_b, dk, dv, Tmax, d_meta, pt_o, pt_ml, qk_new, nsplit, nrows, skp ? p_o : nullptr, skp,
+                             skp ? L.l2_b : nullptr, dh, dh2, L.n1_w, L.n1_b, xp, st);
+    ok = ok && launch_skinny_gemm_sb_combine(L.out_wp, p_o, D_MODEL, SK_OUT, pt_o, pt_ml, nsplit + 1, nrows, st, qk_new);
+  } else if (!launch_dec_attn(p_qkv, qkv_balanced ? SK_QKV_BALANCED : SK_QKV, L.in_b, dk, dv, Tmax, d_meta, xpa, pt_o, pt_ml, nsplit, nrows,
+                              fused ? L.out_wh : nullptr, p_oh, st)) {
+    ok = false;
+  } else if (fused && nsplit > 1) {
+    ok = launch_dec_reduce_ln_split(p_oh, pt_ml, nsplit, L.out_b, dh, dh, L.n2_w, L.n2_b, xp, nrows, st);
+  } else if (fused) {
+    launch_dec_reduce_ln_pack(p_oh, N_HEAD, D_MODEL, L.out_b, dh, dh, L.n2_w, L.n2_b, xp, nrows, st);
+  } else {
+    if (nsplit > 1) launch_dec_attn_combine(pt_o, pt_ml, nsplit, d_active, xpa, nrows, st);
+    launch_skinny_gemm(L.out_wp, xpa, p_o, D_MODEL, D_MODEL, SK_OUT, st, true);
+    launch_dec_reduce_ln_pack(p_o, SK_OUT, D_MODEL, L.out_b, dh, dh, L.n2_w, L.n2_b, xp, nrows, st);
+  }
+  if (!ok) {
+    (void)hipStreamSynchronize(st);
+    cleanup();
+    FAIL(VX_EINVAL, "vx_dev_dec_attn: a launcher refused this configuration (%d rows, %d splits)", nrows, nsplit);
+  }
+  std::vector<float> of(fend);
+  TRYX(xfer_d2h(c, of.data(), df, fend * 4));
+  for (int r = 0; r < nrows; ++r) {
+    TRYX(xfer_d2h(c, kc + (size_t)r * stream_w, dk + (size_t)slot_of[r] * stream_w, stream_w * 4));
+    TRYX(xfer_d2h(c, vc + (size_t)r * stream_w, dv + (size_t)slot_of[r] * stream_w, stream_w * 4));
+  }
+  TRYX(xfer_sync(c));
+  TRY(hipGetLastError());
+  // outputs, indexed by row.  out [SK_OUT][nrows][1024]: the out_proj slabs of the small-batch chain; the other chains: out[0] = h
+  const int np = sb_qkv ? nsplit + 1 : nsplit;
+  for (size_t i = 0; i < (size_t)SK_OUT * nrows * d; ++i) out[i] = VX_DEV_SENTINEL_F;
+  for (size_t i = 0; i < (size_t)nrows * N_HEAD * NPART * 2; ++i) part_ml[i] = VX_DEV_SENTINEL_F;
+  for (int r = 0; r < nrows; ++r) {
+    if (sb_qkv)
+      for (int ks = 0; ks < SK_OUT; ++ks) memcpy(out + ((size_t)ks * nrows + r) * d, &of[f_po + ((size_t)ks * MB + r) * d], d * 4);
+    else memcpy(out + (size_t)r * d, &of[f_dh + (size_t)r * d], d * 4);
+    for (int c4 = 0; c4 < d / 4; ++c4) memcpy(xp_att + (size_t)r * d + 4 * c4, &of[f_xpa + (((size_t)(c4 >> 1) * 64) + r + 32 * (c4 & 1)) * 4], 16);
+    for (int h = 0; h < N_HEAD; ++h)
+      memcpy(part_ml + ((size_t)(r * N_HEAD + h) * NPART) * 2, &of[f_pml + ((size_t)(r * N_HEAD + h) * np) * 2], (size_t)np * 2 * 4);
+  }
+#undef TRY
+#undef TRYX
+  cleanup();
+  return VX_OK;
+}
+
 }  // extern "C"

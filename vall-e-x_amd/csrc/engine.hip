@@ -388,7 +388,7 @@ const float* prefill_hsrc(const vx_ctx* c, const PrefillPlan& p) { return p.trim
 // Decode geometry of a decode batch of nrows rows: context splits of dec_attn, chain choice (host state only; the first fill of a
 // decode batch sets it through ar_prefill, a serving session once for its nd free rows, serve_setup).  `identity`: the launch slot
 // order is the identity (slot == row).
-static void decode_geometry(vx_ctx* c, int nrows, bool identity) {
+void decode_geometry(vx_ctx* c, int nrows, bool identity) {
   // enough (row, head, split) 8-wave workgroups to put >= 2 on every CU; one split (no combine launch) from 32 rows up
   c->nsplit = std::max(1, std::min(16, 512 / (nrows * N_HEAD)));
   // 5 .. 16 rows: ONE 8-wave workgroup per CU (256 / (rows x 16) splits, at least 2) -- round 6 sweep at 5 / 8 / 12 / 16 rows x contexts

@@ -288,6 +288,9 @@ struct ServeSampleArgs;
 // rsa != null (serving session): the step ends in the per-row sampler (serve_sample.hip) instead of dec_sample
 void ar_step_launches(vx_ctx* c, const SampleArgs* sa, const ServeSampleArgs* rsa = nullptr);
 int launch_status(vx_ctx* c);      // VX_EINVAL (+ message) if a launcher refused since the last check
+// decode geometry of a decode batch of nrows rows (engine.hip): sets c->nsplit, c->split_fused, c->sb_chain, c->sb_qkv; `identity`: the
+// launch slot order is the identity.  Also called by vx_dev_dec_attn (bench_harness.hip), which restores the four fields.
+void decode_geometry(vx_ctx* c, int nrows, bool identity);
 // best_of fan-out (beams.hip): one launch per prefill.  pairs [npairs][3] = {source slot, destination slot, cached rows}: that many
 // K / V rows of every (layer, head) are copied between the two arena slots; dh[d] = hsrc[hsrc_row[d]] for the nrows decode rows.
 // Every slot < mbr, every row count <= Tmax (the caller builds the table from its own slot map).
