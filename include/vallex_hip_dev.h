@@ -114,6 +114,44 @@ int vx_dev_attn(vx_ctx* ctx, int32_t variant, int32_t planes, int32_t batch, con
 int vx_dev_dec_attn(vx_ctx* ctx, int32_t nrows, int32_t Tmax, int32_t qkv_balanced, int32_t skp, const int32_t* ctx_len,
                     const int32_t* active, const int32_t* slot_order, float* kc, float* vc, const float* qkv, const float* x_in,
                     const float* resid, float* out, float* xp_att, float* part_ml, int32_t* geom);
+/* ONE launch of the rest of the decode step -- the skinny GEMMs, linear1, reduce + LayerNorm, their small-batch consumers, the
+ * teacher-forced embedding -- through the product launcher on nrows (1 .. 32) chosen rows.  The weights are the context's own device
+ * images of `layer` (in_wp, out_wp, l1_wp, l2_wp, pred_wp as the load-time pack kernels wrote them, the biases and the norms), the
+ * split counts the engine's (4 K slices for in_proj, out_proj and predict, 8 for linear2 and the q columns of the balanced in_proj,
+ * predict padded to 1056 columns), write-through result stores of the general GEMM on when nrows > 4 as in the engine.  Everything
+ * else the launch reads or writes is private scratch pre-filled with VX_DEV_SENTINEL_F; the context's decode state is not touched.
+ * Activation operands travel un-packed as the whole 32-row image [32][K] row-major (the entry packs and un-packs), so the caller
+ * decides what rows nrows .. 31 hold; slabs travel as [slices][32][N] with all 32 rows.  Arguments an op does not use may be NULL.
+ *   op                      variant                       reads                              writes
+ *   EMBED (norm1, layer 0)  0                             tok, pos [nrows]                   h [nrows][1024], xp [32][1024]
+ *   GEMM                    weight VX_DEV_W_*             x [32][K] (K 4096 for linear2)     out [4 | 8][32][3072 | 1024 | 1056]
+ *   QKV_BAL                 0                             x [32][1024]                       out [8][32][3072] (k, v columns: slabs 0 .. 3)
+ *   LINEAR1                 0                             x [32][1024]                       out [32][4096] = relu(x W1^T + b1), the image
+ *   REDUCE_LN               slabs 0 | 4 | 8 | 16          slabs [variant][32][1024], resid   h, xp; resid = the buffer behind the launch
+ *   SB_LN_GEMM (<= 4 rows)  VX_DEV_W_IN | VX_DEV_W_PRED   slabs [8][32][1024], resid         out (as GEMM), h, resid
+ *   SB_LINEAR1 (<= 4 rows)  0                             slabs [4][32][1024], resid         out (as LINEAR1), h, resid
+ * REDUCE_LN: h = resid + (sum of the slabs + bias), xp = LayerNorm(h); 4 and 16 slabs: out_proj's bias and norm2 of `layer`; 8:
+ * linear2's bias of `layer` and norm1 of layer + 1, the final norm behind the last layer; 0: the final norm of resid alone, no bias,
+ * and the kernel is handed no h (h returns the sentinel).  With slabs it works in place as in the engine: resid returns h.
+ * SB_LN_GEMM: the GEMM whose prologue is REDUCE_LN 8 -- in_proj of `layer` >= 1 behind linear2 of layer - 1, or predict behind the
+ * last layer; SB_LINEAR1: linear1 whose prologue is REDUCE_LN 4.  Both write h into the other buffer of the engine's dh / dh2 pair:
+ * resid returns unchanged.  (The engine hands predict no h; the entry does.)
+ * VX_EINVAL, nothing launched: an unknown op or variant, nrows outside 1 .. 32 (1 .. 4 for the small-batch ops), a layer the context
+ * does not have, in_proj through SB_LN_GEMM at layer 0 or predict anywhere but behind the last layer, a tok outside the embedding
+ * table or a pos outside the positional table.  VX_ESTATE while a serving session is open. */
+#define VX_DEV_OP_EMBED 0
+#define VX_DEV_OP_GEMM 1
+#define VX_DEV_OP_QKV_BAL 2
+#define VX_DEV_OP_LINEAR1 3
+#define VX_DEV_OP_REDUCE_LN 4
+#define VX_DEV_OP_SB_LN_GEMM 5
+#define VX_DEV_OP_SB_LINEAR1 6
+#define VX_DEV_W_IN 0
+#define VX_DEV_W_OUT 1
+#define VX_DEV_W_L2 2
+#define VX_DEV_W_PRED 3
+int vx_dev_dec_op(vx_ctx* ctx, int32_t op, int32_t variant, int32_t layer, int32_t nrows, const int32_t* tok, const int32_t* pos,
+                  const float* x, const float* slabs, float* resid, float* out, float* h, float* xp);
 
 #ifdef __cplusplus
 }

@@ -441,3 +441,312 @@ def dec_append_expected(case, w):
     t = (t + w["in_b"].astype(np.float32)).astype(np.float32)
     n = t.shape[0]
     return t[:, 1024:2048].reshape(n, 16, 64), t[:, 2048:].reshape(n, 16, 64)
+
+
+# ---- the GEMM / FFN / LayerNorm half of one decode step (vx_dev_dec_op; csrc/decode.hip) -------------------------------------------
+# weight -> (N, padded N, K, K slices) of the engine (engine_ctx.h: SK_QKV, SK_OUT, SK_L2, SK_PRED, PRED_NPAD)
+FFN_GEMMS = {"in_proj": (3072, 3072, 1024, 4), "out_proj": (1024, 1024, 1024, 4), "linear2": (1024, 1024, 4096, 8), "predict": (1025, 1056, 1024, 4)}
+FFN_ROWS = (5, 7, 16, 17, 32)             # the general kernels
+FFN_SB_ROWS = (1, 2, 3, 4)                # the small-batch consumers
+FFN_GEMM_SETS = ("normal", "model", "cancel")
+FFN_LN_SETS = ("normal", "mean1e3", "const", "mag1e4", "slabs1e4")
+FFN_FILL = np.float32(-1.0e30)            # what image / slab rows behind the last row hold: the entry's sentinel
+
+
+def ffn_weights(sd, nl):
+    """the AR decoder's weights of a synth state dict: w[layer][name], w['norm'], w['pred'], w['emb'], w['alpha']"""
+    w = {}
+    for l in range(nl):
+        p = f"ar_decoder.layers.{l}."
+        w[l] = dict(in_proj=sd[p + "self_attn.in_proj_weight"], in_b=sd[p + "self_attn.in_proj_bias"], out_proj=sd[p + "self_attn.out_proj.weight"],
+                    out_b=sd[p + "self_attn.out_proj.bias"], linear1=sd[p + "linear1.weight"], l1_b=sd[p + "linear1.bias"],
+                    linear2=sd[p + "linear2.weight"], l2_b=sd[p + "linear2.bias"], n1=(sd[p + "norm1.weight"], sd[p + "norm1.bias"]),
+                    n2=(sd[p + "norm2.weight"], sd[p + "norm2.bias"]))
+    w["norm"] = (sd["ar_decoder.norm.weight"], sd["ar_decoder.norm.bias"])
+    w["pred"] = sd["ar_predict_layer.weight"]
+    w["emb"] = sd["ar_audio_embedding.word_embeddings.weight"]
+    w["alpha"] = np.float32(sd["ar_audio_position.alpha"][0])
+    w["nl"] = nl
+    return w
+
+
+def ffn_weight(w, name, layer):
+    return w["pred"] if name == "predict" else w[layer][name]
+
+
+def linear_ref(x, wt, bias=None, relu=False):
+    """x W^T (+ bias) (ReLU) in float64 on the fp32 operands"""
+    y = np.asarray(x, np.float64) @ np.asarray(wt, np.float64).T
+    if bias is not None:
+        y = y + np.asarray(bias, np.float64)
+    return np.maximum(y, 0.0) if relu else y
+
+
+def linear_fp32(x, wt, bias=None, relu=False):
+    """the yardstick: torch-CPU fp32 F.linear (F.relu)"""
+    import torch
+    import torch.nn.functional as F
+    T = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.float32))
+    y = F.linear(T(x), T(wt), T(bias))
+    return (F.relu(y) if relu else y).numpy()
+
+
+def reduce_ln_ref(slabs, bias, resid, norm):
+    """(h, LayerNorm(h)) in float64: h = resid + sum of the slabs + bias; slabs (SK, n, 1024) or None, bias or None"""
+    h = np.asarray(resid, np.float64)
+    if slabs is not None and len(slabs):
+        h = h + np.asarray(slabs, np.float64).sum(0)
+    if bias is not None:
+        h = h + np.asarray(bias, np.float64)
+    return h, layer_norm_ref(h, norm[0], norm[1])
+
+
+def reduce_ln_fp32(slabs, bias, resid, norm):
+    """the yardstick: the same in torch-CPU fp32 (sum over the slab axis, F.layer_norm)"""
+    import torch
+    import torch.nn.functional as F
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32))
+    h = T(resid)
+    if slabs is not None and len(slabs):
+        s = T(slabs).sum(0)
+        h = h + (s + T(bias) if bias is not None else s)
+    return h.numpy(), F.layer_norm(h, (1024,), T(norm[0]), T(norm[1]), 1e-5).numpy()
+
+
+def reduce_h_exact(slabs, bias, resid):
+    """h as the reduce kernels form it in fp32: resid + ((((p0 + p1) + ...) + p_last) + bias)"""
+    v = np.array(slabs[0], np.float32)
+    for ks in range(1, len(slabs)):
+        v = (v + np.asarray(slabs[ks], np.float32)).astype(np.float32)
+    if bias is not None:
+        v = (v + np.asarray(bias, np.float32)).astype(np.float32)
+    return (np.asarray(resid, np.float32) + v).astype(np.float32)
+
+
+def embed_exact(emb, alpha, pe, tok, pos):
+    """fp32(emb[tok] + fp32(alpha * pe[pos])): two roundings, what torch computes for emb + alpha * pe (modules/embedding.py:93-97)"""
+    return (emb[tok] + (np.float32(alpha) * pe[pos]).astype(np.float32)).astype(np.float32)
+
+
+def embed_ref(emb, alpha, pe, tok, pos):
+    return emb[tok].astype(np.float64) + np.float64(alpha) * pe[pos].astype(np.float64)
+
+
+# identity probes: every kernel as a reader of its own weight image
+def probe_plan(K):
+    """the K / 32 launches that walk every k once: row b of launch j holds 2^(b % 5 - 2) at column b * (K / 32) + j and zeros elsewhere, so
+    the 32 k's of one launch spread over every K slice and every wave of a slice"""
+    return [np.arange(32) * (K // 32) + j for j in range(K // 32)]
+
+
+def probe_scale():
+    return np.ldexp(np.float32(1.0), np.arange(32) % 5 - 2).astype(np.float32)
+
+
+def probe_image(ks, K, nrows=32):
+    """the un-packed x image of one probe launch; rows nrows .. 31 hold the sentinel"""
+    x = np.zeros((32, K), np.float32)
+    x[np.arange(32), ks] = probe_scale()
+    x[nrows:] = FFN_FILL
+    return x
+
+
+def slab_of(n, k, K, sk):
+    """the slab of skinny_gemm_kernel that owns k (every column alike): k // (K / sk)"""
+    return np.asarray(k) // (K // sk) + 0 * np.asarray(n)
+
+
+def slab_of_balanced(n, k):
+    """skinny_qkv_bal_kernel: the q columns (n < 1024) are cut into eight K slices of 128, the k and v columns into four of 256"""
+    n, k = np.asarray(n), np.asarray(k)
+    return np.where(n < 1024, k // 128, k // 256)
+
+
+def probe_expected(wt, ks, npad, sk, balanced=False):
+    """what a GEMM probe launch must leave: (sk, 32, npad) fp32; the balanced layout's unwritten k, v columns of slabs 4 .. 7 hold
+    the sentinel, padding columns hold 0"""
+    N, K = wt.shape
+    exp = np.zeros((sk, 32, npad), np.float32)
+    if balanced:
+        exp[4:, :, 1024:] = FFN_FILL
+    sc = probe_scale()
+    cols = np.arange(N)
+    for b, k in enumerate(ks):
+        s = slab_of_balanced(cols, k) if balanced else slab_of(cols, k, K, sk)
+        exp[s, b, cols] = wt[:, k] * sc[b]
+    return exp
+
+
+def probe_expected_linear1(wt, bias, ks):
+    """max(fp32(fp32(W[n][k] 2^e) + b1[n]), 0) of every row: (32, 4096)"""
+    sc = probe_scale()
+    return np.maximum((wt[:, ks].T * sc[:, None]).astype(np.float32) + bias[None].astype(np.float32), np.float32(0.0)).astype(np.float32)
+
+
+# operand sets
+def cancel_columns(name):
+    """the output columns the 'cancel' set cancels on: x lies in the null space of these rows of W.  Fewer than K of them (a fixed
+    weight with N >= K rows has no x that cancels on every column: the smallest singular value of a 3072 x 1024 matrix bounds
+    |W x| / |x| from below), spread over every column tile"""
+    N, _, K, _ = FFN_GEMMS.get(name, (4096, 4096, 1024, 1))
+    return np.arange(0, N, max(1, -(-2 * N // K)))
+
+
+def gemm_operands(kind, wt, name, nrows, seed):
+    """x (32, K) fp32 of a GEMM set; rows nrows .. 31 hold the sentinel.  normal: unit normal; model: normal with per-channel gains from
+    {0.1, 1, 4}; cancel: a unit normal projected onto the null space of the rows cancel_columns(name) of W (float64, then rounded)"""
+    rng = np.random.default_rng(seed)
+    K = wt.shape[1]
+    x = rng.normal(0.0, 1.0, (32, K))
+    if kind == "model":
+        x = x * rng.choice([0.1, 1.0, 4.0], K)
+    elif kind == "cancel":
+        ws = wt[cancel_columns(name)].astype(np.float64)
+        x = x - np.linalg.solve(ws @ ws.T, ws @ x.T).T @ ws
+    elif kind != "normal":
+        raise ValueError(kind)
+    x = x.astype(np.float32)
+    x[nrows:] = FFN_FILL
+    return x
+
+
+def cancellation(x, wt, cols):
+    """max over the rows and the columns `cols` of |x . w_n| / sum_k |x_k w_nk| in float64"""
+    x, ws = np.asarray(x, np.float64), np.asarray(wt, np.float64)[cols]
+    return float((np.abs(x @ ws.T) / (np.abs(x) @ np.abs(ws).T)).max())
+
+
+def ln_operands(kind, sk, bias, nrows, seed):
+    """launches [(slabs (sk, 32, 1024) fp32, resid (nrows, 1024) fp32)] of a LayerNorm set; h = resid + sum of the slabs + bias.
+      normal    resid unit normal, slabs normal / sqrt(sk)        mean1e3   h = 1e3 + a spread of 1 (a one-pass variance is wrong)
+      const     h exactly constant (the first slab holds -bias: variance 0, rstd = eps^-1/2) in the first launch; the fp32 yardstick is
+                exact there, so further launches hold constants with a spread of 1e-4 (variance far below eps) for the ratio
+      mag1e4    h of magnitude 1e4                               slabs1e4  slabs of +-1e4 that cancel to order 1 (sk >= 2)
+    slab rows nrows .. 31 hold the sentinel"""
+    rng = np.random.default_rng(seed)
+    zb = np.zeros(1024, np.float32) if bias is None else np.asarray(bias, np.float32)
+
+    def done(slabs, resid):
+        slabs = np.asarray(slabs, np.float32).reshape(sk, 32, 1024)
+        slabs[:, nrows:] = FFN_FILL
+        return slabs, np.asarray(resid, np.float32)[:nrows].copy()
+
+    slabs = rng.normal(0.0, 1.0 / np.sqrt(max(sk, 1)), (sk, 32, 1024))
+    resid = rng.normal(0.0, 1.0, (32, 1024))
+    if kind == "normal":
+        return [done(slabs, resid)]
+    if kind == "mean1e3":
+        return [done(0.1 * slabs, 1.0e3 + resid)]
+    if kind == "mag1e4":
+        return [done(slabs, 1.0e4 * resid)]
+    if kind == "slabs1e4":
+        if sk < 2:
+            raise ValueError("no slabs to cancel")
+        big = rng.uniform(0.5, 1.5, (sk // 2, 32, 1024)) * 1.0e4 * rng.choice([-1.0, 1.0], (sk // 2, 32, 1024))
+        s = slabs.astype(np.float32)
+        s[0::2] = big.astype(np.float32)
+        s[1::2] = (slabs[1::2] - big).astype(np.float32)
+        return [done(s, resid)]
+    if kind == "const":
+        s = np.zeros((sk, 32, 1024), np.float32)
+        if sk:
+            s[0] = -zb
+        c = np.array([3.0, 1.1, -2.7, 10.3, 0.1, -7.3, 1.0e-3, 20.0], np.float32)[np.arange(32) % 8]
+        out = [done(s.copy(), np.repeat(c[:, None], 1024, 1))]
+        # next to a constant c the LayerNorm result moves by rstd = 316 for every unit of (x - mean), and (x - mean) comes in units of
+        # ulp(c): a row's error is its mean's last bit, in the kernel and in the yardstick alike, so one row says nothing -- at least 16
+        # rows go into the pool, each a constant of 0.1 .. 3 plus a spread of 1e-4 (hundreds of ulps; variance 1e-8, 0.1 % of eps)
+        for _ in range(-(-16 // nrows)):
+            cr = rng.uniform(0.1, 3.0, (32, 1)) * rng.choice([-1.0, 1.0], (32, 1))
+            out.append(done(s.copy(), cr + 1.0e-4 * rng.normal(0.0, 1.0, (32, 1024))))
+        return out
+    raise ValueError(kind)
+
+
+FFN_OPS = ("gemm:in_proj", "gemm:out_proj", "gemm:linear2", "gemm:predict", "qkv_bal", "linear1", "reduce_ln:0", "reduce_ln:4", "reduce_ln:8",
+           "reduce_ln:16")
+FFN_SB_OPS = ("sb_ln_gemm:in_proj", "sb_ln_gemm:predict", "sb_linear1")
+_FFN_CASES = {}
+
+
+def ffn_sets(op):
+    if op.startswith(("gemm", "qkv_bal", "linear1")):
+        return FFN_GEMM_SETS
+    return tuple(k for k in FFN_LN_SETS if not (op == "reduce_ln:0" and k == "slabs1e4"))
+
+
+def ffn_layer(op, nrows, nl=2):
+    """the layer a case runs on: alternating with the row count, except where the op fixes it"""
+    if op.startswith("sb_ln_gemm"):
+        return nl - 1
+    return nrows % nl
+
+
+def ffn_reduce_params(w, layer, sk):
+    """(bias, norm) of a reduce + LayerNorm launch as the engine pairs them (engine.hip ar_step_launches)"""
+    if sk == 0:
+        return None, w["norm"]
+    if sk == 8:
+        return w[layer]["l2_b"], (w[layer + 1]["n1"] if layer + 1 < w["nl"] else w["norm"])
+    return w[layer]["out_b"], w[layer]["n2"]
+
+
+def ffn_case(op, nrows, kind, w):
+    """launches of one (op, row count, operand set): [dict(args = keyword arguments of Engine.dev_dec_op, ref, yard = {quantity: rows
+    < nrows})] with the float64 reference and the torch-CPU fp32 yardstick on the fp32 operands.  Quantities: 'sum' (the slab sum of a
+    GEMM, no bias), 'act' (linear1's ReLU output), 'xp' (the LayerNorm output)."""
+    import zlib
+    key = (op, nrows, kind)
+    if key in _FFN_CASES:
+        return _FFN_CASES[key]
+    seed = zlib.crc32(repr(key).encode())
+    name, _, arg = op.partition(":")
+    layer = ffn_layer(op, nrows, w["nl"])
+    out = []
+    if name in ("gemm", "qkv_bal", "linear1"):
+        wname = arg if name == "gemm" else "in_proj" if name == "qkv_bal" else "linear1"
+        wt = ffn_weight(w, wname, layer)
+        x = gemm_operands(kind, wt, wname, nrows, seed)
+        args = dict(op=name, nrows=nrows, layer=layer, x=x)
+        if name == "gemm":
+            args["weight"] = arg
+        bias, relu, q = (w[layer]["l1_b"], True, "act") if name == "linear1" else (None, False, "sum")
+        out.append(dict(args=args, ref={q: linear_ref(x[:nrows], wt, bias, relu)}, yard={q: linear_fp32(x[:nrows], wt, bias, relu)}))
+    else:
+        sk = int(arg) if name == "reduce_ln" else 8 if name == "sb_ln_gemm" else 4
+        # the small-batch consumers: REDUCE_LN 8 of the layer below in front of in_proj, of the last layer in front of predict; REDUCE_LN 4
+        rl = layer - 1 if op == "sb_ln_gemm:in_proj" else layer
+        bias, norm = ffn_reduce_params(w, rl, sk)
+        for slabs, resid in ln_operands(kind, sk, bias, nrows, seed):
+            args = dict(op=name, nrows=nrows, layer=layer, slabs=slabs if sk else None, resid=resid)
+            sl = slabs[:, :nrows] if sk else None
+            (_, xr), (_, xy) = reduce_ln_ref(sl, bias, resid, norm), reduce_ln_fp32(sl, bias, resid, norm)
+            if name == "reduce_ln":
+                args["sk"] = sk
+                ref, yard = {"xp": xr}, {"xp": xy}
+            elif name == "sb_ln_gemm":
+                args["weight"] = arg
+                wt = ffn_weight(w, arg, layer)
+                ref, yard = {"sum": linear_ref(xr, wt)}, {"sum": linear_fp32(xy, wt)}
+            else:
+                ref = {"act": linear_ref(xr, w[layer]["linear1"], w[layer]["l1_b"], True)}
+                yard = {"act": linear_fp32(xy, w[layer]["linear1"], w[layer]["l1_b"], True)}
+            out.append(dict(args=args, ref=ref, yard=yard, bias=bias, norm=norm))
+    if len(_FFN_CASES) >= 64:
+        _FFN_CASES.pop(next(iter(_FFN_CASES)))
+    _FFN_CASES[key] = out
+    return out
+
+
+def ffn_chain_ref(slabs, resid, w, layer):
+    """norm2 -> linear1 -> ReLU -> linear2 -> + residual -> the next norm -> predict of `layer` (the last one: the final norm) from
+    the out_proj slabs and the residual rows: (float64 logits, torch-CPU fp32 logits), (n, 1025)"""
+    L = w[layer]
+    bias8, norm8 = ffn_reduce_params(w, layer, 8)
+    res = []
+    for red, lin in ((reduce_ln_ref, linear_ref), (reduce_ln_fp32, linear_fp32)):
+        h, x = red(slabs, L["out_b"], resid, L["n2"])
+        y = lin(lin(x, L["linear1"], L["l1_b"], True), L["linear2"])
+        _, x2 = red(y[None], bias8, h, norm8)
+        res.append(lin(x2, w["pred"]))
+    return res[0], res[1]

@@ -132,3 +132,25 @@ def test_dev_dec_attn_prototype_matches_binding(lib):
     want = [kinds[a.rsplit(" ", 1)[0]] for a in args]
     assert lib.vx_dev_dec_attn.restype is C.c_int and len(lib.vx_dev_dec_attn.argtypes) == 17
     assert list(lib.vx_dev_dec_attn.argtypes) == want
+
+
+def test_dev_dec_op_prototype_matches_binding(lib):
+    """the header's prototype of vx_dev_dec_op and the ctypes signature agree argument by argument (13 of them), and the op / weight
+    codes of the header are the binding's"""
+    import ctypes as C
+    from vallex_amd._capi import DEV_OPS, DEV_WEIGHTS
+    raw = open(os.path.join(ROOT, "include", "vallex_hip_dev.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
+    proto = re.search(r"\bint vx_dev_dec_op\((.*?)\);", hdr, re.S).group(1)
+    args = [" ".join(a.split()) for a in proto.split(",")]
+    assert args == ["vx_ctx* ctx", "int32_t op", "int32_t variant", "int32_t layer", "int32_t nrows", "const int32_t* tok", "const int32_t* pos",
+                    "const float* x", "const float* slabs", "float* resid", "float* out", "float* h", "float* xp"], args
+    kinds = {"vx_ctx*": C.c_void_p, "int32_t": C.c_int32, "const int32_t*": C.POINTER(C.c_int32), "float*": C.POINTER(C.c_float),
+             "const float*": C.POINTER(C.c_float)}
+    want = [kinds[a.rsplit(" ", 1)[0]] for a in args]
+    assert lib.vx_dev_dec_op.restype is C.c_int and len(lib.vx_dev_dec_op.argtypes) == 13
+    assert list(lib.vx_dev_dec_op.argtypes) == want
+    ops = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"#define VX_DEV_OP_(\w+) (\d+)", hdr)}
+    assert ops == DEV_OPS
+    wts = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define VX_DEV_W_(\w+) (\d+)", hdr)}
+    assert wts == {"IN": DEV_WEIGHTS["in_proj"], "OUT": DEV_WEIGHTS["out_proj"], "L2": DEV_WEIGHTS["linear2"], "PRED": DEV_WEIGHTS["predict"]}

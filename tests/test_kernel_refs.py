@@ -201,3 +201,186 @@ def test_dec_attn_launch_plans_cover_the_edges():
     # one row count per chain x split count of the engine's table
     assert chains == {("sb_qkv", 16), ("sb_qkv", 8), ("sb_qkv", 4), ("unfused", 3), ("unfused", 2), ("split_fused", 4), ("split_fused", 3),
                       ("split_fused", 2), ("fused", 1)}
+
+
+# ---- the GEMM / FFN / LayerNorm half of the decode step (tests/test_gpu_kernel_dec_ffn.py) ------------------------------------------
+@pytest.fixture(scope="module")
+def ffn_sd():
+    from oracle import synth
+    sd = synth.vallex_state_dict(2, 1, 0.0)
+    return sd, R.ffn_weights(sd, 2)
+
+
+@pytest.mark.parametrize("layer", [0, 1])
+def test_ffn_reference_matches_oracle_layer(ffn_sd, layer):
+    """norm2 -> linear1 -> ReLU -> linear2 -> + residual -> the next norm (-> predict behind the last layer) in float64 == the oracle's
+    decoder layer on the synthetic 2-layer state dict, stage by stage and as the chain the GPU file runs"""
+    sd, w = ffn_sd
+    orc = VallexOracle(sd, 2)
+    rng = np.random.default_rng(31 + layer)
+    slabs = rng.normal(0.0, 0.5, (4, 6, 1024)).astype(np.float32)
+    resid = rng.normal(0.0, 1.0, (6, 1024)).astype(np.float32)
+    p = f"ar_decoder.layers.{layer}."
+    L = w[layer]
+    x0 = torch.from_numpy(resid) + (torch.from_numpy(slabs).sum(0) + torch.from_numpy(L["out_b"]))          # x + attn_out
+    n2 = orc._ln(x0, p + "norm2")
+    ffn = orc._ffn(n2, p)
+    x1 = x0 + ffn
+    nxt = orc._ln(x1, f"ar_decoder.layers.{layer + 1}.norm1" if layer == 0 else "ar_decoder.norm")
+
+    def close(got, want, what):
+        want = want.numpy().astype(np.float64)
+        assert np.abs(got - want).max() < 2e-5 * max(1.0, np.abs(want).max()), (what, np.abs(got - want).max())
+
+    h, x = R.reduce_ln_ref(slabs, L["out_b"], resid, L["n2"])
+    close(h, x0, "h")
+    close(x, n2, "norm2")
+    act = R.linear_ref(x, L["linear1"], L["l1_b"], relu=True)
+    close(act, F.relu(F.linear(n2, orc.w[p + "linear1.weight"], orc.w[p + "linear1.bias"])), "linear1")
+    assert (act == 0).any() and (act > 0).any()
+    y = R.linear_ref(act, L["linear2"])
+    bias8, norm8 = R.ffn_reduce_params(w, layer, 8)
+    h2, x2 = R.reduce_ln_ref(y[None], bias8, h, norm8)
+    close(h2, x1, "h behind linear2")
+    close(x2, nxt, "the next norm")
+    if layer == 1:
+        want = orc.ar_logits(nxt)
+        close(R.linear_ref(x2, w["pred"]), want, "predict")
+        ref, yard = R.ffn_chain_ref(slabs, resid, w, 1)
+        close(ref, want, "chain")
+        err = np.abs(yard - ref).max()
+        assert 0 < err < 1e-4 and np.abs(yard - want.numpy()).max() < 2e-5, err
+    # the fp32 yardsticks are the oracle's arithmetic
+    hy, xy = R.reduce_ln_fp32(slabs, L["out_b"], resid, L["n2"])
+    assert np.abs(hy - x0.numpy()).max() < 2e-6 and np.abs(xy - n2.numpy()).max() < 2e-6
+    assert np.abs(R.linear_fp32(xy, L["linear1"], L["l1_b"], True) - F.relu(F.linear(n2, orc.w[p + "linear1.weight"], orc.w[p + "linear1.bias"])).numpy()).max() < 2e-5
+    # the kernels' ordered fp32 slab sum is close to float64 and not the same thing
+    he = R.reduce_h_exact(slabs, L["out_b"], resid)
+    assert he.dtype == np.float32 and 0 < np.abs(he - h).max() < 1e-5
+
+
+def test_embed_reference_matches_oracle():
+    from oracle import synth
+    from oracle.vallex_oracle import sine_pe
+    sd = synth.vallex_state_dict(2, 1, 0.0)
+    w = R.ffn_weights(sd, 2)
+    pe = sine_pe(4000).numpy()
+    tok, pos = np.array([0, 1, 1023, 1024]), np.array([0, 1, 3999, 7])
+    want = torch.from_numpy(w["emb"][tok]) + torch.from_numpy(sd["ar_audio_position.alpha"]) * torch.from_numpy(pe[pos])
+    np.testing.assert_array_equal(R.embed_exact(w["emb"], w["alpha"], pe, tok, pos), want.numpy())
+    assert np.abs(R.embed_ref(w["emb"], w["alpha"], pe, tok, pos) - want.numpy()).max() < 1e-6
+    # a fused multiply-add differs somewhere on these rows: the exact probe can see a contraction
+    fma = (w["emb"][tok].astype(np.float64) + np.float64(w["alpha"]) * pe[pos].astype(np.float64)).astype(np.float32)
+    assert (fma != want.numpy()).any()
+
+
+def test_probe_plans_partition_every_k():
+    for name, (N, npad, K, sk) in list(R.FFN_GEMMS.items()) + [("linear1", (4096, 4096, 1024, 1))]:
+        plan = R.probe_plan(K)
+        assert len(plan) == K // 32 and all(len(ks) == 32 for ks in plan)
+        assert sorted(np.concatenate(plan).tolist()) == list(range(K)), name
+        # one launch reaches every K slice of the general kernel and of the balanced one
+        assert set((plan[0] // (K // sk)).tolist()) == set(range(sk)), name
+        x = R.probe_image(plan[3], K, nrows=5)
+        assert (x[5:] == R.FFN_FILL).all() and np.count_nonzero(x[:5]) == 5 and x[2, plan[3][2]] == 1.0 and x[0, plan[3][0]] == 0.25
+    assert set((R.probe_plan(1024)[0] // 128).tolist()) == set(range(8))
+    assert sum(len(p) for p in (R.probe_plan(1024),) * 4 + (R.probe_plan(4096),)) == 256          # launches of the walk over every weight
+
+
+def test_probe_expected_slabs():
+    """the expected slab of (column, k) is what decode.hip says: k // (K / SK) in skinny_gemm_kernel; skinny_qkv_bal_kernel cuts the q
+    columns into eight slices of 128 and the k, v columns into four of 256"""
+    rng = np.random.default_rng(8)
+    for name, (N, npad, K, sk) in R.FFN_GEMMS.items():
+        per = K // sk
+        for k in (0, per - 1, per, K - 1):
+            assert (R.slab_of(np.arange(N), k, K, sk) == k // per).all()
+        assert {name: per}[name] == {"in_proj": 256, "out_proj": 256, "linear2": 512, "predict": 256}[name]
+    n = np.arange(3072)
+    for k in (0, 127, 128, 255, 256, 1023):
+        s = R.slab_of_balanced(n, k)
+        assert (s[:1024] == k // 128).all() and (s[1024:] == k // 256).all()
+    assert R.slab_of_balanced(0, 1023) == 7 and R.slab_of_balanced(1024, 1023) == 3 and R.slab_of_balanced(3071, 255) == 0
+    wt = rng.uniform(-1, 1, (1025, 1024)).astype(np.float32)
+    ks = R.probe_plan(1024)[9]
+    exp = R.probe_expected(wt, ks, 1056, 4)
+    assert (exp[:, :, 1025:] == 0).all()
+    np.testing.assert_array_equal(exp.sum(0)[:, :1025], wt[:, ks].T * R.probe_scale()[:, None])
+    for b in (0, 13, 31):
+        own = ks[b] // 256
+        assert np.count_nonzero(exp[own, b]) > 1000 and not exp[[s for s in range(4) if s != own], b].any()
+    wq = rng.uniform(-1, 1, (3072, 1024)).astype(np.float32)
+    exp = R.probe_expected(wq, ks, 3072, 8, balanced=True)
+    assert (exp[4:, :, 1024:] == R.FFN_FILL).all()
+    for b in (0, 13, 31):
+        k = ks[b]
+        np.testing.assert_array_equal(exp[k // 128, b, :1024], wq[:1024, k] * R.probe_scale()[b])
+        np.testing.assert_array_equal(exp[k // 256, b, 1024:], wq[1024:, k] * R.probe_scale()[b])
+        assert not exp[[s for s in range(8) if s != k // 128], b, :1024].any() and not exp[[s for s in range(4) if s != k // 256], b, 1024:].any()
+    # the scales keep every product exact: W 2^e is a power-of-two multiple
+    assert set(R.probe_scale().tolist()) == {0.25, 0.5, 1.0, 2.0, 4.0}
+    b1 = rng.uniform(-1, 1, 4096).astype(np.float32)
+    w1 = rng.uniform(-1, 1, (4096, 1024)).astype(np.float32)
+    e1 = R.probe_expected_linear1(w1, b1, ks)
+    assert e1.shape == (32, 4096) and (e1 >= 0).all() and (e1 == 0).any() and e1[3, 5] == max(np.float32(w1[5, ks[3]] * R.probe_scale()[3]) + b1[5], 0)
+
+
+def test_cancelling_set_cancels(ffn_sd):
+    """on the columns it names, the float64 result of the 'cancel' set is at least 100 x smaller than the sum of the absolute terms (it
+    is ~1e-8 of it: only the rounding of x to fp32 is left), for every weight and every row; the normal set is nowhere near"""
+    _, w = ffn_sd
+    for name in ("in_proj", "out_proj", "linear1", "linear2", "predict"):
+        wt = R.ffn_weight(w, name, 1)
+        cols = R.cancel_columns(name)
+        assert 256 <= len(cols) < wt.shape[1] and cols[0] == 0 and cols[-1] >= wt.shape[0] - 8, name           # every column tile
+        x = R.gemm_operands("cancel", wt, name, 32, 3)
+        assert R.cancellation(x, wt, cols) < 1e-2, name
+        assert x.std() > 0.5                                                                           # still order-1 operands
+        xn = R.gemm_operands("normal", wt, name, 32, 3)
+        assert np.median(np.abs(xn.astype(np.float64) @ wt[cols].astype(np.float64).T) / (np.abs(xn.astype(np.float64)) @ np.abs(wt[cols].astype(np.float64)).T)) > 1e-2
+
+
+def test_ln_operand_sets_are_what_they_claim(ffn_sd):
+    _, w = ffn_sd
+    bias = w[0]["l2_b"]
+    for sk in (0, 4, 8, 16):
+        b = bias if sk else None
+        for kind in R.FFN_LN_SETS:
+            if kind == "slabs1e4" and sk == 0:
+                continue
+            for j, (slabs, resid) in enumerate(R.ln_operands(kind, sk, b, 5, 4)):
+                assert slabs.shape == (sk, 32, 1024) and resid.shape == (5, 1024) and (slabs[:, 5:] == R.FFN_FILL).all()
+                h, _ = R.reduce_ln_ref(slabs[:, :5] if sk else None, b, resid, w["norm"])
+                if kind == "mean1e3":
+                    assert np.abs(h.mean(-1) - 1e3).max() < 1 and 0.5 < h.std(-1).min() and h.std(-1).max() < 2
+                if kind == "const":
+                    if j == 0:
+                        assert (h == h[:, :1]).all()                          # exactly constant in float64: variance 0
+                        assert (R.reduce_h_exact(slabs[:, :5], b, resid) == h).all() if sk else True
+                    else:
+                        assert 0 < h.var(-1).max() < 1e-5 * 1e-2              # far below eps: rstd = eps^-1/2 to 1 %
+                if kind == "mag1e4":
+                    assert 5e3 < h.std(-1).min()
+                if kind == "slabs1e4":
+                    assert np.abs(slabs[:, :5]).min() > 4e3 and np.abs(slabs[:, :5].astype(np.float64).sum(0)).max() < 10
+
+
+@pytest.mark.parametrize("op", R.FFN_OPS + R.FFN_SB_OPS)
+def test_ffn_yardstick_pools_are_nonzero(ffn_sd, op):
+    """the precondition of the ratio test: on every (op, row count, operand set) the torch-CPU fp32 yardstick has an error against
+    float64, as rms and as max, pooled over the launches of the set"""
+    _, w = ffn_sd
+    for nrows in (R.FFN_SB_ROWS if op in R.FFN_SB_OPS else R.FFN_ROWS):
+        for kind in R.ffn_sets(op):
+            launches = R.ffn_case(op, nrows, kind, w)
+            for q in launches[0]["ref"]:
+                e = np.concatenate([(l["yard"][q].astype(np.float64) - l["ref"][q]).reshape(-1) for l in launches])
+                assert len(e) == len(launches) * nrows * launches[0]["ref"][q].shape[-1]
+                assert np.isfinite(e).all() and np.abs(e).max() > 0 and np.sqrt(np.mean(e ** 2)) > 0, (op, nrows, kind, q)
+                if kind == "cancel":
+                    cols = R.cancel_columns(op.partition(":")[2] or ("in_proj" if op == "qkv_bal" else "linear1"))
+                    if op != "linear1":                                         # (behind the bias and the ReLU the columns no longer cancel)
+                        assert np.abs(launches[0]["yard"][q][:, cols].astype(np.float64) - launches[0]["ref"][q][:, cols]).max() > 0
+    if op == "gemm:predict":
+        ref, yard = R.ffn_chain_ref(*[a[:, :5] if a.ndim == 3 else a for a in R.ln_operands("normal", 4, w[1]["out_b"], 5, 1)[0]], w, 1)
+        assert np.abs(yard - ref).max() > 0

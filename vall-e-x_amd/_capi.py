@@ -84,10 +84,13 @@ SYMBOLS = ["vx_abi_version", "vx_create", "vx_destroy", "vx_last_error", "vx_syn
 # ... and include/vallex_hip_dev.h: measurement / kernel development, never called by the mirrors of the reference API
 DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kernel", "vx_bench_gemm", "vx_bench_attn",
                "vx_bench_gemm_clock", "vx_bench_gemm_epilogue", "vx_dev_sample", "vx_dev_attn", "vx_dev_sample_filtered",
-               "vx_dev_dec_attn"]
+               "vx_dev_dec_attn", "vx_dev_dec_op"]
 # sentinels the correctness entries pre-fill their outputs with (include/vallex_hip_dev.h)
 DEV_SENTINEL_I = -123456789
 DEV_SENTINEL_F = np.float32(-1.0e30)
+# ops and weights of vx_dev_dec_op (VX_DEV_OP_* / VX_DEV_W_* of include/vallex_hip_dev.h)
+DEV_OPS = {"embed": 0, "gemm": 1, "qkv_bal": 2, "linear1": 3, "reduce_ln": 4, "sb_ln_gemm": 5, "sb_linear1": 6}
+DEV_WEIGHTS = {"in_proj": 0, "out_proj": 1, "linear2": 2, "predict": 3}
 DEV_SAMPLE_CFG = ("kernel", "splitk", "top_k", "force_eos_at", "active", "n_gen", "cur_pos", "ctx_len", "text_len", "gen_stride")
 
 # vx_row_done_fn of vx_infer_continuous: (user, caller row, codes [frames][8] int64, frames)
@@ -171,6 +174,8 @@ def load_library() -> C.CDLL:
     lib.vx_dev_dec_attn.argtypes = [ctx, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_float),
                                     P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
                                     P(C.c_int32)]
+    lib.vx_dev_dec_op.argtypes = [ctx, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_int32), P(C.c_int32), P(C.c_float), P(C.c_float),
+                                  P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float)]
     lib.vx_last_stats.argtypes = [ctx, P(C.c_int64), P(C.c_int64), P(C.c_double), P(C.c_double)]
     lib.vx_last_truncated.argtypes = [ctx, P(C.c_int32)]
     lib.vx_last_fallbacks.argtypes = [ctx, P(C.c_int32), P(C.c_int32), P(C.c_int64)]
@@ -605,6 +610,44 @@ class Engine:
                                            _ptr(xp_att, C.c_float), _ptr(part_ml, C.c_float), _ptr(geom, C.c_int32)))
         return dict(nsplit=int(geom[0]), sb_qkv=bool(geom[1]), split_fused=bool(geom[2]), out=out, xp_att=xp_att, part_ml=part_ml,
                     k=k, v=v, k0=k0, v0=v0)
+
+    def dev_dec_op(self, op: str, nrows: int, layer: int = 0, weight: str = None, sk: int = None, tok=None, pos=None, x=None,
+                   slabs=None, resid=None):
+        """vx_dev_dec_op: one launch of the decode step's GEMM / FFN / LayerNorm half on chosen operands (include/vallex_hip_dev.h).
+        op: a key of DEV_OPS; weight (gemm, sb_ln_gemm): a key of DEV_WEIGHTS; sk (reduce_ln): 0, 4, 8 or 16 slabs.  x: the whole
+        un-packed image (32, K); slabs (slices, 32, 1024); resid (nrows, 1024); tok, pos (nrows,).  Returns a dict with what the op
+        writes: out -- slabs (slices, 32, N) or the linear1 image (32, 4096) --, h (nrows, 1024), xp (32, 1024), and resid: the
+        residual buffer behind the launch."""
+        n = int(nrows)
+        # (an op, weight or slab count the tables do not know goes to the entry as the number it is: the entry refuses it)
+        variant = int(DEV_WEIGHTS.get(weight, weight)) if weight is not None else int(sk) if sk is not None else 0
+        code = int(DEV_OPS.get(op, op))
+        op = {v: k_ for k_, v in DEV_OPS.items()}.get(code, "")
+        f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+        i32 = lambda a: None if a is None else np.ascontiguousarray(a, np.int32)
+        tok, pos, x, slabs = i32(tok), i32(pos), f32(x), f32(slabs)
+        resid = None if resid is None else np.array(resid, np.float32, order="C")            # in and out: a copy
+        k = 4096 if weight == "linear2" else 1024
+        n_sl = {"reduce_ln": max(variant, 0), "sb_ln_gemm": 8, "sb_linear1": 4}.get(op, 0)
+        for a, shape, what in ((tok, (n,), "tok"), (pos, (n,), "pos"), (x, (32, k), "x"), (slabs, (n_sl, 32, 1024), "slabs"),
+                               (resid, (n, 1024), "resid")):
+            if a is not None and a.shape != shape:
+                raise ValueError(f"{what} must be {shape}, got {a.shape}")
+        out = None
+        if op in ("gemm", "sb_ln_gemm"):
+            out = np.empty({"in_proj": (4, 32, 3072), "out_proj": (4, 32, 1024), "linear2": (8, 32, 1024),
+                            "predict": (4, 32, 1056)}.get(weight, (8, 32, 3072)), np.float32)
+        elif op == "qkv_bal":
+            out = np.empty((8, 32, 3072), np.float32)
+        elif op in ("linear1", "sb_linear1"):
+            out = np.empty((32, 4096), np.float32)
+        h = np.empty((n, 1024), np.float32) if op in ("embed", "reduce_ln", "sb_ln_gemm", "sb_linear1") and 1 <= n <= 32 else None
+        xp = np.empty((32, 1024), np.float32) if op in ("embed", "reduce_ln") else None
+        pf = lambda a: None if a is None else _ptr(a, C.c_float)
+        pi = lambda a: None if a is None else _ptr(a, C.c_int32)
+        self._chk(self.lib.vx_dev_dec_op(self.ctx, code, variant, int(layer), n, pi(tok), pi(pos), pf(x), pf(slabs), pf(resid), pf(out), pf(h),
+                                         pf(xp)))
+        return {k_: v for k_, v in (("out", out), ("h", h), ("xp", xp), ("resid", resid)) if v is not None}
 
     def last_fallbacks(self):
         """phases of the last call that left the fp16 range of the f16x2 kernels and were re-run in fp32 (+ lifetime count)"""

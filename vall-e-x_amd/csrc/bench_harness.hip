@@ -920,4 +920,159 @@ int vx_dev_dec_attn(vx_ctx* c, int32_t nrows, int32_t Tmax, int32_t qkv_balanced
   return VX_OK;
 }
 
+// vx_dev_dec_op: ONE launch of the other half of ar_step_launches -- the skinny GEMMs, linear1, the reduce + LayerNorm kernels, their
+// small-batch consumers and the teacher-forced embedding -- through the product launcher, on caller-chosen activations.  The weights
+// are the context's own device images (in_wp / out_wp / l1_wp / l2_wp / pred_wp, biases, norms): what pack_weight_kernel and
+// pack_weight16_kernel wrote at load time is what the launch reads.  Split counts and the write-through rule are the engine's.
+// Everything the launch reads or writes besides the weights is private scratch pre-filled with the sentinel.
+int vx_dev_dec_op(vx_ctx* c, int32_t op, int32_t variant, int32_t layer, int32_t nrows, const int32_t* tok, const int32_t* pos,
+                  const float* x, const float* slabs, float* resid, float* out, float* h, float* xp) {
+  if (!c) return VX_EINVAL;
+  if (c->serve) FAIL(VX_ESTATE, "vx_dev_dec_op: a serving session is open on this context (vx_serve_close it first)");
+  if (!c->finalized || c->ar.empty()) FAIL(VX_ESTATE, "vx_dev_dec_op: weights not finalized");
+  if (op < VX_DEV_OP_EMBED || op > VX_DEV_OP_SB_LINEAR1) FAIL(VX_EINVAL, "vx_dev_dec_op: unknown op %d", op);
+  if (nrows < 1 || nrows > MB) FAIL(VX_EINVAL, "vx_dev_dec_op: nrows must be 1 .. %d", MB);
+  const int NL = (int)c->ar.size();
+  if (layer < 0 || layer >= NL) FAIL(VX_EINVAL, "vx_dev_dec_op: layer must be 0 .. %d", NL - 1);
+  const bool sb = op == VX_DEV_OP_SB_LN_GEMM || op == VX_DEV_OP_SB_LINEAR1;
+  if (sb && nrows > SB_ROWS) FAIL(VX_EINVAL, "vx_dev_dec_op: the small-batch ops take at most %d rows", SB_ROWS);
+  const LayerW& L = c->ar[layer];
+  const float *fin_g = W(c, "ar_decoder.norm.weight"), *fin_b = W(c, "ar_decoder.norm.bias");
+  const float* emb_tab = W(c, "ar_audio_embedding.word_embeddings.weight");
+  const float* emb_alpha = W(c, "ar_audio_position.alpha");
+  if (!fin_g || !fin_b || !emb_tab || !emb_alpha || !c->pred_wp || !c->pe) FAIL(VX_ESTATE, "vx_dev_dec_op: the context has no AR decoder");
+  constexpr int d = D_MODEL;
+  // the GEMM role: weight image, padded columns, K, K slices of the output
+  const float* wp = nullptr;
+  int Npad = 0, K = d, sk = 0;
+  if (op == VX_DEV_OP_GEMM || op == VX_DEV_OP_SB_LN_GEMM) {
+    if (variant == VX_DEV_W_IN) { wp = L.in_wp; Npad = 3 * d; sk = SK_QKV; }
+    else if (variant == VX_DEV_W_OUT) { wp = L.out_wp; Npad = d; sk = SK_OUT; }
+    else if (variant == VX_DEV_W_L2) { wp = L.l2_wp; Npad = d; K = D_FF; sk = SK_L2; }
+    else if (variant == VX_DEV_W_PRED) { wp = c->pred_wp; Npad = PRED_NPAD; sk = SK_PRED; }
+    else FAIL(VX_EINVAL, "vx_dev_dec_op: unknown weight %d (0 in_proj, 1 out_proj, 2 linear2, 3 predict)", variant);
+    if (op == VX_DEV_OP_SB_LN_GEMM) {
+      if (variant != VX_DEV_W_IN && variant != VX_DEV_W_PRED) FAIL(VX_EINVAL, "vx_dev_dec_op: sb_ln_gemm runs in_proj or predict");
+      if (variant == VX_DEV_W_IN && layer == 0) FAIL(VX_EINVAL, "vx_dev_dec_op: in_proj of layer 0 has no linear2 slabs in front of it");
+      if (variant == VX_DEV_W_PRED && layer != NL - 1) FAIL(VX_EINVAL, "vx_dev_dec_op: predict follows the last layer (%d)", NL - 1);
+    }
+  } else if (op == VX_DEV_OP_REDUCE_LN) {
+    if (variant != 0 && variant != SK_OUT && variant != SK_L2 && variant != N_HEAD)
+      FAIL(VX_EINVAL, "vx_dev_dec_op: reduce_ln takes 0, %d, %d or %d slabs", SK_OUT, SK_L2, N_HEAD);
+  } else if (variant != 0) {
+    FAIL(VX_EINVAL, "vx_dev_dec_op: op %d has no variant %d", op, variant);
+  }
+  if (op == VX_DEV_OP_QKV_BAL) { wp = L.in_wp; Npad = 3 * d; sk = SK_QKV_BAL_Q; }
+  if (op == VX_DEV_OP_LINEAR1 || op == VX_DEV_OP_SB_LINEAR1) wp = L.l1_wp;
+  const int sk_in = op == VX_DEV_OP_REDUCE_LN ? variant : op == VX_DEV_OP_SB_LN_GEMM ? SK_L2 : op == VX_DEV_OP_SB_LINEAR1 ? SK_OUT : 0;
+  const bool reads_x = op == VX_DEV_OP_GEMM || op == VX_DEV_OP_QKV_BAL || op == VX_DEV_OP_LINEAR1;
+  const bool reads_resid = op == VX_DEV_OP_REDUCE_LN || sb;
+  const bool writes_out = op != VX_DEV_OP_EMBED && op != VX_DEV_OP_REDUCE_LN;
+  const bool writes_h = op == VX_DEV_OP_EMBED || reads_resid;
+  const bool writes_xp = op == VX_DEV_OP_EMBED || op == VX_DEV_OP_REDUCE_LN;
+  if ((op == VX_DEV_OP_EMBED && (!tok || !pos)) || (reads_x && !x) || (sk_in && !slabs) || (reads_resid && !resid) || (writes_out && !out) ||
+      (writes_h && !h) || (writes_xp && !xp))
+    FAIL(VX_EINVAL, "vx_dev_dec_op: op %d: null argument", op);
+  if (wp == nullptr && (reads_x || sb)) FAIL(VX_ESTATE, "vx_dev_dec_op: the context has no packed image of this weight");
+  if (op == VX_DEV_OP_EMBED) {
+    const auto it = c->w.find("ar_audio_embedding.word_embeddings.weight");
+    const long emb_rows = it->second.shape.empty() ? 0 : (long)it->second.shape[0];
+    for (int r = 0; r < nrows; ++r)
+      if (tok[r] < 0 || tok[r] >= emb_rows || pos[r] < 0 || pos[r] >= c->pe_rows)
+        FAIL(VX_EINVAL, "vx_dev_dec_op: row %d: tok must be 0 .. %ld, pos 0 .. %d", r, emb_rows - 1, c->pe_rows - 1);
+  }
+  HIPCHK(hipSetDevice(c->dev));
+
+  static_assert(SK_OUT <= N_HEAD && SK_L2 <= N_HEAD, "the slab scratch holds N_HEAD slabs");
+  static_assert(SK_QKV_BAL_Q * 3 * D_MODEL >= D_FF && SK_QKV_BAL_Q * 3 * D_MODEL >= SK_L2 * D_MODEL && SK_QKV_BAL_Q * 3 * D_MODEL >= SK_PRED * PRED_NPAD &&
+                SK_QKV_BAL_Q >= SK_QKV, "the output scratch is sized by the balanced in_proj");
+  const size_t f_x = 0, f_sl = f_x + (size_t)MB * D_FF, f_out = f_sl + (size_t)N_HEAD * MB * d, f_dh = f_out + (size_t)SK_QKV_BAL_Q * MB * 3 * d,
+               f_dh2 = f_dh + (size_t)MB * d, f_xp = f_dh2 + (size_t)MB * d, fend = f_xp + (size_t)MB * d;
+  float* df = nullptr;
+  int* di = nullptr;                                                       // tok [MB] | pos [MB]
+  auto cleanup = [&]() { if (df) (void)hipFree(df); if (di) (void)hipFree(di); };
+  hipError_t he;
+#define TRY(x) if ((he = (x)) != hipSuccess) { cleanup(); c->err = std::string(#x) + ": " + hipGetErrorString(he); return VX_EHIP; }
+#define TRYX(x) do { if (int _e = (x)) { cleanup(); return _e; } } while (0)
+  // the packed-x image (decode.hip): float4 column c4 of row b at ((c4 >> 1) * 64 + b + 32 * (c4 & 1)) * 4, for any K
+  auto pack_image = [](float* img, const float* rows, int kk) {
+    for (int b = 0; b < MB; ++b)
+      for (int c4 = 0; c4 < kk / 4; ++c4) memcpy(img + (((size_t)(c4 >> 1) * 64) + b + 32 * (c4 & 1)) * 4, rows + (size_t)b * kk + 4 * c4, 16);
+  };
+  auto unpack_image = [](float* rows, const float* img, int kk) {
+    for (int b = 0; b < MB; ++b)
+      for (int c4 = 0; c4 < kk / 4; ++c4) memcpy(rows + (size_t)b * kk + 4 * c4, img + (((size_t)(c4 >> 1) * 64) + b + 32 * (c4 & 1)) * 4, 16);
+  };
+  TRY(hipMalloc((void**)&df, fend * 4));
+  TRY(hipMalloc((void**)&di, (size_t)2 * MB * 4));
+  {
+    std::vector<float> hf(fend, VX_DEV_SENTINEL_F);
+    std::vector<int> hi(2 * MB, 0);
+    if (reads_x) pack_image(&hf[f_x], x, K);
+    if (sk_in) memcpy(&hf[f_sl], slabs, (size_t)sk_in * MB * d * 4);
+    if (reads_resid) memcpy(&hf[f_dh], resid, (size_t)nrows * d * 4);
+    if (op == VX_DEV_OP_EMBED) for (int r = 0; r < nrows; ++r) { hi[r] = tok[r]; hi[MB + r] = pos[r]; }
+    TRYX(xfer_h2d(c, df, hf.data(), fend * 4));
+    TRYX(xfer_h2d(c, di, hi.data(), hi.size() * 4));
+  }
+  float *dx = df + f_x, *dsl = df + f_sl, *dout = df + f_out, *dh = df + f_dh, *dh2 = df + f_dh2, *dxp = df + f_xp;
+  hipStream_t st = c->stream;
+  const bool last = layer + 1 == NL;
+  bool ok = true;
+  switch (op) {
+    case VX_DEV_OP_EMBED:
+      launch_dec_embed_ln_pack(di, di + MB, emb_tab, emb_alpha, c->pe, dh, c->ar[0].n1_w, c->ar[0].n1_b, dxp, nrows, st);
+      break;
+    case VX_DEV_OP_GEMM:
+      launch_skinny_gemm(wp, dx, dout, Npad, K, sk, st, nrows > SB_ROWS);
+      break;
+    case VX_DEV_OP_QKV_BAL:
+      launch_skinny_qkv_balanced(wp, dx, dout, st);
+      break;
+    case VX_DEV_OP_LINEAR1:
+      launch_skinny16_relu_pack(wp, dx, L.l1_b, dout, D_FF, D_MODEL, st);
+      break;
+    case VX_DEV_OP_REDUCE_LN:
+      // the engine's four uses: behind out_proj (4 slabs, or 16 head slabs of the fused dec_attn) with norm2, behind linear2 with the
+      // next layer's norm1 or the final norm, and the final norm alone in front of the first logits (no slabs, no bias, no h); in place
+      if (variant == 0) launch_dec_reduce_ln_pack(nullptr, 0, D_MODEL, nullptr, dh, nullptr, fin_g, fin_b, dxp, nrows, st);
+      else if (variant == SK_L2)
+        launch_dec_reduce_ln_pack(dsl, SK_L2, D_MODEL, L.l2_b, dh, dh, last ? fin_g : c->ar[layer + 1].n1_w, last ? fin_b : c->ar[layer + 1].n1_b, dxp,
+                                  nrows, st);
+      else launch_dec_reduce_ln_pack(dsl, variant, D_MODEL, L.out_b, dh, dh, L.n2_w, L.n2_b, dxp, nrows, st);
+      break;
+    case VX_DEV_OP_SB_LN_GEMM:
+      // (the engine hands predict a null h_out; here both weights get one, so that the prologue's slab sum is seen)
+      if (variant == VX_DEV_W_PRED) ok = launch_skinny_gemm_sb_ln(wp, dout, Npad, sk, dsl, SK_L2, L.l2_b, dh, dh2, fin_g, fin_b, nrows, st);
+      else ok = launch_skinny_gemm_sb_ln(wp, dout, Npad, sk, dsl, SK_L2, c->ar[layer - 1].l2_b, dh, dh2, L.n1_w, L.n1_b, nrows, st);
+      break;
+    default:
+      ok = launch_skinny16_sb_ln(wp, L.l1_b, dout, D_FF, dsl, SK_OUT, L.out_b, dh, dh2, L.n2_w, L.n2_b, nrows, st);
+      break;
+  }
+  if (!ok) {
+    (void)hipStreamSynchronize(st);
+    cleanup();
+    FAIL(VX_EINVAL, "vx_dev_dec_op: a launcher refused this configuration (op %d, %d rows)", op, nrows);
+  }
+  const bool image_out = op == VX_DEV_OP_LINEAR1 || op == VX_DEV_OP_SB_LINEAR1;
+  const size_t n_out = !writes_out ? 0 : image_out ? (size_t)MB * D_FF : (size_t)sk * MB * Npad;
+  std::vector<float> o_out(image_out ? n_out : 0), o_xp(writes_xp ? (size_t)MB * d : 0);
+  if (n_out) TRYX(xfer_d2h(c, image_out ? o_out.data() : out, dout, n_out * 4));
+  // h: the reduce kernel works in place as in the engine (dh); the small-batch consumers write the other buffer of the dh / dh2
+  // pair; reduce_ln without slabs is handed no h at all, and the caller gets the buffer nothing was stored to
+  const bool h_apart = sb || (op == VX_DEV_OP_REDUCE_LN && variant == 0);
+  if (writes_h) TRYX(xfer_d2h(c, h, h_apart ? dh2 : dh, (size_t)nrows * d * 4));
+  if (writes_xp) TRYX(xfer_d2h(c, o_xp.data(), dxp, o_xp.size() * 4));
+  if (reads_resid) TRYX(xfer_d2h(c, resid, dh, (size_t)nrows * d * 4));      // what the residual buffer holds behind the launch
+  TRYX(xfer_sync(c));
+  TRY(hipGetLastError());
+  if (image_out) unpack_image(out, o_out.data(), D_FF);
+  if (writes_xp) unpack_image(xp, o_xp.data(), d);
+#undef TRY
+#undef TRYX
+  cleanup();
+  return VX_OK;
+}
+
 }  // extern "C"
