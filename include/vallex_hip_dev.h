@@ -153,6 +153,42 @@ int vx_dev_dec_attn(vx_ctx* ctx, int32_t nrows, int32_t Tmax, int32_t qkv_balanc
 int vx_dev_dec_op(vx_ctx* ctx, int32_t op, int32_t variant, int32_t layer, int32_t nrows, const int32_t* tok, const int32_t* pos,
                   const float* x, const float* slabs, float* resid, float* out, float* h, float* xp);
 
+/* ONE full-sequence GEMM through a product launcher on caller operands:
+ *   C[m][n] = resid[rr(m)][n] + colscale[n] * act(sum_k A[ga(m)][k] W[n][k] + bias[n]),  m < M, n < N
+ * with ga(m) = gather ? gather[m] : m and rr(m) = resid_rows ? resid_rows[m] : m.  M, N, K <= 4096; N % 4 == 0, K % 32 == 0.
+ *   kernel   0 .. 4     launch_gemm_f32, variant `kernel` (0: the product's choice)
+ *            10 .. 15   launch_gemm_f16x2 with tn = 0 (the product's choice), 128, 256, 257, -128, -129
+ *            20, 21     launch_gemm_bf16x3, launch_gemm_bf16x3_dma: plain epilogue only (no gather, bias, resid, colscale, act)
+ *   A [rowsA][lda] (lda >= K, lda % 4 == 0; rowsA >= M without gather); bias, colscale [N]; resid [rowsR][ldr] (ldr >= N, ldr % 4 == 0;
+ *   rowsR >= M without resid_rows); gather, resid_rows [M].  act: 0 none, 1 ReLU, 2 GELU, 3 ELU.  colscale, GELU and ELU: kernels 0 .. 4.
+ * f16x2: A is split by launch_split2h at the activation scale 2^5 (the gather applied there, as the engine does) into planes whose
+ * pad rows behind M hold VX_DEV_SENTINEL_H (finite garbage the kernels must keep out of every stored element); W [N][K] is split at
+ * 2^w_shift (0 .. 24), or for w_shift = -1 at the shift the loader's rule derives from max |w| (absmax kernel + h2_weight_shift);
+ * descale = 2^-(5 + shift).  w_src != 0 (W must be NULL): the context's own load-time planes of layer w_layer with their recorded shift,
+ * w_src 1 .. 4 = in_w3, out_w3, l1_w3, l2_w3 of the AR stack, 5 .. 8 of the NAR stack (N and K must be the weight's).
+ *   flags & VX_DEV_GEMM_OUT_PLANES (f16x2, N % 256 == 0): the launch writes out_planes instead of fp32 rows; C may be NULL
+ *   flags & VX_DEV_GEMM_INPLACE (ldr == N, no resid_rows): the launch runs with C == resid
+ *   C [rowsC][N], M <= rowsC <= M + 64: rows the launch did not write hold VX_DEV_SENTINEL_F
+ *   planes [2][roundup(M, 256)][N] (OUT_PLANES), a_planes [2][roundup(M, 256)][K] (f16x2, optional): head and tail plane, un-tiled, as
+ *       fp16 bit patterns; words the launch did not write hold VX_DEV_SENTINEL_H
+ *   info [3] = {the f16x2 range flag behind the launches, the weight shift used (-1: not f16x2), 0}
+ * VX_EINVAL, nothing launched, for anything outside the above; VX_ESTATE while a serving session is open or when w_src asks for planes
+ * the context does not hold. */
+#define VX_DEV_GEMM_OUT_PLANES 1
+#define VX_DEV_GEMM_INPLACE 2
+int vx_dev_gemm(vx_ctx* ctx, int32_t kernel, int32_t flags, int32_t M, int32_t N, int32_t K, const float* A, int32_t rowsA, int32_t lda,
+                const int32_t* gather, const float* W, int32_t w_src, int32_t w_layer, int32_t w_shift, const float* bias,
+                const float* resid, int32_t rowsR, int32_t ldr, const int32_t* resid_rows, const float* colscale, int32_t act, float* C,
+                int32_t rowsC, uint16_t* planes, uint16_t* a_planes, int32_t* info);
+/* ONE launch_layernorm on caller rows: y = (LN(x) * g + b) * ada_w + ada_b with eps 1e-5; C = 1024 or 384; rows 1 .. 4096.
+ *   x [rows][ldx] (ldx >= C, ldx % 4 == 0, ldx <= 8192); g, b [C] both or neither; ada_w, ada_b [C] both or neither
+ *   y [rowsY][C], rows <= rowsY <= rows + 64, or NULL (C = 1024 with planes only): rows the launch did not write hold VX_DEV_SENTINEL_F
+ *   planes [2][roundup(rows, 256)][1024] or NULL (C = 1024 only): the f16x2 planes the launch writes next to / instead of y, un-tiled
+ *       fp16 bit patterns; words not written hold VX_DEV_SENTINEL_H.  *range_flag = the f16x2 range flag behind the launch.
+ * VX_EINVAL, nothing launched, for anything outside the above; VX_ESTATE while a serving session is open. */
+int vx_dev_layernorm(vx_ctx* ctx, int32_t rows, int32_t C, int32_t ldx, const float* x, const float* g, const float* b, const float* ada_w,
+                     const float* ada_b, float* y, int32_t rowsY, uint16_t* planes, int32_t* range_flag);
+
 #ifdef __cplusplus
 }
 #endif

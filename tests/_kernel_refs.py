@@ -750,3 +750,206 @@ def ffn_chain_ref(slabs, resid, w, layer):
         _, x2 = red(y[None], bias8, h, norm8)
         res.append(lin(x2, w["pred"]))
     return res[0], res[1]
+
+
+# ---- the full-sequence GEMMs and layernorm_kernel (tests/test_gpu_kernel_gemm.py) ---------------------------------------------------
+H2_ACT_SHIFT = 5              # activations are split at 2^5 (vx_common.h)
+H2_TILE = 256                 # rows of a plane tile, both operands
+H2_LIMIT = 65504.0            # |X| at or above this (or non-finite) raises the range flag
+H2_SENT = np.uint16(0xFBFF)   # VX_DEV_SENTINEL_H
+
+
+def h2_split_ref(x, shift):
+    """(head, tail) fp16 of X = x 2^shift: head = fp16(X), tail = fp16(X - head), both round-to-nearest-even with fp16 subnormals --
+    h2_split of csrc/vx_common.h"""
+    X = np.asarray(x, np.float32) * np.float32(2.0 ** shift)
+    with np.errstate(over="ignore", invalid="ignore"):
+        h = X.astype(np.float16)
+        t = (X - h.astype(np.float32)).astype(np.float16)
+    return h, t
+
+
+def h2_value(x, shift):
+    """(head + tail) 2^-shift in float64: the operand the f16x2 kernels see"""
+    h, t = h2_split_ref(x, shift)
+    return (h.astype(np.float64) + t.astype(np.float64)) * 2.0 ** -shift
+
+
+def h2_range_bad(x, shift):
+    """what h2_split calls bad: not |X| < 65504 (so NaN and +-inf too)"""
+    with np.errstate(over="ignore", invalid="ignore"):
+        X = np.asarray(x, np.float32) * np.float32(2.0 ** shift)
+        return bool((~(np.abs(X) < np.float32(H2_LIMIT))).any())
+
+
+def h2_tile_index(r, k, K, tile_rows=H2_TILE):
+    """half-word index of element (r, k) inside one tile-major plane [rows / tile][K / 32][tile][32]"""
+    r, k = np.asarray(r, np.int64), np.asarray(k, np.int64)
+    return (((r // tile_rows) * (K // 32) + k // 32) * tile_rows + r % tile_rows) * 32 + k % 32
+
+
+def h2_weight_shift_ref(absmax):
+    """the loader's rule: max |w| 2^shift in [16384, 32768), shift clamped to 0 .. 24; 24 for a zero or non-finite maximum"""
+    absmax = float(np.float32(absmax))
+    if not (absmax > 0.0) or not np.isfinite(absmax):
+        return 24
+    _, ex = np.frexp(absmax)                       # absmax = m 2^ex, 0.5 <= m < 1
+    return int(min(24, max(0, 15 - int(ex))))
+
+
+def h2_gemm_model(a, w, shift):
+    """float64 model of the f16x2 product: (head.head + head.tail + tail.head) 2^-(5 + shift); the tail.tail term is dropped"""
+    ah, at = (p.astype(np.float64) for p in h2_split_ref(a, H2_ACT_SHIFT))
+    wh, wt = (p.astype(np.float64) for p in h2_split_ref(w, shift))
+    return (ah @ wh.T + ah @ wt.T + at @ wh.T) * 2.0 ** -(H2_ACT_SHIFT + shift)
+
+
+def h2_model_bound(a, w, shift):
+    """bound of |model - a W^T| per element: with d(x) = max(2^-22 |x|, 2^-25 2^-s) the split error of an operand at shift s,
+    sum_k (d(a_k) |w_k| + |a_k| d(w_k)) + 2^-22 sum_k |a_k w_k|  (the last term: the dropped tail.tail products)"""
+    a, w = np.abs(np.asarray(a, np.float64)), np.abs(np.asarray(w, np.float64))
+    da = np.maximum(2.0 ** -22 * a, 2.0 ** -25 * 2.0 ** -H2_ACT_SHIFT)
+    dw = np.maximum(2.0 ** -22 * w, 2.0 ** -25 * 2.0 ** -shift)
+    return da @ w.T + a @ dw.T + 2.0 ** -22 * (a @ w.T)
+
+
+def chain_bound(a, w):
+    """K 2^-24 sum_k |a_k w_k| per output element: what K fp32 additions into one accumulator can lose, each at most 2^-24 of a
+    partial sum that sum_k |a_k w_k| bounds"""
+    a, w = np.abs(np.asarray(a, np.float64)), np.abs(np.asarray(w, np.float64))
+    return a.shape[1] * 2.0 ** -24 * (a @ w.T)
+
+
+def chain_fp32(a, w):
+    """a W^T as ONE k-ordered fp32 chain per element (numpy's cumsum adds in order): the summation order of the GEMM kernels"""
+    a, w = np.asarray(a, np.float32), np.asarray(w, np.float32)
+    return np.stack([np.cumsum(a[:, None, :] * w[None, n0:n0 + 8, :], axis=-1, dtype=np.float32)[..., -1] for n0 in range(0, len(w), 8)], 1).reshape(len(a), -1)
+
+
+def _act64(y, act):
+    import torch
+    if act == 1:
+        return np.maximum(y, 0.0)
+    if act == 2:
+        return 0.5 * y * (1.0 + torch.erf(torch.from_numpy(y * np.sqrt(0.5))).numpy())
+    if act == 3:
+        return np.where(y > 0, y, np.expm1(np.minimum(y, 0.0)))
+    return y
+
+
+def gemm_ref(a, w, bias=None, act=0, colscale=None, resid=None, pre=None):
+    """the GemmArgs contract in float64: resid + colscale act(a W^T + bias); act 0 none, 1 ReLU, 2 GELU (erf), 3 ELU.  pre: a sum to
+    use instead of a W^T (the f16x2 model)"""
+    y = np.asarray(a, np.float64) @ np.asarray(w, np.float64).T if pre is None else np.asarray(pre, np.float64)
+    if bias is not None:
+        y = y + np.asarray(bias, np.float64)
+    y = _act64(y, act)
+    if colscale is not None:
+        y = y * np.asarray(colscale, np.float64)
+    if resid is not None:
+        y = np.asarray(resid, np.float64) + y
+    return y
+
+
+def gemm_fp32(a, w, bias=None, act=0, colscale=None, resid=None):
+    """the yardstick: the same in torch-CPU fp32 (F.linear, F.relu / F.gelu / F.elu)"""
+    import torch
+    import torch.nn.functional as F
+    T = lambda v: None if v is None else torch.from_numpy(np.ascontiguousarray(v, np.float32))
+    y = F.linear(T(a), T(w), T(bias))
+    y = (lambda v: v, F.relu, F.gelu, F.elu)[act](y)
+    if colscale is not None:
+        y = y * T(colscale)
+    if resid is not None:
+        y = T(resid) + y
+    return y.numpy()
+
+
+def ln_ref(x, g=None, b=None, aw=None, ab=None):
+    """float64 (LN(x) g + b) aw + ab with eps 1e-5; any pair may be None"""
+    C = np.asarray(x).shape[-1]
+    y = layer_norm_ref(x, np.ones(C) if g is None else g, np.zeros(C) if b is None else b)
+    if aw is not None:
+        y = np.asarray(aw, np.float64) * y + np.asarray(ab, np.float64)
+    return y
+
+
+def ln_fp32(x, g=None, b=None, aw=None, ab=None):
+    """the yardstick: torch-CPU fp32 F.layer_norm, then weight * y + bias as AdaptiveLayerNorm does"""
+    import torch
+    import torch.nn.functional as F
+    T = lambda v: None if v is None else torch.from_numpy(np.ascontiguousarray(v, np.float32))
+    x = T(x)
+    y = F.layer_norm(x, (x.shape[-1],), T(g), T(b), 1e-5)
+    if aw is not None:
+        y = T(aw) * y + T(ab)
+    return y.numpy()
+
+
+GEMM_SETS = ("normal", "model", "wide", "cancel")
+
+
+def gemm_cancel_rows(N, K):
+    """the rows of W the 'cancel' set cancels on: every r-th, fewer than K / 2 of them"""
+    return np.arange(0, N, max(1, -(-2 * N // K)))
+
+
+def gemm_set(kind, M, N, K, seed, wmax=None):
+    """(a (M, K), w (N, K)) fp32.  w: a normal of sigma 1 / sqrt(K), scaled to max |w| = wmax when one is given.  normal: a unit normal; model: a normal with per-channel gains {0.1, 1, 4}; wide:
+    |a| = e^u, u uniform in [-12, 6), |w| = e^u', u' in [-12, 0), random signs, and the first elements of row 0 of a at the upper edge
+    of the f16x2 range (2046.9: X = 65500.8); cancel: a unit normal projected onto the null space of the rows gemm_cancel_rows of w"""
+    rng = np.random.default_rng(seed)
+    a = rng.normal(0.0, 1.0, (M, K))
+    w = rng.normal(0.0, 1.0 / np.sqrt(K), (N, K))
+    if kind == "model":
+        a = a * rng.choice([0.1, 1.0, 4.0], K)
+    elif kind == "wide":
+        a = np.exp(rng.uniform(-12.0, 6.0, (M, K))) * rng.choice([-1.0, 1.0], (M, K))
+        w = np.exp(rng.uniform(-12.0, 0.0, (N, K))) * rng.choice([-1.0, 1.0], (N, K))
+        a[0, :4] = [2046.9, -2046.9, 2046.0, 1.0e-6]
+    elif kind not in ("normal", "cancel"):
+        raise ValueError(kind)
+    if wmax is not None:
+        w = w * (wmax / np.abs(w).max())
+    w = w.astype(np.float32)
+    if kind == "cancel":
+        ws = w[gemm_cancel_rows(N, K)].astype(np.float64)
+        a = a - np.linalg.solve(ws @ ws.T, ws @ a.T).T @ ws
+    return a.astype(np.float32), w
+
+
+LN_SETS = ("normal", "mean1e3", "const", "mag1e4", "offset")
+
+
+def ln_set(kind, rows, C, seed):
+    """x (rows, C) fp32 of a LayerNorm set: normal; mean1e3 = 1e3 + a spread of 1; const = row 0 exactly constant, the other rows a
+    constant of 0.1 .. 3 plus a spread of 1e-4 (variance far below eps); mag1e4 = magnitude 1e4; offset = 3e4 + a spread of 10"""
+    rng = np.random.default_rng(seed)
+    x = rng.normal(0.0, 1.0, (rows, C))
+    if kind == "mean1e3":
+        x = 1.0e3 + x
+    elif kind == "mag1e4":
+        x = 1.0e4 * x
+    elif kind == "offset":
+        x = 3.0e4 + 10.0 * x
+    elif kind == "const":
+        cr = rng.uniform(0.1, 3.0, (rows, 1)) * rng.choice([-1.0, 1.0], (rows, 1))
+        x = cr + 1.0e-4 * x
+        x[0] = 10.25                 # few mantissa bits: every partial sum of the row is exact, so mean == x and x - mean == 0
+    elif kind != "normal":
+        raise ValueError(kind)
+    return x.astype(np.float32)
+
+
+def f16x2_choice(M, N, K):
+    """which instantiation launch_gemm_f16x2 picks on its own (tn = 0), restated from csrc/gemm_f16x2.hip: the cost model between
+    256 x 256 and 128 x 128 tiles, then the four-wave kernel for 256 x 256 unless K is a single tile, four LDS stages for at most 256
+    tiles of 128 x 128.  (The fifth instantiation, 256 x 128, is only ever forced.)"""
+    mt256, mt128 = (M + 255) // 256, (M + 127) // 128
+    t128 = mt128 * ((N + 127) // 128)
+    rem = t128 % 512
+    c128 = (t128 // 512) * 2.3 + (0.0 if rem == 0 else 1.3 if rem <= 256 else 2.3)
+    c256 = ((mt256 * (N // 256) + 255) // 256) * 4.0 if N % 256 == 0 else 1e30
+    if c256 < c128:
+        return "w4_256x256" if K >= 64 else "w8_256x256"
+    return "128x128_s4" if t128 <= 256 else "128x128_s2"

@@ -154,3 +154,41 @@ def test_dev_dec_op_prototype_matches_binding(lib):
     assert ops == DEV_OPS
     wts = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define VX_DEV_W_(\w+) (\d+)", hdr)}
     assert wts == {"IN": DEV_WEIGHTS["in_proj"], "OUT": DEV_WEIGHTS["out_proj"], "L2": DEV_WEIGHTS["linear2"], "PRED": DEV_WEIGHTS["predict"]}
+
+
+def _proto_matches(lib, name, want_args):
+    import ctypes as C
+    hdr = open(os.path.join(ROOT, "include", "vallex_hip_dev.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    proto = re.search(r"\bint %s\((.*?)\);" % name, hdr, re.S).group(1)
+    args = [" ".join(a.split()) for a in proto.split(",")]
+    assert args == want_args, args
+    kinds = {"vx_ctx*": C.c_void_p, "int32_t": C.c_int32, "const int32_t*": C.POINTER(C.c_int32), "int32_t*": C.POINTER(C.c_int32),
+             "float*": C.POINTER(C.c_float), "const float*": C.POINTER(C.c_float), "uint16_t*": C.POINTER(C.c_uint16)}
+    fn = getattr(lib, name)
+    assert fn.restype is C.c_int and list(fn.argtypes) == [kinds[a.rsplit(" ", 1)[0]] for a in args]
+    return hdr
+
+
+def test_dev_gemm_prototype_matches_binding(lib):
+    """the header's prototype of vx_dev_gemm and the ctypes signature agree argument by argument (26 of them); flags and sentinels too"""
+    from vallex_amd import _capi
+    hdr = _proto_matches(lib, "vx_dev_gemm", [
+        "vx_ctx* ctx", "int32_t kernel", "int32_t flags", "int32_t M", "int32_t N", "int32_t K", "const float* A", "int32_t rowsA", "int32_t lda",
+        "const int32_t* gather", "const float* W", "int32_t w_src", "int32_t w_layer", "int32_t w_shift", "const float* bias", "const float* resid",
+        "int32_t rowsR", "int32_t ldr", "const int32_t* resid_rows", "const float* colscale", "int32_t act", "float* C", "int32_t rowsC",
+        "uint16_t* planes", "uint16_t* a_planes", "int32_t* info"])
+    assert len(lib.vx_dev_gemm.argtypes) == 26
+    assert int(re.search(r"#define VX_DEV_GEMM_OUT_PLANES (\d+)", hdr).group(1)) == _capi.DEV_GEMM_OUT_PLANES
+    assert int(re.search(r"#define VX_DEV_GEMM_INPLACE (\d+)", hdr).group(1)) == _capi.DEV_GEMM_INPLACE
+    assert int(re.search(r"#define VX_DEV_SENTINEL_H (0x[0-9A-Fa-f]+)", hdr).group(1), 16) == _capi.DEV_SENTINEL_H
+    assert sorted(_capi.DEV_GEMM_KERNELS.values()) == [0, 1, 2, 3, 4, 10, 11, 12, 13, 14, 15, 20, 21]
+    assert sorted(_capi.DEV_GEMM_WSRC.values()) == list(range(1, 9))
+
+
+def test_dev_layernorm_prototype_matches_binding(lib):
+    """the header's prototype of vx_dev_layernorm and the ctypes signature agree argument by argument (13 of them)"""
+    _proto_matches(lib, "vx_dev_layernorm", [
+        "vx_ctx* ctx", "int32_t rows", "int32_t C", "int32_t ldx", "const float* x", "const float* g", "const float* b", "const float* ada_w",
+        "const float* ada_b", "float* y", "int32_t rowsY", "uint16_t* planes", "int32_t* range_flag"])
+    assert len(lib.vx_dev_layernorm.argtypes) == 13

@@ -84,13 +84,21 @@ SYMBOLS = ["vx_abi_version", "vx_create", "vx_destroy", "vx_last_error", "vx_syn
 # ... and include/vallex_hip_dev.h: measurement / kernel development, never called by the mirrors of the reference API
 DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kernel", "vx_bench_gemm", "vx_bench_attn",
                "vx_bench_gemm_clock", "vx_bench_gemm_epilogue", "vx_dev_sample", "vx_dev_attn", "vx_dev_sample_filtered",
-               "vx_dev_dec_attn", "vx_dev_dec_op"]
+               "vx_dev_dec_attn", "vx_dev_dec_op", "vx_dev_gemm", "vx_dev_layernorm"]
 # sentinels the correctness entries pre-fill their outputs with (include/vallex_hip_dev.h)
 DEV_SENTINEL_I = -123456789
 DEV_SENTINEL_F = np.float32(-1.0e30)
 # ops and weights of vx_dev_dec_op (VX_DEV_OP_* / VX_DEV_W_* of include/vallex_hip_dev.h)
 DEV_OPS = {"embed": 0, "gemm": 1, "qkv_bal": 2, "linear1": 3, "reduce_ln": 4, "sb_ln_gemm": 5, "sb_linear1": 6}
 DEV_WEIGHTS = {"in_proj": 0, "out_proj": 1, "linear2": 2, "predict": 3}
+# kernel codes, weight sources and flags of vx_dev_gemm
+DEV_GEMM_KERNELS = {"f32": 0, "f32_reg": 1, "f32_dma256x128": 2, "f32_dma128x128": 3, "f32_dma256x256": 4,
+                    "f16x2": 10, "f16x2_256x128": 11, "f16x2_256x256_w8": 12, "f16x2_256x256_w4": 13, "f16x2_128x128": 14,
+                    "f16x2_128x128_s2": 15, "bf16x3": 20, "bf16x3_dma": 21}
+DEV_GEMM_WSRC = {"ar.in_proj": 1, "ar.out_proj": 2, "ar.linear1": 3, "ar.linear2": 4,
+                 "nar.in_proj": 5, "nar.out_proj": 6, "nar.linear1": 7, "nar.linear2": 8}
+DEV_GEMM_OUT_PLANES, DEV_GEMM_INPLACE = 1, 2
+DEV_SENTINEL_H = 0xFBFF
 DEV_SAMPLE_CFG = ("kernel", "splitk", "top_k", "force_eos_at", "active", "n_gen", "cur_pos", "ctx_len", "text_len", "gen_stride")
 
 # vx_row_done_fn of vx_infer_continuous: (user, caller row, codes [frames][8] int64, frames)
@@ -176,6 +184,11 @@ def load_library() -> C.CDLL:
                                     P(C.c_int32)]
     lib.vx_dev_dec_op.argtypes = [ctx, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_int32), P(C.c_int32), P(C.c_float), P(C.c_float),
                                   P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float)]
+    lib.vx_dev_gemm.argtypes = [ctx, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), C.c_int32, C.c_int32, P(C.c_int32),
+                                P(C.c_float), C.c_int32, C.c_int32, C.c_int32, P(C.c_float), P(C.c_float), C.c_int32, C.c_int32, P(C.c_int32),
+                                P(C.c_float), C.c_int32, P(C.c_float), C.c_int32, P(C.c_uint16), P(C.c_uint16), P(C.c_int32)]
+    lib.vx_dev_layernorm.argtypes = [ctx, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
+                                     P(C.c_float), P(C.c_float), C.c_int32, P(C.c_uint16), P(C.c_int32)]
     lib.vx_last_stats.argtypes = [ctx, P(C.c_int64), P(C.c_int64), P(C.c_double), P(C.c_double)]
     lib.vx_last_truncated.argtypes = [ctx, P(C.c_int32)]
     lib.vx_last_fallbacks.argtypes = [ctx, P(C.c_int32), P(C.c_int32), P(C.c_int64)]
@@ -648,6 +661,63 @@ class Engine:
         self._chk(self.lib.vx_dev_dec_op(self.ctx, code, variant, int(layer), n, pi(tok), pi(pos), pf(x), pf(slabs), pf(resid), pf(out), pf(h),
                                          pf(xp)))
         return {k_: v for k_, v in (("out", out), ("h", h), ("xp", xp), ("resid", resid)) if v is not None}
+
+    def dev_gemm(self, kernel, a: np.ndarray, w=None, m: int = None, k: int = None, gather=None, bias=None, resid=None, resid_rows=None,
+                 colscale=None, act: int = 0, w_src=None, w_layer: int = 0, w_shift: int = -1, n: int = None, out_planes: bool = False,
+                 inplace: bool = False, a_planes: bool = False, extra_rows: int = 3):
+        """vx_dev_gemm: one full-sequence GEMM launch on chosen operands (include/vallex_hip_dev.h).  kernel: a key of DEV_GEMM_KERNELS
+        (or its code); a (rowsA, lda) float32 of which the first k columns are the operand (k default lda); w (N, K) float32 or w_src, a
+        key of DEV_GEMM_WSRC, with w_layer (then n is needed); m: output rows (default: len(gather) or rowsA).  Returns a dict: c
+        (m + extra_rows, N) float32 or None with out_planes, planes / a_planes (2, roundup(m, 256), N | K) uint16 or None, flag, shift."""
+        f32 = lambda v: None if v is None else np.ascontiguousarray(v, np.float32)
+        i32 = lambda v: None if v is None else np.ascontiguousarray(v, np.int32)
+        a, w, bias, resid, colscale, gather, resid_rows = f32(a), f32(w), f32(bias), f32(resid), f32(colscale), i32(gather), i32(resid_rows)
+        if a.ndim != 2 or (w is not None and w.ndim != 2) or (resid is not None and resid.ndim != 2):
+            raise ValueError("a, w and resid are 2-D")
+        rows_a, lda = a.shape
+        k = int(lda if k is None else k)
+        m = int(m if m is not None else len(gather) if gather is not None else rows_a)
+        n = int(w.shape[0] if w is not None else n)
+        if w is not None and w.shape[1] != k:
+            raise ValueError(f"w must be (N, {k}), got {w.shape}")
+        for v, shape, what in ((bias, (n,), "bias"), (colscale, (n,), "colscale"), (gather, (m,), "gather"), (resid_rows, (m,), "resid_rows")):
+            if v is not None and v.shape != shape:
+                raise ValueError(f"{what} must be {shape}, got {v.shape}")
+        rows_r, ldr = resid.shape if resid is not None else (0, 0)
+        m256 = -(-max(m, 1) // 256) * 256
+        c = None if out_planes else np.empty((max(m + int(extra_rows), 0), n), np.float32)
+        pl = np.empty((2, m256, n), np.uint16) if out_planes else None
+        apl = np.empty((2, m256, k), np.uint16) if a_planes else None
+        info = np.zeros(3, np.int32)
+        pf = lambda v: None if v is None else _ptr(v, C.c_float)
+        pi = lambda v: None if v is None else _ptr(v, C.c_int32)
+        ph = lambda v: None if v is None else _ptr(v, C.c_uint16)
+        flags = (DEV_GEMM_OUT_PLANES if out_planes else 0) | (DEV_GEMM_INPLACE if inplace else 0)
+        self._chk(self.lib.vx_dev_gemm(self.ctx, int(DEV_GEMM_KERNELS.get(kernel, kernel)), flags, m, n, k, pf(a), rows_a, lda, pi(gather),
+                                       pf(w), int(DEV_GEMM_WSRC.get(w_src, w_src or 0)), int(w_layer), int(w_shift), pf(bias), pf(resid),
+                                       rows_r, ldr, pi(resid_rows), pf(colscale), int(act), pf(c), 0 if c is None else len(c), ph(pl),
+                                       ph(apl), _ptr(info, C.c_int32)))
+        return dict(c=c, planes=pl, a_planes=apl, flag=int(info[0]), shift=int(info[1]))
+
+    def dev_layernorm(self, x: np.ndarray, c: int = 1024, g=None, b=None, ada_w=None, ada_b=None, want_y: bool = True,
+                      want_planes: bool = False, extra_rows: int = 3):
+        """vx_dev_layernorm: one launch_layernorm on x (rows, ldx) float32, normalising the first c columns of every row.  Returns a
+        dict: y (rows + extra_rows, c) or None, planes (2, roundup(rows, 256), 1024) uint16 or None, flag."""
+        f32 = lambda v: None if v is None else np.ascontiguousarray(v, np.float32)
+        x, g, b, ada_w, ada_b = f32(x), f32(g), f32(b), f32(ada_w), f32(ada_b)
+        if x.ndim != 2:
+            raise ValueError("x is 2-D")
+        for v in (g, b, ada_w, ada_b):
+            if v is not None and v.shape != (int(c),):
+                raise ValueError(f"g, b, ada_w, ada_b must be ({c},)")
+        rows, ldx = x.shape
+        y = np.empty((rows + int(extra_rows), int(c)), np.float32) if want_y else None
+        pl = np.empty((2, -(-max(rows, 1) // 256) * 256, 1024), np.uint16) if want_planes else None
+        flag = C.c_int32()
+        pf = lambda v: None if v is None else _ptr(v, C.c_float)
+        self._chk(self.lib.vx_dev_layernorm(self.ctx, rows, int(c), ldx, pf(x), pf(g), pf(b), pf(ada_w), pf(ada_b), pf(y),
+                                            0 if y is None else len(y), None if pl is None else _ptr(pl, C.c_uint16), C.byref(flag)))
+        return dict(y=y, planes=pl, flag=flag.value)
 
     def last_fallbacks(self):
         """phases of the last call that left the fp16 range of the f16x2 kernels and were re-run in fp32 (+ lifetime count)"""

@@ -1075,4 +1075,229 @@ int vx_dev_dec_op(vx_ctx* c, int32_t op, int32_t variant, int32_t layer, int32_t
   return VX_OK;
 }
 
+// un-tile one f16x2 plane pair (tile-major [rows / 256][K / 32][256][32], vx_common.h) into [2][rows256][K] row-major half-words
+static void dev_untile_planes(uint16_t* dst, const std::vector<unsigned short>& src, long pstride, long rows256, int K) {
+  for (int p = 0; p < 2; ++p)
+    for (long r = 0; r < rows256; ++r)
+      for (int kt = 0; kt < K / 32; ++kt)
+        memcpy(dst + ((size_t)p * rows256 + r) * K + (size_t)kt * 32,
+               &src[(size_t)p * pstride + ((((size_t)(r >> 8) * (K / 32)) + kt) * 256 + (r & 255)) * 32], 64);
+}
+
+// vx_dev_gemm: ONE full-sequence GEMM through a product launcher (launch_gemm_f32 / launch_gemm_f16x2 / launch_gemm_bf16x3[_dma]) on
+// caller operands, with the operand preparation of proj(): launch_split2h at H2_ACT_SCALE with the gather for A, the loader's
+// absmax -> shift -> launch_split2h for W (or the context's own load-time planes), descale = 2^-(5 + shift).  Everything is private
+// scratch: outputs pre-filled with the sentinels, the plane buffers too (the pad rows of a last tile are finite garbage).
+int vx_dev_gemm(vx_ctx* c, int32_t kernel, int32_t flags, int32_t M, int32_t N, int32_t K, const float* A, int32_t rowsA, int32_t lda,
+                const int32_t* gather, const float* Wt, int32_t w_src, int32_t w_layer, int32_t w_shift, const float* bias,
+                const float* resid, int32_t rowsR, int32_t ldr, const int32_t* resid_rows, const float* colscale, int32_t act, float* Cout,
+                int32_t rowsC, uint16_t* planes, uint16_t* a_planes, int32_t* info) {
+  if (!c) return VX_EINVAL;
+  if (c->serve) FAIL(VX_ESTATE, "vx_dev_gemm: a serving session is open on this context (vx_serve_close it first)");
+  constexpr int CAP = 4096, LD_CAP = 8192;
+  const bool f32k = kernel >= 0 && kernel <= 4, h2k = kernel >= 10 && kernel <= 15, x3k = kernel == 20 || kernel == 21;
+  if (!f32k && !h2k && !x3k) FAIL(VX_EINVAL, "vx_dev_gemm: kernel must be 0 .. 4 (fp32), 10 .. 15 (f16x2) or 20, 21 (bf16x3)");
+  if (!A || !info || M < 1 || M > CAP || N < 4 || N > CAP || N % 4 || K < 32 || K > CAP || K % 32)
+    FAIL(VX_EINVAL, "vx_dev_gemm: null argument, or M, N, K outside 1 .. %d with N %% 4 == 0 and K %% 32 == 0", CAP);
+  if (lda < K || lda > LD_CAP || lda % 4 || rowsA < 1 || rowsA > 2 * CAP || (!gather && rowsA < M))
+    FAIL(VX_EINVAL, "vx_dev_gemm: K <= lda <= %d with lda %% 4 == 0; 1 <= rowsA <= %d, rowsA >= M without a gather", LD_CAP, 2 * CAP);
+  if (gather) for (int m = 0; m < M; ++m) if (gather[m] < 0 || gather[m] >= rowsA) FAIL(VX_EINVAL, "vx_dev_gemm: gather[%d] outside A", m);
+  if (flags & ~(VX_DEV_GEMM_OUT_PLANES | VX_DEV_GEMM_INPLACE)) FAIL(VX_EINVAL, "vx_dev_gemm: unknown flag");
+  const bool out_pl = flags & VX_DEV_GEMM_OUT_PLANES, inplace = flags & VX_DEV_GEMM_INPLACE;
+  if (act < ACT_NONE || act > ACT_ELU || (!f32k && (colscale || act > ACT_RELU)))
+    FAIL(VX_EINVAL, "vx_dev_gemm: act must be 0 .. 3; colscale, GELU and ELU are the fp32 kernels'");
+  if (x3k && (gather || bias || resid || resid_rows || colscale || act || flags))
+    FAIL(VX_EINVAL, "vx_dev_gemm: the bf16x3 kernels run with the plain epilogue here");
+  if (resid) {
+    if (ldr < N || ldr > LD_CAP || ldr % 4 || rowsR < 1 || rowsR > 2 * CAP || (!resid_rows && rowsR < M))
+      FAIL(VX_EINVAL, "vx_dev_gemm: N <= ldr <= %d with ldr %% 4 == 0; 1 <= rowsR <= %d, rowsR >= M without resid_rows", LD_CAP, 2 * CAP);
+    if (resid_rows) for (int m = 0; m < M; ++m) if (resid_rows[m] < 0 || resid_rows[m] >= rowsR) FAIL(VX_EINVAL, "vx_dev_gemm: resid_rows[%d] outside resid", m);
+  } else if (resid_rows || inplace) FAIL(VX_EINVAL, "vx_dev_gemm: resid_rows / the in-place flag without resid");
+  if (inplace && (resid_rows || ldr != N || out_pl)) FAIL(VX_EINVAL, "vx_dev_gemm: in place: ldr == N, no resid_rows, no out_planes");
+  if (out_pl && (!h2k || N % 256 || !planes)) FAIL(VX_EINVAL, "vx_dev_gemm: out_planes: an f16x2 kernel, N %% 256 == 0 and a planes buffer");
+  if (!out_pl && (!Cout || planes)) FAIL(VX_EINVAL, "vx_dev_gemm: C is null (or planes given) without the out_planes flag");
+  if (Cout && (rowsC < M || rowsC > M + 64)) FAIL(VX_EINVAL, "vx_dev_gemm: rowsC must be M .. M + 64");
+  if (a_planes && !h2k) FAIL(VX_EINVAL, "vx_dev_gemm: a_planes goes with the f16x2 kernels");
+  const unsigned short* ctx_w3 = nullptr;
+  int shift = -1;
+  if (w_src != 0) {
+    if (!h2k || Wt || w_src < 1 || w_src > 8) FAIL(VX_EINVAL, "vx_dev_gemm: w_src 1 .. 8 goes with an f16x2 kernel and a null W");
+    if (!c->finalized || c->gemm_mode != 0) FAIL(VX_ESTATE, "vx_dev_gemm: the context holds no f16x2 weight planes");
+    const std::vector<LayerW>& st = w_src <= 4 ? c->ar : c->nar;
+    if (w_layer < 0 || w_layer >= (int)st.size()) FAIL(VX_EINVAL, "vx_dev_gemm: w_layer must be 0 .. %d", (int)st.size() - 1);
+    const LayerW& L = st[w_layer];
+    const int which = (w_src - 1) & 3;
+    ctx_w3 = which == 0 ? L.in_w3 : which == 1 ? L.out_w3 : which == 2 ? L.l1_w3 : L.l2_w3;
+    const int wn = which == 0 ? 3 * D_MODEL : which == 2 ? D_FF : D_MODEL, wk = which == 3 ? D_FF : D_MODEL;
+    if (N != wn || K != wk) FAIL(VX_EINVAL, "vx_dev_gemm: this weight is [%d][%d]", wn, wk);
+    const auto it = c->w_shift.find(ctx_w3);
+    if (!ctx_w3 || it == c->w_shift.end()) FAIL(VX_ESTATE, "vx_dev_gemm: the context has no planes of this weight");
+    shift = it->second;
+  } else {
+    if (!Wt) FAIL(VX_EINVAL, "vx_dev_gemm: W is null");
+    if (w_shift < -1 || w_shift > 24) FAIL(VX_EINVAL, "vx_dev_gemm: w_shift must be -1 (the loader's rule) or 0 .. 24");
+  }
+  HIPCHK(hipSetDevice(c->dev));
+
+  const long M256 = (M + 255) / 256 * 256;
+  const long a_pl = h2k ? h2_plane(M, K, H2_TILE_A) : (long)M * K, w_pl = h2k ? h2_plane(N, K, H2_TILE_W) : (long)N * K;
+  const long o_pl = h2_plane(M, N, H2_TILE_A);
+  const int P = h2k ? 2 : 3;
+  float *dA = nullptr, *dW = nullptr, *dbias = nullptr, *dcs = nullptr, *dres = nullptr, *dC = nullptr;
+  unsigned short *dA3 = nullptr, *dW3 = nullptr, *dP = nullptr;
+  int* di = nullptr;                                                  // range flag | absmax bits | gather [M] | resid_rows [M]
+  auto cleanup = [&]() {
+    for (void* p : {(void*)dA, (void*)dW, (void*)dbias, (void*)dcs, (void*)dres, (void*)dC, (void*)dA3, (void*)dW3, (void*)dP, (void*)di})
+      if (p) (void)hipFree(p);
+  };
+  hipError_t he;
+  // an error return drains the ring first: a queued xfer_d2h must not be delivered into host buffers that are gone by then
+#define TRY(x) if ((he = (x)) != hipSuccess) { (void)xfer_sync(c); cleanup(); c->err = std::string(#x) + ": " + hipGetErrorString(he); return VX_EHIP; }
+#define TRYX(x) do { if (int _e = (x)) { const std::string _m = c->err; (void)xfer_sync(c); c->err = _m; cleanup(); return _e; } } while (0)
+  TRY(hipMalloc((void**)&dA, (size_t)rowsA * lda * 4));
+  TRYX(xfer_h2d(c, dA, A, (size_t)rowsA * lda * 4));
+  if (Wt) {
+    TRY(hipMalloc((void**)&dW, (size_t)N * K * 4));
+    TRYX(xfer_h2d(c, dW, Wt, (size_t)N * K * 4));
+  }
+  if (bias) { TRY(hipMalloc((void**)&dbias, (size_t)N * 4)); TRYX(xfer_h2d(c, dbias, bias, (size_t)N * 4)); }
+  if (colscale) { TRY(hipMalloc((void**)&dcs, (size_t)N * 4)); TRYX(xfer_h2d(c, dcs, colscale, (size_t)N * 4)); }
+  if (resid && !inplace) { TRY(hipMalloc((void**)&dres, (size_t)rowsR * ldr * 4)); TRYX(xfer_h2d(c, dres, resid, (size_t)rowsR * ldr * 4)); }
+  {
+    std::vector<int> hi(2 + 2 * (size_t)M, 0);
+    if (gather) memcpy(&hi[2], gather, (size_t)M * 4);
+    if (resid_rows) memcpy(&hi[2 + M], resid_rows, (size_t)M * 4);
+    TRY(hipMalloc((void**)&di, hi.size() * 4));
+    TRYX(xfer_h2d(c, di, hi.data(), hi.size() * 4));
+  }
+  int* dflag = di;
+  const int *dgather = gather ? di + 2 : nullptr, *drr = resid_rows ? di + 2 + M : nullptr;
+  if (Cout) {
+    TRY(hipMalloc((void**)&dC, (size_t)rowsC * N * 4));
+    std::vector<float> fill((size_t)rowsC * N, VX_DEV_SENTINEL_F);
+    if (inplace) memcpy(fill.data(), resid, (size_t)M * N * 4);      // ldr == N: the residual rows are the output rows
+    TRYX(xfer_h2d(c, dC, fill.data(), fill.size() * 4));
+  }
+  if (!f32k) {
+    TRY(hipMalloc((void**)&dA3, (size_t)P * a_pl * 2));
+    std::vector<unsigned short> fill((size_t)P * std::max(a_pl, std::max(w_pl, o_pl)), VX_DEV_SENTINEL_H);
+    TRYX(xfer_h2d(c, dA3, fill.data(), (size_t)P * a_pl * 2));
+    if (!ctx_w3) {
+      TRY(hipMalloc((void**)&dW3, (size_t)P * w_pl * 2));
+      TRYX(xfer_h2d(c, dW3, fill.data(), (size_t)P * w_pl * 2));
+    }
+    if (out_pl) {
+      TRY(hipMalloc((void**)&dP, (size_t)2 * o_pl * 2));
+      TRYX(xfer_h2d(c, dP, fill.data(), (size_t)2 * o_pl * 2));
+    }
+  }
+  hipStream_t st = c->stream;
+  if (f32k) {
+    GemmArgs g{};
+    g.A = dA; g.lda = lda; g.W = dW; g.ldw = K; g.bias = dbias; g.resid = inplace ? dC : dres; g.ldr = ldr; g.colscale = dcs;
+    g.C = dC; g.ldc = N; g.M = M; g.N = N; g.K = K; g.act = act; g.row_gather = dgather; g.resid_rows = drr;
+    launch_gemm_f32(g, st, kernel);
+  } else {
+    if (h2k) {
+      launch_split2h(dA, lda, M, K, dgather, dA3, a_pl, H2_TILE_A, dflag, H2_ACT_SCALE, st);          // as proj()
+      if (!ctx_w3) {
+        if (w_shift >= 0) shift = w_shift;
+        else {                                                                                        // as the loader (weights.hip)
+          unsigned bits = 0;
+          launch_absmax(dW, (long)N * K, reinterpret_cast<unsigned*>(di + 1), st);
+          TRYX(xfer_d2h(c, &bits, di + 1, 4));
+          TRYX(xfer_sync(c));
+          float mx;
+          memcpy(&mx, &bits, sizeof mx);
+          shift = h2_weight_shift(mx);
+        }
+        launch_split2h(dW, K, N, K, nullptr, dW3, w_pl, H2_TILE_W, dflag, ldexpf(1.0f, shift), st);
+      }
+    } else {
+      launch_split3(dA, lda, M, K, nullptr, dA3, a_pl, st);
+      launch_split3(dW, K, N, K, nullptr, dW3, w_pl, st);
+    }
+    GemmX3Args g{};
+    g.A = dA3; g.a_plane = a_pl; g.W = ctx_w3 ? ctx_w3 : dW3; g.w_plane = w_pl; g.bias = dbias; g.resid = inplace ? dC : dres; g.ldr = ldr;
+    g.C = dC; g.ldc = N; g.M = M; g.N = N; g.K = K; g.act = act;
+    g.out_planes = out_pl ? dP : nullptr; g.out_plane = out_pl ? o_pl : 0; g.range_flag = dflag; g.resid_rows = drr;
+    if (h2k) g.descale = ldexpf(1.0f, -(H2_ACT_SHIFT + shift));
+    static const int tn_of[6] = {0, 128, 256, 257, -128, -129};
+    if (h2k) launch_gemm_f16x2(g, st, tn_of[kernel - 10]);
+    else if (kernel == 20) launch_gemm_bf16x3(g, st);
+    else launch_gemm_bf16x3_dma(g, st);
+  }
+  int flag = 0;
+  std::vector<unsigned short> hp(out_pl ? (size_t)2 * o_pl : 0), hap(a_planes ? (size_t)2 * a_pl : 0);
+  if (Cout) TRYX(xfer_d2h(c, Cout, dC, (size_t)rowsC * N * 4));
+  if (out_pl) TRYX(xfer_d2h(c, hp.data(), dP, hp.size() * 2));
+  if (a_planes) TRYX(xfer_d2h(c, hap.data(), dA3, hap.size() * 2));
+  TRYX(xfer_d2h(c, &flag, dflag, 4));
+  TRYX(xfer_sync(c));
+  TRY(hipGetLastError());
+  if (out_pl) dev_untile_planes(planes, hp, o_pl, M256, N);
+  if (a_planes) dev_untile_planes(a_planes, hap, a_pl, M256, K);
+  info[0] = flag; info[1] = h2k ? shift : -1; info[2] = 0;
+#undef TRY
+#undef TRYX
+  cleanup();
+  return VX_OK;
+}
+
+// vx_dev_layernorm: ONE launch_layernorm on caller rows (private scratch, outputs pre-filled with the sentinels).
+int vx_dev_layernorm(vx_ctx* c, int32_t rows, int32_t C, int32_t ldx, const float* x, const float* g, const float* b, const float* ada_w,
+                     const float* ada_b, float* y, int32_t rowsY, uint16_t* planes, int32_t* range_flag) {
+  if (!c) return VX_EINVAL;
+  if (c->serve) FAIL(VX_ESTATE, "vx_dev_layernorm: a serving session is open on this context (vx_serve_close it first)");
+  if (!x || rows < 1 || rows > 4096 || (C != 1024 && C != 384) || ldx < C || ldx > 8192 || ldx % 4)
+    FAIL(VX_EINVAL, "vx_dev_layernorm: null x, rows outside 1 .. 4096, C not 1024 / 384, or ldx outside C .. 8192 with ldx %% 4 == 0");
+  if (!g != !b || !ada_w != !ada_b) FAIL(VX_EINVAL, "vx_dev_layernorm: g / b and ada_w / ada_b come in pairs");
+  if (planes && C != 1024) FAIL(VX_EINVAL, "vx_dev_layernorm: planes go with C = 1024");
+  if (!y && !planes) FAIL(VX_EINVAL, "vx_dev_layernorm: neither y nor planes");
+  if (y && (rowsY < rows || rowsY > rows + 64)) FAIL(VX_EINVAL, "vx_dev_layernorm: rowsY must be rows .. rows + 64");
+  HIPCHK(hipSetDevice(c->dev));
+  const long R256 = (rows + 255) / 256 * 256, pstride = h2_plane(rows, C, H2_TILE_A);
+  float *dx = nullptr, *dv = nullptr, *dy = nullptr;                // dv: g | b | ada_w | ada_b
+  unsigned short* dpl = nullptr;
+  int* dflag = nullptr;
+  auto cleanup = [&]() { for (void* p : {(void*)dx, (void*)dv, (void*)dy, (void*)dpl, (void*)dflag}) if (p) (void)hipFree(p); };
+  hipError_t he;
+  // an error return drains the ring first: a queued xfer_d2h must not be delivered into host buffers that are gone by then
+#define TRY(x) if ((he = (x)) != hipSuccess) { (void)xfer_sync(c); cleanup(); c->err = std::string(#x) + ": " + hipGetErrorString(he); return VX_EHIP; }
+#define TRYX(x) do { if (int _e = (x)) { const std::string _m = c->err; (void)xfer_sync(c); c->err = _m; cleanup(); return _e; } } while (0)
+  TRY(hipMalloc((void**)&dx, (size_t)rows * ldx * 4));
+  TRYX(xfer_h2d(c, dx, x, (size_t)rows * ldx * 4));
+  TRY(hipMalloc((void**)&dv, (size_t)4 * C * 4));
+  const float* hv[4] = {g, b, ada_w, ada_b};
+  for (int i = 0; i < 4; ++i) if (hv[i]) TRYX(xfer_h2d(c, dv + (size_t)i * C, hv[i], (size_t)C * 4));
+  TRY(hipMalloc((void**)&dflag, 4));
+  const int zero = 0;
+  TRYX(xfer_h2d(c, dflag, &zero, 4));
+  if (y) {
+    TRY(hipMalloc((void**)&dy, (size_t)rowsY * C * 4));
+    std::vector<float> fill((size_t)rowsY * C, VX_DEV_SENTINEL_F);
+    TRYX(xfer_h2d(c, dy, fill.data(), fill.size() * 4));
+  }
+  if (planes) {
+    TRY(hipMalloc((void**)&dpl, (size_t)2 * pstride * 2));
+    std::vector<unsigned short> fill((size_t)2 * pstride, VX_DEV_SENTINEL_H);
+    TRYX(xfer_h2d(c, dpl, fill.data(), fill.size() * 2));
+  }
+  launch_layernorm(dx, ldx, dy, C, rows, C, LN_EPS, g ? dv : nullptr, b ? dv + C : nullptr, ada_w ? dv + 2 * C : nullptr,
+                   ada_b ? dv + 3 * C : nullptr, c->stream, dpl, pstride, dflag);
+  int flag = 0;
+  std::vector<unsigned short> hp(planes ? (size_t)2 * pstride : 0);
+  if (y) TRYX(xfer_d2h(c, y, dy, (size_t)rowsY * C * 4));
+  if (planes) TRYX(xfer_d2h(c, hp.data(), dpl, hp.size() * 2));
+  TRYX(xfer_d2h(c, &flag, dflag, 4));
+  TRYX(xfer_sync(c));
+  TRY(hipGetLastError());
+  if (planes) dev_untile_planes(planes, hp, pstride, R256, C);
+  if (range_flag) *range_flag = flag;
+#undef TRY
+#undef TRYX
+  cleanup();
+  return VX_OK;
+}
+
 }  // extern "C"

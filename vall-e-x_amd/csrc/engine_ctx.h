@@ -234,6 +234,16 @@ int dev_alloc(vx_ctx* c, T** p, size_t count, bool zero = true) {
 
 const float* W(vx_ctx* c, const std::string& name);
 
+// f16x2 weight planes (vx_common.h): the shift of a tensor from its max |w| -- max |w| * 2^shift in [16384, 32768), shift clamped to
+// 0 .. 24; a zero or non-finite maximum takes 24.  The loader (weights.hip) and vx_dev_gemm (bench_harness.hip) share it.
+inline int h2_weight_shift(float absmax) {
+  if (!(absmax > 0.f) || !(absmax < __builtin_inff())) return 24;
+  int ex;
+  (void)frexpf(absmax, &ex);
+  const int shift = 15 - ex;
+  return shift < 0 ? 0 : shift > 24 ? 24 : shift;
+}
+
 // ---- profiling helpers: an event pair around one launch --------------------------------------------------
 struct ProfScope {
   vx_ctx* c;

@@ -218,8 +218,7 @@ int vx_finalize_weights(vx_ctx* c) {
         SYNC();
         float mx;
         memcpy(&mx, &bits, sizeof mx);
-        int shift = 24;
-        if (mx > 0.f && isfinite(mx)) { int ex; (void)frexpf(mx, &ex); shift = std::max(0, std::min(24, 15 - ex)); }
+        const int shift = h2_weight_shift(mx);
         c->w_shift[*out] = shift;
         launch_split2h(Wt, K, N, K, nullptr, *out, h2_plane(N, K, H2_TILE_W), H2_TILE_W, c->range_flag, ldexpf(1.0f, shift), c->stream);
       } else launch_split3(Wt, K, N, K, nullptr, *out, (long)N * K, c->stream);
