@@ -266,6 +266,32 @@ int vx_ar_step(vx_ctx* ctx, const int32_t* tokens);
 /* NAR stages only (models/vallex.py:600-686): codes0 [batch][codes0_stride] first-codebook ids, lens [batch] */
 int vx_nar(vx_ctx* ctx, const vx_batch* b, const int32_t* codes0, int32_t codes0_stride, const int32_t* lens,
            int64_t* out_codes, int32_t out_stride);
+/* Teacher-forced scoring: the log-probability the model gives codes that already exist -- the argument of F.cross_entropy in
+ * VALLE.forward (the AR stack on the first codebook, the NAR stages on codebooks 2 .. 8) and the quantity best_of selects on,
+ * sum(logp) / len^penalty (models/vallex.py:572, :583-594).  One full-sequence pass per part instead of one cached step per frame.
+ *   codes [batch][codes_stride][8] int64: vx_infer's output layout, a result can be passed straight back; lens [batch],
+ *   0 <= T_b <= max_new; batch <= max_batch (groups of min(max_batch, 32) rows).  logp, rank [batch][out_stride][8]; eos_logp,
+ *   eos_rank [batch].
+ *   - Column 0 (VX_SCORE_AR): log-softmax over the 1025 AR logits of the row that predicts frame t, given the text, the prompt's first
+ *     codebook and codes[b][:t][0]; no temperature, no filter (the sampler's logp at top_k <= 0, temperature 1).  eos_logp[b],
+ *     eos_rank[b]: the same for id 1024 at the row behind the last frame, so sum_t logp[b][t][0] + eos_logp[b] is sum(logp) of
+ *     models/vallex.py:572 for that beam.  T_b = 0 is allowed: only the EOS pair is written.
+ *   - Columns q = 1 .. 7 (VX_SCORE_NAR): log-softmax over the 1024 logits of NAR stage q - 1 at frame t, given the text, the whole
+ *     prompt and codes[b][:][0 .. q-1].  The stages run the kernels of vx_nar on the same shapes: scoring what vx_infer generated
+ *     scores bit-identical logits.
+ *   - rank = number of logits STRICTLY greater than the target's (0: the target is an arg-max, ties included).
+ *   - Columns of a part that was not asked for and frames behind T_b are not written; an output pointer only that part needs may be NULL.
+ * Nothing is written to the KV arena and no decode state is touched.  Both passes sit behind the f16x2 range guard (a raised flag
+ * re-runs the pass in fp32 and counts in vx_last_fallbacks: the AR pass as a prefill phase, the NAR pass as a NAR phase).  The first
+ * call allocates its device buffers (vx_destroy frees them).  vx_last_stats then reports 0 AR steps, the scored frames and the
+ * AR-pass / NAR-pass milliseconds.
+ * VX_EINVAL, nothing launched, the message naming the field: everything vx_infer refuses in the batch; parts outside 1 .. 3; a length
+ * outside 0 .. max_new; codes_stride or out_stride below a length; a code outside 0 .. 1023 in a part that reads it (AR: codebook 0;
+ * NAR: all eight); while a serving session is open.  VX_ESTATE before vx_finalize_weights. */
+#define VX_SCORE_AR 1
+#define VX_SCORE_NAR 2
+int vx_score(vx_ctx* ctx, const vx_batch* b, const int64_t* codes, int32_t codes_stride, const int32_t* lens, int32_t parts,
+             float* logp, int32_t* rank, int32_t out_stride, float* eos_logp, int32_t* eos_rank);
 /* copy a named debug buffer (needs cfg.debug_taps) -- or, when no tap has that name, a tensor exactly as vx_load_tensor stored it
  * (read-back check of an upload) -- to the host; returns the number of floats copied or < 0 */
 int64_t vx_read_tap(vx_ctx* ctx, const char* name, float* dst, int64_t max_floats);

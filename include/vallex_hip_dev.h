@@ -188,6 +188,14 @@ int vx_dev_gemm(vx_ctx* ctx, int32_t kernel, int32_t flags, int32_t M, int32_t N
  * VX_EINVAL, nothing launched, for anything outside the above; VX_ESTATE while a serving session is open. */
 int vx_dev_layernorm(vx_ctx* ctx, int32_t rows, int32_t C, int32_t ldx, const float* x, const float* g, const float* b, const float* ada_w,
                      const float* ada_b, float* y, int32_t rowsY, uint16_t* planes, int32_t* range_flag);
+/* ONE launch of score_rows_kernel (csrc/score.hip, the kernel behind vx_score) on caller rows:
+ *   m = max_j l_j, s = sum_j expf(l_j - m), logp = (l_t - m) - logf(s), rank = #{j : l_j > l_t} over the columns j < ncols of row r,
+ *   t = targets[r].  logits [rows][ld], ncols 1024 or 1025, ld >= ncols, ld % 4 == 0, ld <= 8192 (columns ncols .. ld-1 are padding
+ *   and influence nothing); rows 1 .. 4096; targets [rows] in 0 .. ncols-1.
+ *   logp, rank [rows_out], rows <= rows_out <= rows + 64: entries the launch did not write hold VX_DEV_SENTINEL_F / VX_DEV_SENTINEL_I.
+ * VX_EINVAL, nothing launched, for anything outside the above; VX_ESTATE while a serving session is open. */
+int vx_dev_score_rows(vx_ctx* ctx, int32_t rows, int32_t ncols, int32_t ld, const float* logits, const int32_t* targets,
+                      float* logp, int32_t* rank, int32_t rows_out);
 
 #ifdef __cplusplus
 }

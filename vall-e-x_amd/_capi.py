@@ -80,11 +80,11 @@ SYMBOLS = ["vx_abi_version", "vx_create", "vx_destroy", "vx_last_error", "vx_syn
            "vx_infer", "vx_vocos_decode", "vx_encodec_decode", "vx_encodec_encode", "vx_ar_prefill", "vx_ar_logits", "vx_ar_step",
            "vx_nar", "vx_read_tap", "vx_last_stats", "vx_last_truncated", "vx_last_fallbacks", "vx_fallback_state",
            "vx_fallback_reset", "vx_arith_mode", "vx_infer_continuous", "vx_serve_open", "vx_serve_submit", "vx_serve_run",
-           "vx_serve_close", "vx_serve_submit_ex", "vx_serve_cancel", "vx_serve_submit_filtered"]
+           "vx_serve_close", "vx_serve_submit_ex", "vx_serve_cancel", "vx_serve_submit_filtered", "vx_score"]
 # ... and include/vallex_hip_dev.h: measurement / kernel development, never called by the mirrors of the reference API
 DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kernel", "vx_bench_gemm", "vx_bench_attn",
                "vx_bench_gemm_clock", "vx_bench_gemm_epilogue", "vx_dev_sample", "vx_dev_attn", "vx_dev_sample_filtered",
-               "vx_dev_dec_attn", "vx_dev_dec_op", "vx_dev_gemm", "vx_dev_layernorm"]
+               "vx_dev_dec_attn", "vx_dev_dec_op", "vx_dev_gemm", "vx_dev_layernorm", "vx_dev_score_rows"]
 # sentinels the correctness entries pre-fill their outputs with (include/vallex_hip_dev.h)
 DEV_SENTINEL_I = -123456789
 DEV_SENTINEL_F = np.float32(-1.0e30)
@@ -99,6 +99,8 @@ DEV_GEMM_WSRC = {"ar.in_proj": 1, "ar.out_proj": 2, "ar.linear1": 3, "ar.linear2
                  "nar.in_proj": 5, "nar.out_proj": 6, "nar.linear1": 7, "nar.linear2": 8}
 DEV_GEMM_OUT_PLANES, DEV_GEMM_INPLACE = 1, 2
 DEV_SENTINEL_H = 0xFBFF
+SCORE_AR, SCORE_NAR = 1, 2             # VX_SCORE_* of include/vallex_hip.h (parts of vx_score)
+SCORE_PARTS = {"ar": SCORE_AR, "nar": SCORE_NAR, "both": SCORE_AR | SCORE_NAR}
 DEV_SAMPLE_CFG = ("kernel", "splitk", "top_k", "force_eos_at", "active", "n_gen", "cur_pos", "ctx_len", "text_len", "gen_stride")
 
 # vx_row_done_fn of vx_infer_continuous: (user, caller row, codes [frames][8] int64, frames)
@@ -189,6 +191,10 @@ def load_library() -> C.CDLL:
                                 P(C.c_float), C.c_int32, P(C.c_float), C.c_int32, P(C.c_uint16), P(C.c_uint16), P(C.c_int32)]
     lib.vx_dev_layernorm.argtypes = [ctx, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
                                      P(C.c_float), P(C.c_float), C.c_int32, P(C.c_uint16), P(C.c_int32)]
+    lib.vx_score.argtypes = [ctx, P(vx_batch), P(C.c_int64), C.c_int32, P(C.c_int32), C.c_int32, P(C.c_float), P(C.c_int32), C.c_int32,
+                             P(C.c_float), P(C.c_int32)]
+    lib.vx_dev_score_rows.argtypes = [ctx, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), P(C.c_int32), P(C.c_float), P(C.c_int32),
+                                      C.c_int32]
     lib.vx_last_stats.argtypes = [ctx, P(C.c_int64), P(C.c_int64), P(C.c_double), P(C.c_double)]
     lib.vx_last_truncated.argtypes = [ctx, P(C.c_int32)]
     lib.vx_last_fallbacks.argtypes = [ctx, P(C.c_int32), P(C.c_int32), P(C.c_int64)]
@@ -450,6 +456,44 @@ class Engine:
                                   _ptr(out, C.c_int64), stride))
         self._warn_fallbacks()
         return [out[i, : lens[i]].copy() for i in range(batch.n)]
+
+    # ---- teacher-forced scoring ----
+    def score_into(self, batch: Batch, codes: np.ndarray, lens, parts, logp, rank, eos_logp, eos_rank, codes_stride=None,
+                   out_stride=None):
+        """vx_score on caller arrays: codes (n, codes_stride, 8) int64, lens (n,); logp float32 / rank int32 (n, out_stride, 8),
+        eos_logp float32 / eos_rank int32 (n,) are written in place (only what `parts` covers; an array the part does not need may
+        be None).  The strides default to the arrays' own."""
+        codes = np.ascontiguousarray(codes, np.int64)
+        lens = np.ascontiguousarray(lens, np.int32)
+        for a, ty in ((logp, np.float32), (rank, np.int32), (eos_logp, np.float32), (eos_rank, np.int32)):
+            if a is not None and not (a.dtype == ty and a.flags.c_contiguous):
+                raise ValueError("output arrays are C-contiguous float32 (logp, eos_logp) / int32 (rank, eos_rank)")
+        p = lambda a, ty: None if a is None else _ptr(a, ty)
+        cs = codes.shape[1] if codes_stride is None else int(codes_stride)
+        os_ = (logp if logp is not None else rank).shape[1] if out_stride is None else int(out_stride)
+        self._chk(self.lib.vx_score(self.ctx, C.byref(batch.c), _ptr(codes, C.c_int64), cs, _ptr(lens, C.c_int32),
+                                    int(SCORE_PARTS.get(parts, parts)), p(logp, C.c_float), p(rank, C.c_int32), os_,
+                                    p(eos_logp, C.c_float), p(eos_rank, C.c_int32)))
+        self._warn_fallbacks()
+
+    def score(self, batch: Batch, codes_list: Sequence[np.ndarray], parts=3):
+        """vx_score: log-probability and rank the model gives the codes of codes_list[i] (T_i, 8), as Engine.infer returns them, for
+        row i of `batch`.  parts: 1 / "ar" (column 0 and the EOS pair), 2 / "nar" (columns 1 .. 7), 3 / "both".  Returns per row
+        (logp (T, 8) float32, rank (T, 8) int32, eos_logp, eos_rank); what `parts` leaves out is NaN / -1."""
+        n = batch.n
+        if len(codes_list) != n:
+            raise ValueError(f"{len(codes_list)} code arrays for {n} rows")
+        cl = [np.asarray(c, np.int64).reshape(-1, 8) for c in codes_list]
+        lens = np.array([len(c) for c in cl], np.int32)
+        stride = max(1, int(lens.max()))
+        codes = np.zeros((n, stride, 8), np.int64)
+        for i, c in enumerate(cl):
+            codes[i, : len(c)] = c
+        logp = np.full((n, stride, 8), np.nan, np.float32)
+        rank = np.full((n, stride, 8), -1, np.int32)
+        elp, erk = np.full(n, np.nan, np.float32), np.full(n, -1, np.int32)
+        self.score_into(batch, codes, lens, parts, logp, rank, elp, erk)
+        return [(logp[i, : lens[i]].copy(), rank[i, : lens[i]].copy(), float(elp[i]), int(erk[i])) for i in range(n)]
 
     def read_tap(self, name: str, n: int) -> np.ndarray:
         out = np.zeros(n, np.float32)
@@ -718,6 +762,25 @@ class Engine:
         self._chk(self.lib.vx_dev_layernorm(self.ctx, rows, int(c), ldx, pf(x), pf(g), pf(b), pf(ada_w), pf(ada_b), pf(y),
                                             0 if y is None else len(y), None if pl is None else _ptr(pl, C.c_uint16), C.byref(flag)))
         return dict(y=y, planes=pl, flag=flag.value)
+
+    def dev_score_rows(self, logits: np.ndarray, targets, ncols: int, extra_rows: int = 3, logp=None, rank=None):
+        """vx_dev_score_rows: one launch of score_rows_kernel on logits (rows, ld) float32, scoring targets[r] over the first ncols
+        columns of row r.  Returns (logp (rows + extra_rows,) float32, rank (rows + extra_rows,) int32); entries behind `rows` hold the
+        sentinels.  logp / rank: caller arrays to write instead (their length is rows_out)."""
+        x = np.ascontiguousarray(logits, np.float32)
+        t = np.ascontiguousarray(targets, np.int32)
+        if x.ndim != 2 or t.shape != (x.shape[0],):
+            raise ValueError("logits is (rows, ld), targets (rows,)")
+        rows, ld = x.shape
+        if logp is None:
+            logp = np.empty(rows + int(extra_rows), np.float32)
+        if rank is None:
+            rank = np.empty(len(logp), np.int32)
+        if not (logp.dtype == np.float32 and rank.dtype == np.int32 and logp.shape == rank.shape and logp.ndim == 1):
+            raise ValueError("logp float32 and rank int32, 1-D, of one length")
+        self._chk(self.lib.vx_dev_score_rows(self.ctx, rows, int(ncols), ld, _ptr(x, C.c_float), _ptr(t, C.c_int32),
+                                             _ptr(logp, C.c_float), _ptr(rank, C.c_int32), len(logp)))
+        return logp, rank
 
     def last_fallbacks(self):
         """phases of the last call that left the fp16 range of the f16x2 kernels and were re-run in fp32 (+ lifetime count)"""

@@ -131,8 +131,8 @@ void gemm(vx_ctx* c, const float* A, int lda, const float* Wt, int ldw, const fl
 // f16x2 mode extras: `a_pre` = A operand already in plane form (skip the split pass); `out_pl` = write the result as the next
 // GEMM's A planes (K = N) instead of fp32 rows (C may then be null).
 void proj(vx_ctx* c, const float* A, int lda, const float* Wf, const unsigned short* W3, const float* bias,
-          const float* resid, int ldr, float* C, int ldc, long M, int N, int K, int act, const int* gather = nullptr,
-          const unsigned short* a_pre = nullptr, unsigned short* out_pl = nullptr, const int* resid_rows = nullptr) {
+          const float* resid, int ldr, float* C, int ldc, long M, int N, int K, int act, const int* gather,
+          const unsigned short* a_pre, unsigned short* out_pl, const int* resid_rows) {
   if (c->gemm_mode == 2 || !W3) {
     gemm(c, A, lda, Wf, K, bias, resid, ldr, nullptr, C, ldc, M, N, K, act, gather, 2, resid_rows);
     return;
@@ -161,18 +161,12 @@ void proj(vx_ctx* c, const float* A, int lda, const float* Wf, const unsigned sh
 // produce those rows: attention queries, out_proj, norm2 and the FFN run on the Mc = sum T_b compacted rows.  Every op of the
 // block treats rows independently, so each kept row goes through exactly the arithmetic it would see untrimmed: same ids, same
 // logits, bit for bit.  The compacted residual stream lives in c->fxn (f16x2 mode: unused otherwise) or in the QKV buffer (fp32 mode).
-struct Trim {
-  long Mc;               // kept rows
-  const int* q_first;    // [batch] first kept sequence-local row (S + Tp)
-  const int* c_off;      // [batch] first compacted row of the sequence
-  const int* rows;       // [Mc] packed row of every compacted row (residual gather)
-  double attn_flops;     // 4 * T_b * L_b * 1024 summed: the queries that are still computed
-};
+// (struct Trim: engine_ctx.h -- the teacher-forced scoring passes of score.hip trim the same way)
 
 // one pre-norm block on packed rows (modules/transformer.py:296-302 / :337-347) -- shared by AR prefill and NAR
 int full_layer(vx_ctx* c, const LayerW& L, long M, const int* seq_off, const int* seq_len, const int* prefix_len,
                int batch, int max_len, const float* ada1, const float* ada2, float* kcl, float* vcl,
-               const int* row_b, const int* row_t, double attn_flops, const Trim* tr = nullptr) {
+               const int* row_b, const int* row_t, double attn_flops, const Trim* tr) {
   // f16x2 mode: every producer of a GEMM operand (the two LayerNorms, the attention, linear1's epilogue) writes the operand
   // planes itself -- no fp32 round trip of the normalised / attended / hidden activations and no split pass on any edge.
   const bool pl = c->gemm_mode == 0;
@@ -698,13 +692,13 @@ int ar_step_run(vx_ctx* c, const SampleArgs* sa, const std::string& sig, int nst
 
 // ---- sticky fp32 fallback bookkeeping (engine_ctx.h) -----------------------------------------------------------
 // does this phase go to the fp32 kernels directly?  In sticky mode yes, except every FB_STICKY_PROBE_EVERY-th phase (a probe on f16x2)
-static bool fb_direct(vx_ctx* c, bool sticky, int& age) {
+bool fb_direct(vx_ctx* c, bool sticky, int& age) {
   if (!sticky || !range_guarded(c)) return false;
   if (++age >= FB_STICKY_PROBE_EVERY) { age = 0; return false; }
   return true;
 }
 // outcome of a phase that RAN on f16x2: a raise counts towards sticky mode, a clean pass resets the count and leaves sticky mode
-static void fb_outcome(vx_ctx* c, bool raised, int& raises, bool& sticky, int& age) {
+void fb_outcome(vx_ctx* c, bool raised, int& raises, bool& sticky, int& age) {
   if (!range_guarded(c)) return;
   if (!raised) { raises = 0; sticky = false; age = 0; return; }
   if (++raises >= FB_STICKY_AFTER && !sticky) { sticky = true; age = 0; ++c->sticky_engaged; }
@@ -832,7 +826,6 @@ static unsigned long long beam_seed(unsigned long long seed, int k) {
 }
 
 // ---- NAR: 7 stages (models/vallex.py:600-686, prefix_mode 1) ----------------------------------------------------
-constexpr int VX_RETRY_F32 = 1;      // internal: the phase raised the f16x2 range flag, run it again on the fp32 kernels
 int nar_generate_once(vx_ctx* c, const vx_batch* b, int r0, int nb, const std::vector<int>& T, const int* codes0,
                       long codes0_stride, std::vector<int>& out_codes /* [7][sumT] */, long& sumT_out) {
   const int NL = c->NL;

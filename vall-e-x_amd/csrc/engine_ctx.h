@@ -2,7 +2,8 @@
 // weights.hip: ingest of the reference state-dict; vocoders.hip: Vocos head, EnCodec decoder / encoder drivers;
 // beams.hip: the best_of fan-out; admit.hip / serve.hip: admission kernels of the continuous schedule / the serving session;
 // serve_sample.hip: the serving session's per-row sampler;
-// bench_harness.hip: the measurement entries of include/vallex_hip_dev.h).  Not part of the public C ABI.
+// bench_harness.hip: the measurement entries of include/vallex_hip_dev.h; score.hip: teacher-forced scoring, vx_score).
+// Not part of the public C ABI.
 #pragma once
 
 #include <math.h>
@@ -152,6 +153,12 @@ struct vx_ctx {
   vx_serve* serve = nullptr;       // the open serving session (vx_serve_open); it owns the decode state while it is open
   int* row_smp = nullptr;          // [MB][4] per-row sampling record of the session's sampler (first vx_serve_open allocates it)
   int* row_flt = nullptr;          // [MB][4] per-row filter record {top_p bits, penalty bits, window, min_frames}, allocated with row_smp
+
+  // teacher-forced scoring (score.hip): allocated by the first vx_score, a context that never scores holds none of it
+  float* sc_predw = nullptr;       // ar_predict_layer.weight zero-padded to [1028][1024] (the full-sequence GEMMs need N % 4 == 0)
+  float* sc_logits = nullptr;      // AR logits of the scored rows [sum (T_b + 1)][1028] when flogits is too small for them
+  float* sc_logp = nullptr;        // [8 mbr (max_new + 1)] log-probabilities of the targets, as the kernel wrote them
+  int* sc_rank = nullptr;          // ... and their ranks
 
   // graph
   hipGraphExec_t graph_exec = nullptr, graph_exec_n = nullptr;   // one decode step / GRAPH_STEPS steps per launch
@@ -369,6 +376,33 @@ struct ServeSampleArgs {
   int wt;
 };
 bool launch_serve_sample(const ServeSampleArgs& a, hipStream_t s);
+
+// Row trimming of the LAST decoder layer of a NAR stage (f16x2 mode, and since round 6 the reference-arithmetic fp32 mode): only the
+// generated frames of every sequence reach a predict layer (models/vallex.py:672-679), so behind the K / V projection -- which
+// attention needs for ALL rows -- the layer only has to produce those rows: attention queries, out_proj, norm2 and the FFN run on the
+// Mc = sum T_b compacted rows.  Every op of the block treats rows independently, so each kept row goes through exactly the arithmetic
+// it would see untrimmed: same ids, same logits, bit for bit.  The compacted residual stream lives in c->fxn (f16x2 mode: unused
+// otherwise) or in the QKV buffer (fp32 mode).
+struct Trim {
+  long Mc;               // kept rows
+  const int* q_first;    // [batch] first kept sequence-local row (S + Tp)
+  const int* c_off;      // [batch] first compacted row of the sequence
+  const int* rows;       // [Mc] packed row of every compacted row (residual gather)
+  double attn_flops;     // 4 * T_b * L_b * 1024 summed: the queries that are still computed
+};
+// engine.hip, shared with the scoring passes (score.hip)
+constexpr int VX_RETRY_F32 = 1;      // internal: the phase raised the f16x2 range flag, run it again on the fp32 kernels
+void proj(vx_ctx* c, const float* A, int lda, const float* Wf, const unsigned short* W3, const float* bias, const float* resid, int ldr,
+          float* C, int ldc, long M, int N, int K, int act, const int* gather = nullptr, const unsigned short* a_pre = nullptr,
+          unsigned short* out_pl = nullptr, const int* resid_rows = nullptr);
+int full_layer(vx_ctx* c, const LayerW& L, long M, const int* seq_off, const int* seq_len, const int* prefix_len, int batch, int max_len,
+               const float* ada1, const float* ada2, float* kcl, float* vcl, const int* row_b, const int* row_t, double attn_flops,
+               const Trim* tr = nullptr);
+int prefill_tables(vx_ctx* c, const vx_batch* b, int r0, int nb, PrefillPlan& p, MetaBuilder& mb);
+bool fb_direct(vx_ctx* c, bool sticky, int& age);
+void fb_outcome(vx_ctx* c, bool raised, int& raises, bool& sticky, int& age);
+// score.hip: (log-probability, rank) of targets[r] in logits[r][0 .. ncols-1], one wavefront per row
+void launch_score_rows(const float* logits, int ld, int rows, int ncols, const int* targets, float* logp, int* rank, hipStream_t s);
 
 struct F32Scope {            // the full-sequence path on the exact-fp32 kernels for the lifetime of the object
   vx_ctx* c;

@@ -1,0 +1,454 @@
+// Teacher-forced scoring: how likely the model finds codes that already exist (vx_score, include/vallex_hip.h).
+// The quantity VALLE.forward feeds to F.cross_entropy (models/vallex.py: the AR stack on the first codebook, the NAR stages on
+// codebooks 2 .. 8) and the one best_of selects on (sum(logp) / len^penalty, models/vallex.py:572, :583-594).  Both passes drive the
+// full-sequence layers of engine.hip (full_layer + Trim) with the GIVEN codes as inputs; the one new kernel turns logit rows into
+// (log-probability, rank) of a target id.
+#include "engine_ctx.h"
+
+#include "../../include/vallex_hip_dev.h"
+
+namespace vxe {
+
+// ---------------------------------------------------------------------------------------------
+// (logp, rank) of targets[row] in logits[row][0 .. ncols-1]:  m = max_j l_j, s = sum_j expf(l_j - m), logp = (l_t - m) - logf(s),
+// rank = #{j : l_j > l_t} (strictly: rank 0 = the target is an arg-max, ties included).  One wavefront per row, four rows per block;
+// the row is read once, as 16-byte loads held in registers (ncols <= 1280), wave-shuffle reductions, no LDS.  Columns ncols .. ld-1
+// are padding: a 16-byte group that starts behind ncols is not loaded, the tail of the group that straddles ncols is masked.
+// ---------------------------------------------------------------------------------------------
+constexpr int SCORE_GROUPS = 5;              // float4 groups per lane: 5 x 64 x 4 = 1280 columns
+constexpr int SCORE_MAX_COLS = SCORE_GROUPS * 64 * 4;
+
+__global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict__ logits, int ld, int rows, int ncols,
+                                                         const int* __restrict__ targets, float* __restrict__ logp,
+                                                         int* __restrict__ rank) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const float* xr = logits + (long)row * ld;
+  const int t = targets[row];
+  float v[SCORE_GROUPS * 4];
+  float m = -INFINITY, lt = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < SCORE_GROUPS; ++i) {
+    const int c = (i * 64 + lane) * 4;
+    f32x4 q = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    if (c < ncols) q = *reinterpret_cast<const f32x4*>(xr + c);      // c + 3 < ld: ld >= ncols, ld % 4 == 0
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float x = c + e < ncols ? q[e] : -INFINITY;
+      v[i * 4 + e] = x;
+      m = fmaxf(m, x);
+      if (c + e == t) lt = x;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    m = fmaxf(m, __shfl_xor(m, o, 64));
+    lt = fmaxf(lt, __shfl_xor(lt, o, 64));                           // one lane holds l_t, the others -inf
+  }
+  float s = 0.f;
+  int above = 0;
+#pragma unroll
+  for (int i = 0; i < SCORE_GROUPS; ++i) {
+    const int c = (i * 64 + lane) * 4;
+    float ex[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const bool in = c + e < ncols;
+      ex[e] = in ? expf(v[i * 4 + e] - m) : 0.f;
+      above += (in && v[i * 4 + e] > lt) ? 1 : 0;
+    }
+    s += (ex[0] + ex[1]) + (ex[2] + ex[3]);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    s += __shfl_xor(s, o, 64);
+    above += __shfl_xor(above, o, 64);
+  }
+  if (lane == 0) {
+    logp[row] = (lt - m) - logf(s);
+    rank[row] = above;
+  }
+}
+
+void launch_score_rows(const float* logits, int ld, int rows, int ncols, const int* targets, float* logp, int* rank, hipStream_t s) {
+  if (rows <= 0) return;
+  hipLaunchKernelGGL(score_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, logits, ld, rows, ncols, targets, logp, rank);
+}
+
+// ---------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------
+constexpr int SCORE_LD = 1028;               // AR logits row: 1025 columns padded to the GEMMs' N % 4 == 0
+
+// device memory only a scoring context needs: the padded predict weight, the result buffers, and a logits buffer when the NAR
+// stages' one (mbr x max_new rows of 1024) cannot hold mbr x (max_new + 1) rows of 1028
+static int score_buffers(vx_ctx* c) {
+  if (c->sc_predw) return VX_OK;
+  const long rows = (long)c->mbr * (c->cfg.max_new + 1);
+  float *logp = nullptr, *pw = nullptr;
+  int* rank = nullptr;
+  if (int e = dev_alloc(c, &logp, (size_t)rows * N_Q)) return e;
+  if (int e = dev_alloc(c, &rank, (size_t)rows * N_Q)) return e;
+  if (((long)c->mbr * c->cfg.max_new + 128) * AUDIO_VOCAB < rows * SCORE_LD)
+    if (int e = dev_alloc(c, &c->sc_logits, (size_t)rows * SCORE_LD)) return e;
+  if (int e = dev_alloc(c, &pw, (size_t)SCORE_LD * D_MODEL)) return e;      // zeroed: rows 1025 .. 1027 stay zero
+  HIPCHK(hipMemcpyAsync(pw, W(c, "ar_predict_layer.weight"), (size_t)AR_LOGITS * D_MODEL * sizeof(float), hipMemcpyDeviceToDevice,
+                        c->stream));
+  c->sc_logp = logp; c->sc_rank = rank; c->sc_predw = pw;
+  return VX_OK;
+}
+
+// the scored codes of caller rows r0 .. r0+nb-1: codes [batch][stride][8] int64 (vx_infer's output layout)
+struct ScoreRows {
+  const vx_batch* b;
+  const int64_t* codes;
+  long stride;
+  int r0, nb;
+  std::vector<int> T;
+  int code(int i, int t, int q) const { return (int)codes[((long)(r0 + i) * stride + t) * N_Q + q]; }
+};
+
+// AR pass of one group: text, then BOS ++ prompt codebook 0 ++ codes[:, 0] under the prefix-LM mask of the prefill; nothing goes
+// into the KV arena and no decode state is touched.  The last layer computes only the T_b + 1 rows that predict frame 0 .. T_b - 1
+// and the stop decision.  logp / rank [sum (T_b + 1)]: row T_b of a sequence scores EOS.
+static int score_ar_once(vx_ctx* c, const ScoreRows& R, std::vector<float>& logp, std::vector<int>& rank) {
+  const int nb = R.nb, NL = c->NL;
+  const vx_batch* b = R.b;
+  // the prefill's tables of a batch whose prompts are the callers' with the given frames appended (only codebook 0 is read)
+  int ps = 1;
+  for (int i = 0; i < nb; ++i) ps = std::max(ps, b->prompt_lens[R.r0 + i] + R.T[i]);
+  std::vector<int32_t> pc((size_t)nb * ps * N_Q, 0), pl(nb);
+  for (int i = 0; i < nb; ++i) {
+    const int Tp = b->prompt_lens[R.r0 + i];
+    pl[i] = Tp + R.T[i];
+    for (int t = 0; t < Tp; ++t) pc[((size_t)i * ps + t) * N_Q] = b->prompt_codes[((long)(R.r0 + i) * b->prompt_stride + t) * N_Q];
+    for (int t = 0; t < R.T[i]; ++t) pc[((size_t)i * ps + Tp + t) * N_Q] = R.code(i, t, 0);
+  }
+  vx_batch bx = *b;
+  bx.batch = nb;
+  bx.text_ids = b->text_ids + (long)R.r0 * b->text_stride; bx.text_lang = b->text_lang + (long)R.r0 * b->text_stride;
+  bx.text_lens = b->text_lens + R.r0;
+  bx.prompt_codes = pc.data(); bx.prompt_stride = ps; bx.prompt_lens = pl.data();
+  PrefillPlan p;
+  MetaBuilder mb(c);
+  if (int e = prefill_tables(c, &bx, 0, nb, p, mb)) return e;
+  std::vector<int> q_first(nb), c_off(nb), rows, tg;
+  long Mc = 0;
+  double trim_flops = 0, attn_flops = 0;
+  for (int i = 0; i < nb; ++i) {
+    const int Tp = b->prompt_lens[R.r0 + i];
+    q_first[i] = p.S_[i] + Tp; c_off[i] = (int)Mc;
+    for (int t = 0; t <= R.T[i]; ++t) {
+      rows.push_back(p.seq_off[i] + q_first[i] + t);
+      tg.push_back(t < R.T[i] ? R.code(i, t, 0) : EOS_ID);
+    }
+    Mc += R.T[i] + 1;
+    trim_flops += 4.0 * (R.T[i] + 1) * (double)p.seq_len[i] * D_MODEL;
+    attn_flops += 4.0 * p.seq_len[i] * (double)p.seq_len[i] * D_MODEL;
+  }
+  const long o_qf = mb.add(q_first), o_co = mb.add(c_off), o_rows = mb.add(rows), o_tg = mb.add(tg);
+  if (int e = upload_meta(c)) return e;
+
+  launch_embed_rows(c->fx, mb.dev(p.o_dt), W(c, "ar_text_embedding.word_embeddings.weight"), mb.dev(p.o_it),
+                    W(c, "ar_language_embedding.word_embeddings.weight"), mb.dev(p.o_lt), W(c, "ar_text_position.alpha"),
+                    c->pe, mb.dev(p.o_pt), p.n_t, c->stream);
+  launch_embed_rows(c->fx, mb.dev(p.o_da), W(c, "ar_audio_embedding.word_embeddings.weight"), mb.dev(p.o_ia), nullptr,
+                    nullptr, W(c, "ar_audio_position.alpha"), c->pe, mb.dev(p.o_pa), p.n_a, c->stream);
+  // p.trim: the arithmetic can trim (f16x2 throughout, or fp32 throughout) -- bf16x3, the mixed switches and debug_taps run
+  // every row and gather
+  const Trim tr{Mc, mb.dev(o_qf), mb.dev(o_co), mb.dev(o_rows), trim_flops};
+  for (int l = 0; l < NL; ++l)
+    if (int e = full_layer(c, c->ar[l], p.M, mb.dev(p.o_off), mb.dev(p.o_len), mb.dev(p.o_S), nb, p.max_len, nullptr, nullptr,
+                           nullptr, nullptr, nullptr, nullptr, attn_flops, (p.trim && l == NL - 1) ? &tr : nullptr))
+      return e;
+  // ar_decoder.norm on the kept rows, then ar_predict_layer on the fp32 GEMM (models/vallex.py:568)
+  const float *ng = W(c, "ar_decoder.norm.weight"), *nbias = W(c, "ar_decoder.norm.bias");
+  float* lg = c->sc_logits ? c->sc_logits : c->flogits;
+  const float* A;
+  const int* gather = nullptr;
+  if (p.trim && p.trim_h2) {             // compacted rows in fxn; fx is free behind the last layer
+    launch_layernorm(c->fxn, D_MODEL, c->fx, D_MODEL, (int)Mc, D_MODEL, LN_EPS, ng, nbias, nullptr, nullptr, c->stream);
+    A = c->fx;
+  } else if (p.trim) {                   // compacted rows in the QKV buffer
+    launch_layernorm(c->fqkv, D_MODEL, c->fxn, D_MODEL, (int)Mc, D_MODEL, LN_EPS, ng, nbias, nullptr, nullptr, c->stream);
+    A = c->fxn;
+  } else {
+    launch_layernorm(c->fx, D_MODEL, c->fxn, D_MODEL, (int)p.M, D_MODEL, LN_EPS, ng, nbias, nullptr, nullptr, c->stream);
+    A = c->fxn; gather = mb.dev(o_rows);
+  }
+  gemm(c, A, D_MODEL, c->sc_predw, D_MODEL, nullptr, nullptr, 0, nullptr, lg, SCORE_LD, Mc, SCORE_LD, D_MODEL, ACT_NONE, gather, 2);
+  launch_score_rows(lg, SCORE_LD, (int)Mc, AR_LOGITS, mb.dev(o_tg), c->sc_logp, c->sc_rank, c->stream);
+  HIPCHK(hipGetLastError());
+  logp.resize(Mc); rank.resize(Mc);
+  D2H(logp.data(), c->sc_logp, (size_t)Mc * sizeof(float));
+  D2H(rank.data(), c->sc_rank, (size_t)Mc * sizeof(int));
+  int flag = 0;                          // the range flag rides on the sync that brings the results back
+  if (range_guarded(c)) D2H(&flag, c->range_flag, sizeof(int));
+  SYNC();
+  if (flag) {
+    HIPCHK(hipMemsetAsync(c->range_flag, 0, sizeof(int), c->stream));
+    return VX_RETRY_F32;
+  }
+  return VX_OK;
+}
+
+// NAR pass of one group: the loop of nar_generate_once (engine.hip) -- same tables, same trimming, same final AdaLN norm, same
+// pred_w3 projection, the same kernels on the same shapes -- with the GIVEN codes[.., st + 1] accumulated behind stage st instead
+// of the arg-max, and scored instead of chosen.  logp / rank [7][sum T_b].
+static int score_nar_once(vx_ctx* c, const ScoreRows& R, std::vector<float>& logp, std::vector<int>& rank, long& sumT_out) {
+  const int NL = c->NL, nb = R.nb, r0 = R.r0;
+  const vx_batch* b = R.b;
+  const std::vector<int>& T = R.T;
+  std::vector<int> seq_off(nb), seq_len(nb), dst_t, id_t, lang_t, pos_t, ycodes, ynj, ydst, ypos, gen_rows, gen_y, q_first(nb), c_off(nb);
+  long M = 0, Y = 0, sumT = 0;
+  int max_len = 0;
+  double trim_attn_flops = 0;
+  for (int i = 0; i < nb; ++i) {
+    const int r = r0 + i, S = b->text_lens[r], Tp = b->prompt_lens[r];
+    seq_off[i] = (int)M; seq_len[i] = S + Tp + T[i];
+    q_first[i] = S + Tp; c_off[i] = (int)sumT;
+    trim_attn_flops += 4.0 * T[i] * (double)seq_len[i] * D_MODEL;
+    max_len = std::max(max_len, seq_len[i]);
+    for (int s = 0; s < S; ++s) {
+      dst_t.push_back((int)M + s);
+      id_t.push_back(b->text_ids[(long)r * b->text_stride + s]);
+      lang_t.push_back(b->text_lang[(long)r * b->text_stride + s]);
+      pos_t.push_back(s);
+    }
+    for (int t = 0; t < Tp + T[i]; ++t) {
+      if (t < Tp) {
+        for (int j = 0; j < N_Q; ++j) ycodes.push_back(b->prompt_codes[((long)r * b->prompt_stride + t) * N_Q + j]);
+        ynj.push_back(N_Q);
+      } else {
+        ycodes.push_back(R.code(i, t - Tp, 0));
+        for (int j = 1; j < N_Q; ++j) ycodes.push_back(0);
+        ynj.push_back(1);
+        gen_rows.push_back((int)M + S + t);
+        gen_y.push_back((int)Y + t);
+      }
+      ydst.push_back((int)M + S + t);
+      ypos.push_back(t);
+    }
+    M += seq_len[i]; Y += Tp + T[i]; sumT += T[i];
+  }
+  sumT_out = sumT;
+  logp.assign((size_t)(N_Q - 1) * sumT, 0.f);
+  rank.assign((size_t)(N_Q - 1) * sumT, 0);
+  if (sumT == 0) return VX_OK;
+  if (M > c->Mmax) FAIL(VX_EINVAL, "NAR rows %ld exceed arena %ld", M, c->Mmax);
+  std::vector<int> tg((size_t)(N_Q - 1) * sumT);           // [7][sumT]: the targets of stage st = the given codebook st + 1
+  for (int st = 0; st < N_Q - 1; ++st) {
+    long off = 0;
+    for (int i = 0; i < nb; ++i) {
+      for (int t = 0; t < T[i]; ++t) tg[(size_t)st * sumT + off + t] = R.code(i, t, st + 1);
+      off += T[i];
+    }
+  }
+  MetaBuilder mb(c);
+  const long o_off = mb.add(seq_off), o_len = mb.add(seq_len), o_dt = mb.add(dst_t), o_it = mb.add(id_t),
+             o_lt = mb.add(lang_t), o_pt = mb.add(pos_t), o_yc = mb.add(ycodes), o_nj = mb.add(ynj), o_yd = mb.add(ydst),
+             o_yp = mb.add(ypos), o_gr = mb.add(gen_rows), o_gy = mb.add(gen_y), o_qf = mb.add(q_first), o_co = mb.add(c_off),
+             o_tg = mb.add(tg);
+  if (int e = upload_meta(c)) return e;
+
+  launch_nar_yemb_init(c->fyemb, c->nar_tabs_dev, mb.dev(o_yc), mb.dev(o_nj), (int)Y, c->stream);
+  double attn_flops = 0;
+  for (int i = 0; i < nb; ++i) attn_flops += 4.0 * seq_len[i] * (double)seq_len[i] * D_MODEL;
+  const int nnorm = 2 * NL + 1;
+  for (int st = 0; st < N_Q - 1; ++st) {
+    launch_embed_rows(c->fx, mb.dev(o_dt), W(c, "nar_text_embedding.word_embeddings.weight"), mb.dev(o_it),
+                      W(c, "nar_language_embedding.word_embeddings.weight"), mb.dev(o_lt),
+                      W(c, "nar_text_position.alpha"), c->pe, mb.dev(o_pt), (int)dst_t.size(), c->stream);
+    launch_add_pe_scatter(c->fx, mb.dev(o_yd), c->fyemb, W(c, "nar_audio_position.alpha"), c->pe, mb.dev(o_yp), (int)Y,
+                          c->stream);
+    const float* ada = c->ada + (size_t)st * nnorm * 2 * D_MODEL;
+    const bool trim_h2 = c->gemm_mode == 0 && c->attn_x3 && c->attn_h2, trim_f32 = c->gemm_mode == 2 && !c->attn_x3;
+    const bool trim = c->nar_trim && (trim_h2 || trim_f32) && !c->cfg.debug_taps;
+    const Trim tr{sumT, mb.dev(o_qf), mb.dev(o_co), mb.dev(o_gr), trim_attn_flops};
+    for (int l = 0; l < NL; ++l)
+      if (int e = full_layer(c, c->nar[l], M, mb.dev(o_off), mb.dev(o_len), nullptr, nb, max_len,
+                             ada + (size_t)(2 * l) * 2 * D_MODEL, ada + (size_t)(2 * l + 1) * 2 * D_MODEL, nullptr, nullptr,
+                             nullptr, nullptr, attn_flops, (trim && l == NL - 1) ? &tr : nullptr))
+        return e;
+    const float* adaf = ada + (size_t)(2 * NL) * 2 * D_MODEL;
+    char nm[64];
+    snprintf(nm, sizeof nm, "nar_predict_layers.%d.weight", st);
+    if (trim && trim_f32) {
+      launch_layernorm(c->fqkv, D_MODEL, c->fxn, D_MODEL, (int)sumT, D_MODEL, LN_EPS, W(c, "nar_decoder.norm.norm.weight"),
+                       W(c, "nar_decoder.norm.norm.bias"), adaf, adaf + D_MODEL, c->stream);
+      proj(c, c->fxn, D_MODEL, W(c, nm), c->pred_w3[st], nullptr, nullptr, 0, c->flogits, AUDIO_VOCAB, sumT, AUDIO_VOCAB, D_MODEL, ACT_NONE);
+    } else if (trim) {
+      launch_layernorm(c->fxn, D_MODEL, nullptr, D_MODEL, (int)sumT, D_MODEL, LN_EPS, W(c, "nar_decoder.norm.norm.weight"),
+                       W(c, "nar_decoder.norm.norm.bias"), adaf, adaf + D_MODEL, c->stream, c->fa3, h2_plane(sumT, D_MODEL, H2_TILE_A),
+                       c->range_flag);
+      proj(c, nullptr, D_MODEL, W(c, nm), c->pred_w3[st], nullptr, nullptr, 0, c->flogits, AUDIO_VOCAB, sumT, AUDIO_VOCAB, D_MODEL,
+           ACT_NONE, nullptr, c->fa3);
+    } else {
+      launch_layernorm(c->fx, D_MODEL, c->fxn, D_MODEL, (int)M, D_MODEL, LN_EPS, W(c, "nar_decoder.norm.norm.weight"),
+                       W(c, "nar_decoder.norm.norm.bias"), adaf, adaf + D_MODEL, c->stream);
+      proj(c, c->fxn, D_MODEL, W(c, nm), c->pred_w3[st], nullptr, nullptr, 0, c->flogits, AUDIO_VOCAB, sumT, AUDIO_VOCAB, D_MODEL,
+           ACT_NONE, mb.dev(o_gr));
+    }
+    const int* given = mb.dev(o_tg) + (long)st * sumT;
+    launch_score_rows(c->flogits, AUDIO_VOCAB, (int)sumT, AUDIO_VOCAB, given, c->sc_logp + (long)st * sumT, c->sc_rank + (long)st * sumT,
+                      c->stream);
+    if (st == 0 && c->fb_nar_raises > 0 && range_guarded(c)) {      // as nar_generate_once: an early look behind stage 0
+      int early = 0;
+      D2H(&early, c->range_flag, sizeof(int));
+      SYNC();
+      if (early) {
+        HIPCHK(hipMemsetAsync(c->range_flag, 0, sizeof(int), c->stream));
+        return VX_RETRY_F32;
+      }
+    }
+    if (st < N_Q - 2) {
+      snprintf(nm, sizeof nm, "nar_audio_embeddings.%d.word_embeddings.weight", st + 1);
+      launch_embed_accum(c->fyemb, mb.dev(o_gy), W(c, nm), given, (int)sumT, c->stream);
+    }
+  }
+  HIPCHK(hipGetLastError());
+  D2H(logp.data(), c->sc_logp, logp.size() * sizeof(float));
+  D2H(rank.data(), c->sc_rank, rank.size() * sizeof(int));
+  int flag = 0;
+  if (range_guarded(c)) D2H(&flag, c->range_flag, sizeof(int));
+  SYNC();
+  if (flag) {
+    HIPCHK(hipMemsetAsync(c->range_flag, 0, sizeof(int), c->stream));
+    return VX_RETRY_F32;
+  }
+  return VX_OK;
+}
+
+// a pass behind the f16x2 range guard, as vx_ar_prefill / vx_nar run theirs: a raised flag re-runs it on the fp32 kernels, counts
+// in vx_last_fallbacks and towards sticky mode
+template <typename Once>
+static int score_guarded(vx_ctx* c, bool& sticky, int& age, int& raises, int& st_fb, Once once) {
+  int e = VX_RETRY_F32;
+  if (!fb_direct(c, sticky, age)) {
+    e = once();
+    if (e == VX_OK || e == VX_RETRY_F32) fb_outcome(c, e == VX_RETRY_F32, raises, sticky, age);
+    if (e != VX_RETRY_F32) return e;
+  }
+  ++st_fb; ++c->fb_total;
+  if ((e = ensure_f32_buffers(c))) return e;
+  F32Scope f32(c);
+  return once();
+}
+
+}  // namespace vxe
+
+extern "C" {
+
+int vx_score(vx_ctx* c, const vx_batch* b, const int64_t* codes, int32_t codes_stride, const int32_t* lens, int32_t parts,
+             float* logp, int32_t* rank, int32_t out_stride, float* eos_logp, int32_t* eos_rank) {
+  if (!c) return VX_EINVAL;
+  if (c->serve) FAIL(VX_EINVAL, "vx_score: a serving session is open on this context (vx_serve_close it first)");
+  HIPCHK(hipSetDevice(c->dev));
+  if (int e = check_batch(c, b, c->cfg.max_batch)) return e;
+  if (parts < 1 || parts > 3) FAIL(VX_EINVAL, "vx_score: parts must be VX_SCORE_AR, VX_SCORE_NAR or both (1 .. 3), got %d", parts);
+  const bool do_ar = parts & VX_SCORE_AR, do_nar = parts & VX_SCORE_NAR;
+  if (!codes || !lens) FAIL(VX_EINVAL, "vx_score: null codes or lens");
+  if (!logp || !rank) FAIL(VX_EINVAL, "vx_score: null logp or rank");
+  if (do_ar && (!eos_logp || !eos_rank)) FAIL(VX_EINVAL, "vx_score: VX_SCORE_AR needs eos_logp and eos_rank");
+  for (int i = 0; i < b->batch; ++i) {
+    const int T = lens[i];
+    if (T < 0 || T > c->cfg.max_new) FAIL(VX_EINVAL, "vx_score: row %d: lens %d outside 0 .. max_new (%d)", i, T, c->cfg.max_new);
+    if (T > codes_stride) FAIL(VX_EINVAL, "vx_score: row %d: codes_stride %d below lens %d", i, codes_stride, T);
+    if (T > out_stride) FAIL(VX_EINVAL, "vx_score: row %d: out_stride %d below lens %d", i, out_stride, T);
+  }
+  for (int i = 0; i < b->batch; ++i)
+    for (int t = 0; t < lens[i]; ++t)
+      for (int q = 0; q < (do_nar ? N_Q : 1); ++q) {
+        const int64_t v = codes[((long)i * codes_stride + t) * N_Q + q];
+        if (v < 0 || v >= AUDIO_VOCAB) FAIL(VX_EINVAL, "vx_score: codes: row %d frame %d codebook %d: %lld outside 0 .. 1023", i, t, q, (long long)v);
+      }
+  if (int e = score_buffers(c)) return e;
+  c->st_steps = 0; c->st_frames = 0; c->st_ar_ms = 0; c->st_nar_ms = 0; c->st_truncated = 0;
+  c->st_fb_prefill = c->st_fb_nar = 0;
+  hipEvent_t e0 = c->ev_t[0], e1 = c->ev_t[1], e2 = c->ev_t[2];
+  for (int r0 = 0; r0 < b->batch; r0 += c->mbr) {
+    ScoreRows R{b, codes, codes_stride, r0, std::min(c->mbr, b->batch - r0), {}};
+    R.T.assign(lens + r0, lens + r0 + R.nb);
+    std::vector<float> lp_a, lp_n;
+    std::vector<int> rk_a, rk_n;
+    long sumT = 0;
+    HIPCHK(hipEventRecord(e0, c->stream));
+    if (do_ar)
+      if (int e = score_guarded(c, c->sticky_prefill_f32, c->sticky_prefill_age, c->fb_prefill_raises, c->st_fb_prefill,
+                                [&] { return score_ar_once(c, R, lp_a, rk_a); }))
+        return e;
+    HIPCHK(hipEventRecord(e1, c->stream));
+    if (do_nar)
+      if (int e = score_guarded(c, c->sticky_nar_f32, c->sticky_nar_age, c->fb_nar_raises, c->st_fb_nar,
+                                [&] { return score_nar_once(c, R, lp_n, rk_n, sumT); }))
+        return e;
+    HIPCHK(hipEventRecord(e2, c->stream));
+    HIPCHK(hipEventSynchronize(e2));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1)); c->st_ar_ms += ms;
+    HIPCHK(hipEventElapsedTime(&ms, e1, e2)); c->st_nar_ms += ms;
+    long off_a = 0, off_n = 0;
+    for (int i = 0; i < R.nb; ++i) {
+      const int T = R.T[i];
+      c->st_frames += T;
+      for (int t = 0; t < T; ++t) {
+        const long o = ((long)(r0 + i) * out_stride + t) * N_Q;
+        if (do_ar) { logp[o] = lp_a[off_a + t]; rank[o] = rk_a[off_a + t]; }
+        if (do_nar)
+          for (int st = 0; st < N_Q - 1; ++st) {
+            logp[o + st + 1] = lp_n[(size_t)st * sumT + off_n + t];
+            rank[o + st + 1] = rk_n[(size_t)st * sumT + off_n + t];
+          }
+      }
+      if (do_ar) { eos_logp[r0 + i] = lp_a[off_a + T]; eos_rank[r0 + i] = rk_a[off_a + T]; }
+      off_a += T + 1; off_n += T;
+    }
+  }
+  return VX_OK;
+}
+
+// vx_dev_score_rows: ONE launch of score_rows_kernel on caller rows (private scratch, outputs pre-filled with the sentinels).
+int vx_dev_score_rows(vx_ctx* c, int32_t rows, int32_t ncols, int32_t ld, const float* logits, const int32_t* targets, float* logp,
+                      int32_t* rank, int32_t rows_out) {
+  if (!c) return VX_EINVAL;
+  if (c->serve) FAIL(VX_ESTATE, "vx_dev_score_rows: a serving session is open on this context (vx_serve_close it first)");
+  if (!logits || !targets || !logp || !rank) FAIL(VX_EINVAL, "vx_dev_score_rows: null logits, targets, logp or rank");
+  if (rows < 1 || rows > 4096) FAIL(VX_EINVAL, "vx_dev_score_rows: rows outside 1 .. 4096");
+  if (ncols != AUDIO_VOCAB && ncols != AR_LOGITS) FAIL(VX_EINVAL, "vx_dev_score_rows: ncols must be 1024 or 1025");
+  if (ld < ncols || ld > 8192 || ld % 4) FAIL(VX_EINVAL, "vx_dev_score_rows: ld outside ncols .. 8192 or ld %% 4 != 0");
+  if (rows_out < rows || rows_out > rows + 64) FAIL(VX_EINVAL, "vx_dev_score_rows: rows_out must be rows .. rows + 64");
+  for (int i = 0; i < rows; ++i)
+    if (targets[i] < 0 || targets[i] >= ncols) FAIL(VX_EINVAL, "vx_dev_score_rows: targets[%d] = %d outside 0 .. ncols - 1", i, targets[i]);
+  static_assert(AR_LOGITS <= SCORE_MAX_COLS, "score_rows_kernel holds a row in SCORE_GROUPS float4 per lane");
+  HIPCHK(hipSetDevice(c->dev));
+  float *dx = nullptr, *dlp = nullptr;
+  int *dt = nullptr, *drk = nullptr;
+  auto cleanup = [&]() { for (void* p : {(void*)dx, (void*)dlp, (void*)dt, (void*)drk}) if (p) (void)hipFree(p); };
+  hipError_t he;
+  // an error return drains the ring first: a queued xfer_d2h must not be delivered into host buffers that are gone by then
+#define TRY(x) if ((he = (x)) != hipSuccess) { (void)xfer_sync(c); cleanup(); c->err = std::string(#x) + ": " + hipGetErrorString(he); return VX_EHIP; }
+#define TRYX(x) do { if (int _e = (x)) { const std::string _m = c->err; (void)xfer_sync(c); c->err = _m; cleanup(); return _e; } } while (0)
+  TRY(hipMalloc((void**)&dx, (size_t)rows * ld * 4));
+  TRYX(xfer_h2d(c, dx, logits, (size_t)rows * ld * 4));
+  TRY(hipMalloc((void**)&dt, (size_t)rows * 4));
+  TRYX(xfer_h2d(c, dt, targets, (size_t)rows * 4));
+  TRY(hipMalloc((void**)&dlp, (size_t)rows_out * 4));
+  TRY(hipMalloc((void**)&drk, (size_t)rows_out * 4));
+  {
+    const std::vector<float> ff(rows_out, VX_DEV_SENTINEL_F);
+    const std::vector<int> fi(rows_out, VX_DEV_SENTINEL_I);
+    TRYX(xfer_h2d(c, dlp, ff.data(), ff.size() * 4));
+    TRYX(xfer_h2d(c, drk, fi.data(), fi.size() * 4));
+  }
+  launch_score_rows(dx, ld, rows, ncols, dt, dlp, drk, c->stream);
+  TRYX(xfer_d2h(c, logp, dlp, (size_t)rows_out * 4));
+  TRYX(xfer_d2h(c, rank, drk, (size_t)rows_out * 4));
+  TRYX(xfer_sync(c));
+  TRY(hipGetLastError());
+#undef TRY
+#undef TRYX
+  cleanup();
+  return VX_OK;
+}
+
+}  // extern "C"

@@ -282,6 +282,36 @@ class VALLE:
                                  length_penalty=length_penalty, return_worst=return_worst, continuous=continuous,
                                  on_row=on_row)
 
+    # ---- teacher-forced scoring (vx_score) ---------------------------------------------------------------------
+    def score(self, x, x_lens, y, enroll_x_lens, codes, prompt_language: str = None,
+              text_language: Union[str, List[str]] = None, parts: str = "both"):
+        """How likely the model finds `codes` (1, T, 8), as `inference` returns them, for the same x / y / languages: the quantity
+        `VALLE.forward` feeds to F.cross_entropy and `inference` selects its best_of beam on (models/vallex.py:572, :583-594).
+        Returns a dict: logp (T, 8) float32 and rank (T, 8) int32 -- column 0 from the AR stack given the earlier frames' first
+        codebook, column q from NAR stage q - 1 given codebooks 0 .. q-1; rank = number of strictly larger logits -- and eos_logp,
+        eos_rank: the stop decision behind the last frame.  sum(logp[:, 0]) + eos_logp is the beam's sum(logp).
+        parts: "ar", "nar" or "both"; what is left out is NaN / -1."""
+        xa, xl, ya, ca = _np(x), _np(x_lens), _np(y), _np(codes)
+        assert xa.ndim == 2, xa.shape                      # the checks of inference (models/vallex.py:488-493)
+        assert xl.ndim == 1, xl.shape
+        assert ya.ndim == 3, ya.shape
+        assert ya.shape[0] == 1, ya.shape
+        assert np.all(xl > 0)
+        assert ca.ndim == 3 and ca.shape[0] == 1 and ca.shape[2] == 8, ca.shape
+        S = int(xl.max())
+        row = dict(text=xa[0, :S], prompt=ya[0], enroll=int(_np(enroll_x_lens)), prompt_language=prompt_language,
+                   text_language=text_language)
+        return self.score_batch([row], [ca[0]], parts=parts)[0]
+
+    def score_batch(self, rows: Sequence[dict], codes_list: Sequence[np.ndarray], parts: str = "both") -> List[dict]:
+        """`score` for the row dicts of `inference_batch`: codes_list[i] (T_i, 8) is scored for rows[i], one call for all rows."""
+        if parts not in ("ar", "nar", "both"):
+            raise ValueError(f"parts must be 'ar', 'nar' or 'both', got {parts!r}")
+        if len(rows) != len(codes_list):
+            raise ValueError(f"{len(codes_list)} code arrays for {len(rows)} rows")
+        res = self.engine.score(self.make_batch(rows), [_np(c, np.int64).reshape(-1, 8) for c in codes_list], parts)
+        return [dict(logp=lp, rank=rk, eos_logp=el, eos_rank=er) for lp, rk, el, er in res]
+
     def serve(self, top_k: int = -100, temperature: float = 1.0, sync_every: int = 8, force_eos_at=None, max_steps: int = 32,
               post=None, **kw) -> "Server":
         """A threaded serving front end (include/vallex_hip.h vx_serve_*): `Server.submit(row, best_of=..., seed=...)` may be called
