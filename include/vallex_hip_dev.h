@@ -197,6 +197,66 @@ int vx_dev_layernorm(vx_ctx* ctx, int32_t rows, int32_t C, int32_t ldx, const fl
 int vx_dev_score_rows(vx_ctx* ctx, int32_t rows, int32_t ncols, int32_t ld, const float* logits, const int32_t* targets,
                       float* logp, int32_t* rank, int32_t rows_out);
 
+/* ONE launch of a glue kernel of the waveform half -- the Vocos head (csrc/vocos.hip) and the EnCodec decoder / encoder
+ * (csrc/encodec.hip) -- through its product launcher on caller operands.  Everything the launch reads or writes is private scratch of
+ * the call (the context's arenas are not touched); the only context state read is the window table of OVERLAP_ADD and what TABLES
+ * returns.  Every output is pre-filled with VX_DEV_SENTINEL_F (codes: VX_DEV_SENTINEL_L), and holds `extra` (0 .. 64) more rows or
+ * samples than the launch may write, so the caller sees both what was not written and that nothing was written behind the end.
+ * dims is an int32 array whose meaning depends on op; arguments an op does not name may be NULL.  "rows" are 1 .. 4096.
+ *
+ *   CODEBOOK_SUM   dims {rows, extra}; ia = codes [rows][8], each 0 .. 1023; a = codebook [8192][128]
+ *                  out = feat [rows + extra][128]: feat[r] = sum_q codebook[1024 q + codes[r][q]], fp32 adds in ascending q
+ *   IM2COL7        dims {rows, extra}; a = x [rows][128]; ia = row_t, ib = row_len [rows]: row r is frame row_t[r] of a packed sequence of
+ *                  row_len[r] frames (0 <= row_t < row_len, and the whole sequence lies inside the rows)
+ *                  out [rows + extra][896]: out[r][128 tap + c] = x[r + tap - 3][c] inside the row's own sequence, 0 outside
+ *   DWCONV7        dims {rows, extra, C}, C 384 | 512; a = x [rows][C], w [C][7], bias [C]; ia, ib as IM2COL7
+ *                  out [rows + extra][C]: out[r][c] = bias[c] + sum_tap w[c][tap] x[r + tap - 3][c]
+ *   ISTFT_PREP     dims {rows, extra}; a = o [rows][1408] (log-magnitudes 0 .. 640, phases 641 .. 1281, padding behind)
+ *                  out = reim [rows + extra][1312]: min(expf(o[k]), 100) * (cosf(p), sinf(p)) at k and 641 + k, columns 1282 .. 1311 zero
+ *   OVERLAP_ADD    dims {batch, extra, frames, audio_stride}; a = windowed frames [frames][1280]; ia = seq_off, ib = seq_len [batch]
+ *                  (batch 1 .. 32; every sequence inside the frames); the hann^2 table is THE CONTEXT'S (Vocos weights loaded)
+ *                  out = audio [batch x audio_stride + extra], or for audio_stride 0 (the product's: packed like the frames)
+ *                  [320 frames + extra]: sample s of sequence b = (sum_f frames[f][s + 480 - 320 f]) / (sum_f win2[s + 480 - 320 f])
+ *   IM2COL_SEQ     dims {batch, extra, frames, C, k, mode, elu, R}; a = x [frames R][C]; ia, ib as OVERLAP_ADD, in frames of R rows each
+ *                  C 4 .. 512 with C % 4 == 0; mode 0 (causal Conv1d, reflect into the zero-extended input) with k 1 .. 7, mode 1
+ *                  (ConvTranspose1d) with k = 2; elu 0 | 1; R 1 .. 320
+ *                  out [frames R + extra][k C]
+ *   LSTM_CELL      dims {batch, splitk, frames, t, extra}; splitk 1 | 2; a = part [2][32][2048] (slab 1 is not read for splitk 1);
+ *                  b = xg [frames][2048]; w = skip [frames][512] or NULL; ia, ib as OVERLAP_ADD
+ *                  out = cstate [32][512] and out2 = h [32][512], both in and out (h travels un-packed: the entry packs it into the
+ *                  packed-x image of the recurrence GEMM and un-packs it again, so the caller decides what untouched sequences hold);
+ *                  out3 = y [frames + extra][512].  Sequences with t >= seq_len[b] are finished: nothing of theirs is written.
+ *   FINAL_CONV     dims {batch, extra, frames, R, audio_stride}; a = x [frames R][32], w [32][7], bias [1]; ia, ib as IM2COL_SEQ;
+ *                  audio_stride >= R x the longest sequence;  out = audio [batch x audio_stride + extra]
+ *   ENC_FIRST_CONV dims {L, extra}, L 1 .. 65536; a = wav [L], w [32][7], bias [32];  out [L + extra][32]
+ *   ENC_PAD_ELU    dims {Lc, out_rows, C, r}, Lc 1 .. 65536, C as IM2COL_SEQ, r 1 .. 16; a = x [Lc][C]
+ *                  out [out_rows][C], rows <= out_rows <= rows + 64; geom = {rows, Le, n_out}: the geometry comes from the host rule the
+ *                  encoder itself uses (enc_pad_geom), so the rule is under test with the kernel
+ *   RVQ_SELECT     dims {rows, extra, q}, q 0 .. 7; a = resid [rows][128], b = scores [rows][1024], w = e2 [1024], bias = codebook [1024][128]
+ *                  out = resid - codebook[code] [rows + extra][128]; codes [rows + extra][8] int64: only column q is written.  The code is
+ *                  the lowest index of the largest -((|r|^2 - 2 score) + e2) and always lies in 0 .. 1023: a row without any comparable
+ *                  distance (all NaN) gets code 0.
+ *   TABLES         no launch: reads back the tables built at load time.  out = vc_dft [1280][1312], out2 = vc_win2 [1280] (Vocos weights),
+ *                  out3 = en_e2 [8][1024] (EnCodec encoder weights); a NULL table is skipped; VX_ESTATE if an asked one is not loaded.
+ * VX_EINVAL, nothing launched and no output touched, for anything outside the above (an unknown op, rows or sizes outside their range,
+ * a sequence that leaves its operand, a code outside 0 .. 1023, q outside 0 .. 7, an operand of more than 2^24 elements);
+ * VX_ESTATE while a serving session is open. */
+#define VX_DEV_SENTINEL_L (-1234567890123456789LL)
+#define VX_DEV_WAVE_CODEBOOK_SUM 0
+#define VX_DEV_WAVE_IM2COL7 1
+#define VX_DEV_WAVE_DWCONV7 2
+#define VX_DEV_WAVE_ISTFT_PREP 3
+#define VX_DEV_WAVE_OVERLAP_ADD 4
+#define VX_DEV_WAVE_IM2COL_SEQ 5
+#define VX_DEV_WAVE_LSTM_CELL 6
+#define VX_DEV_WAVE_FINAL_CONV 7
+#define VX_DEV_WAVE_ENC_FIRST_CONV 8
+#define VX_DEV_WAVE_ENC_PAD_ELU 9
+#define VX_DEV_WAVE_RVQ_SELECT 10
+#define VX_DEV_WAVE_TABLES 11
+int vx_dev_wave_op(vx_ctx* ctx, int32_t op, const int32_t* dims, const float* a, const float* b, const float* w, const float* bias,
+                   const int32_t* ia, const int32_t* ib, float* out, float* out2, float* out3, int64_t* codes, int32_t* geom);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,7 +164,8 @@ def _proto_matches(lib, name, want_args):
     args = [" ".join(a.split()) for a in proto.split(",")]
     assert args == want_args, args
     kinds = {"vx_ctx*": C.c_void_p, "int32_t": C.c_int32, "const int32_t*": C.POINTER(C.c_int32), "int32_t*": C.POINTER(C.c_int32),
-             "float*": C.POINTER(C.c_float), "const float*": C.POINTER(C.c_float), "uint16_t*": C.POINTER(C.c_uint16)}
+             "float*": C.POINTER(C.c_float), "const float*": C.POINTER(C.c_float), "uint16_t*": C.POINTER(C.c_uint16),
+             "int64_t*": C.POINTER(C.c_int64)}
     fn = getattr(lib, name)
     assert fn.restype is C.c_int and list(fn.argtypes) == [kinds[a.rsplit(" ", 1)[0]] for a in args]
     return hdr
@@ -192,3 +193,17 @@ def test_dev_layernorm_prototype_matches_binding(lib):
         "vx_ctx* ctx", "int32_t rows", "int32_t C", "int32_t ldx", "const float* x", "const float* g", "const float* b", "const float* ada_w",
         "const float* ada_b", "float* y", "int32_t rowsY", "uint16_t* planes", "int32_t* range_flag"])
     assert len(lib.vx_dev_layernorm.argtypes) == 13
+
+
+def test_dev_wave_op_prototype_matches_binding(lib):
+    """the header's prototype of vx_dev_wave_op and the ctypes signature agree argument by argument (14 of them); the op codes and the
+    64-bit sentinel of the code buffer are the binding's"""
+    from vallex_amd import _capi
+    hdr = _proto_matches(lib, "vx_dev_wave_op", [
+        "vx_ctx* ctx", "int32_t op", "const int32_t* dims", "const float* a", "const float* b", "const float* w", "const float* bias",
+        "const int32_t* ia", "const int32_t* ib", "float* out", "float* out2", "float* out3", "int64_t* codes", "int32_t* geom"])
+    assert len(lib.vx_dev_wave_op.argtypes) == 14
+    ops = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"#define VX_DEV_WAVE_(\w+) (\d+)", hdr)}
+    assert ops == _capi.DEV_WAVE_OPS and sorted(ops.values()) == list(range(12))
+    assert int(re.search(r"#define VX_DEV_SENTINEL_L \((-\d+)LL\)", hdr).group(1)) == _capi.DEV_SENTINEL_L
+    assert "vx_dev_wave_op" in _capi.DEV_SYMBOLS

@@ -167,6 +167,56 @@ def test_hip_encoder_matches_transformers_port():
 
 
 @pytest.mark.gpu
+def test_hip_encoder_matches_the_oracle_on_short_prompts():
+    """waveforms at which the host geometry of the strided convs enters its short-input branch (an input not longer than a conv's
+    pad is zero-extended before the reflect: 1, 2 samples; one frame and the lengths around it: 319, 320, 321; two frames and one
+    sample: 641), batched two at a time with unequal lengths, against the CPU oracle on every waveform alone.  Integer output: the
+    bar is equality wherever the float64 gap between the two nearest codewords allows it (_codes_agree_up_to_ties)."""
+    from tests._util import get_model
+    m = get_model(2, 0, 2.5, max_new=64, max_batch=4)
+    dec = encodec_state_dict(3)
+    sd = dict(dec)
+    sd.update(encodec_encoder_state_dict(4))
+    m.load_encodec_state_dict(sd)
+    orc = EncodecEncoderOracle(encodec_encoder_state_dict(4), dec)
+    rng = np.random.default_rng(9)
+    wavs = {L: (0.1 * rng.standard_normal(L)).astype(np.float32) for L in (1, 2, 100, 319, 320, 321, 641)}
+    ties = frames = 0
+    for pair in ((1, 641), (321, 2), (100, 320), (319, 1)):
+        got = m.engine.encodec_encode([wavs[L] for L in pair])
+        for L, codes in zip(pair, got):
+            emb = orc.embeddings(wavs[L][None])
+            gold = orc.quantize(emb)[0]
+            assert codes.shape == gold.shape == (-(-L // 320), 8), (L, codes.shape)
+            assert codes.min() >= 0 and codes.max() < 1024
+            ties += _codes_agree_up_to_ties(codes, gold, emb.numpy()[0], dec)
+            frames += len(gold)
+    print(f"short prompts: {frames - ties} of {frames} frames bit-identical on all 8 codebooks, {ties} decided by a near-tie")
+
+
+@pytest.mark.gpu
+def test_hip_encoder_keeps_codes_in_range_for_a_non_finite_sample():
+    """one NaN sample in a prompt waveform leaves frames without any comparable codeword distance: every code the encoder returns
+    must still be a table index (rvq_select_kernel: such a frame gets code 0), for the row with the NaN and for its batch neighbour"""
+    from tests._util import get_model
+    m = get_model(2, 0, 2.5, max_new=64, max_batch=4)
+    dec = encodec_state_dict(3)
+    sd = dict(dec)
+    sd.update(encodec_encoder_state_dict(4))
+    m.load_encodec_state_dict(sd)
+    rng = np.random.default_rng(10)
+    wav = (0.1 * rng.standard_normal(1000)).astype(np.float32)
+    clean = m.engine.encodec_encode([wav])[0]
+    wav_nan = wav.copy()
+    wav_nan[500] = np.nan
+    bad, other = m.engine.encodec_encode([wav_nan, wav])
+    assert bad.shape == other.shape == (4, 8)
+    assert bad.min() >= 0 and bad.max() < 1024, bad
+    np.testing.assert_array_equal(other, clean)                        # the neighbour of the batch is not affected
+    assert m.engine.encodec_decode([bad])[0].shape == (4 * 320,)       # and the codes can be gathered by
+
+
+@pytest.mark.gpu
 def test_make_prompt_writes_a_reference_format_preset(tmp_path):
     """prompt enrolment end to end (utils/prompt_making.py:57-84): waveform -> EnCodec encoder + RVQ on the GPU -> .npz in the
     reference's wire format -> usable as `prompt=` of generate_audio."""

@@ -84,7 +84,7 @@ SYMBOLS = ["vx_abi_version", "vx_create", "vx_destroy", "vx_last_error", "vx_syn
 # ... and include/vallex_hip_dev.h: measurement / kernel development, never called by the mirrors of the reference API
 DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kernel", "vx_bench_gemm", "vx_bench_attn",
                "vx_bench_gemm_clock", "vx_bench_gemm_epilogue", "vx_dev_sample", "vx_dev_attn", "vx_dev_sample_filtered",
-               "vx_dev_dec_attn", "vx_dev_dec_op", "vx_dev_gemm", "vx_dev_layernorm", "vx_dev_score_rows"]
+               "vx_dev_dec_attn", "vx_dev_dec_op", "vx_dev_gemm", "vx_dev_layernorm", "vx_dev_score_rows", "vx_dev_wave_op"]
 # sentinels the correctness entries pre-fill their outputs with (include/vallex_hip_dev.h)
 DEV_SENTINEL_I = -123456789
 DEV_SENTINEL_F = np.float32(-1.0e30)
@@ -99,6 +99,10 @@ DEV_GEMM_WSRC = {"ar.in_proj": 1, "ar.out_proj": 2, "ar.linear1": 3, "ar.linear2
                  "nar.in_proj": 5, "nar.out_proj": 6, "nar.linear1": 7, "nar.linear2": 8}
 DEV_GEMM_OUT_PLANES, DEV_GEMM_INPLACE = 1, 2
 DEV_SENTINEL_H = 0xFBFF
+# ops of vx_dev_wave_op (VX_DEV_WAVE_* of include/vallex_hip_dev.h) and the 64-bit sentinel of its code buffer
+DEV_WAVE_OPS = {"codebook_sum": 0, "im2col7": 1, "dwconv7": 2, "istft_prep": 3, "overlap_add": 4, "im2col_seq": 5, "lstm_cell": 6,
+                "final_conv": 7, "enc_first_conv": 8, "enc_pad_elu": 9, "rvq_select": 10, "tables": 11}
+DEV_SENTINEL_L = -1234567890123456789
 SCORE_AR, SCORE_NAR = 1, 2             # VX_SCORE_* of include/vallex_hip.h (parts of vx_score)
 SCORE_PARTS = {"ar": SCORE_AR, "nar": SCORE_NAR, "both": SCORE_AR | SCORE_NAR}
 DEV_SAMPLE_CFG = ("kernel", "splitk", "top_k", "force_eos_at", "active", "n_gen", "cur_pos", "ctx_len", "text_len", "gen_stride")
@@ -195,6 +199,8 @@ def load_library() -> C.CDLL:
                              P(C.c_float), P(C.c_int32)]
     lib.vx_dev_score_rows.argtypes = [ctx, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), P(C.c_int32), P(C.c_float), P(C.c_int32),
                                       C.c_int32]
+    lib.vx_dev_wave_op.argtypes = [ctx, C.c_int32, P(C.c_int32), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_int32),
+                                   P(C.c_int32), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_int64), P(C.c_int32)]
     lib.vx_last_stats.argtypes = [ctx, P(C.c_int64), P(C.c_int64), P(C.c_double), P(C.c_double)]
     lib.vx_last_truncated.argtypes = [ctx, P(C.c_int32)]
     lib.vx_last_fallbacks.argtypes = [ctx, P(C.c_int32), P(C.c_int32), P(C.c_int64)]
@@ -781,6 +787,27 @@ class Engine:
         self._chk(self.lib.vx_dev_score_rows(self.ctx, rows, int(ncols), ld, _ptr(x, C.c_float), _ptr(t, C.c_int32),
                                              _ptr(logp, C.c_float), _ptr(rank, C.c_int32), len(logp)))
         return logp, rank
+
+    def dev_wave_op(self, op, dims, a=None, b=None, w=None, bias=None, ia=None, ib=None, out=None, out2=None, out3=None, codes=None):
+        """vx_dev_wave_op: one launch of a Vocos / EnCodec glue kernel (op: a key of DEV_WAVE_OPS or its code) on caller operands; the
+        meaning of dims and of the operands per op is documented in include/vallex_hip_dev.h.  a, b, w, bias are float32 inputs, ia, ib
+        int32 inputs.  out, out2, out3 (float32) and codes (int64) are written IN PLACE and must be C-contiguous arrays of the size the
+        header states (the entry fills them with the sentinels first; cstate and h of lstm_cell are read, too).  Returns geom (3,)
+        int32 (enc_pad_elu: rows, Le, n_out)."""
+        f32 = lambda v: None if v is None else np.ascontiguousarray(v, np.float32)
+        i32 = lambda v: None if v is None else np.ascontiguousarray(v, np.int32)
+        a, b, w, bias, ia, ib = f32(a), f32(b), f32(w), f32(bias), i32(ia), i32(ib)
+        dims = np.ascontiguousarray(list(dims) + [0] * 8, np.int32)
+        for v, dt in ((out, np.float32), (out2, np.float32), (out3, np.float32), (codes, np.int64)):
+            if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.flags.c_contiguous and v.flags.writeable):
+                raise ValueError("out, out2, out3 are writeable C-contiguous float32 arrays, codes int64")
+        geom = np.zeros(3, np.int32)
+        pf = lambda v: None if v is None else _ptr(v, C.c_float)
+        pi = lambda v: None if v is None else _ptr(v, C.c_int32)
+        self._chk(self.lib.vx_dev_wave_op(self.ctx, int(DEV_WAVE_OPS.get(op, op)), _ptr(dims, C.c_int32), pf(a), pf(b), pf(w), pf(bias),
+                                          pi(ia), pi(ib), pf(out), pf(out2), pf(out3),
+                                          None if codes is None else _ptr(codes, C.c_int64), _ptr(geom, C.c_int32)))
+        return geom
 
     def last_fallbacks(self):
         """phases of the last call that left the fp16 range of the f16x2 kernels and were re-run in fp32 (+ lifetime count)"""

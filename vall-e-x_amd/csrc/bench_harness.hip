@@ -994,21 +994,12 @@ int vx_dev_dec_op(vx_ctx* c, int32_t op, int32_t variant, int32_t layer, int32_t
   hipError_t he;
 #define TRY(x) if ((he = (x)) != hipSuccess) { cleanup(); c->err = std::string(#x) + ": " + hipGetErrorString(he); return VX_EHIP; }
 #define TRYX(x) do { if (int _e = (x)) { cleanup(); return _e; } } while (0)
-  // the packed-x image (decode.hip): float4 column c4 of row b at ((c4 >> 1) * 64 + b + 32 * (c4 & 1)) * 4, for any K
-  auto pack_image = [](float* img, const float* rows, int kk) {
-    for (int b = 0; b < MB; ++b)
-      for (int c4 = 0; c4 < kk / 4; ++c4) memcpy(img + (((size_t)(c4 >> 1) * 64) + b + 32 * (c4 & 1)) * 4, rows + (size_t)b * kk + 4 * c4, 16);
-  };
-  auto unpack_image = [](float* rows, const float* img, int kk) {
-    for (int b = 0; b < MB; ++b)
-      for (int c4 = 0; c4 < kk / 4; ++c4) memcpy(rows + (size_t)b * kk + 4 * c4, img + (((size_t)(c4 >> 1) * 64) + b + 32 * (c4 & 1)) * 4, 16);
-  };
   TRY(hipMalloc((void**)&df, fend * 4));
   TRY(hipMalloc((void**)&di, (size_t)2 * MB * 4));
   {
     std::vector<float> hf(fend, VX_DEV_SENTINEL_F);
     std::vector<int> hi(2 * MB, 0);
-    if (reads_x) pack_image(&hf[f_x], x, K);
+    if (reads_x) dev_pack_image(&hf[f_x], x, K);
     if (sk_in) memcpy(&hf[f_sl], slabs, (size_t)sk_in * MB * d * 4);
     if (reads_resid) memcpy(&hf[f_dh], resid, (size_t)nrows * d * 4);
     if (op == VX_DEV_OP_EMBED) for (int r = 0; r < nrows; ++r) { hi[r] = tok[r]; hi[MB + r] = pos[r]; }
@@ -1067,8 +1058,8 @@ int vx_dev_dec_op(vx_ctx* c, int32_t op, int32_t variant, int32_t layer, int32_t
   if (reads_resid) TRYX(xfer_d2h(c, resid, dh, (size_t)nrows * d * 4));      // what the residual buffer holds behind the launch
   TRYX(xfer_sync(c));
   TRY(hipGetLastError());
-  if (image_out) unpack_image(out, o_out.data(), D_FF);
-  if (writes_xp) unpack_image(xp, o_xp.data(), d);
+  if (image_out) dev_unpack_image(out, o_out.data(), D_FF);
+  if (writes_xp) dev_unpack_image(xp, o_xp.data(), d);
 #undef TRY
 #undef TRYX
   cleanup();

@@ -208,7 +208,9 @@ void launch_enc_pad_elu(const float* x, long L, long Le, int C, int left, long r
 
 // One residual-VQ step (EncodecEuclideanCodebook.quantize + EncodecResidualVectorQuantizer.encode's residual update):
 //   code = argmax_c -( |r|^2 - 2 s_c + |e_c|^2 ),  s = r . E^T from the GEMM;  r -= E[code].
-// One workgroup per frame; ties -> lowest index.
+// One workgroup per frame; ties -> lowest index.  The code is always a table index 0 .. 1023: a frame without any comparable
+// distance (all NaN or -Inf: one non-finite sample of the waveform is enough) gets code 0, as argmax_rows_kernel (rows.hip)
+// does -- the code is gathered by here (codebook[code]) and by every embedding table downstream.
 __global__ __launch_bounds__(256) void rvq_select_kernel(float* __restrict__ resid, const float* __restrict__ scores,
                                                          const float* __restrict__ e2,
                                                          const float* __restrict__ codebook,
@@ -247,7 +249,7 @@ __global__ __launch_bounds__(256) void rvq_select_kernel(float* __restrict__ res
     }
     __syncthreads();
   }
-  const int code = sh_i[0];
+  const int code = sh_i[0] < NC ? sh_i[0] : 0;                     // NC: no thread saw a comparable distance
   if (tid == 0) codes[row * 8 + q] = code;
   if (tid < D) r[tid] -= codebook[(long)code * D + tid];
 }

@@ -2,7 +2,8 @@
 // weights.hip: ingest of the reference state-dict; vocoders.hip: Vocos head, EnCodec decoder / encoder drivers;
 // beams.hip: the best_of fan-out; admit.hip / serve.hip: admission kernels of the continuous schedule / the serving session;
 // serve_sample.hip: the serving session's per-row sampler;
-// bench_harness.hip: the measurement entries of include/vallex_hip_dev.h; score.hip: teacher-forced scoring, vx_score).
+// bench_harness.hip: the measurement entries of include/vallex_hip_dev.h; score.hip: teacher-forced scoring, vx_score;
+// dev_wave.hip: vx_dev_wave_op, the correctness entry of the Vocos / EnCodec glue kernels).
 // Not part of the public C ABI.
 #pragma once
 
@@ -228,6 +229,30 @@ int xfer_sync(vx_ctx* c);                                                      /
 #define H2D(dst, src, bytes) do { if (int _e = xfer_h2d(c, (dst), (src), (bytes))) return _e; } while (0)
 #define D2H(dst, src, bytes) do { if (int _e = xfer_d2h(c, (dst), (src), (bytes))) return _e; } while (0)
 #define SYNC() do { if (int _e = xfer_sync(c)) return _e; } while (0)
+
+// geometry of the padded copy launch_enc_pad_elu writes in front of a causal Conv1d(k = 2r, stride r) on Lc input rows (EncodecConv1d):
+// n_out = ceil(Lc / r) output frames; rows = (n_out + 1) r rows of the copy (left pad r + Lc + the right pad that completes the last
+// frame); Le = the length the input is zero-extended to before reflecting (Le > Lc only for inputs not longer than the larger pad,
+// _pad1d).  One rule for the encoder (vocoders.hip) and the correctness entry (dev_wave.hip).
+struct EncPadGeom { long n_out, rows, Le; };
+inline EncPadGeom enc_pad_geom(long Lc, int r) {
+  const long n_out = (Lc + r - 1) / r;
+  const long rows = (n_out + 1) * r, extra = n_out * r - Lc;       // extra: the right pad
+  const long max_pad = std::max<long>(r, extra);
+  const long Le = Lc <= max_pad ? Lc + (max_pad - Lc + 1) : Lc;    // EncodecConv1d._pad1d: short inputs are zero-extended
+  return {n_out, rows, Le};
+}
+
+// host side of the packed-x image (decode.hip) for the correctness entries: float4 column c4 of row b at
+// ((c4 >> 1) * 64 + b + 32 * (c4 & 1)) * 4, for any K; rows [MB][kk] row-major
+inline void dev_pack_image(float* img, const float* rows, int kk) {
+  for (int b = 0; b < MB; ++b)
+    for (int c4 = 0; c4 < kk / 4; ++c4) memcpy(img + (((size_t)(c4 >> 1) * 64) + b + 32 * (c4 & 1)) * 4, rows + (size_t)b * kk + 4 * c4, 16);
+}
+inline void dev_unpack_image(float* rows, const float* img, int kk) {
+  for (int b = 0; b < MB; ++b)
+    for (int c4 = 0; c4 < kk / 4; ++c4) memcpy(rows + (size_t)b * kk + 4 * c4, img + (((size_t)(c4 >> 1) * 64) + b + 32 * (c4 & 1)) * 4, 16);
+}
 
 template <typename T>
 int dev_alloc(vx_ctx* c, T** p, size_t count, bool zero = true) {

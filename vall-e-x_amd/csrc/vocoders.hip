@@ -244,10 +244,8 @@ int vx_encodec_encode(vx_ctx* c, const float* wav, int64_t wav_stride, const int
         gemm(c, c->ec_h, ldh, c->en_w3[s4], ldh, W(c, pR + ".block3.bias"), c->ec_sc, C, nullptr, c->ec_out, C, Lc, C, ldh, ACT_NONE);
         // ELU + Conv1d(C, 2C, k = 2r, stride r), causal: left pad r, right pad to a whole frame (both reflect); the window
         // of output frame t' is rows [t' r, (t' + 2) r) of the padded copy -> a GEMM with overlapping A rows (lda = r C)
-        const long rows = (n_out + 1) * r, extra = n_out * r - Lc;
-        const long max_pad = std::max<long>(r, extra);
-        const long Le = Lc <= max_pad ? Lc + (max_pad - Lc + 1) : Lc;         // EncodecConv1d._pad1d: short inputs are zero-extended
-        launch_enc_pad_elu(c->ec_out, Lc, Le, C, r, rows, c->ec_col, st);
+        const EncPadGeom pg = enc_pad_geom(Lc, r);                            // pg.n_out == n_out
+        launch_enc_pad_elu(c->ec_out, Lc, pg.Le, C, r, pg.rows, c->ec_col, st);
         float* dst = s4 < 3 ? c->ec_a : c->ec_x0 + (size_t)seq_off[i] * 512;
         gemm(c, c->ec_col, r * C, c->en_wd[s4], 2 * r * C, W(c, pD + ".bias"), nullptr, 0, nullptr, dst, 2 * C, n_out, 2 * C, 2 * r * C,
              ACT_NONE);
