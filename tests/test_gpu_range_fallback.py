@@ -210,3 +210,104 @@ def test_a_clean_phase_resets_the_consecutive_count():
         assert_codes(f"in-range call {call}", _run(m2, c, [row], u)[0], golden(base))
     assert m2.engine.fallback_state() == dict(prefill=False, nar=False, times_engaged=0)
     assert m2.engine.last_fallbacks()["lifetime"] == 0
+
+
+# ---- the guard of the three schedulers and of the vx_ar_prefill seam, counted exactly -----------------------------------------------
+# The AR-only rescaled model (the one of test_a_clean_phase_resets_the_consecutive_count): every prefill leaves the fp16 range, every
+# NAR phase is clean, so the counters below do not depend on how many NAR groups a schedule forms.  FB_STICKY_AFTER = 2: the second
+# consecutive raise of a kind engages sticky mode; FB_STICKY_PROBE_EVERY = 32: none of these tests reaches a probe.  A phase that runs
+# on the fp32 kernels directly still counts in last_fallbacks() and in the lifetime total.
+
+def _ar_only_model(max_batch):
+    """a FRESH engine (its own context: counters at zero) on the AR-only rescaled weights of nl2_range_ffn; (model, case, base name)"""
+    from oracle import synth
+    from tests import _util
+    base, kind = RANGE_CASES["nl2_range_ffn"]
+    c = ALL["nl2_range_ffn"]
+    sd = synth.vallex_state_dict(c["num_layers"], c["seed"], c["eos_gain"])
+    m = _util.VALLE(1024, 16, c["num_layers"], norm_first=True, add_prenet=False, prefix_mode=1, share_embedding=True,
+                    nar_scale_factor=1.0, prepend_bos=True, num_quantizers=8, engine_max_new=320, engine_max_prompt=400,
+                    engine_max_text=256, engine_max_batch=max_batch)
+    m.to("cuda:0").load_state_dict(synth.out_of_range_state_dict(sd, c["num_layers"], kind, stacks=("ar",)), strict=True)
+    return m, c, base
+
+
+def test_continuous_guard_counts_probe_and_direct_rounds():
+    """vx_infer_continuous, max_batch 4, four short fillers + the golden row: the first fill and the one admission round (exactly one
+    row waits).  Call 1: both rounds raise and are re-run (2 phases; the second raise engages sticky mode).  Call 2: both rounds go to
+    the fp32 kernels directly and are still counted."""
+    from oracle import synth
+    from oracle.vallex_oracle import VallexOracle
+    from tests.test_gpu_continuous import _assert_golden, _fillers, _oracle_row
+    m, c, base = _ar_only_model(4)
+    row, us = inputs_row(c)
+    rows = _fillers(4, 67_000) + [row]
+    cols = [synth.uniforms(4096, 1, 68_000 + i)[:, 0] for i in range(len(rows))]
+    if us is not None:
+        cols[4] = us
+    orc = VallexOracle(synth.vallex_state_dict(c["num_layers"], c["seed"], c["eos_gain"]), c["num_layers"])
+    refs = [_oracle_row(rows[i], cols[i], top_k=c["top_k"], force_eos_at=c["force_eos_at"], orc=orc) for i in range(4)]
+    e = m.engine
+    life0, eng0 = e.last_fallbacks()["lifetime"], e.fallback_state()["times_engaged"]
+    for call in range(2):
+        outs = m.inference_batch(rows, top_k=c["top_k"], uniforms=np.stack(cols, axis=1), force_eos_at=c["force_eos_at"], continuous=True)
+        fb, st = e.last_fallbacks(), e.fallback_state()
+        print(f"continuous call {call}: {fb} {st}")
+        assert (fb["prefill"], fb["nar"]) == (2, 0), (call, fb)
+        assert fb["lifetime"] == life0 + 2 * (call + 1), (call, fb)
+        assert (st["prefill"], st["nar"], st["times_engaged"]) == (True, False, eng0 + 1), (call, st)
+        _assert_golden(f"call {call}: golden row admitted as row 4", outs[4], golden(base))
+        for i in range(4):
+            np.testing.assert_array_equal(outs[i], refs[i], err_msg=f"call {call}: filler {i}")
+
+
+def test_serve_guard_counts_probe_and_direct_rounds():
+    """serving session, max_batch 8: wave 1 = four fillers, wave 2 (after 2 steps) = the golden row + the same row with best_of 3, which
+    need the four free rows: one admission round per wave.  Session 1: both rounds raise and are re-run (the second engages sticky
+    mode); session 2 on the same context: both rounds direct, still counted, no new engagement."""
+    from oracle import synth
+    from oracle.vallex_oracle import VallexOracle
+    from tests._util import case_row
+    from tests.test_gpu_serve import _alone, _assert_golden, _oracle_req, _serve, _short
+    m, c, base = _ar_only_model(8)
+    _, row, gus = case_row(base)
+    fill = _short(4, 93_000)
+    fill_reqs = [dict(uniforms=synth.uniforms(128, 1, 93_500 + i)) for i in range(4)]
+    us3 = np.concatenate([gus[:, None], synth.uniforms(4096, 2, 93_900)], axis=1)
+    reqs = [dict(uniforms=gus), dict(best_of=3, uniforms=us3)]
+    e = m.engine
+    life0, eng0 = e.last_fallbacks()["lifetime"], e.fallback_state()["times_engaged"]
+    sessions = []
+    for k in range(2):
+        with e.serve(top_k=c["top_k"], force_eos_at=c["force_eos_at"]) as sess:
+            got, ids, _ = _serve(sess, m, [(fill, fill_reqs), ([row, row], reqs)], max_steps=2)
+        fb, st = e.last_fallbacks(), e.fallback_state()
+        print(f"serve session {k}: rounds counted {m.serve_fallbacks} {fb} {st}")
+        assert m.serve_fallbacks == 2, (k, m.serve_fallbacks)
+        assert fb["lifetime"] == life0 + 2 * (k + 1), (k, fb)
+        assert (st["prefill"], st["nar"], st["times_engaged"]) == (True, False, eng0 + 1), (k, st)
+        sessions.append((got, ids))
+    alone3 = _alone(m, row, reqs[1], c["top_k"], c["force_eos_at"])[0]
+    orc = VallexOracle(synth.vallex_state_dict(c["num_layers"], c["seed"], c["eos_gain"]), c["num_layers"])
+    refs = [_oracle_req(orc, fill[i], fill_reqs[i], c["top_k"], c["force_eos_at"]) for i in range(4)]
+    for k, (got, ids) in enumerate(sessions):
+        _assert_golden(f"session {k}: golden row admitted mid-session", got[ids[1][0]], golden(base)["codes"][0])
+        np.testing.assert_array_equal(got[ids[1][1]], alone3, err_msg=f"session {k}: best_of 3")
+        for i in range(4):
+            np.testing.assert_array_equal(got[ids[0][i]], refs[i], err_msg=f"session {k}: filler {i}")
+
+
+def test_ar_prefill_seam_guard_counts_probe_and_direct():
+    """vx_ar_prefill (no sync of its own to ride on: it reads the flag synchronously): one fp32 phase per call, re-run after a probe in
+    calls 1 and 2, direct in call 3; sticky from the second call on"""
+    m, c, base = _ar_only_model(4)
+    row, _ = inputs_row(c)
+    e = m.engine
+    life0, eng0 = e.last_fallbacks()["lifetime"], e.fallback_state()["times_engaged"]
+    for call in range(3):
+        e.ar_prefill(m.make_batch([row]))
+        fb, st = e.last_fallbacks(), e.fallback_state()
+        print(f"seam call {call}: {fb} {st}")
+        assert (fb["prefill"], fb["nar"], fb["lifetime"]) == (1, 0, life0 + call + 1), (call, fb)
+        assert (st["prefill"], st["nar"]) == (call >= 1, False), (call, st)
+        assert st["times_engaged"] == eng0 + (call >= 1), (call, st)

@@ -1,4 +1,4 @@
-// Continuous schedule (vx_infer_continuous, engine.hip): the kernels that admit waiting caller rows into the decode rows that
+// Continuous schedule (vx_infer_continuous, schedule.hip admit_common / admit_rows): the kernels that admit waiting caller rows into the decode rows that
 // finished rows left free, between two decode steps of a running batch.  Everything else an admission runs is the existing code:
 // the full-sequence prefill (engine.hip prefill_layers, K / V into the free rows' arena slots), the final norm + predict layer
 // (dec_reduce_ln_pack + skinny GEMM, here into scratch buffers the step does not carry: dh2 / xp_att) and the unchanged sampler,

@@ -1,4 +1,4 @@
-// best_of fan-out (vx_infer with best_of = N > 1): every caller row of a micro-batch is prefilled ONCE and decoded as N beams
+// best_of fan-out (vx_infer with best_of = N > 1, schedule.hip; the beam groups of a serving session): every caller row of a micro-batch is prefilled ONCE and decoded as N beams
 // (the reference repeats the prompt N times and prefills N times, models/vallex.py:525-527).  One launch per prefill copies
 //   - the prefilled K / V of row i (its seq_len[i] cached rows of every layer and head) from the arena slot of decode row i*N to the
 //     arena slots of decode rows i*N + 1 .. i*N + N-1 (the KV arena is indexed by launch slot, engine.hip ar_prefill), and

@@ -1,10 +1,9 @@
-// Engine: context, weight ingest, arenas, launch sequences and the C ABI (include/vallex_hip.h).
+// Engine: context, pinned transfer ring, launch sequences of the three phases (AR prefill, one cached decode step, the 7 NAR stages)
+// and their C ABI seams (include/vallex_hip.h: vx_ar_prefill / vx_ar_logits / vx_ar_step / vx_nar), the stats getters.
 // Host-side counterpart of VALLE.inference (models/vallex.py:458-686) + the Vocos call of
-// utils/generation.py:148-150; every hot op is a hand-written gfx950 kernel from the sibling .hip files.
+// utils/generation.py:148-150; every hot op is a hand-written gfx950 kernel from the sibling .hip files.  The schedulers that
+// sequence the phases (vx_infer, vx_infer_continuous, the serving session) are in schedule.hip.
 #include "engine_ctx.h"
-
-#include <deque>
-#include <memory>
 
 namespace {
 // the message of a failed vx_create (no context to hang it on): per thread, contexts are created from several host threads
@@ -156,13 +155,7 @@ void proj(vx_ctx* c, const float* A, int lda, const float* Wf, const unsigned sh
   else launch_gemm_bf16x3(g, c->stream);
 }
 
-// Row trimming of the LAST decoder layer of a NAR stage (f16x2 mode, and since round 6 the reference-arithmetic fp32 mode): only the generated frames of every sequence reach a predict
-// layer (models/vallex.py:672-679), so behind the K / V projection -- which attention needs for ALL rows -- the layer only has to
-// produce those rows: attention queries, out_proj, norm2 and the FFN run on the Mc = sum T_b compacted rows.  Every op of the
-// block treats rows independently, so each kept row goes through exactly the arithmetic it would see untrimmed: same ids, same
-// logits, bit for bit.  The compacted residual stream lives in c->fxn (f16x2 mode: unused otherwise) or in the QKV buffer (fp32 mode).
-// (struct Trim: engine_ctx.h -- the teacher-forced scoring passes of score.hip trim the same way)
-
+// (row trimming of a stack's last layer, `tr`: struct Trim, engine_ctx.h)
 // one pre-norm block on packed rows (modules/transformer.py:296-302 / :337-347) -- shared by AR prefill and NAR
 int full_layer(vx_ctx* c, const LayerW& L, long M, const int* seq_off, const int* seq_len, const int* prefix_len,
                int batch, int max_len, const float* ada1, const float* ada2, float* kcl, float* vcl,
@@ -272,8 +265,7 @@ int take_range_flag(vx_ctx* c, bool* raised) {
 int check_batch(vx_ctx* c, const vx_batch* b, int max_rows) {
   if (!c->finalized) FAIL(VX_ESTATE, "weights not finalized");
   if (!b) FAIL(VX_EINVAL, "null batch");
-  if (b->struct_size != sizeof(vx_batch))
-    FAIL(VX_EINVAL, "vx_batch.struct_size is %u, this library expects %zu (ABI version %d)", b->struct_size, sizeof(vx_batch), VX_ABI_VERSION);
+  CHECK_STRUCT(*b, vx_batch);
   if (b->batch <= 0 || b->batch > max_rows) FAIL(VX_EINVAL, "batch must be in 1..%d", max_rows);
   for (int i = 0; i < b->batch; ++i) {
     const int S = b->text_lens[i], Tp = b->prompt_lens[i];
@@ -294,9 +286,20 @@ int check_batch(vx_ctx* c, const vx_batch* b, int max_rows) {
   return VX_OK;
 }
 
+// text row s of caller row r at packed row M + s: (destination, token id, language id, position) of launch_embed_rows
+static void text_rows(const vx_batch* b, int r, int M, std::vector<int>& dst, std::vector<int>& id, std::vector<int>& lang,
+                      std::vector<int>& pos) {
+  for (int s = 0; s < b->text_lens[r]; ++s) {
+    dst.push_back(M + s);
+    id.push_back(b->text_ids[(long)r * b->text_stride + s]);
+    lang.push_back(b->text_lang[(long)r * b->text_stride + s]);
+    pos.push_back(s);
+  }
+}
+
 // ---- AR prefill (models/vallex.py:497-562, first ar_decoder.infer call) ------------------------------------
 // The full-sequence part of a prefill (tables, embeddings, the prefix-LM layers that fill the KV arena) is shared by the first fill
-// of a decode batch (ar_prefill) and by the admission of waiting rows into a running one (continuous schedule, admit_rows below).
+// of a decode batch (ar_prefill) and by the admission of waiting rows into a running one (admit_common of schedule.hip: the continuous schedule and the serving session).
 // prefill_tables builds the sequence tables of caller rows r0 .. r0+nb-1 into `mb`; row_b (the arena slot of every packed row) is
 // left as PREFILL row indices: the caller maps them to slots and adds them (o_rb) before upload_meta.
 int prefill_tables(vx_ctx* c, const vx_batch* b, int r0, int nb, PrefillPlan& p, MetaBuilder& mb) {
@@ -310,12 +313,7 @@ int prefill_tables(vx_ctx* c, const vx_batch* b, int r0, int nb, PrefillPlan& p,
     const int r = r0 + i, S = b->text_lens[r], Tp = b->prompt_lens[r];
     p.seq_off[i] = (int)M; p.seq_len[i] = S + 1 + Tp; p.S_[i] = S;
     max_len = std::max(max_len, p.seq_len[i]);
-    for (int s = 0; s < S; ++s) {
-      dst_t.push_back((int)M + s);
-      id_t.push_back(b->text_ids[(long)r * b->text_stride + s]);
-      lang_t.push_back(b->text_lang[(long)r * b->text_stride + s]);
-      pos_t.push_back(s);
-    }
+    text_rows(b, r, (int)M, dst_t, id_t, lang_t, pos_t);
     for (int t = 0; t <= Tp; ++t) {                       // BOS then prompt codebook 0 (models/vallex.py:515-517)
       dst_a.push_back((int)M + S + t);
       id_a.push_back(t == 0 ? BOS_ID : b->prompt_codes[((long)r * b->prompt_stride + (t - 1)) * N_Q]);
@@ -346,15 +344,20 @@ int prefill_tables(vx_ctx* c, const vx_batch* b, int r0, int nb, PrefillPlan& p,
   return VX_OK;
 }
 
-// embeddings + the prefix-LM layers (K / V into the arena slots of p.row_b); the last row of every sequence is then row
-// p.hrow(i) of prefill_hsrc(c, p)
-int prefill_layers(vx_ctx* c, const PrefillPlan& p, const MetaBuilder& mb) {
-  const int NL = c->NL, nb = p.nb;
+// text and BOS ++ audio embeddings of the packed rows of a prefill into fx (shared with the AR scoring pass, score.hip)
+void prefill_embed(vx_ctx* c, const PrefillPlan& p, const MetaBuilder& mb) {
   launch_embed_rows(c->fx, mb.dev(p.o_dt), W(c, "ar_text_embedding.word_embeddings.weight"), mb.dev(p.o_it),
                     W(c, "ar_language_embedding.word_embeddings.weight"), mb.dev(p.o_lt), W(c, "ar_text_position.alpha"),
                     c->pe, mb.dev(p.o_pt), p.n_t, c->stream);
   launch_embed_rows(c->fx, mb.dev(p.o_da), W(c, "ar_audio_embedding.word_embeddings.weight"), mb.dev(p.o_ia), nullptr,
                     nullptr, W(c, "ar_audio_position.alpha"), c->pe, mb.dev(p.o_pa), p.n_a, c->stream);
+}
+
+// embeddings + the prefix-LM layers (K / V into the arena slots of p.row_b); the last row of every sequence is then row
+// p.hrow(i) of prefill_hsrc(c, p)
+int prefill_layers(vx_ctx* c, const PrefillPlan& p, const MetaBuilder& mb) {
+  const int NL = c->NL, nb = p.nb;
+  prefill_embed(c, p, mb);
   if (int e = tap_store(c, "ar_prefill_in", c->fx, (size_t)p.M * D_MODEL)) return e;
 
   double attn_flops = 0;
@@ -427,12 +430,24 @@ void decode_geometry(vx_ctx* c, int nrows, bool identity) {
   }
 }
 
+// The decode state of rows 0 .. nrows-1 from tables staged in mb (offsets of [nrows] ints; o_meta [nrows][4]): the first fill of a
+// decode batch (ar_prefill) and the empty batch of a serving session (serve_setup) set it with the same eight device copies
+int reset_decode_state(vx_ctx* c, const MetaBuilder& mb, int nrows, long o_pos, long o_ctx, long o_zero, long o_active, long o_text,
+                       long o_meta, long o_slot) {
+  const struct { int* dst; long off; int ints; } copies[] = {{c->cur_pos, o_pos, 1},   {c->ctx_len, o_ctx, 1},   {c->n_gen, o_zero, 1},
+                                                            {c->cur_tok, o_zero, 1},  {c->active, o_active, 1}, {c->text_len, o_text, 1},
+                                                            {c->slot_meta, o_meta, 4}, {c->slot_of, o_slot, 1}};
+  for (const auto& x : copies)
+    HIPCHK(hipMemcpyAsync(x.dst, mb.dev(x.off), (size_t)x.ints * nrows * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+  return VX_OK;
+}
+
 // First fill of a decode batch: the prefill of caller rows r0 .. r0+nb-1 plus the decode state and geometry that only the first
 // fill sets up (slot order, context splits, chain choice, cur_batch).
 // beams > 1: best_of.  The reference repeats the prompt N times and runs N identical prefills (models/vallex.py:525-527); here
 // every one of the nb rows is prefilled once and decode row i*beams + j (j < beams) continues from prefill row i: its KV cache
 // and residual row are fanned out to the beams (beams.hip), which then sample independently.
-int ar_prefill(vx_ctx* c, const vx_batch* b, int r0, int nb, int beams = 1) {
+int ar_prefill(vx_ctx* c, const vx_batch* b, int r0, int nb, int beams) {
   const int NL = c->NL;
   const int nrows = nb * beams;                      // decode rows after this call
   PrefillPlan p;
@@ -491,15 +506,7 @@ int ar_prefill(vx_ctx* c, const vx_batch* b, int r0, int nb, int beams = 1) {
     o_fp = mb.add(fpairs); o_fr = mb.add(frow);
   }
   if (int e = upload_meta(c)) return e;
-  const size_t ib = nrows * sizeof(int);
-  HIPCHK(hipMemcpyAsync(c->cur_pos, mb.dev(o_sp), ib, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->ctx_len, mb.dev(o_sc), ib, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->n_gen, mb.dev(o_z), ib, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->cur_tok, mb.dev(o_z), ib, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->active, mb.dev(o_1), ib, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->text_len, mb.dev(o_sS), ib, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->slot_meta, mb.dev(o_meta), 4 * ib, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->slot_of, mb.dev(o_slot), ib, hipMemcpyDeviceToDevice, c->stream));
+  if (int e = reset_decode_state(c, mb, nrows, o_sp, o_sc, o_z, o_1, o_sS, o_meta, o_slot)) return e;
   H2D(c->n_active, &nrows, sizeof(int));
   c->cur_batch = nrows;
   bool identity = true;
@@ -664,8 +671,7 @@ int launch_status(vx_ctx* c) {
 // graph -- between two hipGraphLaunch calls the GPU idles for ~9 us (kernel traces, profiles/r04_gaps_*.csv: the gap behind every
 // dec_sample launch), which a multi-step graph pays once per GRAPH_STEPS steps.  All step state (positions, lengths, flags, the
 // sampler's counters) lives on the device, so a replay is position independent.
-constexpr int GRAPH_STEPS = 4;
-int ar_step_run(vx_ctx* c, const SampleArgs* sa, const std::string& sig, int nsteps = 1, const ServeSampleArgs* rsa = nullptr) {
+int ar_step_run(vx_ctx* c, const SampleArgs* sa, const std::string& sig, int nsteps, const ServeSampleArgs* rsa) {
   if (!c->cfg.use_graph || c->prof_on == 1 || (!sa && !rsa)) {
     for (int i = 0; i < nsteps; ++i) ar_step_launches(c, sa, rsa);
     HIPCHK(hipGetLastError());
@@ -690,149 +696,26 @@ int ar_step_run(vx_ctx* c, const SampleArgs* sa, const std::string& sig, int nst
   return VX_OK;
 }
 
-// ---- sticky fp32 fallback bookkeeping (engine_ctx.h) -----------------------------------------------------------
-// does this phase go to the fp32 kernels directly?  In sticky mode yes, except every FB_STICKY_PROBE_EVERY-th phase (a probe on f16x2)
-bool fb_direct(vx_ctx* c, bool sticky, int& age) {
-  if (!sticky || !range_guarded(c)) return false;
-  if (++age >= FB_STICKY_PROBE_EVERY) { age = 0; return false; }
-  return true;
+// the end of every guarded phase's `once` (engine_ctx.h: guarded)
+int retry_if_raised(vx_ctx* c, int flag) {
+  if (!flag) return VX_OK;
+  HIPCHK(hipMemsetAsync(c->range_flag, 0, sizeof(int), c->stream));
+  return VX_RETRY_F32;
 }
-// outcome of a phase that RAN on f16x2: a raise counts towards sticky mode, a clean pass resets the count and leaves sticky mode
-void fb_outcome(vx_ctx* c, bool raised, int& raises, bool& sticky, int& age) {
-  if (!range_guarded(c)) return;
-  if (!raised) { raises = 0; sticky = false; age = 0; return; }
-  if (++raises >= FB_STICKY_AFTER && !sticky) { sticky = true; age = 0; ++c->sticky_engaged; }
-}
-
-// ---- AR generation for one micro-batch -----------------------------------------------------------------------
-// caller rows r0 .. r0+nb-1, each decoded as `beams` rows (decode row i*beams + j: beam j of row r0 + i); `seed` is the sampler's
-// seed for this micro-batch (unused with injected uniforms)
-int ar_generate(vx_ctx* c, const vx_batch* b, const vx_sampling* s, int r0, int nb, std::vector<int>& n_gen,
-                std::vector<int>& gen, int beams, unsigned long long seed) {
-  const int nb_rows = nb;                            // rows of the caller's batch that this micro-batch prefills
-  // a context whose prefills keep leaving the fp16 range runs them on the exact-fp32 kernels straight away (sticky fallback)
-  const bool direct_f32 = fb_direct(c, c->sticky_prefill_f32, c->sticky_prefill_age);
-  if (direct_f32) {
-    ++c->st_fb_prefill; ++c->fb_total;
-    if (int e = ensure_f32_buffers(c)) return e;
-    F32Scope f32(c);
-    if (int e = ar_prefill(c, b, r0, nb_rows, beams)) return e;
-  } else if (int e = ar_prefill(c, b, r0, nb_rows, beams)) return e;
-  const long ub = (long)b->batch * beams;            // columns of the caller's uniforms: [steps][batch x best_of]
-  nb = nb_rows * beams;                              // decode rows from here on
-  if (s->uniforms) {
-    // slice [steps][batch x beams] -> [steps][nb] for this micro-batch: columns r0*beams .. (r0 + nb_rows)*beams
-    // only the first gen_stride + 1 draws can ever be consumed (one per generated frame + the terminating sample)
-    const long steps = std::min<long>(s->uniforms_steps, c->gen_stride + 1);
-    if (steps * nb > c->uniforms_cap) FAIL(VX_EINVAL, "too many uniforms (%ld steps)", steps);
-    std::vector<float> u((size_t)steps * nb);
-    for (long t = 0; t < steps; ++t)
-      for (int i = 0; i < nb; ++i) u[t * nb + i] = s->uniforms[t * ub + (long)r0 * beams + i];
-    H2D(c->d_uniforms, u.data(), u.size() * sizeof(float));
-    SYNC();
-  }
-  // the seed of the counter-based sampler lives in a device word: a new seed per call (the reference's contract, every call
-  // draws from torch's generator) does not change the captured step graph
-  H2D(c->seed_dev, &seed, sizeof seed);
-  SampleArgs sa = make_sample_args(c, s, 1, nullptr);
-  std::vector<int> act(nb);
-  bool any = true, raised = false;
-  // first token from the prefill logits; the host sync that tells whether anything is still active also brings the range
-  // flag of the prefill back (f16x2 guard, see F32Scope)
-  auto first_sample = [&]() -> int {
-    int flag = 0;
-    HIPCHK(hipMemsetAsync(c->sum_logp, 0, MB * sizeof(float), c->stream));
-    LAUNCH(launch_dec_sample(sa, c->stream));
-    if (int e = launch_status(c)) return e;
-    D2H(act.data(), c->active, nb * sizeof(int));
-    if (range_guarded(c) && !direct_f32) D2H(&flag, c->range_flag, sizeof(int));
-    SYNC();
-    raised = flag != 0;
-    any = std::any_of(act.begin(), act.end(), [](int v) { return v != 0; });
-    return VX_OK;
-  };
-  if (int e = first_sample()) return e;
-  if (!direct_f32) fb_outcome(c, raised, c->fb_prefill_raises, c->sticky_prefill_f32, c->sticky_prefill_age);
-  if (raised) {
-    // an operand of the prefill left the fp16 range: the K/V cache, the residual row and the logits are not to be trusted.
-    // Re-run the prefill on the exact-fp32 kernels (it resets the decode state) and sample the first token again.
-    HIPCHK(hipMemsetAsync(c->range_flag, 0, sizeof(int), c->stream));
-    ++c->st_fb_prefill; ++c->fb_total;
-    if (int e = ensure_f32_buffers(c)) return e;
-    {
-      F32Scope f32(c);
-      if (int e = ar_prefill(c, b, r0, nb_rows, beams)) return e;
-      if (int e = first_sample()) return e;
-    }
-  }
-  char sig[160];
-  snprintf(sig, sizeof sig, "b%d ns%d c%d%d%d k%d t%a u%d f%d l%d", nb, c->nsplit, (int)c->sb_chain, (int)c->sb_qkv, (int)c->split_fused, sa.top_k, sa.temperature,
-           sa.uniforms != nullptr, sa.force_eos_at, sa.sum_logp != nullptr);
-  const int sync_every = s->sync_every > 0 ? s->sync_every : 8;
-  // with a forced EOS every row is inactive after force_eos_at steps: do not run on to the next host poll
-  const int hard_cap = s->force_eos_at >= 0 ? std::min(c->gen_stride + 2, s->force_eos_at) : c->gen_stride + 2;
-  int steps = 0;
-  // GRAPH_STEPS steps per graph launch while that neither crosses a host poll nor the cap (nsteps is 1 or GRAPH_STEPS: two graphs)
-  const int gs = (c->graph_multi && sync_every % GRAPH_STEPS == 0) ? GRAPH_STEPS : 1;
-  while (any && steps < hard_cap) {
-    const int n = (steps % gs == 0 && steps + gs <= hard_cap) ? gs : 1;
-    if (int e = ar_step_run(c, &sa, sig, n)) return e;
-    steps += n;
-    if (steps % sync_every == 0) {
-      D2H(act.data(), c->active, nb * sizeof(int));
-      SYNC();
-      any = std::any_of(act.begin(), act.end(), [](int v) { return v != 0; });
-    }
-  }
-  n_gen.resize(nb);
-  gen.resize((size_t)nb * c->gen_stride);
-  D2H(n_gen.data(), c->n_gen, nb * sizeof(int));
-  D2H(gen.data(), c->gen, gen.size() * sizeof(int));
+int sync_guarded(vx_ctx* c) {
+  int flag = 0;
+  if (range_guarded(c)) D2H(&flag, c->range_flag, sizeof(int));
   SYNC();
-  c->st_steps += steps;
-  if (c->prof_on) {
-    // algorithmic KV bytes: every decode step of an active row reads ctx rows of K and V in all layers
-    for (int i = 0; i < nb; ++i)
-      for (int t = 1; t <= n_gen[i]; ++t)
-        c->prof[0].bytes += (double)c->NL * ((double)(c->h_L[i] + t) * 2.0 * D_MODEL * 4.0);
-    c->prof[1].bytes += (double)steps * ((double)c->NL * 12.0 * D_MODEL * D_MODEL + (double)AR_LOGITS * D_MODEL) * 4.0;
-  }
-  return VX_OK;
-}
-
-// best_of selection of one row's N beams (models/vallex.py:583-594): sum(logp) / len^length_penalty with len = torch.sum(y != EOS) =
-// BOS + prompt + frames; the first index wins ties; return_worst picks the lowest.  vx_infer and the serving session both call it.
-static int select_beam(const float* slp, const int* n_gen, int N, int Tp, float length_penalty, bool return_worst) {
-  int best = 0, worst = 0;
-  double bv = 0, wv = 0;
-  for (int j = 0; j < N; ++j) {
-    const double len = 1.0 + Tp + n_gen[j];
-    const double v = (double)(float)((float)slp[j] / powf((float)len, length_penalty));
-    if (j == 0 || v > bv) { bv = v; best = j; }
-    if (j == 0 || v < wv) { wv = v; worst = j; }
-  }
-  return return_worst ? worst : best;
-}
-
-// best_of: the sampler's seed of micro-batch k.  The counter-based sampler mixes (seed, decode row, step), so without this the beams
-// of the first row of every micro-batch would draw the same streams.  Micro-batch 0 keeps the caller's seed: a batch-1 call (one
-// micro-batch) draws exactly what it drew before batched best_of existed.
-static unsigned long long beam_seed(unsigned long long seed, int k) {
-  if (k == 0) return seed;
-  unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (unsigned long long)k;      // splitmix64 of (seed, k)
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
+  return retry_if_raised(c, flag);
 }
 
 // ---- NAR: 7 stages (models/vallex.py:600-686, prefix_mode 1) ----------------------------------------------------
-int nar_generate_once(vx_ctx* c, const vx_batch* b, int r0, int nb, const std::vector<int>& T, const int* codes0,
-                      long codes0_stride, std::vector<int>& out_codes /* [7][sumT] */, long& sumT_out) {
-  const int NL = c->NL;
+// tables of one NAR pass over caller rows r0 .. r0+nb-1, T[i] generated frames each, code0(i, t) = the first-codebook id of frame t
+// (engine_ctx.h: NarPlan; shared with the scoring pass of score.hip).  p.sumT == 0: nothing to run, nothing was added to mb.
+int nar_plan(vx_ctx* c, const vx_batch* b, int r0, int nb, const std::vector<int>& T, const std::function<int(int, int)>& code0,
+             MetaBuilder& mb, NarPlan& p) {
   std::vector<int> seq_off(nb), seq_len(nb), dst_t, id_t, lang_t, pos_t, ycodes, ynj, ydst, ypos, gen_rows, gen_y, q_first(nb), c_off(nb);
   long M = 0, Y = 0, sumT = 0;
-  int max_len = 0;
-  double trim_attn_flops = 0;
   {      // the host builds ~0.3 M ints of row metadata while the GPU waits between the AR and the NAR phase: no reallocation on the way
     size_t nS = 0, nY = 0, nT = 0;
     for (int i = 0; i < nb; ++i) { nS += b->text_lens[r0 + i]; nY += b->prompt_lens[r0 + i] + T[i]; nT += T[i]; }
@@ -841,24 +724,22 @@ int nar_generate_once(vx_ctx* c, const vx_batch* b, int r0, int nb, const std::v
     ycodes.reserve(nY * N_Q);
     gen_rows.reserve(nT); gen_y.reserve(nT);
   }
+  p = NarPlan{};
+  p.nb = nb;
   for (int i = 0; i < nb; ++i) {
     const int r = r0 + i, S = b->text_lens[r], Tp = b->prompt_lens[r];
     seq_off[i] = (int)M; seq_len[i] = S + Tp + T[i];
     q_first[i] = S + Tp; c_off[i] = (int)sumT;
-    trim_attn_flops += 4.0 * T[i] * (double)seq_len[i] * D_MODEL;
-    max_len = std::max(max_len, seq_len[i]);
-    for (int s = 0; s < S; ++s) {
-      dst_t.push_back((int)M + s);
-      id_t.push_back(b->text_ids[(long)r * b->text_stride + s]);
-      lang_t.push_back(b->text_lang[(long)r * b->text_stride + s]);
-      pos_t.push_back(s);
-    }
+    p.trim_attn_flops += 4.0 * T[i] * (double)seq_len[i] * D_MODEL;
+    p.attn_flops += 4.0 * seq_len[i] * (double)seq_len[i] * D_MODEL;
+    p.max_len = std::max(p.max_len, seq_len[i]);
+    text_rows(b, r, (int)M, dst_t, id_t, lang_t, pos_t);
     for (int t = 0; t < Tp + T[i]; ++t) {
       if (t < Tp) {
         for (int j = 0; j < N_Q; ++j) ycodes.push_back(b->prompt_codes[((long)r * b->prompt_stride + t) * N_Q + j]);
         ynj.push_back(N_Q);
       } else {
-        ycodes.push_back(codes0[(long)i * codes0_stride + (t - Tp)]);
+        ycodes.push_back(code0(i, t - Tp));
         for (int j = 1; j < N_Q; ++j) ycodes.push_back(0);
         ynj.push_back(1);
         gen_rows.push_back((int)M + S + t);
@@ -869,798 +750,120 @@ int nar_generate_once(vx_ctx* c, const vx_batch* b, int r0, int nb, const std::v
     }
     M += seq_len[i]; Y += Tp + T[i]; sumT += T[i];
   }
-  sumT_out = sumT;
-  out_codes.assign((size_t)(N_Q - 1) * sumT, 0);
+  p.M = M; p.Y = Y; p.sumT = sumT; p.n_t = (int)dst_t.size();
   if (sumT == 0) return VX_OK;
   if (M > c->Mmax) FAIL(VX_EINVAL, "NAR rows %ld exceed arena %ld", M, c->Mmax);
+  p.o_off = mb.add(seq_off); p.o_len = mb.add(seq_len); p.o_dt = mb.add(dst_t); p.o_it = mb.add(id_t); p.o_lt = mb.add(lang_t);
+  p.o_pt = mb.add(pos_t); p.o_yc = mb.add(ycodes); p.o_nj = mb.add(ynj); p.o_yd = mb.add(ydst); p.o_yp = mb.add(ypos);
+  p.o_gr = mb.add(gen_rows); p.o_gy = mb.add(gen_y); p.o_qf = mb.add(q_first); p.o_co = mb.add(c_off);
+  return VX_OK;
+}
+
+// stage st of a NAR pass up to its logits of the generated rows, c->flogits [sumT][1024]: text + accumulated audio embeddings, the NL
+// layers, the final AdaLN norm and predict layer st.  `taps`: the debug taps of the generating pass (nar_layer_out.*, nar_logits*).
+int nar_stage(vx_ctx* c, const NarPlan& p, const MetaBuilder& mb, int st, bool taps) {
+  const int NL = c->NL, nnorm = 2 * NL + 1;
+  const long M = p.M, sumT = p.sumT;
+  launch_embed_rows(c->fx, mb.dev(p.o_dt), W(c, "nar_text_embedding.word_embeddings.weight"), mb.dev(p.o_it),
+                    W(c, "nar_language_embedding.word_embeddings.weight"), mb.dev(p.o_lt),
+                    W(c, "nar_text_position.alpha"), c->pe, mb.dev(p.o_pt), p.n_t, c->stream);
+  launch_add_pe_scatter(c->fx, mb.dev(p.o_yd), c->fyemb, W(c, "nar_audio_position.alpha"), c->pe, mb.dev(p.o_yp), (int)p.Y,
+                        c->stream);
+  const float* ada = c->ada + (size_t)st * nnorm * 2 * D_MODEL;
+  // the last layer only has to produce the generated rows (struct Trim); the per-layer taps want every row
+  // f16x2 projections + f16x2 attention, or the reference arithmetic (fp32 projections + fp32 attention); the mixed modes of the
+  // VX_GEMM_* / VX_ATTN_* switches and bf16x3 run every row
+  const bool trim_h2 = c->gemm_mode == 0 && c->attn_x3 && c->attn_h2, trim_f32 = c->gemm_mode == 2 && !c->attn_x3;
+  const bool trim = c->nar_trim && (trim_h2 || trim_f32) && !c->cfg.debug_taps;
+  const Trim tr{sumT, mb.dev(p.o_qf), mb.dev(p.o_co), mb.dev(p.o_gr), p.trim_attn_flops};
+  for (int l = 0; l < NL; ++l) {
+    if (int e = full_layer(c, c->nar[l], M, mb.dev(p.o_off), mb.dev(p.o_len), nullptr, p.nb, p.max_len,
+                           ada + (size_t)(2 * l) * 2 * D_MODEL, ada + (size_t)(2 * l + 1) * 2 * D_MODEL, nullptr, nullptr,
+                           nullptr, nullptr, p.attn_flops, (trim && l == NL - 1) ? &tr : nullptr))
+      return e;
+    if (taps && c->cfg.debug_taps && st == 0) {
+      char nm[64];
+      snprintf(nm, sizeof nm, "nar_layer_out.%d", l);
+      if (int e = tap_store(c, nm, c->fx, (size_t)M * D_MODEL)) return e;
+    }
+  }
+  const float* adaf = ada + (size_t)(2 * NL) * 2 * D_MODEL;
+  const float *ng = W(c, "nar_decoder.norm.norm.weight"), *nbias = W(c, "nar_decoder.norm.norm.bias");
+  char nm[64];
+  snprintf(nm, sizeof nm, "nar_predict_layers.%d.weight", st);
+  if (trim && trim_f32) {
+    // the compacted residual stream (in the QKV buffer, full_layer) holds exactly the rows the predict layer reads: no gather
+    launch_layernorm(c->fqkv, D_MODEL, c->fxn, D_MODEL, (int)sumT, D_MODEL, LN_EPS, ng, nbias, adaf, adaf + D_MODEL, c->stream);
+    proj(c, c->fxn, D_MODEL, W(c, nm), c->pred_w3[st], nullptr, nullptr, 0, c->flogits, AUDIO_VOCAB, sumT, AUDIO_VOCAB, D_MODEL, ACT_NONE);
+  } else if (trim) {
+    // the compacted residual stream (fxn) holds exactly the rows the predict layer reads: the final norm writes the GEMM's
+    // operand planes itself (bit-identical to a split of its fp32 result), no gather, no split pass
+    launch_layernorm(c->fxn, D_MODEL, nullptr, D_MODEL, (int)sumT, D_MODEL, LN_EPS, ng, nbias, adaf, adaf + D_MODEL, c->stream, c->fa3,
+                     h2_plane(sumT, D_MODEL, H2_TILE_A), c->range_flag);
+    proj(c, nullptr, D_MODEL, W(c, nm), c->pred_w3[st], nullptr, nullptr, 0, c->flogits, AUDIO_VOCAB, sumT, AUDIO_VOCAB, D_MODEL,
+         ACT_NONE, nullptr, c->fa3);
+  } else {
+    launch_layernorm(c->fx, D_MODEL, c->fxn, D_MODEL, (int)M, D_MODEL, LN_EPS, ng, nbias, adaf, adaf + D_MODEL, c->stream);
+    proj(c, c->fxn, D_MODEL, W(c, nm), c->pred_w3[st], nullptr, nullptr, 0, c->flogits, AUDIO_VOCAB, sumT, AUDIO_VOCAB, D_MODEL,
+         ACT_NONE, mb.dev(p.o_gr));
+  }
+  if (taps && c->cfg.debug_taps) {                     // "nar_logits0" .. "nar_logits6": every stage's logits of the generated rows
+    snprintf(nm, sizeof nm, "nar_logits%d", st);
+    if (int e = tap_store(c, nm, c->flogits, (size_t)sumT * AUDIO_VOCAB)) return e;
+  }
+  return VX_OK;
+}
+
+// this context has left the fp16 range in a NAR phase before: look at the flag behind stage 0 already, so that an out-of-range model
+// does not pay six more f16x2 stages before the fp32 re-run (costs one host sync; never in the common case)
+int nar_early_flag(vx_ctx* c, int st) {
+  if (st != 0 || c->fb_nar_raises <= 0 || !range_guarded(c)) return VX_OK;
+  int early = 0;
+  D2H(&early, c->range_flag, sizeof(int));
+  SYNC();
+  return retry_if_raised(c, early);
+}
+
+int nar_generate_once(vx_ctx* c, const vx_batch* b, int r0, int nb, const std::vector<int>& T, const int* codes0,
+                      long codes0_stride, std::vector<int>& out_codes /* [7][sumT] */, long& sumT_out) {
   MetaBuilder mb(c);
-  const long o_off = mb.add(seq_off), o_len = mb.add(seq_len), o_dt = mb.add(dst_t), o_it = mb.add(id_t),
-             o_lt = mb.add(lang_t), o_pt = mb.add(pos_t), o_yc = mb.add(ycodes), o_nj = mb.add(ynj), o_yd = mb.add(ydst),
-             o_yp = mb.add(ypos), o_gr = mb.add(gen_rows), o_gy = mb.add(gen_y), o_qf = mb.add(q_first), o_co = mb.add(c_off);
-  std::vector<int> zeros((size_t)(N_Q - 1) * sumT, 0);
-  const long o_samples = mb.add(zeros);
+  NarPlan p;
+  if (int e = nar_plan(c, b, r0, nb, T, [&](int i, int t) { return codes0[(long)i * codes0_stride + t]; }, mb, p)) return e;
+  const long sumT = sumT_out = p.sumT;
+  out_codes.assign((size_t)(N_Q - 1) * sumT, 0);
+  if (sumT == 0) return VX_OK;
+  const long o_samples = mb.add(out_codes);            // zeros [7][sumT]: every stage's arg-max ids
   if (int e = upload_meta(c)) return e;
 
-  launch_nar_yemb_init(c->fyemb, c->nar_tabs_dev, mb.dev(o_yc), mb.dev(o_nj), (int)Y, c->stream);
-  double attn_flops = 0;
-  for (int i = 0; i < nb; ++i) attn_flops += 4.0 * seq_len[i] * (double)seq_len[i] * D_MODEL;
-  const int nnorm = 2 * NL + 1;
+  launch_nar_yemb_init(c->fyemb, c->nar_tabs_dev, mb.dev(p.o_yc), mb.dev(p.o_nj), (int)p.Y, c->stream);
   for (int st = 0; st < N_Q - 1; ++st) {
-    launch_embed_rows(c->fx, mb.dev(o_dt), W(c, "nar_text_embedding.word_embeddings.weight"), mb.dev(o_it),
-                      W(c, "nar_language_embedding.word_embeddings.weight"), mb.dev(o_lt),
-                      W(c, "nar_text_position.alpha"), c->pe, mb.dev(o_pt), (int)dst_t.size(), c->stream);
-    launch_add_pe_scatter(c->fx, mb.dev(o_yd), c->fyemb, W(c, "nar_audio_position.alpha"), c->pe, mb.dev(o_yp), (int)Y,
-                          c->stream);
-    const float* ada = c->ada + (size_t)st * nnorm * 2 * D_MODEL;
-    // the last layer only has to produce the generated rows (struct Trim); the per-layer taps want every row
-    // f16x2 projections + f16x2 attention, or the reference arithmetic (fp32 projections + fp32 attention); the mixed modes of the
-    // VX_GEMM_* / VX_ATTN_* switches and bf16x3 run every row
-    const bool trim_h2 = c->gemm_mode == 0 && c->attn_x3 && c->attn_h2, trim_f32 = c->gemm_mode == 2 && !c->attn_x3;
-    const bool trim = c->nar_trim && (trim_h2 || trim_f32) && !c->cfg.debug_taps;
-    const Trim tr{sumT, mb.dev(o_qf), mb.dev(o_co), mb.dev(o_gr), trim_attn_flops};
-    for (int l = 0; l < NL; ++l) {
-      if (int e = full_layer(c, c->nar[l], M, mb.dev(o_off), mb.dev(o_len), nullptr, nb, max_len,
-                             ada + (size_t)(2 * l) * 2 * D_MODEL, ada + (size_t)(2 * l + 1) * 2 * D_MODEL, nullptr, nullptr,
-                             nullptr, nullptr, attn_flops, (trim && l == NL - 1) ? &tr : nullptr))
-        return e;
-      if (c->cfg.debug_taps && st == 0) {
-        char nm[64];
-        snprintf(nm, sizeof nm, "nar_layer_out.%d", l);
-        if (int e = tap_store(c, nm, c->fx, (size_t)M * D_MODEL)) return e;
-      }
-    }
-    const float* adaf = ada + (size_t)(2 * NL) * 2 * D_MODEL;
-    char nm[64];
-    snprintf(nm, sizeof nm, "nar_predict_layers.%d.weight", st);
-    if (trim && trim_f32) {
-      // the compacted residual stream (in the QKV buffer, full_layer) holds exactly the rows the predict layer reads: no gather
-      launch_layernorm(c->fqkv, D_MODEL, c->fxn, D_MODEL, (int)sumT, D_MODEL, LN_EPS, W(c, "nar_decoder.norm.norm.weight"),
-                       W(c, "nar_decoder.norm.norm.bias"), adaf, adaf + D_MODEL, c->stream);
-      proj(c, c->fxn, D_MODEL, W(c, nm), c->pred_w3[st], nullptr, nullptr, 0, c->flogits, AUDIO_VOCAB, sumT, AUDIO_VOCAB, D_MODEL, ACT_NONE);
-    } else if (trim) {
-      // the compacted residual stream (fxn) holds exactly the rows the predict layer reads: the final norm writes the GEMM's
-      // operand planes itself (bit-identical to a split of its fp32 result), no gather, no split pass
-      launch_layernorm(c->fxn, D_MODEL, nullptr, D_MODEL, (int)sumT, D_MODEL, LN_EPS, W(c, "nar_decoder.norm.norm.weight"),
-                       W(c, "nar_decoder.norm.norm.bias"), adaf, adaf + D_MODEL, c->stream, c->fa3, h2_plane(sumT, D_MODEL, H2_TILE_A),
-                       c->range_flag);
-      proj(c, nullptr, D_MODEL, W(c, nm), c->pred_w3[st], nullptr, nullptr, 0, c->flogits, AUDIO_VOCAB, sumT, AUDIO_VOCAB, D_MODEL,
-           ACT_NONE, nullptr, c->fa3);
-    } else {
-      launch_layernorm(c->fx, D_MODEL, c->fxn, D_MODEL, (int)M, D_MODEL, LN_EPS, W(c, "nar_decoder.norm.norm.weight"),
-                       W(c, "nar_decoder.norm.norm.bias"), adaf, adaf + D_MODEL, c->stream);
-      proj(c, c->fxn, D_MODEL, W(c, nm), c->pred_w3[st], nullptr, nullptr, 0, c->flogits, AUDIO_VOCAB, sumT, AUDIO_VOCAB, D_MODEL,
-           ACT_NONE, mb.dev(o_gr));
-    }
-    if (c->cfg.debug_taps) {                             // "nar_logits0" .. "nar_logits6": every stage's logits of the generated rows
-      snprintf(nm, sizeof nm, "nar_logits%d", st);
-      if (int e = tap_store(c, nm, c->flogits, (size_t)sumT * AUDIO_VOCAB)) return e;
-    }
+    if (int e = nar_stage(c, p, mb, st, true)) return e;
     int* samples = c->imeta + o_samples + (long)st * sumT;
     launch_argmax_rows(c->flogits, AUDIO_VOCAB, (int)sumT, AUDIO_VOCAB, samples, c->stream);
-    if (st == 0 && c->fb_nar_raises > 0 && range_guarded(c)) {
-      // this context has left the fp16 range in a NAR phase before: look at the flag behind stage 0 already, so that an
-      // out-of-range model does not pay six more f16x2 stages before the fp32 re-run (costs one host sync; never in the common case)
-      int early = 0;
-      D2H(&early, c->range_flag, sizeof(int));
-      SYNC();
-      if (early) {
-        HIPCHK(hipMemsetAsync(c->range_flag, 0, sizeof(int), c->stream));
-        return VX_RETRY_F32;
-      }
-    }
+    if (int r = nar_early_flag(c, st)) return r;
     if (st < N_Q - 2) {
+      char nm[64];
       snprintf(nm, sizeof nm, "nar_audio_embeddings.%d.word_embeddings.weight", st + 1);
-      launch_embed_accum(c->fyemb, mb.dev(o_gy), W(c, nm), samples, (int)sumT, c->stream);
+      launch_embed_accum(c->fyemb, mb.dev(p.o_gy), W(c, nm), samples, (int)sumT, c->stream);
     }
   }
   D2H(out_codes.data(), c->imeta + o_samples, out_codes.size() * sizeof(int));
-  int flag = 0;                        // the range flag rides on the sync that brings the ids back
-  if (range_guarded(c)) D2H(&flag, c->range_flag, sizeof(int));
-  SYNC();
-  if (flag) {
-    HIPCHK(hipMemsetAsync(c->range_flag, 0, sizeof(int), c->stream));
-    return VX_RETRY_F32;
-  }
-  return VX_OK;
+  return sync_guarded(c);            // the range flag rides on the sync that brings the ids back
 }
 
 int nar_generate(vx_ctx* c, const vx_batch* b, int r0, int nb, const std::vector<int>& T, const int* codes0,
                  long codes0_stride, std::vector<int>& out_codes /* [7][sumT] */, long& sumT_out) {
-  int e = VX_RETRY_F32;
-  const bool direct_f32 = fb_direct(c, c->sticky_nar_f32, c->sticky_nar_age);          // sticky fallback (engine_ctx.h)
-  if (!direct_f32) {
-    e = nar_generate_once(c, b, r0, nb, T, codes0, codes0_stride, out_codes, sumT_out);
-    if (e == VX_OK || e == VX_RETRY_F32) fb_outcome(c, e == VX_RETRY_F32, c->fb_nar_raises, c->sticky_nar_f32, c->sticky_nar_age);
-    if (e != VX_RETRY_F32) return e;
-  }
-  // an operand of one of the 7 stages left the fp16 range: the whole phase (again) on the exact-fp32 kernels (F32Scope)
-  ++c->st_fb_nar; ++c->fb_total;
-  if ((e = ensure_f32_buffers(c))) return e;
-  F32Scope f32(c);
-  return nar_generate_once(c, b, r0, nb, T, codes0, codes0_stride, out_codes, sumT_out);
+  // a raise: an operand of one of the 7 stages left the fp16 range, the whole phase runs again on the exact-fp32 kernels
+  return guarded(c, nar_kind(c), [&] { return nar_generate_once(c, b, r0, nb, T, codes0, codes0_stride, out_codes, sumT_out); });
 }
 
-// ---- continuous schedule (vx_infer_continuous) ---------------------------------------------------------------
-// One decode batch of nd = min(mbr, batch) rows for the whole call: the first fill is ar_prefill of caller rows 0 .. nd-1 (it sets
-// the geometry: slot order, context splits, chain choice -- fixed from then on, so the captured step graph never changes); at every
-// host poll (every sync_every steps, and at the step where a row reaches its cap) the rows that stopped are harvested (n_gen + gen row to the host) and waiting caller rows, first come first served, are
-// admitted into the freed decode rows: one prefill per admission round into the freed rows' KV slots, then the first sample of
-// the admitted rows alone.  Harvested rows go through the NAR stages in groups of mbr (the rest once nothing is left to decode),
-// between two decode steps: nar_generate only touches the full-sequence buffers.
-
-// caller rows `rows` of b gathered into a batch of their own (prefill / NAR of a non-contiguous row set)
-struct SubBatch {
-  std::vector<int32_t> ids, lang, tl, pc, pl;
-  vx_batch b{};
-  SubBatch(const vx_batch* src, const std::vector<int>& rows) {
-    const int n = (int)rows.size(), ts = src->text_stride, ps = src->prompt_stride;
-    ids.resize((size_t)n * ts); lang.resize((size_t)n * ts); pc.resize((size_t)n * ps * N_Q); tl.resize(n); pl.resize(n);
-    for (int i = 0; i < n; ++i) {
-      const int r = rows[i];
-      std::copy_n(src->text_ids + (long)r * ts, ts, ids.begin() + (size_t)i * ts);
-      std::copy_n(src->text_lang + (long)r * ts, ts, lang.begin() + (size_t)i * ts);
-      std::copy_n(src->prompt_codes + (long)r * ps * N_Q, (size_t)ps * N_Q, pc.begin() + (size_t)i * ps * N_Q);
-      tl[i] = src->text_lens[r]; pl[i] = src->prompt_lens[r];
-    }
-    b = *src;
-    b.batch = n; b.text_ids = ids.data(); b.text_lang = lang.data(); b.text_lens = tl.data();
-    b.prompt_codes = pc.data(); b.prompt_lens = pl.data();
+// dst [T][8]: codebook 0 from codes0_row[t], codebooks 1 .. 7 from the stage-major NAR output oc [7][sumT] at row offset `off`
+void interleave_codes(int64_t* dst, const int* codes0_row, const std::vector<int>& oc, long sumT, long off, int T) {
+  for (int t = 0; t < T; ++t) {
+    int64_t* o = dst + (long)t * N_Q;
+    o[0] = codes0_row[t];
+    for (int st = 0; st < N_Q - 1; ++st) o[st + 1] = oc[(size_t)st * sumT + off + t];
   }
-};
-
-// the sampler's draws of caller rows crow[i] into decode columns drow[i] of d_uniforms (launch_admit_uniforms); the tables go into
-// the MetaBuilder of the phase, before its upload
-struct UniformCols { long o_pairs = 0, o_staged = -1; int n = 0, steps = 0; };
-static int uniform_cols(vx_ctx* c, const vx_batch* b, const vx_sampling* s, const std::vector<int>& drow, const std::vector<int>& crow,
-                        MetaBuilder& mb, UniformCols& u) {
-  // only the first gen_stride + 1 draws of a row can ever be consumed (one per generated frame + the terminating sample)
-  u.n = (int)drow.size();
-  u.steps = s->uniforms ? (int)std::min<long>(s->uniforms_steps, c->gen_stride + 1) : c->gen_stride + 1;
-  if ((long)u.steps * c->cur_batch > c->uniforms_cap) FAIL(VX_EINVAL, "too many uniforms (%d steps)", u.steps);
-  std::vector<int> pairs(2 * u.n);
-  for (int i = 0; i < u.n; ++i) { pairs[2 * i] = drow[i]; pairs[2 * i + 1] = crow[i]; }
-  u.o_pairs = mb.add(pairs);
-  if (s->uniforms) {       // column r of the caller's [uniforms_steps][batch], staged as [n][steps] (float bits in the int tables)
-    std::vector<int> st((size_t)u.n * u.steps);
-    for (int i = 0; i < u.n; ++i)
-      for (int t = 0; t < u.steps; ++t) memcpy(&st[(size_t)i * u.steps + t], &s->uniforms[(long)t * b->batch + crow[i]], sizeof(float));
-    u.o_staged = mb.add(st);
-  }
-  return VX_OK;
-}
-static void uniform_cols_launch(vx_ctx* c, const vx_sampling* s, const UniformCols& u, const MetaBuilder& mb) {
-  const float* staged = u.o_staged >= 0 ? reinterpret_cast<const float*>(mb.dev(u.o_staged)) : nullptr;
-  launch_admit_uniforms(mb.dev(u.o_pairs), u.n, staged, u.steps, s->seed, c->d_uniforms, c->cur_batch, c->stream);
-}
-
-// admission of caller rows crow[i] (sub-batch sb, row i) into the free decode rows drow[i] of the running decode batch, up to and
-// including their first sample.  The rows still decoding keep every piece of their state: the prefill scatters K / V into the
-// admitted rows' slots only, its final norm + predict layer run on scratch copies (dh2 / xp_att: the step recomputes both before
-// it reads them; the logits of rows that are not admitted are never read), and the sampler commits the admitted rows only.
-static int admit_rows(vx_ctx* c, const vx_batch* b, const vx_sampling* s, const SampleArgs& sa, const std::vector<int>& drow,
-                      const std::vector<int>& crow, const std::vector<int>& slot_of) {
-  const int k = (int)drow.size(), nd = c->cur_batch;
-  SubBatch sb(b, crow);
-  PrefillPlan p;
-  MetaBuilder mb(c);
-  if (int e = prefill_tables(c, &sb.b, 0, k, p, mb)) return e;
-  for (int& rb : p.row_b) rb = slot_of[drow[rb]];
-  p.o_rb = mb.add(p.row_b);
-  std::vector<int> tab(5 * k), adm(nd, 0), saved(nd, 0);
-  for (int i = 0; i < k; ++i) {
-    tab[5 * i] = drow[i]; tab[5 * i + 1] = sb.pl[i]; tab[5 * i + 2] = p.seq_len[i]; tab[5 * i + 3] = p.S_[i]; tab[5 * i + 4] = p.hrow(i);
-    adm[drow[i]] = 1;
-  }
-  const long o_tab = mb.add(tab), o_adm = mb.add(adm), o_saved = mb.add(saved);
-  UniformCols uc;
-  if (int e = uniform_cols(c, b, s, drow, crow, mb, uc)) return e;
-  if (int e = upload_meta(c)) return e;
-  uniform_cols_launch(c, s, uc, mb);
-  if (int e = prefill_layers(c, p, mb)) return e;
-  launch_admit_rows(mb.dev(o_tab), k, prefill_hsrc(c, p), c->dh2, c->cur_tok, c->cur_pos, c->ctx_len, c->n_gen, c->text_len,
-                    c->slot_meta, c->slot_of, c->stream);
-  launch_dec_reduce_ln_pack(nullptr, 0, D_MODEL, nullptr, c->dh2, nullptr, W(c, "ar_decoder.norm.weight"),
-                            W(c, "ar_decoder.norm.bias"), c->xp_att, nd, c->stream);
-  launch_skinny_gemm(c->pred_wp, c->xp_att, c->p_logits, PRED_NPAD, D_MODEL, SK_PRED, c->stream);
-  int* sv = c->imeta + o_saved;
-  launch_admit_mask(0, mb.dev(o_adm), sv, nd, c->active, c->slot_meta, c->slot_of, c->n_active, c->stream);
-  LAUNCH(launch_dec_sample(sa, c->stream));
-  launch_admit_mask(1, mb.dev(o_adm), sv, nd, c->active, c->slot_meta, c->slot_of, c->n_active, c->stream);
-  return launch_status(c);
-}
-
-int infer_continuous(vx_ctx* c, const vx_batch* b, const vx_sampling* s, vx_row_done_fn on_row, void* user, int64_t* out_codes,
-                     int32_t out_stride, int32_t* out_lens) {
-  const int B = b->batch, nd = std::min(c->mbr, B);
-  hipEvent_t e0 = c->ev_t[0], e1 = c->ev_t[1], e2 = c->ev_t[2];
-  HIPCHK(hipEventRecord(e0, c->stream));
-  // per decode row: the caller row in it (-1: free), the step count at its admission and the step by which it has stopped at the
-  // latest (the sampler stops a row at n_gen = min(16 S, gen_stride, force_eos_at))
-  std::vector<int> occ(nd, -1), done_by(nd, 0), act(nd, 0), ng(nd, 0), slot_of(nd);
-  std::vector<std::vector<int>> rowgen(B);           // first-codebook ids of every harvested row (D2H target: never reallocated)
-  std::vector<int> pend;                             // harvested rows waiting for their NAR stages, in the order they completed
-  int next = 0;                                      // first caller row not admitted yet
-  long steps = 0;
-  const int first_cap = s->force_eos_at >= 0 ? std::min(c->gen_stride, s->force_eos_at) : c->gen_stride;
-  auto row_cap = [&](int r) { return std::min(first_cap, 16 * b->text_lens[r]); };
-  auto cut_by_arena = [&](int n, int S) {
-    return n >= c->gen_stride && c->gen_stride < 16 * S && !(s->force_eos_at >= 0 && s->force_eos_at <= c->gen_stride);
-  };
-  SampleArgs sa{};
-  // one admission round (first fill or admission) with the f16x2 range guard of ar_generate: a raised flag re-runs the round,
-  // prefill and first sample, on the exact-fp32 kernels; it counts in vx_last_fallbacks and towards sticky mode
-  auto round = [&](const std::vector<int>& drow, const std::vector<int>& crow) -> int {
-    const bool first = occ[0] < 0 && next == 0;
-    bool raised = false;
-    auto attempt = [&](bool read_flag) -> int {
-      if (first) {
-        if (int e = ar_prefill(c, b, 0, nd)) return e;
-        sa = make_sample_args(c, s, 1, nullptr);
-        sa.uniforms = c->d_uniforms;                 // every row draws from its own column, injected or counter-based
-        MetaBuilder mb(c);
-        UniformCols uc;
-        if (int e = uniform_cols(c, b, s, drow, crow, mb, uc)) return e;
-        if (int e = upload_meta(c)) return e;
-        uniform_cols_launch(c, s, uc, mb);
-        LAUNCH(launch_dec_sample(sa, c->stream));
-        if (int e = launch_status(c)) return e;
-        D2H(slot_of.data(), c->slot_of, nd * sizeof(int));
-      } else if (int e = admit_rows(c, b, s, sa, drow, crow, slot_of)) return e;
-      int flag = 0;
-      D2H(act.data(), c->active, nd * sizeof(int));
-      D2H(ng.data(), c->n_gen, nd * sizeof(int));
-      if (read_flag) D2H(&flag, c->range_flag, sizeof(int));
-      SYNC();
-      raised = flag != 0;
-      return VX_OK;
-    };
-    const bool direct_f32 = fb_direct(c, c->sticky_prefill_f32, c->sticky_prefill_age);
-    if (direct_f32) {
-      ++c->st_fb_prefill; ++c->fb_total;
-      if (int e = ensure_f32_buffers(c)) return e;
-      F32Scope f32(c);
-      if (int e = attempt(false)) return e;
-    } else {
-      if (int e = attempt(range_guarded(c))) return e;
-      fb_outcome(c, raised, c->fb_prefill_raises, c->sticky_prefill_f32, c->sticky_prefill_age);
-      if (raised) {
-        HIPCHK(hipMemsetAsync(c->range_flag, 0, sizeof(int), c->stream));
-        ++c->st_fb_prefill; ++c->fb_total;
-        if (int e = ensure_f32_buffers(c)) return e;
-        F32Scope f32(c);
-        if (int e = attempt(false)) return e;
-      }
-    }
-    for (size_t i = 0; i < drow.size(); ++i) { occ[drow[i]] = crow[i]; done_by[drow[i]] = (int)steps + row_cap(crow[i]); }
-    next += (int)crow.size();
-    return VX_OK;
-  };
-  // NAR stages of the first n pending rows, then their codes to the caller
-  auto nar_group = [&](int n) -> int {
-    std::vector<int> rows(pend.begin(), pend.begin() + n), T(n), codes0((size_t)n * c->gen_stride, 0), oc;
-    pend.erase(pend.begin(), pend.begin() + n);
-    SYNC();                                          // the harvested gen rows have arrived
-    for (int i = 0; i < n; ++i) {
-      T[i] = (int)rowgen[rows[i]].size();
-      std::copy(rowgen[rows[i]].begin(), rowgen[rows[i]].end(), codes0.begin() + (size_t)i * c->gen_stride);
-    }
-    SubBatch sb(b, rows);
-    long sumT = 0;
-    HIPCHK(hipEventRecord(e1, c->stream));
-    if (int e = nar_generate(c, &sb.b, 0, n, T, codes0.data(), c->gen_stride, oc, sumT)) return e;
-    HIPCHK(hipEventRecord(e2, c->stream));
-    HIPCHK(hipEventSynchronize(e2));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, e1, e2)); c->st_nar_ms += ms;
-    long off = 0;
-    for (int i = 0; i < n; ++i) {
-      const int r = rows[i];
-      out_lens[r] = T[i];
-      c->st_frames += T[i];
-      if (cut_by_arena(T[i], b->text_lens[r])) ++c->st_truncated;
-      int64_t* o0 = out_codes + (long)r * out_stride * N_Q;
-      for (int t = 0; t < T[i]; ++t) {
-        int64_t* o = o0 + (long)t * N_Q;
-        o[0] = codes0[(size_t)i * c->gen_stride + t];
-        for (int st = 0; st < N_Q - 1; ++st) o[st + 1] = oc[(size_t)st * sumT + off + t];
-      }
-      off += T[i];
-      if (on_row) on_row(user, r, o0, T[i]);
-    }
-    return VX_OK;
-  };
-
-  {
-    std::vector<int> first(nd);
-    for (int i = 0; i < nd; ++i) first[i] = i;
-    if (int e = round(first, first)) return e;
-  }
-  char sig[160];
-  snprintf(sig, sizeof sig, "b%d ns%d c%d%d%d k%d t%a u%d f%d l%d", nd, c->nsplit, (int)c->sb_chain, (int)c->sb_qkv, (int)c->split_fused, sa.top_k,
-           sa.temperature, sa.uniforms != nullptr, sa.force_eos_at, sa.sum_logp != nullptr);
-  const int sync_every = s->sync_every > 0 ? s->sync_every : 8;
-  const int gs = (c->graph_multi && sync_every % GRAPH_STEPS == 0) ? GRAPH_STEPS : 1;
-  for (;;) {
-    // harvest: the rows that stopped hand their ids to the host (delivered at the next sync) and free their decode rows
-    std::vector<int> freed;
-    for (int d = 0; d < nd; ++d) {
-      if (occ[d] < 0 || act[d]) continue;
-      const int r = occ[d];
-      if (ng[d] > out_stride) FAIL(VX_EINVAL, "out_stride %d too small for %d frames", out_stride, ng[d]);
-      rowgen[r].assign(ng[d], 0);
-      if (ng[d]) D2H(rowgen[r].data(), c->gen + (size_t)d * c->gen_stride, ng[d] * sizeof(int));
-      pend.push_back(r);
-      occ[d] = -1;
-    }
-    for (int d = 0; d < nd; ++d) if (occ[d] < 0) freed.push_back(d);
-    // admission (policy: whenever a poll finds a free row), FIFO over the waiting caller rows
-    if (next < B && !freed.empty()) {
-      const int k = std::min<int>((int)freed.size(), B - next);
-      std::vector<int> drow(freed.begin(), freed.begin() + k), crow(k);
-      for (int i = 0; i < k; ++i) crow[i] = next + i;
-      if (int e = round(drow, crow)) return e;
-      continue;                                      // an admitted row may have stopped at its first sample
-    }
-    const bool live = std::any_of(occ.begin(), occ.end(), [](int r) { return r >= 0; });
-    while ((int)pend.size() >= c->mbr || (!live && !pend.empty()))
-      if (int e = nar_group(std::min<int>(c->mbr, (int)pend.size()))) return e;
-    if (!live) break;
-    // decode steps up to the next host poll, or up to the step by which a live row has stopped at the latest (its cap: that poll
-    // is sure to free a row -- without it a row capped between two polls would leave its decode row idle until the next one)
-    long soonest = (steps / sync_every + 1) * sync_every;
-    for (int d = 0; d < nd; ++d) if (occ[d] >= 0) soonest = std::min<long>(soonest, done_by[d]);
-    const long target = std::max(soonest, steps + 1);
-    while (steps < target) {
-      const int n = (steps % gs == 0 && steps + gs <= target) ? gs : 1;
-      if (int e = ar_step_run(c, &sa, sig, n)) return e;
-      steps += n;
-    }
-    D2H(act.data(), c->active, nd * sizeof(int));
-    D2H(ng.data(), c->n_gen, nd * sizeof(int));
-    SYNC();
-  }
-  HIPCHK(hipEventRecord(e1, c->stream));
-  HIPCHK(hipEventSynchronize(e1));
-  float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-  c->st_ar_ms = ms - c->st_nar_ms;
-  c->st_steps = steps;
-  return VX_OK;
-}
-
-// ---- serving session (vx_serve_*) ----------------------------------------------------------------------------------
-// A decode batch of nd = min(max_batch, 32) rows that outlives any single call.  Requests are submitted at any time (host copies
-// only); vx_serve_run admits them first come first served into free decode rows, decodes, harvests requests whose beams have all
-// stopped, selects one beam per request and runs the NAR stages in groups.  Geometry (slot order, context splits, chain) is fixed
-// at vx_serve_open for nd free rows (serve_setup), so the captured step graph never changes; every admission, the first included,
-// goes through serve_admit.  DESIGN.md section 10.
-struct ServeReq {
-  int64_t id = 0;
-  int N = 1;                                   // beams
-  float length_penalty = 1.f;
-  bool worst = false;
-  unsigned long long seed = 0;
-  int usteps = 0;                              // injected draws per beam (0: counter-based)
-  int top_k = 1;                               // topk_sampling arguments of this request (vx_request_sampling, or the session's)
-  float temperature = 1.f;
-  int force_eos_at = -1;
-  float top_p = 1.f, rep_penalty = 1.f;        // vx_request_filters (neutral: 1, 1, 0, 0)
-  int rep_window = 0, min_frames = 0;
-  std::vector<float> u;                        // [N][usteps]
-  std::vector<int32_t> ids, lang, pc;          // text ids / language ids [S], prompt codes [Tp][8]
-  int S = 0, Tp = 0;
-  std::vector<int> rows;                       // decode row of every beam
-  std::vector<std::vector<int>> gen;           // first-codebook ids of every harvested beam (D2H targets: never reallocated)
-  std::vector<int> ng;                         // frames of every harvested beam
-  std::vector<float> slp;                      // sum(logp) of every harvested beam
-  int harvested = 0;
-  // the step count at which the sampler has stopped every beam at the latest: min(16 S, gen_stride, force_eos_at)
-  int cap(int gen_stride) const { return std::min(force_eos_at >= 0 ? std::min(gen_stride, force_eos_at) : gen_stride, 16 * S); }
-};
-
-// requests gathered into one vx_batch (prefill / NAR of a request group)
-struct ReqBatch {
-  std::vector<int32_t> ids, lang, tl, pc, pl;
-  vx_batch b{};
-  explicit ReqBatch(const std::vector<ServeReq*>& rq) {
-    const int n = (int)rq.size();
-    int ts = 1, ps = 1;
-    for (const ServeReq* r : rq) { ts = std::max(ts, r->S); ps = std::max(ps, r->Tp); }
-    ids.assign((size_t)n * ts, 0); lang.assign((size_t)n * ts, 0); pc.assign((size_t)n * ps * N_Q, 0); tl.resize(n); pl.resize(n);
-    for (int i = 0; i < n; ++i) {
-      const ServeReq* r = rq[i];
-      std::copy(r->ids.begin(), r->ids.end(), ids.begin() + (size_t)i * ts);
-      std::copy(r->lang.begin(), r->lang.end(), lang.begin() + (size_t)i * ts);
-      std::copy(r->pc.begin(), r->pc.end(), pc.begin() + (size_t)i * ps * N_Q);
-      tl[i] = r->S; pl[i] = r->Tp;
-    }
-    b.struct_size = sizeof(vx_batch); b.batch = n;
-    b.text_ids = ids.data(); b.text_lang = lang.data(); b.text_stride = ts; b.text_lens = tl.data();
-    b.prompt_codes = pc.data(); b.prompt_stride = ps; b.prompt_lens = pl.data();
-  }
-};
-
-}  // namespace vxe
-
-struct vx_serve {
-  vx_ctx* c = nullptr;
-  vx_sampling s{};                             // session-wide: top_k, temperature, force_eos_at, sync_every
-  int nd = 0;
-  int64_t next_id = 0;
-  std::deque<std::unique_ptr<ServeReq>> waiting;
-  std::vector<std::unique_ptr<ServeReq>> live;     // admitted, some beam still decoding
-  std::vector<std::unique_ptr<ServeReq>> pend;     // every beam harvested, NAR stages pending (in the order they completed)
-  std::vector<ServeReq*> occ;                  // per decode row: its request (null: free)
-  std::vector<int> beam, done_by, act, ng, slot_of;
-  long steps = 0;                              // decode steps since vx_serve_open
-  ServeSampleArgs rsa{};                       // the per-row sampler of every step and admission (serve_sample.hip)
-  std::string sig;
-  bool running = false;                        // inside vx_serve_run (on_done): vx_serve_cancel refuses
-};
-
-namespace vxe {
-
-// nd free decode rows: identity slot order, every row inactive (slot record {d, 1, 0}), n_active = 0, and the geometry of nd rows
-static int serve_setup(vx_ctx* c, int nd) {
-  std::vector<int> zero(nd, 0), one(nd, 1), meta(4 * nd, 0), slot(nd);
-  for (int d = 0; d < nd; ++d) { meta[4 * d] = d; meta[4 * d + 1] = 1; slot[d] = d; }
-  MetaBuilder mb(c);
-  const long o_z = mb.add(zero), o_1 = mb.add(one), o_meta = mb.add(meta), o_slot = mb.add(slot);
-  if (int e = upload_meta(c)) return e;
-  const size_t ib = nd * sizeof(int);
-  HIPCHK(hipMemcpyAsync(c->cur_pos, mb.dev(o_z), ib, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->ctx_len, mb.dev(o_1), ib, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->n_gen, mb.dev(o_z), ib, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->cur_tok, mb.dev(o_z), ib, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->active, mb.dev(o_z), ib, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->text_len, mb.dev(o_1), ib, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->slot_meta, mb.dev(o_meta), 4 * ib, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->slot_of, mb.dev(o_slot), ib, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemsetAsync(c->n_active, 0, sizeof(int), c->stream));
-  c->cur_batch = nd;
-  c->h_L.assign(nd, 0);
-  decode_geometry(c, nd, true);
-  SYNC();                                      // the staged tables are consumed before the next MetaBuilder reuses imeta
-  return VX_OK;
-}
-
-// admission of requests rq (their beam rows assigned, rq[i]->rows) into free decode rows, up to and including their first sample.
-// Each request is prefilled once, into the arena slot of its first beam row; the fan-out (beams.hip, pairs only) copies its K / V to
-// the other beams' slots; every beam row gets its own admit_rows entry pointing at the request's prefill row, its own draws (keyed
-// on (request seed, beam) or the request's injected column) and a zero sum_logp.  The rows still decoding keep every piece of their
-// state, as in admit_rows.
-static int serve_admit(vx_serve* v, const std::vector<ServeReq*>& rq) {
-  vx_ctx* c = v->c;
-  const int k = (int)rq.size(), nd = v->nd;
-  ReqBatch rb(rq);
-  PrefillPlan p;
-  MetaBuilder mb(c);
-  if (int e = prefill_tables(c, &rb.b, 0, k, p, mb)) return e;
-  for (int& r : p.row_b) r = v->slot_of[rq[r]->rows[0]];
-  p.o_rb = mb.add(p.row_b);
-  std::vector<int> tab, adm(nd, 0), saved(nd, 0), pairs, staged, utab;
-  const int cap_steps = c->gen_stride + 1;         // draws a row can ever consume: one per generated frame + the terminating one
-  int max_steps = 1;
-  for (int i = 0; i < k; ++i) {
-    const ServeReq* r = rq[i];
-    if (p.seq_len[i] > c->Tmax) FAIL(VX_EINVAL, "request %lld: %d cached rows exceed the arena (%d)", (long long)r->id, p.seq_len[i], c->Tmax);
-    for (int j = 0; j < r->N; ++j) {
-      const int d = r->rows[j];
-      tab.insert(tab.end(), {d, r->Tp, p.seq_len[i], p.S_[i], p.hrow(i)});
-      adm[d] = 1;
-      if (j) pairs.insert(pairs.end(), {v->slot_of[r->rows[0]], v->slot_of[d], p.seq_len[i]});
-    }
-  }
-  // injected draws first (their offsets go into the draw table), as float bits in the int tables
-  std::vector<int> soff(k, -1);
-  for (int i = 0; i < k; ++i) {
-    const ServeReq* r = rq[i];
-    if (!r->usteps) continue;
-    soff[i] = (int)staged.size();
-    const int st = std::min(r->usteps, cap_steps);
-    for (int j = 0; j < r->N; ++j) {
-      const size_t o = staged.size();
-      staged.resize(o + st);
-      memcpy(&staged[o], &r->u[(size_t)j * r->usteps], st * sizeof(float));
-    }
-  }
-  const long o_st = staged.empty() ? 0 : mb.add(staged);
-  for (int i = 0; i < k; ++i) {
-    const ServeReq* r = rq[i];
-    const int st = r->usteps ? std::min(r->usteps, cap_steps) : cap_steps;
-    max_steps = std::max(max_steps, st);
-    for (int j = 0; j < r->N; ++j)
-      utab.insert(utab.end(), {r->rows[j], j, r->usteps ? (int)(o_st + soff[i] + (long)j * st) : -1, st, (int)(uint32_t)r->seed,
-                               (int)(uint32_t)(r->seed >> 32), r->top_k, __builtin_bit_cast(int, r->temperature), r->force_eos_at,
-                               __builtin_bit_cast(int, r->top_p), __builtin_bit_cast(int, r->rep_penalty), r->rep_window,
-                               r->min_frames});
-  }
-  const int nbeam = (int)tab.size() / 5;
-  if ((long)max_steps * nd > c->uniforms_cap) FAIL(VX_EINVAL, "too many uniforms (%d steps)", max_steps);
-  const long o_tab = mb.add(tab), o_adm = mb.add(adm), o_saved = mb.add(saved), o_ut = mb.add(utab),
-             o_fp = pairs.empty() ? 0 : mb.add(pairs);
-  if (int e = upload_meta(c)) return e;
-  launch_serve_uniforms(mb.dev(o_ut), nbeam, max_steps, reinterpret_cast<const float*>(c->imeta), c->d_uniforms, nd, c->sum_logp,
-                        c->row_smp, c->row_flt, c->stream);
-  if (int e = prefill_layers(c, p, mb)) return e;
-  const float* hsrc = prefill_hsrc(c, p);
-  if (!pairs.empty())
-    launch_beam_fanout(c->kc, c->vc, (long)((size_t)c->mbr * N_HEAD * c->Tmax * D_HEAD), c->NL, c->Tmax, mb.dev(o_fp),
-                       (int)pairs.size() / 3, hsrc, nullptr, c->dh, 0, c->stream);
-  launch_admit_rows(mb.dev(o_tab), nbeam, hsrc, c->dh2, c->cur_tok, c->cur_pos, c->ctx_len, c->n_gen, c->text_len, c->slot_meta,
-                    c->slot_of, c->stream);
-  launch_dec_reduce_ln_pack(nullptr, 0, D_MODEL, nullptr, c->dh2, nullptr, W(c, "ar_decoder.norm.weight"),
-                            W(c, "ar_decoder.norm.bias"), c->xp_att, nd, c->stream);
-  launch_skinny_gemm(c->pred_wp, c->xp_att, c->p_logits, PRED_NPAD, D_MODEL, SK_PRED, c->stream);
-  int* sv = c->imeta + o_saved;
-  launch_admit_mask(0, mb.dev(o_adm), sv, nd, c->active, c->slot_meta, c->slot_of, c->n_active, c->stream);
-  LAUNCH(launch_serve_sample(v->rsa, c->stream));
-  launch_admit_mask(1, mb.dev(o_adm), sv, nd, c->active, c->slot_meta, c->slot_of, c->n_active, c->stream);
-  return launch_status(c);
-}
-
-// one admission round with the f16x2 range guard of infer_continuous: a raised flag re-runs the round (prefill, fan-out, first
-// sample) on the exact-fp32 kernels; it counts in vx_last_fallbacks and towards sticky mode
-static int serve_round(vx_serve* v, const std::vector<ServeReq*>& rq) {
-  vx_ctx* c = v->c;
-  const int nd = v->nd;
-  bool raised = false;
-  auto attempt = [&](bool read_flag) -> int {
-    if (int e = serve_admit(v, rq)) return e;
-    int flag = 0;
-    D2H(v->act.data(), c->active, nd * sizeof(int));
-    D2H(v->ng.data(), c->n_gen, nd * sizeof(int));
-    if (read_flag) D2H(&flag, c->range_flag, sizeof(int));
-    SYNC();
-    raised = flag != 0;
-    return VX_OK;
-  };
-  if (fb_direct(c, c->sticky_prefill_f32, c->sticky_prefill_age)) {
-    ++c->st_fb_prefill; ++c->fb_total;
-    if (int e = ensure_f32_buffers(c)) return e;
-    F32Scope f32(c);
-    if (int e = attempt(false)) return e;
-  } else {
-    if (int e = attempt(range_guarded(c))) return e;
-    fb_outcome(c, raised, c->fb_prefill_raises, c->sticky_prefill_f32, c->sticky_prefill_age);
-    if (raised) {
-      HIPCHK(hipMemsetAsync(c->range_flag, 0, sizeof(int), c->stream));
-      ++c->st_fb_prefill; ++c->fb_total;
-      if (int e = ensure_f32_buffers(c)) return e;
-      F32Scope f32(c);
-      if (int e = attempt(false)) return e;
-    }
-  }
-  for (ServeReq* r : rq)
-    for (int j = 0; j < r->N; ++j) {
-      const int d = r->rows[j];
-      v->occ[d] = r; v->beam[d] = j; v->done_by[d] = (int)v->steps + r->cap(c->gen_stride);
-    }
-  return VX_OK;
-}
-
-// NAR stages of the first n pending requests (each reduced to its selected beam), then their codes to the caller
-static int serve_nar_group(vx_serve* v, int n, vx_serve_done_fn on_done, void* user) {
-  vx_ctx* c = v->c;
-  std::vector<std::unique_ptr<ServeReq>> grp;
-  for (int i = 0; i < n; ++i) grp.push_back(std::move(v->pend[i]));
-  v->pend.erase(v->pend.begin(), v->pend.begin() + n);
-  SYNC();                                            // the harvested gen rows and sums have arrived
-  std::vector<ServeReq*> rq(n);
-  std::vector<int> T(n), codes0((size_t)n * c->gen_stride, 0), oc;
-  for (int i = 0; i < n; ++i) {
-    ServeReq* r = rq[i] = grp[i].get();
-    const int pick = select_beam(r->slp.data(), r->ng.data(), r->N, r->Tp, r->length_penalty, r->worst);
-    T[i] = r->ng[pick];
-    std::copy(r->gen[pick].begin(), r->gen[pick].begin() + T[i], codes0.begin() + (size_t)i * c->gen_stride);
-  }
-  ReqBatch rb(rq);
-  long sumT = 0;
-  hipEvent_t e1 = c->ev_t[1], e2 = c->ev_t[2];
-  HIPCHK(hipEventRecord(e1, c->stream));
-  if (int e = nar_generate(c, &rb.b, 0, n, T, codes0.data(), c->gen_stride, oc, sumT)) return e;
-  HIPCHK(hipEventRecord(e2, c->stream));
-  HIPCHK(hipEventSynchronize(e2));
-  float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, e1, e2)); c->st_nar_ms += ms;
-  long off = 0;
-  std::vector<int64_t> out;
-  for (int i = 0; i < n; ++i) {
-    c->st_frames += T[i];
-    const bool forced = rq[i]->force_eos_at >= 0 && rq[i]->force_eos_at <= c->gen_stride;     // the request's own cap
-    if (T[i] >= c->gen_stride && c->gen_stride < 16 * rq[i]->S && !forced) ++c->st_truncated;
-    out.assign((size_t)std::max(1, T[i]) * N_Q, 0);
-    for (int t = 0; t < T[i]; ++t) {
-      int64_t* o = out.data() + (size_t)t * N_Q;
-      o[0] = codes0[(size_t)i * c->gen_stride + t];
-      for (int st = 0; st < N_Q - 1; ++st) o[st + 1] = oc[(size_t)st * sumT + off + t];
-    }
-    off += T[i];
-    if (on_done) on_done(user, rq[i]->id, out.data(), T[i]);
-  }
-  return VX_OK;
-}
-
-static int serve_run(vx_serve* v, int max_steps, vx_serve_done_fn on_done, void* user) {
-  vx_ctx* c = v->c;
-  const int nd = v->nd;
-  hipEvent_t e0 = c->ev_t[0], e1 = c->ev_t[1];
-  HIPCHK(hipEventRecord(e0, c->stream));
-  const long start = v->steps;
-  const int sync_every = v->s.sync_every > 0 ? v->s.sync_every : 8;
-  const int gs = (c->graph_multi && sync_every % GRAPH_STEPS == 0) ? GRAPH_STEPS : 1;
-  for (;;) {
-    // harvest: the beam rows that stopped hand their ids and sums to the host (delivered at the next sync) and free their rows
-    for (int d = 0; d < nd; ++d) {
-      ServeReq* r = v->occ[d];
-      if (!r || v->act[d]) continue;
-      const int j = v->beam[d];
-      r->ng[j] = v->ng[d];
-      r->gen[j].assign(std::max(1, v->ng[d]), 0);
-      if (v->ng[d]) D2H(r->gen[j].data(), c->gen + (size_t)d * c->gen_stride, v->ng[d] * sizeof(int));
-      D2H(&r->slp[j], c->sum_logp + d, sizeof(float));
-      v->occ[d] = nullptr;
-      if (++r->harvested == r->N) {
-        auto it = std::find_if(v->live.begin(), v->live.end(), [&](const std::unique_ptr<ServeReq>& q) { return q.get() == r; });
-        v->pend.push_back(std::move(*it));
-        v->live.erase(it);
-      }
-    }
-    // admission, first come first served: the head waits for best_of free rows, a later request does not overtake it
-    std::vector<int> freed;
-    for (int d = 0; d < nd; ++d) if (!v->occ[d]) freed.push_back(d);
-    std::vector<ServeReq*> rq;
-    size_t used = 0;
-    while (!v->waiting.empty() && (size_t)v->waiting.front()->N <= freed.size() - used) {
-      std::unique_ptr<ServeReq> r = std::move(v->waiting.front());
-      v->waiting.pop_front();
-      r->rows.assign(freed.begin() + used, freed.begin() + used + r->N);
-      used += r->N;
-      r->gen.assign(r->N, {}); r->ng.assign(r->N, 0); r->slp.assign(r->N, 0.f); r->harvested = 0;
-      rq.push_back(r.get());
-      v->live.push_back(std::move(r));
-    }
-    if (!rq.empty()) {
-      if (int e = serve_round(v, rq)) return e;
-      continue;                                      // an admitted beam may have stopped at its first sample
-    }
-    const bool live = std::any_of(v->occ.begin(), v->occ.end(), [](const ServeReq* r) { return r != nullptr; });
-    while ((int)v->pend.size() >= c->mbr)
-      if (int e = serve_nar_group(v, c->mbr, on_done, user)) return e;
-    if (!live || (max_steps > 0 && v->steps - start >= max_steps)) break;
-    // decode steps up to the next host poll, or up to the step by which a live row has stopped at the latest (its cap)
-    long soonest = (v->steps / sync_every + 1) * sync_every;
-    for (int d = 0; d < nd; ++d) if (v->occ[d]) soonest = std::min<long>(soonest, v->done_by[d]);
-    long target = std::max(soonest, v->steps + 1);
-    if (max_steps > 0) target = std::min(target, start + max_steps);
-    while (v->steps < target) {
-      const int n = (v->steps % gs == 0 && v->steps + gs <= target) ? gs : 1;
-      if (int e = ar_step_run(c, nullptr, v->sig, n, &v->rsa)) return e;
-      v->steps += n;
-    }
-    D2H(v->act.data(), c->active, nd * sizeof(int));
-    D2H(v->ng.data(), c->n_gen, nd * sizeof(int));
-    SYNC();
-  }
-  // every request harvested during this call goes through its NAR stages before the call returns
-  while (!v->pend.empty())
-    if (int e = serve_nar_group(v, std::min<int>(c->mbr, (int)v->pend.size()), on_done, user)) return e;
-  HIPCHK(hipEventRecord(e1, c->stream));
-  HIPCHK(hipEventSynchronize(e1));
-  float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-  c->st_ar_ms = ms - c->st_nar_ms;
-  c->st_steps = v->steps - start;
-  SYNC();                                            // beams harvested at the last poll of a request still decoding: delivered now
-  return VX_OK;
-}
-
-// entry points that overwrite the decode state refuse to run while a serving session owns it
-static int serve_busy(vx_ctx* c, const char* what) {
-  if (!c->serve) return VX_OK;
-  FAIL(VX_EINVAL, "%s: a serving session is open on this context (vx_serve_close it first)", what);
-}
-
-// vx_serve_submit / vx_serve_submit_ex / vx_serve_submit_filtered: smp null = the session's top_k / temperature / force_eos_at for
-// every request; flt null = the neutral filters (top_p 1, repetition penalty 1, min_frames 0)
-static int serve_submit(vx_serve* v, const vx_batch* b, const vx_request* req, const vx_request_sampling* smp,
-                        const vx_request_filters* flt, int64_t* ids_out) {
-  vx_ctx* c = v->c;
-  if (int e = check_batch(c, b, 0x7fffffff)) return e;
-  std::vector<vx_request_sampling> rs(b->batch, vx_request_sampling{sizeof(vx_request_sampling), v->s.top_k, v->s.temperature,
-                                                                    v->s.force_eos_at});
-  for (int i = 0; i < b->batch; ++i) {
-    const vx_request& q = req[i];
-    if (q.struct_size != sizeof(vx_request))
-      FAIL(VX_EINVAL, "vx_request.struct_size is %u, this library expects %zu (ABI version %d)", q.struct_size, sizeof(vx_request), VX_ABI_VERSION);
-    if (smp) {
-      const vx_request_sampling& m = smp[i];
-      if (m.struct_size != sizeof(vx_request_sampling))
-        FAIL(VX_EINVAL, "vx_request_sampling.struct_size is %u, this library expects %zu (ABI version %d)", m.struct_size,
-             sizeof(vx_request_sampling), VX_ABI_VERSION);
-      if (!(m.temperature > 0.f) || !std::isfinite(m.temperature))
-        FAIL(VX_EINVAL, "request %d: temperature must be > 0 and finite (got %g)", i, (double)m.temperature);
-      if (m.force_eos_at < -1) FAIL(VX_EINVAL, "request %d: force_eos_at must be >= -1 (got %d)", i, m.force_eos_at);
-      rs[i] = m;
-    }
-    if (flt) {
-      const vx_request_filters& f = flt[i];
-      if (f.struct_size != sizeof(vx_request_filters))
-        FAIL(VX_EINVAL, "vx_request_filters.struct_size is %u, this library expects %zu (ABI version %d)", f.struct_size,
-             sizeof(vx_request_filters), VX_ABI_VERSION);
-      if (!std::isfinite(f.top_p) || !(f.top_p > 0.f) || !(f.top_p <= 1.f))
-        FAIL(VX_EINVAL, "request %d: top_p must be in (0, 1] (got %g)", i, (double)f.top_p);
-      if (!std::isfinite(f.repetition_penalty) || !(f.repetition_penalty > 0.f))
-        FAIL(VX_EINVAL, "request %d: repetition_penalty must be > 0 and finite (got %g)", i, (double)f.repetition_penalty);
-      if (f.repetition_window < 0) FAIL(VX_EINVAL, "request %d: repetition_window must be >= 0 (got %d)", i, f.repetition_window);
-      if (f.min_frames < 0) FAIL(VX_EINVAL, "request %d: min_frames must be >= 0 (got %d)", i, f.min_frames);
-    }
-    const int N = std::max(1, q.best_of);
-    if (N > v->nd) FAIL(VX_EINVAL, "request %d: best_of %d exceeds the session's %d decode rows", i, N, v->nd);
-    if (b->text_lens[i] + 1 + b->prompt_lens[i] > c->Tmax) FAIL(VX_EINVAL, "request %d: the prompt does not fit the arena", i);
-    if (q.uniforms) {
-      // every draw the request can consume: one per generated frame + the terminating one (its own force_eos_at)
-      const int f = rs[i].force_eos_at;
-      const int need = std::min(f >= 0 ? std::min(c->gen_stride, f) : c->gen_stride, 16 * b->text_lens[i]) + 1;
-      if (q.uniforms_steps < need) FAIL(VX_EINVAL, "request %d: %d uniforms steps, it can draw %d", i, q.uniforms_steps, need);
-    }
-  }
-  std::vector<std::unique_ptr<ServeReq>> add;
-  for (int i = 0; i < b->batch; ++i) {
-    const vx_request& q = req[i];
-    auto r = std::make_unique<ServeReq>();
-    r->top_k = rs[i].top_k; r->temperature = rs[i].temperature; r->force_eos_at = rs[i].force_eos_at;
-    if (flt) {
-      r->top_p = flt[i].top_p; r->rep_penalty = flt[i].repetition_penalty;
-      r->rep_window = flt[i].repetition_window; r->min_frames = flt[i].min_frames;
-    }
-    r->N = std::max(1, q.best_of);
-    r->length_penalty = q.length_penalty;
-    r->worst = q.return_worst != 0;
-    r->seed = q.seed;
-    r->S = b->text_lens[i]; r->Tp = b->prompt_lens[i];
-    r->ids.assign(b->text_ids + (long)i * b->text_stride, b->text_ids + (long)i * b->text_stride + r->S);
-    r->lang.assign(b->text_lang + (long)i * b->text_stride, b->text_lang + (long)i * b->text_stride + r->S);
-    r->pc.assign(b->prompt_codes + (long)i * b->prompt_stride * N_Q, b->prompt_codes + ((long)i * b->prompt_stride + r->Tp) * N_Q);
-    if (q.uniforms) {       // [uniforms_steps][N] -> [N][steps], only the draws that can be consumed
-      r->usteps = std::min(q.uniforms_steps, c->gen_stride + 1);
-      r->u.resize((size_t)r->N * r->usteps);
-      for (int j = 0; j < r->N; ++j)
-        for (int t = 0; t < r->usteps; ++t) r->u[(size_t)j * r->usteps + t] = q.uniforms[(long)t * r->N + j];
-    }
-    add.push_back(std::move(r));
-  }
-  for (int i = 0; i < b->batch; ++i) {
-    add[i]->id = v->next_id++;
-    if (ids_out) ids_out[i] = add[i]->id;
-    v->waiting.push_back(std::move(add[i]));
-  }
-  return VX_OK;
-}
-
-// vx_serve_cancel: 0 unknown / delivered / cancelled, 1 waiting (removed), 2 decoding (its rows stop and are free)
-static int serve_cancel(vx_serve* v, int64_t id, int* state) {
-  vx_ctx* c = v->c;
-  *state = 0;
-  auto wi = std::find_if(v->waiting.begin(), v->waiting.end(), [&](const std::unique_ptr<ServeReq>& q) { return q->id == id; });
-  if (wi != v->waiting.end()) {
-    v->waiting.erase(wi);
-    *state = 1;
-    return VX_OK;
-  }
-  auto li = std::find_if(v->live.begin(), v->live.end(), [&](const std::unique_ptr<ServeReq>& q) { return q->id == id; });
-  if (li == v->live.end()) return VX_OK;
-  // its beam rows that are still occupied (a beam harvested earlier has freed its row already): inactive before the next step,
-  // slot records and n_active corrected on the stream, free on the host; the harvest never looks at them again
-  unsigned rows = 0;
-  for (int d = 0; d < v->nd; ++d)
-    if (v->occ[d] == li->get()) { rows |= 1u << d; v->occ[d] = nullptr; }
-  if (rows) launch_serve_cancel(rows, v->nd, c->active, c->slot_meta, c->slot_of, c->n_active, c->stream);
-  HIPCHK(hipGetLastError());
-  SYNC();                                           // the rows are stopped before the call returns (cancel is rare: one sync)
-  v->live.erase(li);
-  *state = 2;
-  return VX_OK;
 }
 
 }  // namespace vxe
@@ -1733,7 +936,7 @@ int vx_create(int device_id, const vx_config* cfg, vx_ctx** out) {
 
 void vx_destroy(vx_ctx* c) {
   if (!c) return;
-  delete c->serve;                 // an open session goes with its context
+  serve_free(c->serve);            // an open session goes with its context
   c->serve = nullptr;
   (void)hipSetDevice(c->dev);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
@@ -1761,18 +964,14 @@ int vx_ar_prefill(vx_ctx* c, const vx_batch* b) {
   HIPCHK(hipSetDevice(c->dev));
   if (int e = check_batch(c, b, c->mbr)) return e;
   c->st_fb_prefill = c->st_fb_nar = 0;
-  bool raised = fb_direct(c, c->sticky_prefill_f32, c->sticky_prefill_age);
-  if (!raised) {
-    if (int e = ar_prefill(c, b, 0, b->batch)) return e;
-    if (int e = take_range_flag(c, &raised)) return e;       // syncs when the mode is guarded
-    fb_outcome(c, raised, c->fb_prefill_raises, c->sticky_prefill_f32, c->sticky_prefill_age);
-  }
-  if (raised) {
-    ++c->st_fb_prefill; ++c->fb_total;
-    if (int e = ensure_f32_buffers(c)) return e;
-    F32Scope f32(c);
-    if (int e = ar_prefill(c, b, 0, b->batch)) return e;
-  }
+  // no sync of its own to ride on: the flag is read synchronously (a no-op on the fp32 kernels)
+  if (int e = guarded(c, prefill_kind(c), [&]() -> int {
+        bool raised = false;
+        if (int e2 = ar_prefill(c, b, 0, b->batch)) return e2;
+        if (int e2 = take_range_flag(c, &raised)) return e2;
+        return raised ? VX_RETRY_F32 : VX_OK;
+      }))
+    return e;
   SYNC();                 // the seam returns with the prefill complete in every mode
   HIPCHK(hipGetLastError());
   return VX_OK;
@@ -1824,226 +1023,9 @@ int vx_nar(vx_ctx* c, const vx_batch* b, const int32_t* codes0, int32_t codes0_s
   if (int e = nar_generate(c, b, 0, b->batch, T, codes0, codes0_stride, oc, sumT)) return e;
   long off = 0;
   for (int i = 0; i < b->batch; ++i) {
-    for (int t = 0; t < T[i]; ++t) {
-      int64_t* o = out_codes + ((long)i * out_stride + t) * N_Q;
-      o[0] = codes0[(long)i * codes0_stride + t];
-      for (int st = 0; st < N_Q - 1; ++st) o[st + 1] = oc[(size_t)st * sumT + off + t];
-    }
+    interleave_codes(out_codes + (long)i * out_stride * N_Q, codes0 + (long)i * codes0_stride, oc, sumT, off, T[i]);
     off += T[i];
   }
-  return VX_OK;
-}
-
-int vx_infer(vx_ctx* c, const vx_batch* b, const vx_sampling* s, int64_t* out_codes, int32_t out_stride,
-             int32_t* out_lens) {
-  if (!c || !s || !out_codes || !out_lens) return VX_EINVAL;
-  if (int e = serve_busy(c, "vx_infer")) return e;
-  HIPCHK(hipSetDevice(c->dev));
-  if (s->struct_size != sizeof(vx_sampling))
-    FAIL(VX_EINVAL, "vx_sampling.struct_size is %u, this library expects %zu (ABI version %d)", s->struct_size, sizeof(vx_sampling), VX_ABI_VERSION);
-  if (int e = check_batch(c, b, c->cfg.max_batch)) return e;
-  if (!(s->temperature > 0.f)) FAIL(VX_EINVAL, "temperature must be > 0");
-  c->st_steps = 0; c->st_frames = 0; c->st_ar_ms = 0; c->st_nar_ms = 0; c->st_truncated = 0;
-  c->st_fb_prefill = c->st_fb_nar = 0;
-  // a row that fills the arena although neither EOS, the reference's 16*S cap nor a forced EOS ended it was cut short
-  auto cut_by_arena = [&](int n, int S) {
-    return n >= c->gen_stride && c->gen_stride < 16 * S && !(s->force_eos_at >= 0 && s->force_eos_at <= c->gen_stride);
-  };
-  hipEvent_t e0 = c->ev_t[0], e1 = c->ev_t[1], e2 = c->ev_t[2];      // owned by the context: nothing to leak on an early return
-  if (s->best_of > 1) {
-    // best-of-N beams of every row (models/vallex.py:491,525-527): each row is decoded as N beams that sample independently, beams
-    // that emit EOS stop; per row, selection on sum(logp) / len^penalty (:583-594), then the NAR stages run on the chosen beams only
-    // (:600).  A micro-batch holds R = mbr / N rows = R*N decode rows; row r's result is what a batch-1 call on that row alone
-    // returns with the same draws (uniforms column r*N + j = beam j of row r).
-    const int N = s->best_of;
-    if (N > c->mbr) FAIL(VX_EINVAL, "best_of %d exceeds the micro-batch (%d)", N, c->mbr);
-    const int R = c->mbr / N;
-    for (int r0 = 0, k = 0; r0 < b->batch; r0 += R, ++k) {
-      const int nb = std::min(R, b->batch - r0);
-      std::vector<int> n_gen, gen, oc;
-      HIPCHK(hipEventRecord(e0, c->stream));
-      if (int e = ar_generate(c, b, s, r0, nb, n_gen, gen, N, beam_seed(s->seed, k))) return e;
-      HIPCHK(hipEventRecord(e1, c->stream));
-      std::vector<float> slp((size_t)nb * N);
-      D2H(slp.data(), c->sum_logp, slp.size() * sizeof(float)); SYNC();
-      std::vector<int> T(nb), codes0((size_t)nb * c->gen_stride);
-      for (int i = 0; i < nb; ++i) {
-        const int pick = i * N + select_beam(&slp[(size_t)i * N], &n_gen[(size_t)i * N], N, b->prompt_lens[r0 + i], s->length_penalty,
-                                             s->return_worst != 0);
-        T[i] = n_gen[pick];
-        if (T[i] > out_stride) FAIL(VX_EINVAL, "out_stride %d too small for %d frames", out_stride, T[i]);
-        std::copy_n(gen.begin() + (size_t)pick * c->gen_stride, c->gen_stride, codes0.begin() + (size_t)i * c->gen_stride);
-      }
-      long sumT = 0;
-      if (int e = nar_generate(c, b, r0, nb, T, codes0.data(), c->gen_stride, oc, sumT)) return e;
-      HIPCHK(hipEventRecord(e2, c->stream));
-      HIPCHK(hipEventSynchronize(e2));
-      float ms = 0;
-      HIPCHK(hipEventElapsedTime(&ms, e0, e1)); c->st_ar_ms += ms;
-      HIPCHK(hipEventElapsedTime(&ms, e1, e2)); c->st_nar_ms += ms;
-      long off = 0;
-      for (int i = 0; i < nb; ++i) {
-        out_lens[r0 + i] = T[i];
-        c->st_frames += T[i];
-        if (cut_by_arena(T[i], b->text_lens[r0 + i])) ++c->st_truncated;
-        for (int t = 0; t < T[i]; ++t) {
-          int64_t* o = out_codes + ((long)(r0 + i) * out_stride + t) * N_Q;
-          o[0] = codes0[(size_t)i * c->gen_stride + t];
-          for (int st = 0; st < N_Q - 1; ++st) o[st + 1] = oc[(size_t)st * sumT + off + t];
-        }
-        off += T[i];
-      }
-    }
-    return VX_OK;
-  }
-  for (int r0 = 0; r0 < b->batch; r0 += c->mbr) {
-    const int nb = std::min(c->mbr, b->batch - r0);
-    std::vector<int> n_gen, gen, oc;
-    HIPCHK(hipEventRecord(e0, c->stream));
-    if (int e = ar_generate(c, b, s, r0, nb, n_gen, gen, 1, s->seed)) return e;
-    HIPCHK(hipEventRecord(e1, c->stream));
-    for (int i = 0; i < nb; ++i)
-      if (n_gen[i] > out_stride) FAIL(VX_EINVAL, "out_stride %d too small for %d frames", out_stride, n_gen[i]);
-    long sumT = 0;
-    if (int e = nar_generate(c, b, r0, nb, n_gen, gen.data(), c->gen_stride, oc, sumT)) return e;
-    HIPCHK(hipEventRecord(e2, c->stream));
-    HIPCHK(hipEventSynchronize(e2));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1)); c->st_ar_ms += ms;
-    HIPCHK(hipEventElapsedTime(&ms, e1, e2)); c->st_nar_ms += ms;
-    long off = 0;
-    for (int i = 0; i < nb; ++i) {
-      out_lens[r0 + i] = n_gen[i];
-      c->st_frames += n_gen[i];
-      if (cut_by_arena(n_gen[i], b->text_lens[r0 + i])) ++c->st_truncated;
-      for (int t = 0; t < n_gen[i]; ++t) {
-        int64_t* o = out_codes + ((long)(r0 + i) * out_stride + t) * N_Q;
-        o[0] = gen[(size_t)i * c->gen_stride + t];
-        for (int st = 0; st < N_Q - 1; ++st) o[st + 1] = oc[(size_t)st * sumT + off + t];
-      }
-      off += n_gen[i];
-    }
-  }
-  return VX_OK;
-}
-
-int vx_infer_continuous(vx_ctx* c, const vx_batch* b, const vx_sampling* s, vx_row_done_fn on_row, void* user, int64_t* out_codes,
-                        int32_t out_stride, int32_t* out_lens) {
-  if (!c || !s || !out_codes || !out_lens) return VX_EINVAL;
-  if (int e = serve_busy(c, "vx_infer_continuous")) return e;
-  HIPCHK(hipSetDevice(c->dev));
-  if (s->struct_size != sizeof(vx_sampling))
-    FAIL(VX_EINVAL, "vx_sampling.struct_size is %u, this library expects %zu (ABI version %d)", s->struct_size, sizeof(vx_sampling), VX_ABI_VERSION);
-  // any number of rows: the call holds device memory for its min(max_batch, 32) decode rows and one NAR group only
-  if (int e = check_batch(c, b, 0x7fffffff)) return e;
-  if (!(s->temperature > 0.f)) FAIL(VX_EINVAL, "temperature must be > 0");
-  if (s->best_of > 1) FAIL(VX_EINVAL, "vx_infer_continuous does not run best_of > 1 (use vx_infer)");
-  c->st_steps = 0; c->st_frames = 0; c->st_ar_ms = 0; c->st_nar_ms = 0; c->st_truncated = 0;
-  c->st_fb_prefill = c->st_fb_nar = 0;
-  return infer_continuous(c, b, s, on_row, user, out_codes, out_stride, out_lens);
-}
-
-int vx_serve_open(vx_ctx* c, const vx_sampling* s, vx_serve** out) {
-  if (!c || !s || !out) return VX_EINVAL;
-  HIPCHK(hipSetDevice(c->dev));
-  if (!c->finalized) FAIL(VX_ESTATE, "weights not finalized");
-  if (s->struct_size != sizeof(vx_sampling))
-    FAIL(VX_EINVAL, "vx_sampling.struct_size is %u, this library expects %zu (ABI version %d)", s->struct_size, sizeof(vx_sampling), VX_ABI_VERSION);
-  if (c->serve) FAIL(VX_EINVAL, "a serving session is already open on this context");
-  if (!(s->temperature > 0.f)) FAIL(VX_EINVAL, "temperature must be > 0");
-  if (s->best_of > 1 || s->seed != 0 || s->uniforms || (s->length_penalty != 0.f && s->length_penalty != 1.f) || s->return_worst)
-    FAIL(VX_EINVAL, "vx_serve_open: best_of, seed, uniforms, length_penalty and return_worst are per request (vx_request)");
-  auto* v = new vx_serve();
-  v->c = c;
-  v->s = *s;
-  v->s.best_of = 1; v->s.length_penalty = 1.f;
-  v->nd = c->mbr;
-  v->occ.assign(v->nd, nullptr);
-  v->beam.assign(v->nd, 0); v->done_by.assign(v->nd, 0); v->act.assign(v->nd, 0); v->ng.assign(v->nd, 0);
-  v->slot_of.resize(v->nd);
-  for (int d = 0; d < v->nd; ++d) v->slot_of[d] = d;
-  // the per-row sampling records (allocated once per context, before any step graph of a session is captured)
-  if (!c->row_smp) {
-    if (int e = dev_alloc(c, &c->row_smp, 4 * MB)) { delete v; return e; }
-  }
-  if (!c->row_flt) {
-    if (int e = dev_alloc(c, &c->row_flt, 4 * MB)) { delete v; return e; }
-  }
-  if (int e = serve_setup(c, v->nd)) { delete v; return e; }
-  // the per-row sampler (serve_sample.hip) with dec_sample's buffers: every beam row draws from its own column of d_uniforms
-  // (injected or counter-based) and accumulates sum_logp (best_of is per request); top_k / temperature / force_eos_at come from
-  // row_smp, so they are not part of the graph signature
-  const SampleArgs sa = make_sample_args(c, &v->s, 1, nullptr);
-  ServeSampleArgs& r = v->rsa;
-  r.partial = sa.partial; r.splitk = sa.splitk; r.npad = sa.npad;
-  r.row_smp = c->row_smp;
-  r.row_flt = c->row_flt;           // every admission writes its rows' records; no sample runs on a row before its admission
-  r.uniforms = c->d_uniforms; r.uniforms_stride = sa.uniforms_stride;
-  r.cur_tok = sa.cur_tok; r.cur_pos = sa.cur_pos; r.ctx_len = sa.ctx_len; r.n_gen = sa.n_gen; r.active = sa.active;
-  r.n_active = sa.n_active; r.text_len = sa.text_len; r.slot_meta = sa.slot_meta; r.slot_of = sa.slot_of;
-  r.gen = sa.gen; r.gen_stride = sa.gen_stride; r.sum_logp = c->sum_logp; r.batch = sa.batch;
-  r.emb_tab = sa.emb_tab; r.emb_alpha = sa.emb_alpha; r.pe = sa.pe; r.ln_g = sa.ln_g; r.ln_b = sa.ln_b; r.emb_h = sa.emb_h;
-  r.emb_xp = sa.emb_xp; r.wt = sa.wt;
-  char sig[160];
-  snprintf(sig, sizeof sig, "b%d ns%d c%d%d%d serve-rows u1 l1", v->nd, c->nsplit, (int)c->sb_chain, (int)c->sb_qkv, (int)c->split_fused);
-  v->sig = sig;
-  c->serve = v;
-  *out = v;
-  return VX_OK;
-}
-
-int vx_serve_submit(vx_serve* v, const vx_batch* b, const vx_request* req, int64_t* ids_out) {
-  if (!v || !req) return VX_EINVAL;
-  return serve_submit(v, b, req, nullptr, nullptr, ids_out);
-}
-
-int vx_serve_submit_ex(vx_serve* v, const vx_batch* b, const vx_request* req, const vx_request_sampling* smp, int64_t* ids_out) {
-  if (!v || !req) return VX_EINVAL;
-  return serve_submit(v, b, req, smp, nullptr, ids_out);
-}
-
-int vx_serve_submit_filtered(vx_serve* v, const vx_batch* b, const vx_request* req, const vx_request_sampling* smp,
-                             const vx_request_filters* flt, int64_t* ids_out) {
-  if (!v || !req) return VX_EINVAL;
-  return serve_submit(v, b, req, smp, flt, ids_out);
-}
-
-int vx_serve_cancel(vx_serve* v, int64_t request_id, int32_t* state) {
-  if (!v) return VX_EINVAL;
-  vx_ctx* c = v->c;
-  if (v->running) FAIL(VX_EINVAL, "vx_serve_cancel: called from inside vx_serve_run (on_done); cancel between two vx_serve_run calls");
-  HIPCHK(hipSetDevice(c->dev));
-  int st = 0;
-  if (int e = serve_cancel(v, request_id, &st)) return e;
-  if (state) *state = st;
-  return VX_OK;
-}
-
-int vx_serve_run(vx_serve* v, int32_t max_steps, vx_serve_done_fn on_done, void* user, int32_t* live_requests,
-                 int32_t* waiting_requests) {
-  if (!v) return VX_EINVAL;
-  vx_ctx* c = v->c;
-  if (v->running) FAIL(VX_EINVAL, "vx_serve_run: called from inside vx_serve_run (on_done)");
-  HIPCHK(hipSetDevice(c->dev));
-  c->st_steps = 0; c->st_frames = 0; c->st_ar_ms = 0; c->st_nar_ms = 0; c->st_truncated = 0;
-  c->st_fb_prefill = c->st_fb_nar = 0;
-  v->running = true;
-  const int rc = serve_run(v, max_steps, on_done, user);
-  v->running = false;
-  if (rc) return rc;
-  if (live_requests) *live_requests = (int32_t)v->live.size();
-  if (waiting_requests) *waiting_requests = (int32_t)v->waiting.size();
-  return VX_OK;
-}
-
-int vx_serve_close(vx_serve* v) {
-  if (!v) return VX_EINVAL;
-  vx_ctx* c = v->c;
-  HIPCHK(hipSetDevice(c->dev));
-  SYNC();                                           // no copy in flight may target a request that is about to go
-  c->serve = nullptr;
-  delete v;
-  // the next vx_infer sets its own geometry (ar_prefill); nothing of the session's decode state is read again
   return VX_OK;
 }
 

@@ -1,4 +1,5 @@
-// Internal declarations shared by the engine's translation units (engine.hip: context, AR / NAR drivers and the hot-path ABI;
+// Internal declarations shared by the engine's translation units (engine.hip: context, prefill / decode step / NAR and their seams;
+// schedule.hip: the three host schedulers -- vx_infer, vx_infer_continuous, the serving session -- and their ABI entries;
 // weights.hip: ingest of the reference state-dict; vocoders.hip: Vocos head, EnCodec decoder / encoder drivers;
 // beams.hip: the best_of fan-out; admit.hip / serve.hip: admission kernels of the continuous schedule / the serving session;
 // serve_sample.hip: the serving session's per-row sampler;
@@ -14,6 +15,7 @@
 
 #include <algorithm>
 #include <array>
+#include <functional>
 #include <map>
 #include <string>
 #include <thread>
@@ -215,6 +217,13 @@ struct vx_ctx {
     return (code);                              \
   } while (0)
 
+// every struct that crosses the C ABI carries its size: a caller built against another header is refused, not misread
+#define CHECK_STRUCT(v, T)                                                                                                          \
+  do {                                                                                                                              \
+    if ((v).struct_size != sizeof(T))                                                                                               \
+      FAIL(VX_EINVAL, #T ".struct_size is %u, this library expects %zu (ABI version %d)", (v).struct_size, sizeof(T), VX_ABI_VERSION); \
+  } while (0)
+
 // launchers that compile a split count in return false instead of launching an uninstantiated configuration
 #define LAUNCH(call)                                      \
   do {                                                    \
@@ -368,12 +377,11 @@ void launch_admit_mask(int phase, const int* admitted, int* saved, int nrows, in
 void launch_admit_uniforms(const int* pairs, int n, const float* staged, int steps, unsigned long long seed, float* u, int ncols,
                            hipStream_t s);
 
-// serving session (serve.hip): draws + sum_logp reset of admitted beam rows.  tab [n][6] = {decode row d, beam j, offset of the
-// request's staged draws of beam j in `staged` (-1: counter-based, keyed on (seed, j)), draws to write, seed low, seed high word}
-// ... it also writes the admitted rows' sampling record row_smp[4 d .. 4 d + 3] = {top_k, temperature bits, force_eos_at, 0}:
-// tab [n][9] = the six words above + {top_k, temperature bits, force_eos_at}
-// ... and their filter record row_flt[4 d .. 4 d + 3] = {top_p bits, repetition penalty bits, repetition window, min_frames}:
-// tab [n][13] = the nine words above + those four
+// serving session (serve.hip): one launch per admission writes, for every admitted beam row, its draws, a zero sum_logp and its two
+// per-row records.  tab [n][SERVE_UTAB], 13 words per beam row:
+//   0 decode row d | 1 beam j | 2 offset of beam j's staged draws in `staged` (-1: counter-based, keyed on (seed, j)) | 3 draws to write
+//   4, 5 seed low / high word | 6 top_k | 7 temperature bits | 8 force_eos_at   -> row_smp[4 d ..] = {top_k, temperature bits, force_eos_at, 0}
+//   9 top_p bits | 10 repetition penalty bits | 11 repetition window | 12 min_frames   -> row_flt[4 d ..] = those four
 constexpr int SERVE_UTAB = 13;
 void launch_serve_uniforms(const int* tab, int n, int max_steps, const float* staged, float* u, int ncols, float* sum_logp,
                            int* row_smp, int* row_flt, hipStream_t s);
@@ -424,11 +432,43 @@ int full_layer(vx_ctx* c, const LayerW& L, long M, const int* seq_off, const int
                const float* ada1, const float* ada2, float* kcl, float* vcl, const int* row_b, const int* row_t, double attn_flops,
                const Trim* tr = nullptr);
 int prefill_tables(vx_ctx* c, const vx_batch* b, int r0, int nb, PrefillPlan& p, MetaBuilder& mb);
-bool fb_direct(vx_ctx* c, bool sticky, int& age);
-void fb_outcome(vx_ctx* c, bool raised, int& raises, bool& sticky, int& age);
+// engine.hip, shared with the schedulers (schedule.hip)
+constexpr int GRAPH_STEPS = 4;       // decode steps per multi-step graph launch (ar_step_run)
+int ar_prefill(vx_ctx* c, const vx_batch* b, int r0, int nb, int beams = 1);
+void prefill_embed(vx_ctx* c, const PrefillPlan& p, const MetaBuilder& mb);
+int prefill_layers(vx_ctx* c, const PrefillPlan& p, const MetaBuilder& mb);
+const float* prefill_hsrc(const vx_ctx* c, const PrefillPlan& p);
+int reset_decode_state(vx_ctx* c, const MetaBuilder& mb, int nrows, long o_pos, long o_ctx, long o_zero, long o_active, long o_text,
+                       long o_meta, long o_slot);
+int ar_step_run(vx_ctx* c, const SampleArgs* sa, const std::string& sig, int nsteps = 1, const ServeSampleArgs* rsa = nullptr);
+// one NAR pass (engine.hip; the generating pass and the scoring pass of score.hip drive the same tables and the same stage):
+// offsets into the pass's MetaBuilder
+struct NarPlan {
+  int nb = 0, max_len = 0, n_t = 0;
+  long M = 0, Y = 0, sumT = 0;     // packed rows, prompt + generated frames, generated frames
+  double attn_flops = 0, trim_attn_flops = 0;
+  long o_off = 0, o_len = 0, o_dt = 0, o_it = 0, o_lt = 0, o_pt = 0, o_yc = 0, o_nj = 0, o_yd = 0, o_yp = 0, o_gr = 0, o_gy = 0, o_qf = 0,
+       o_co = 0;
+};
+int nar_plan(vx_ctx* c, const vx_batch* b, int r0, int nb, const std::vector<int>& T, const std::function<int(int, int)>& code0,
+             MetaBuilder& mb, NarPlan& p);
+int nar_stage(vx_ctx* c, const NarPlan& p, const MetaBuilder& mb, int st, bool taps);
+int nar_early_flag(vx_ctx* c, int st);
+int nar_generate(vx_ctx* c, const vx_batch* b, int r0, int nb, const std::vector<int>& T, const int* codes0, long codes0_stride,
+                 std::vector<int>& out_codes /* [7][sumT] */, long& sumT_out);
+void interleave_codes(int64_t* dst, const int* codes0_row, const std::vector<int>& oc, long sumT, long off, int T);
+inline void reset_call_stats(vx_ctx* c) {      // what vx_last_stats / vx_last_truncated / vx_last_fallbacks report is per call
+  c->st_steps = 0; c->st_frames = 0; c->st_ar_ms = 0; c->st_nar_ms = 0; c->st_truncated = 0;
+  c->st_fb_prefill = c->st_fb_nar = 0;
+}
+// schedule.hip: entry points that overwrite the decode state refuse to run while a serving session owns it; vx_destroy frees an open one
+int serve_busy(vx_ctx* c, const char* what);
+void serve_free(vx_serve* v);
 // score.hip: (log-probability, rank) of targets[r] in logits[r][0 .. ncols-1], one wavefront per row
 void launch_score_rows(const float* logits, int ld, int rows, int ncols, const int* targets, float* logp, int* rank, hipStream_t s);
 
+// ---- the f16x2 range guard with sticky fp32 fallback: ONE protocol for every guarded phase -------------------------------------
+// (what the guard is for: engine.hip, above range_guarded; the sticky rule: vx_ctx, above fb_prefill_raises)
 struct F32Scope {            // the full-sequence path on the exact-fp32 kernels for the lifetime of the object
   vx_ctx* c;
   int gm;
@@ -436,5 +476,43 @@ struct F32Scope {            // the full-sequence path on the exact-fp32 kernels
   explicit F32Scope(vx_ctx* c_) : c(c_), gm(c_->gemm_mode), ax(c_->attn_x3) { c->gemm_mode = 2; c->attn_x3 = false; }
   ~F32Scope() { c->gemm_mode = gm; c->attn_x3 = ax; }
 };
+
+// the end of every `once` (below): flag = the range flag as it came back on the phase's own host sync.  Raised: cleared on the stream
+// (the re-run starts from a clean flag) and VX_RETRY_F32; else VX_OK
+int retry_if_raised(vx_ctx* c, int flag);
+// ... preceded by that sync, for a `once` that has queued everything else it wants back: the flag rides along, stream sync, verdict
+int sync_guarded(vx_ctx* c);
+
+// the two phase kinds count and go sticky separately
+struct GuardKind { bool& sticky; int& age; int& raises; int& st_fb; };
+inline GuardKind prefill_kind(vx_ctx* c) { return {c->sticky_prefill_f32, c->sticky_prefill_age, c->fb_prefill_raises, c->st_fb_prefill}; }
+inline GuardKind nar_kind(vx_ctx* c) { return {c->sticky_nar_f32, c->sticky_nar_age, c->fb_nar_raises, c->st_fb_nar}; }
+
+// One guarded phase.  once() runs the phase up to and including the host sync it has anyway, reads the flag on that sync
+// (`if (range_guarded(c)) D2H(&flag, ...)`: false under F32Scope, so the fp32 run reads nothing) and ends in retry_if_raised.
+//   probe (not sticky, or every FB_STICKY_PROBE_EVERY-th phase of a sticky kind): once() on f16x2; a clean pass resets the consecutive
+//     count and leaves sticky mode, a raise counts towards it (FB_STICKY_AFTER) and the phase runs again on the exact-fp32 kernels;
+//   direct (sticky): once() on the fp32 kernels straight away; the counts do not move.
+// Either fp32 run counts in vx_last_fallbacks (k.st_fb) and in the lifetime total.
+template <typename Once>
+int guarded(vx_ctx* c, GuardKind k, Once once) {
+  const bool watch = range_guarded(c);
+  bool direct = watch && k.sticky;
+  if (direct && ++k.age >= FB_STICKY_PROBE_EVERY) { k.age = 0; direct = false; }
+  auto fb_outcome = [&](bool raised) {       // outcome of a phase that RAN on f16x2
+    if (!watch) return;
+    if (!raised) { k.raises = 0; k.sticky = false; k.age = 0; return; }
+    if (++k.raises >= FB_STICKY_AFTER && !k.sticky) { k.sticky = true; k.age = 0; ++c->sticky_engaged; }
+  };
+  if (!direct) {
+    const int e = once();
+    if (e == VX_OK || e == VX_RETRY_F32) fb_outcome(e == VX_RETRY_F32);
+    if (e != VX_RETRY_F32) return e;
+  }
+  ++k.st_fb; ++c->fb_total;
+  if (int e = ensure_f32_buffers(c)) return e;
+  F32Scope f32(c);
+  return once();
+}
 
 }  // namespace vxe

@@ -1,7 +1,7 @@
 // Teacher-forced scoring: how likely the model finds codes that already exist (vx_score, include/vallex_hip.h).
 // The quantity VALLE.forward feeds to F.cross_entropy (models/vallex.py: the AR stack on the first codebook, the NAR stages on
 // codebooks 2 .. 8) and the one best_of selects on (sum(logp) / len^penalty, models/vallex.py:572, :583-594).  Both passes drive the
-// full-sequence layers of engine.hip (full_layer + Trim) with the GIVEN codes as inputs; the one new kernel turns logit rows into
+// full-sequence layers of engine.hip (full_layer + Trim), behind the range guard of engine_ctx.h (guarded), with the GIVEN codes as inputs; the one new kernel turns logit rows into
 // (log-probability, rank) of a target id.
 #include "engine_ctx.h"
 
@@ -149,11 +149,7 @@ static int score_ar_once(vx_ctx* c, const ScoreRows& R, std::vector<float>& logp
   const long o_qf = mb.add(q_first), o_co = mb.add(c_off), o_rows = mb.add(rows), o_tg = mb.add(tg);
   if (int e = upload_meta(c)) return e;
 
-  launch_embed_rows(c->fx, mb.dev(p.o_dt), W(c, "ar_text_embedding.word_embeddings.weight"), mb.dev(p.o_it),
-                    W(c, "ar_language_embedding.word_embeddings.weight"), mb.dev(p.o_lt), W(c, "ar_text_position.alpha"),
-                    c->pe, mb.dev(p.o_pt), p.n_t, c->stream);
-  launch_embed_rows(c->fx, mb.dev(p.o_da), W(c, "ar_audio_embedding.word_embeddings.weight"), mb.dev(p.o_ia), nullptr,
-                    nullptr, W(c, "ar_audio_position.alpha"), c->pe, mb.dev(p.o_pa), p.n_a, c->stream);
+  prefill_embed(c, p, mb);
   // p.trim: the arithmetic can trim (f16x2 throughout, or fp32 throughout) -- bf16x3, the mixed switches and debug_taps run
   // every row and gather
   const Trim tr{Mc, mb.dev(o_qf), mb.dev(o_co), mb.dev(o_rows), trim_flops};
@@ -182,157 +178,49 @@ static int score_ar_once(vx_ctx* c, const ScoreRows& R, std::vector<float>& logp
   logp.resize(Mc); rank.resize(Mc);
   D2H(logp.data(), c->sc_logp, (size_t)Mc * sizeof(float));
   D2H(rank.data(), c->sc_rank, (size_t)Mc * sizeof(int));
-  int flag = 0;                          // the range flag rides on the sync that brings the results back
-  if (range_guarded(c)) D2H(&flag, c->range_flag, sizeof(int));
-  SYNC();
-  if (flag) {
-    HIPCHK(hipMemsetAsync(c->range_flag, 0, sizeof(int), c->stream));
-    return VX_RETRY_F32;
-  }
-  return VX_OK;
+  return sync_guarded(c);           // the range flag rides on the sync that brings the results back
 }
 
-// NAR pass of one group: the loop of nar_generate_once (engine.hip) -- same tables, same trimming, same final AdaLN norm, same
-// pred_w3 projection, the same kernels on the same shapes -- with the GIVEN codes[.., st + 1] accumulated behind stage st instead
-// of the arg-max, and scored instead of chosen.  logp / rank [7][sum T_b].
+// NAR pass of one group: the stages of nar_generate_once (engine.hip nar_plan / nar_stage: same tables, same trimming, same final
+// AdaLN norm, same pred_w3 projection, the same kernels on the same shapes) with the GIVEN codes[.., st + 1] accumulated behind
+// stage st instead of the arg-max, and scored instead of chosen.  logp / rank [7][sum T_b].
 static int score_nar_once(vx_ctx* c, const ScoreRows& R, std::vector<float>& logp, std::vector<int>& rank, long& sumT_out) {
-  const int NL = c->NL, nb = R.nb, r0 = R.r0;
-  const vx_batch* b = R.b;
-  const std::vector<int>& T = R.T;
-  std::vector<int> seq_off(nb), seq_len(nb), dst_t, id_t, lang_t, pos_t, ycodes, ynj, ydst, ypos, gen_rows, gen_y, q_first(nb), c_off(nb);
-  long M = 0, Y = 0, sumT = 0;
-  int max_len = 0;
-  double trim_attn_flops = 0;
-  for (int i = 0; i < nb; ++i) {
-    const int r = r0 + i, S = b->text_lens[r], Tp = b->prompt_lens[r];
-    seq_off[i] = (int)M; seq_len[i] = S + Tp + T[i];
-    q_first[i] = S + Tp; c_off[i] = (int)sumT;
-    trim_attn_flops += 4.0 * T[i] * (double)seq_len[i] * D_MODEL;
-    max_len = std::max(max_len, seq_len[i]);
-    for (int s = 0; s < S; ++s) {
-      dst_t.push_back((int)M + s);
-      id_t.push_back(b->text_ids[(long)r * b->text_stride + s]);
-      lang_t.push_back(b->text_lang[(long)r * b->text_stride + s]);
-      pos_t.push_back(s);
-    }
-    for (int t = 0; t < Tp + T[i]; ++t) {
-      if (t < Tp) {
-        for (int j = 0; j < N_Q; ++j) ycodes.push_back(b->prompt_codes[((long)r * b->prompt_stride + t) * N_Q + j]);
-        ynj.push_back(N_Q);
-      } else {
-        ycodes.push_back(R.code(i, t - Tp, 0));
-        for (int j = 1; j < N_Q; ++j) ycodes.push_back(0);
-        ynj.push_back(1);
-        gen_rows.push_back((int)M + S + t);
-        gen_y.push_back((int)Y + t);
-      }
-      ydst.push_back((int)M + S + t);
-      ypos.push_back(t);
-    }
-    M += seq_len[i]; Y += Tp + T[i]; sumT += T[i];
-  }
-  sumT_out = sumT;
+  const int nb = R.nb;
+  MetaBuilder mb(c);
+  NarPlan p;
+  if (int e = nar_plan(c, R.b, R.r0, nb, R.T, [&](int i, int t) { return R.code(i, t, 0); }, mb, p)) return e;
+  const long sumT = sumT_out = p.sumT;
   logp.assign((size_t)(N_Q - 1) * sumT, 0.f);
   rank.assign((size_t)(N_Q - 1) * sumT, 0);
   if (sumT == 0) return VX_OK;
-  if (M > c->Mmax) FAIL(VX_EINVAL, "NAR rows %ld exceed arena %ld", M, c->Mmax);
   std::vector<int> tg((size_t)(N_Q - 1) * sumT);           // [7][sumT]: the targets of stage st = the given codebook st + 1
   for (int st = 0; st < N_Q - 1; ++st) {
     long off = 0;
     for (int i = 0; i < nb; ++i) {
-      for (int t = 0; t < T[i]; ++t) tg[(size_t)st * sumT + off + t] = R.code(i, t, st + 1);
-      off += T[i];
+      for (int t = 0; t < R.T[i]; ++t) tg[(size_t)st * sumT + off + t] = R.code(i, t, st + 1);
+      off += R.T[i];
     }
   }
-  MetaBuilder mb(c);
-  const long o_off = mb.add(seq_off), o_len = mb.add(seq_len), o_dt = mb.add(dst_t), o_it = mb.add(id_t),
-             o_lt = mb.add(lang_t), o_pt = mb.add(pos_t), o_yc = mb.add(ycodes), o_nj = mb.add(ynj), o_yd = mb.add(ydst),
-             o_yp = mb.add(ypos), o_gr = mb.add(gen_rows), o_gy = mb.add(gen_y), o_qf = mb.add(q_first), o_co = mb.add(c_off),
-             o_tg = mb.add(tg);
+  const long o_tg = mb.add(tg);
   if (int e = upload_meta(c)) return e;
 
-  launch_nar_yemb_init(c->fyemb, c->nar_tabs_dev, mb.dev(o_yc), mb.dev(o_nj), (int)Y, c->stream);
-  double attn_flops = 0;
-  for (int i = 0; i < nb; ++i) attn_flops += 4.0 * seq_len[i] * (double)seq_len[i] * D_MODEL;
-  const int nnorm = 2 * NL + 1;
+  launch_nar_yemb_init(c->fyemb, c->nar_tabs_dev, mb.dev(p.o_yc), mb.dev(p.o_nj), (int)p.Y, c->stream);
   for (int st = 0; st < N_Q - 1; ++st) {
-    launch_embed_rows(c->fx, mb.dev(o_dt), W(c, "nar_text_embedding.word_embeddings.weight"), mb.dev(o_it),
-                      W(c, "nar_language_embedding.word_embeddings.weight"), mb.dev(o_lt),
-                      W(c, "nar_text_position.alpha"), c->pe, mb.dev(o_pt), (int)dst_t.size(), c->stream);
-    launch_add_pe_scatter(c->fx, mb.dev(o_yd), c->fyemb, W(c, "nar_audio_position.alpha"), c->pe, mb.dev(o_yp), (int)Y,
-                          c->stream);
-    const float* ada = c->ada + (size_t)st * nnorm * 2 * D_MODEL;
-    const bool trim_h2 = c->gemm_mode == 0 && c->attn_x3 && c->attn_h2, trim_f32 = c->gemm_mode == 2 && !c->attn_x3;
-    const bool trim = c->nar_trim && (trim_h2 || trim_f32) && !c->cfg.debug_taps;
-    const Trim tr{sumT, mb.dev(o_qf), mb.dev(o_co), mb.dev(o_gr), trim_attn_flops};
-    for (int l = 0; l < NL; ++l)
-      if (int e = full_layer(c, c->nar[l], M, mb.dev(o_off), mb.dev(o_len), nullptr, nb, max_len,
-                             ada + (size_t)(2 * l) * 2 * D_MODEL, ada + (size_t)(2 * l + 1) * 2 * D_MODEL, nullptr, nullptr,
-                             nullptr, nullptr, attn_flops, (trim && l == NL - 1) ? &tr : nullptr))
-        return e;
-    const float* adaf = ada + (size_t)(2 * NL) * 2 * D_MODEL;
-    char nm[64];
-    snprintf(nm, sizeof nm, "nar_predict_layers.%d.weight", st);
-    if (trim && trim_f32) {
-      launch_layernorm(c->fqkv, D_MODEL, c->fxn, D_MODEL, (int)sumT, D_MODEL, LN_EPS, W(c, "nar_decoder.norm.norm.weight"),
-                       W(c, "nar_decoder.norm.norm.bias"), adaf, adaf + D_MODEL, c->stream);
-      proj(c, c->fxn, D_MODEL, W(c, nm), c->pred_w3[st], nullptr, nullptr, 0, c->flogits, AUDIO_VOCAB, sumT, AUDIO_VOCAB, D_MODEL, ACT_NONE);
-    } else if (trim) {
-      launch_layernorm(c->fxn, D_MODEL, nullptr, D_MODEL, (int)sumT, D_MODEL, LN_EPS, W(c, "nar_decoder.norm.norm.weight"),
-                       W(c, "nar_decoder.norm.norm.bias"), adaf, adaf + D_MODEL, c->stream, c->fa3, h2_plane(sumT, D_MODEL, H2_TILE_A),
-                       c->range_flag);
-      proj(c, nullptr, D_MODEL, W(c, nm), c->pred_w3[st], nullptr, nullptr, 0, c->flogits, AUDIO_VOCAB, sumT, AUDIO_VOCAB, D_MODEL,
-           ACT_NONE, nullptr, c->fa3);
-    } else {
-      launch_layernorm(c->fx, D_MODEL, c->fxn, D_MODEL, (int)M, D_MODEL, LN_EPS, W(c, "nar_decoder.norm.norm.weight"),
-                       W(c, "nar_decoder.norm.norm.bias"), adaf, adaf + D_MODEL, c->stream);
-      proj(c, c->fxn, D_MODEL, W(c, nm), c->pred_w3[st], nullptr, nullptr, 0, c->flogits, AUDIO_VOCAB, sumT, AUDIO_VOCAB, D_MODEL,
-           ACT_NONE, mb.dev(o_gr));
-    }
+    if (int e = nar_stage(c, p, mb, st, false)) return e;
     const int* given = mb.dev(o_tg) + (long)st * sumT;
     launch_score_rows(c->flogits, AUDIO_VOCAB, (int)sumT, AUDIO_VOCAB, given, c->sc_logp + (long)st * sumT, c->sc_rank + (long)st * sumT,
                       c->stream);
-    if (st == 0 && c->fb_nar_raises > 0 && range_guarded(c)) {      // as nar_generate_once: an early look behind stage 0
-      int early = 0;
-      D2H(&early, c->range_flag, sizeof(int));
-      SYNC();
-      if (early) {
-        HIPCHK(hipMemsetAsync(c->range_flag, 0, sizeof(int), c->stream));
-        return VX_RETRY_F32;
-      }
-    }
+    if (int r = nar_early_flag(c, st)) return r;
     if (st < N_Q - 2) {
+      char nm[64];
       snprintf(nm, sizeof nm, "nar_audio_embeddings.%d.word_embeddings.weight", st + 1);
-      launch_embed_accum(c->fyemb, mb.dev(o_gy), W(c, nm), given, (int)sumT, c->stream);
+      launch_embed_accum(c->fyemb, mb.dev(p.o_gy), W(c, nm), given, (int)sumT, c->stream);
     }
   }
   HIPCHK(hipGetLastError());
   D2H(logp.data(), c->sc_logp, logp.size() * sizeof(float));
   D2H(rank.data(), c->sc_rank, rank.size() * sizeof(int));
-  int flag = 0;
-  if (range_guarded(c)) D2H(&flag, c->range_flag, sizeof(int));
-  SYNC();
-  if (flag) {
-    HIPCHK(hipMemsetAsync(c->range_flag, 0, sizeof(int), c->stream));
-    return VX_RETRY_F32;
-  }
-  return VX_OK;
-}
-
-// a pass behind the f16x2 range guard, as vx_ar_prefill / vx_nar run theirs: a raised flag re-runs it on the fp32 kernels, counts
-// in vx_last_fallbacks and towards sticky mode
-template <typename Once>
-static int score_guarded(vx_ctx* c, bool& sticky, int& age, int& raises, int& st_fb, Once once) {
-  int e = VX_RETRY_F32;
-  if (!fb_direct(c, sticky, age)) {
-    e = once();
-    if (e == VX_OK || e == VX_RETRY_F32) fb_outcome(c, e == VX_RETRY_F32, raises, sticky, age);
-    if (e != VX_RETRY_F32) return e;
-  }
-  ++st_fb; ++c->fb_total;
-  if ((e = ensure_f32_buffers(c))) return e;
-  F32Scope f32(c);
-  return once();
+  return sync_guarded(c);
 }
 
 }  // namespace vxe
@@ -363,8 +251,7 @@ int vx_score(vx_ctx* c, const vx_batch* b, const int64_t* codes, int32_t codes_s
         if (v < 0 || v >= AUDIO_VOCAB) FAIL(VX_EINVAL, "vx_score: codes: row %d frame %d codebook %d: %lld outside 0 .. 1023", i, t, q, (long long)v);
       }
   if (int e = score_buffers(c)) return e;
-  c->st_steps = 0; c->st_frames = 0; c->st_ar_ms = 0; c->st_nar_ms = 0; c->st_truncated = 0;
-  c->st_fb_prefill = c->st_fb_nar = 0;
+  reset_call_stats(c);
   hipEvent_t e0 = c->ev_t[0], e1 = c->ev_t[1], e2 = c->ev_t[2];
   for (int r0 = 0; r0 < b->batch; r0 += c->mbr) {
     ScoreRows R{b, codes, codes_stride, r0, std::min(c->mbr, b->batch - r0), {}};
@@ -374,14 +261,10 @@ int vx_score(vx_ctx* c, const vx_batch* b, const int64_t* codes, int32_t codes_s
     long sumT = 0;
     HIPCHK(hipEventRecord(e0, c->stream));
     if (do_ar)
-      if (int e = score_guarded(c, c->sticky_prefill_f32, c->sticky_prefill_age, c->fb_prefill_raises, c->st_fb_prefill,
-                                [&] { return score_ar_once(c, R, lp_a, rk_a); }))
-        return e;
+      if (int e = guarded(c, prefill_kind(c), [&] { return score_ar_once(c, R, lp_a, rk_a); })) return e;
     HIPCHK(hipEventRecord(e1, c->stream));
     if (do_nar)
-      if (int e = score_guarded(c, c->sticky_nar_f32, c->sticky_nar_age, c->fb_nar_raises, c->st_fb_nar,
-                                [&] { return score_nar_once(c, R, lp_n, rk_n, sumT); }))
-        return e;
+      if (int e = guarded(c, nar_kind(c), [&] { return score_nar_once(c, R, lp_n, rk_n, sumT); })) return e;
     HIPCHK(hipEventRecord(e2, c->stream));
     HIPCHK(hipEventSynchronize(e2));
     float ms = 0;

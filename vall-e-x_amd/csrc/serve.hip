@@ -1,4 +1,4 @@
-// Serving session (vx_serve_*, engine.hip): the per-admission kernel of a beam-group admission.  Everything else an admission runs
+// Serving session (vx_serve_*, schedule.hip serve_admit): the per-admission kernel of a beam-group admission.  Everything else an admission runs
 // is existing code: the prefill of the admitted requests (engine.hip prefill_layers, K / V into the arena slot of every request's
 // first beam row), the K / V copy to the other beams' slots (beams.hip, pairs only), the decode state of every beam row
 // (admit.hip admit_rows_kernel, one entry per beam row, all pointing at the request's prefill row), the final norm + predict layer

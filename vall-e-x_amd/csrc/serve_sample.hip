@@ -1,4 +1,4 @@
-// Serving session (vx_serve_*, engine.hip): the sampler of every decode step and of every admission's first sample.
+// Serving session (vx_serve_*, schedule.hip): the sampler of every decode step and of every admission's first sample.
 //
 // serve_sample_kernel computes exactly what dec_sample_kernel (decode.hip) computes -- split-K reduction of the predict layer's
 // logits, temperature, the top-k walk with ties, the inverse-CDF draw, sum(logp), the stop rule and the fused embedding + norm1 of
