@@ -292,6 +292,26 @@ int vx_nar(vx_ctx* ctx, const vx_batch* b, const int32_t* codes0, int32_t codes0
 #define VX_SCORE_NAR 2
 int vx_score(vx_ctx* ctx, const vx_batch* b, const int64_t* codes, int32_t codes_stride, const int32_t* lens, int32_t parts,
              float* logp, int32_t* rank, int32_t out_stride, float* eos_logp, int32_t* eos_rank);
+/* Text alignment: where in the text a frame came from.  attn[b][t][s], t < lens[b], s < text_lens[b], is the weighted sum over the
+ * layers l and heads h of the probability that the AR row predicting frame t (sequence-local row S + Tp + t of
+ * text ++ BOS ++ prompt ++ frames, models/vallex.py:535-549) puts on text position s -- the prompt's text included: the caller
+ * knows `enroll`.  One teacher-forced full-sequence AR pass over the given codes (vx_score's), with one more launch per weighted
+ * layer; exact fp32 softmax of that layer's q and k, whatever arithmetic the pass runs in.
+ *   codes [batch][codes_stride][8] int64, vx_infer's output layout; only codebook 0 of codes and of the prompt is read.  lens [batch],
+ *   0 <= T_b <= max_new (T_b = 0: the row writes nothing); batch <= max_batch (groups of min(max_batch, 32) rows).
+ *   head_weights [num_layers][16], finite, >= 0, not all zero -- or NULL: 1 / (16 num_layers) each, and every row of attn then sums
+ *   to the text's share of the attention, at most 1.  Which heads of a trained checkpoint follow the speech is the caller's
+ *   calibration.  Nothing behind the last weighted layer's in_proj runs.
+ *   attn [batch][out_stride][text_out_stride]: elements outside t < lens[b], s < text_lens[b] are not written.
+ * Nothing is written to the KV arena and no decode state is touched.  The pass sits behind the f16x2 range guard (a raised flag
+ * re-runs it in fp32 from a zeroed sum and counts in vx_last_fallbacks as a prefill phase).  The first call allocates its device
+ * buffer, min(max_batch, 32) * max_new rows of max_text floats (vx_destroy frees it).  vx_last_stats then reports 0 AR steps, the
+ * aligned frames, the pass's milliseconds as AR ms and 0 NAR ms.
+ * VX_EINVAL, nothing launched, the message naming the field: everything vx_infer refuses in the batch; a length outside
+ * 0 .. max_new; codes_stride or out_stride below a length; text_out_stride below a text length; a codebook-0 id outside 0 .. 1023;
+ * head_weights non-finite, negative or all zero; while a serving session is open.  VX_ESTATE before vx_finalize_weights. */
+int vx_align(vx_ctx* ctx, const vx_batch* b, const int64_t* codes, int32_t codes_stride, const int32_t* lens,
+             const float* head_weights, float* attn, int32_t out_stride, int32_t text_out_stride);
 /* copy a named debug buffer (needs cfg.debug_taps) -- or, when no tap has that name, a tensor exactly as vx_load_tensor stored it
  * (read-back check of an upload) -- to the host; returns the number of floats copied or < 0 */
 int64_t vx_read_tap(vx_ctx* ctx, const char* name, float* dst, int64_t max_floats);

@@ -196,6 +196,21 @@ int vx_dev_layernorm(vx_ctx* ctx, int32_t rows, int32_t C, int32_t ldx, const fl
  * VX_EINVAL, nothing launched, for anything outside the above; VX_ESTATE while a serving session is open. */
 int vx_dev_score_rows(vx_ctx* ctx, int32_t rows, int32_t ncols, int32_t ld, const float* logits, const int32_t* targets,
                       float* logp, int32_t* rank, int32_t rows_out);
+/* ONE launch of align_rows_kernel (csrc/align.hip, the kernel behind vx_align) on caller rows of one layer:
+ *   out[out_off + t][s] += sum_h w[h] * softmax_j(0.125 * q_r,h . k_j,h)[s]  for t < n_rows, s < S, r = q_first + t, over the keys
+ *   j = 0 .. r of the sequence (all text, causal audio: r >= S).  qkv [M][3072], packed rows: q in columns 0 .. 1023, k in
+ *   1024 .. 2047, head h at h * 64; M 1 .. 8192.  tab [nseq][6] = {seq_off, seq_len, S, q_first, n_rows, out_off} per sequence,
+ *   nseq 1 .. 32: the sequence inside [0, M), S >= 1, q_first >= S, n_rows >= 0, q_first + n_rows <= seq_len, the output rows
+ *   [out_off, out_off + n_rows) inside [0, rows_out) and disjoint between sequences.  w [16] finite and >= 0; a head with
+ *   w[h] == 0 is skipped (never read).  out [rows_out][ld_out] is IN / OUT, ld_out >= every S: the caller's contents go in, the
+ *   reported elements come back increased, every other element as it was.  The kernel works on tiles of VX_DEV_ALIGN_ROW_TILE
+ *   reported rows and VX_DEV_ALIGN_KEY_TILE keys.
+ * VX_EINVAL, nothing launched, the message naming the field, for anything outside the above; VX_ESTATE while a serving session is
+ * open. */
+#define VX_DEV_ALIGN_ROW_TILE 32
+#define VX_DEV_ALIGN_KEY_TILE 32
+int vx_dev_align_rows(vx_ctx* ctx, int32_t M, int32_t nseq, const int32_t* tab, const float* qkv, const float* w, float* out,
+                      int32_t rows_out, int32_t ld_out);
 
 /* ONE launch of a glue kernel of the waveform half -- the Vocos head (csrc/vocos.hip) and the EnCodec decoder / encoder
  * (csrc/encodec.hip) -- through its product launcher on caller operands.  Everything the launch reads or writes is private scratch of

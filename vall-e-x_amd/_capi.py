@@ -80,11 +80,11 @@ SYMBOLS = ["vx_abi_version", "vx_create", "vx_destroy", "vx_last_error", "vx_syn
            "vx_infer", "vx_vocos_decode", "vx_encodec_decode", "vx_encodec_encode", "vx_ar_prefill", "vx_ar_logits", "vx_ar_step",
            "vx_nar", "vx_read_tap", "vx_last_stats", "vx_last_truncated", "vx_last_fallbacks", "vx_fallback_state",
            "vx_fallback_reset", "vx_arith_mode", "vx_infer_continuous", "vx_serve_open", "vx_serve_submit", "vx_serve_run",
-           "vx_serve_close", "vx_serve_submit_ex", "vx_serve_cancel", "vx_serve_submit_filtered", "vx_score"]
+           "vx_serve_close", "vx_serve_submit_ex", "vx_serve_cancel", "vx_serve_submit_filtered", "vx_score", "vx_align"]
 # ... and include/vallex_hip_dev.h: measurement / kernel development, never called by the mirrors of the reference API
 DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kernel", "vx_bench_gemm", "vx_bench_attn",
                "vx_bench_gemm_clock", "vx_bench_gemm_epilogue", "vx_dev_sample", "vx_dev_attn", "vx_dev_sample_filtered",
-               "vx_dev_dec_attn", "vx_dev_dec_op", "vx_dev_gemm", "vx_dev_layernorm", "vx_dev_score_rows", "vx_dev_wave_op"]
+               "vx_dev_dec_attn", "vx_dev_dec_op", "vx_dev_gemm", "vx_dev_layernorm", "vx_dev_score_rows", "vx_dev_align_rows", "vx_dev_wave_op"]
 # sentinels the correctness entries pre-fill their outputs with (include/vallex_hip_dev.h)
 DEV_SENTINEL_I = -123456789
 DEV_SENTINEL_F = np.float32(-1.0e30)
@@ -105,6 +105,7 @@ DEV_WAVE_OPS = {"codebook_sum": 0, "im2col7": 1, "dwconv7": 2, "istft_prep": 3, 
 DEV_SENTINEL_L = -1234567890123456789
 SCORE_AR, SCORE_NAR = 1, 2             # VX_SCORE_* of include/vallex_hip.h (parts of vx_score)
 SCORE_PARTS = {"ar": SCORE_AR, "nar": SCORE_NAR, "both": SCORE_AR | SCORE_NAR}
+DEV_ALIGN_ROW_TILE, DEV_ALIGN_KEY_TILE = 32, 32      # VX_DEV_ALIGN_* of include/vallex_hip_dev.h: tiles of align_rows_kernel
 DEV_SAMPLE_CFG = ("kernel", "splitk", "top_k", "force_eos_at", "active", "n_gen", "cur_pos", "ctx_len", "text_len", "gen_stride")
 
 # vx_row_done_fn of vx_infer_continuous: (user, caller row, codes [frames][8] int64, frames)
@@ -198,6 +199,9 @@ def load_library() -> C.CDLL:
     lib.vx_score.argtypes = [ctx, P(vx_batch), P(C.c_int64), C.c_int32, P(C.c_int32), C.c_int32, P(C.c_float), P(C.c_int32), C.c_int32,
                              P(C.c_float), P(C.c_int32)]
     lib.vx_dev_score_rows.argtypes = [ctx, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), P(C.c_int32), P(C.c_float), P(C.c_int32),
+                                      C.c_int32]
+    lib.vx_align.argtypes = [ctx, P(vx_batch), P(C.c_int64), C.c_int32, P(C.c_int32), P(C.c_float), P(C.c_float), C.c_int32, C.c_int32]
+    lib.vx_dev_align_rows.argtypes = [ctx, C.c_int32, C.c_int32, P(C.c_int32), P(C.c_float), P(C.c_float), P(C.c_float), C.c_int32,
                                       C.c_int32]
     lib.vx_dev_wave_op.argtypes = [ctx, C.c_int32, P(C.c_int32), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_int32),
                                    P(C.c_int32), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_int64), P(C.c_int32)]
@@ -501,6 +505,46 @@ class Engine:
         self.score_into(batch, codes, lens, parts, logp, rank, elp, erk)
         return [(logp[i, : lens[i]].copy(), rank[i, : lens[i]].copy(), float(elp[i]), int(erk[i])) for i in range(n)]
 
+    # ---- text alignment ----
+    def align_into(self, batch: Batch, codes: np.ndarray, lens, attn: np.ndarray, head_weights=None, codes_stride=None,
+                   out_stride=None, text_out_stride=None):
+        """vx_align on caller arrays: codes (n, codes_stride, 8) int64, lens (n,); attn float32 (n, out_stride, text_out_stride) is
+        written in place, only [b, :lens[b], :text_len[b]].  head_weights (num_layers, 16) or None (uniform).  The strides default
+        to the arrays' own."""
+        codes = np.ascontiguousarray(codes, np.int64)
+        lens = np.ascontiguousarray(lens, np.int32)
+        if not (isinstance(attn, np.ndarray) and attn.dtype == np.float32 and attn.flags.c_contiguous and attn.ndim == 3):
+            raise ValueError("attn is a C-contiguous float32 array (n, out_stride, text_out_stride)")
+        hw = None
+        if head_weights is not None:
+            hw = np.ascontiguousarray(head_weights, np.float32)
+            if hw.shape != (self.cfg.num_layers, 16):
+                raise ValueError(f"head_weights is ({self.cfg.num_layers}, 16), got {hw.shape}")
+        self._chk(self.lib.vx_align(self.ctx, C.byref(batch.c), _ptr(codes, C.c_int64),
+                                    codes.shape[1] if codes_stride is None else int(codes_stride), _ptr(lens, C.c_int32),
+                                    None if hw is None else _ptr(hw, C.c_float), _ptr(attn, C.c_float),
+                                    attn.shape[1] if out_stride is None else int(out_stride),
+                                    attn.shape[2] if text_out_stride is None else int(text_out_stride)))
+        self._warn_fallbacks()
+
+    def align(self, batch: Batch, codes_list: Sequence[np.ndarray], head_weights=None):
+        """vx_align: attention of the AR row that predicts frame t of codes_list[i] (T_i, 8) over the text of row i of `batch` (the
+        prompt's text included), summed over layers and heads with head_weights (num_layers, 16); None: 1 / (16 num_layers) each.
+        Returns a list of (T_i, S_i) float32 arrays."""
+        n = batch.n
+        if len(codes_list) != n:
+            raise ValueError(f"{len(codes_list)} code arrays for {n} rows")
+        cl = [np.asarray(c, np.int64).reshape(-1, 8) for c in codes_list]
+        lens = np.array([len(c) for c in cl], np.int32)
+        stride = max(1, int(lens.max()))
+        codes = np.zeros((n, stride, 8), np.int64)
+        for i, c in enumerate(cl):
+            codes[i, : len(c)] = c
+        S = np.asarray(batch.text_lens, np.int32)
+        attn = np.zeros((n, stride, max(1, int(S.max()))), np.float32)
+        self.align_into(batch, codes, lens, attn, head_weights)
+        return [attn[i, : lens[i], : S[i]].copy() for i in range(n)]
+
     def read_tap(self, name: str, n: int) -> np.ndarray:
         out = np.zeros(n, np.float32)
         got = self.lib.vx_read_tap(self.ctx, name.encode(), _ptr(out, C.c_float), n)
@@ -787,6 +831,21 @@ class Engine:
         self._chk(self.lib.vx_dev_score_rows(self.ctx, rows, int(ncols), ld, _ptr(x, C.c_float), _ptr(t, C.c_int32),
                                              _ptr(logp, C.c_float), _ptr(rank, C.c_int32), len(logp)))
         return logp, rank
+
+    def dev_align_rows(self, qkv: np.ndarray, tab, w, out: np.ndarray):
+        """vx_dev_align_rows: one launch of align_rows_kernel on qkv (M, 3072) float32 (q | k | v of one layer, packed rows).  tab
+        (nseq, 6) int32 = (seq_off, seq_len, S, q_first, n_rows, out_off) per sequence, w (16,) head weights.  out (rows_out, ld_out)
+        float32 is IN / OUT: its contents go in, the reported elements come back increased, in place.  Returns out."""
+        x = np.ascontiguousarray(qkv, np.float32)
+        t = np.ascontiguousarray(tab, np.int32)
+        wv = np.ascontiguousarray(w, np.float32)
+        if x.ndim != 2 or x.shape[1] != 3072 or t.ndim != 2 or t.shape[1] != 6 or wv.shape != (16,):
+            raise ValueError("qkv is (M, 3072), tab (nseq, 6), w (16,)")
+        if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.flags.writeable and out.ndim == 2):
+            raise ValueError("out is a writeable C-contiguous float32 array (rows_out, ld_out)")
+        self._chk(self.lib.vx_dev_align_rows(self.ctx, x.shape[0], t.shape[0], _ptr(t, C.c_int32), _ptr(x, C.c_float), _ptr(wv, C.c_float),
+                                             _ptr(out, C.c_float), out.shape[0], out.shape[1]))
+        return out
 
     def dev_wave_op(self, op, dims, a=None, b=None, w=None, bias=None, ia=None, ib=None, out=None, out2=None, out3=None, codes=None):
         """vx_dev_wave_op: one launch of a Vocos / EnCodec glue kernel (op: a key of DEV_WAVE_OPS or its code) on caller operands; the

@@ -159,7 +159,7 @@ void proj(vx_ctx* c, const float* A, int lda, const float* Wf, const unsigned sh
 // one pre-norm block on packed rows (modules/transformer.py:296-302 / :337-347) -- shared by AR prefill and NAR
 int full_layer(vx_ctx* c, const LayerW& L, long M, const int* seq_off, const int* seq_len, const int* prefix_len,
                int batch, int max_len, const float* ada1, const float* ada2, float* kcl, float* vcl,
-               const int* row_b, const int* row_t, double attn_flops, const Trim* tr) {
+               const int* row_b, const int* row_t, double attn_flops, const Trim* tr, const AlignTap* tap) {
   // f16x2 mode: every producer of a GEMM operand (the two LayerNorms, the attention, linear1's epilogue) writes the operand
   // planes itself -- no fp32 round trip of the normalised / attended / hidden activations and no split pass on any edge.
   const bool pl = c->gemm_mode == 0;
@@ -169,6 +169,10 @@ int full_layer(vx_ctx* c, const LayerW& L, long M, const int* seq_off, const int
   proj(c, c->fxn, D_MODEL, L.in_w, L.in_w3, L.in_b, nullptr, 0, c->fqkv, 3 * D_MODEL, M, 3 * D_MODEL, D_MODEL, ACT_NONE, nullptr,
        pl ? c->fa3 : nullptr);
   if (kcl) launch_kv_scatter(c->fqkv, row_b, row_t, (int)M, kcl, vcl, c->Tmax, c->stream);
+  if (tap) {                                       // vx_align: q and k are read here, before anything reuses the QKV buffer
+    launch_align_rows(c->fqkv, tap->tab, tap->nseq, tap->max_rows, tap->w, tap->out, tap->ld_out, c->stream);
+    if (tap->stop) return VX_OK;
+  }
   const bool att_pl = pl && c->attn_x3;
   if (tr && !pl) {
     // reference arithmetic (fp32 projections + fp32 attention, round 6): the same trimming on fp32 rows.  The compacted residual

@@ -162,6 +162,9 @@ struct vx_ctx {
   float* sc_logits = nullptr;      // AR logits of the scored rows [sum (T_b + 1)][1028] when flogits is too small for them
   float* sc_logp = nullptr;        // [8 mbr (max_new + 1)] log-probabilities of the targets, as the kernel wrote them
   int* sc_rank = nullptr;          // ... and their ranks
+  // text alignment (vx_align, score.hip): allocated by the first vx_align
+  float* al_out = nullptr;         // [mbr max_new][roundup(max_text, 4)] attention of the aligned frames over the text, summed over layers
+  float* al_w = nullptr;           // [NL][16] head weights of the call
 
   // graph
   hipGraphExec_t graph_exec = nullptr, graph_exec_n = nullptr;   // one decode step / GRAPH_STEPS steps per launch
@@ -423,6 +426,18 @@ struct Trim {
   const int* rows;       // [Mc] packed row of every compacted row (residual gather)
   double attn_flops;     // 4 * T_b * L_b * 1024 summed: the queries that are still computed
 };
+// Attention tap of full_layer (vx_align): behind the in_proj -- the fp32 QKV buffer holds the layer's q and k in every arithmetic
+// mode, and the trimmed fp32 path reuses it behind the attention -- ONE launch of align_rows_kernel (align.hip) adds the layer's
+// weighted text attention of the rows in `tab` to `out`.  stop: nothing behind the tap is needed, the layer ends there.
+struct AlignTap {
+  const int* tab;        // [nseq][6] = {seq_off, seq_len, S, q_first, n_rows, out_off}
+  int nseq, max_rows;    // max_rows: the largest n_rows
+  const float* w;        // [16] the layer's head weights
+  float* out;
+  int ld_out;
+  bool stop;
+};
+void launch_align_rows(const float* qkv, const int* tab, int nseq, int max_rows, const float* w, float* out, int ld_out, hipStream_t s);
 // engine.hip, shared with the scoring passes (score.hip)
 constexpr int VX_RETRY_F32 = 1;      // internal: the phase raised the f16x2 range flag, run it again on the fp32 kernels
 void proj(vx_ctx* c, const float* A, int lda, const float* Wf, const unsigned short* W3, const float* bias, const float* resid, int ldr,
@@ -430,7 +445,7 @@ void proj(vx_ctx* c, const float* A, int lda, const float* Wf, const unsigned sh
           unsigned short* out_pl = nullptr, const int* resid_rows = nullptr);
 int full_layer(vx_ctx* c, const LayerW& L, long M, const int* seq_off, const int* seq_len, const int* prefix_len, int batch, int max_len,
                const float* ada1, const float* ada2, float* kcl, float* vcl, const int* row_b, const int* row_t, double attn_flops,
-               const Trim* tr = nullptr);
+               const Trim* tr = nullptr, const AlignTap* tap = nullptr);
 int prefill_tables(vx_ctx* c, const vx_batch* b, int r0, int nb, PrefillPlan& p, MetaBuilder& mb);
 // engine.hip, shared with the schedulers (schedule.hip)
 constexpr int GRAPH_STEPS = 4;       // decode steps per multi-step graph launch (ar_step_run)

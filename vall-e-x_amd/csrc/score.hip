@@ -3,6 +3,10 @@
 // codebooks 2 .. 8) and the one best_of selects on (sum(logp) / len^penalty, models/vallex.py:572, :583-594).  Both passes drive the
 // full-sequence layers of engine.hip (full_layer + Trim), behind the range guard of engine_ctx.h (guarded), with the GIVEN codes as inputs; the one new kernel turns logit rows into
 // (log-probability, rank) of a target id.
+// Text alignment (vx_align) is the same AR pass with a tap in every weighted layer: align_rows_kernel (align.hip) turns the layer's q and k
+// into the attention of the frames' rows over the text.
+#include <cmath>
+
 #include "engine_ctx.h"
 
 #include "../../include/vallex_hip_dev.h"
@@ -108,13 +112,11 @@ struct ScoreRows {
   int code(int i, int t, int q) const { return (int)codes[((long)(r0 + i) * stride + t) * N_Q + q]; }
 };
 
-// AR pass of one group: text, then BOS ++ prompt codebook 0 ++ codes[:, 0] under the prefix-LM mask of the prefill; nothing goes
-// into the KV arena and no decode state is touched.  The last layer computes only the T_b + 1 rows that predict frame 0 .. T_b - 1
-// and the stop decision.  logp / rank [sum (T_b + 1)]: row T_b of a sequence scores EOS.
-static int score_ar_once(vx_ctx* c, const ScoreRows& R, std::vector<float>& logp, std::vector<int>& rank) {
-  const int nb = R.nb, NL = c->NL;
+// The AR pass over GIVEN frames, shared by the scoring and the alignment pass: the prefill's tables of a batch whose prompts are the
+// callers' with the given frames appended (only codebook 0 is read).  q_first[i] = S + Tp: the sequence-local row that predicts frame 0.
+static int given_tables(vx_ctx* c, const ScoreRows& R, MetaBuilder& mb, PrefillPlan& p, std::vector<int>& q_first, double& attn_flops) {
+  const int nb = R.nb;
   const vx_batch* b = R.b;
-  // the prefill's tables of a batch whose prompts are the callers' with the given frames appended (only codebook 0 is read)
   int ps = 1;
   for (int i = 0; i < nb; ++i) ps = std::max(ps, b->prompt_lens[R.r0 + i] + R.T[i]);
   std::vector<int32_t> pc((size_t)nb * ps * N_Q, 0), pl(nb);
@@ -129,22 +131,42 @@ static int score_ar_once(vx_ctx* c, const ScoreRows& R, std::vector<float>& logp
   bx.text_ids = b->text_ids + (long)R.r0 * b->text_stride; bx.text_lang = b->text_lang + (long)R.r0 * b->text_stride;
   bx.text_lens = b->text_lens + R.r0;
   bx.prompt_codes = pc.data(); bx.prompt_stride = ps; bx.prompt_lens = pl.data();
+  if (int e = prefill_tables(c, &bx, 0, nb, p, mb)) return e;
+  q_first.resize(nb);
+  attn_flops = 0;
+  for (int i = 0; i < nb; ++i) {
+    q_first[i] = p.S_[i] + b->prompt_lens[R.r0 + i];
+    attn_flops += 4.0 * p.seq_len[i] * (double)p.seq_len[i] * D_MODEL;
+  }
+  return VX_OK;
+}
+
+// layer l of the AR stack on the packed rows of `p` under the prefix-LM mask; nothing goes into the KV arena
+static int given_layer(vx_ctx* c, const PrefillPlan& p, const MetaBuilder& mb, int l, double attn_flops, const Trim* tr,
+                       const AlignTap* tap = nullptr) {
+  return full_layer(c, c->ar[l], p.M, mb.dev(p.o_off), mb.dev(p.o_len), mb.dev(p.o_S), p.nb, p.max_len, nullptr, nullptr, nullptr, nullptr,
+                    nullptr, nullptr, attn_flops, tr, tap);
+}
+
+// AR pass of one group: text, then BOS ++ prompt codebook 0 ++ codes[:, 0] under the prefix-LM mask of the prefill; nothing goes
+// into the KV arena and no decode state is touched.  The last layer computes only the T_b + 1 rows that predict frame 0 .. T_b - 1
+// and the stop decision.  logp / rank [sum (T_b + 1)]: row T_b of a sequence scores EOS.
+static int score_ar_once(vx_ctx* c, const ScoreRows& R, std::vector<float>& logp, std::vector<int>& rank) {
+  const int nb = R.nb, NL = c->NL;
   PrefillPlan p;
   MetaBuilder mb(c);
-  if (int e = prefill_tables(c, &bx, 0, nb, p, mb)) return e;
-  std::vector<int> q_first(nb), c_off(nb), rows, tg;
-  long Mc = 0;
+  std::vector<int> q_first, c_off(nb), rows, tg;
   double trim_flops = 0, attn_flops = 0;
+  if (int e = given_tables(c, R, mb, p, q_first, attn_flops)) return e;
+  long Mc = 0;
   for (int i = 0; i < nb; ++i) {
-    const int Tp = b->prompt_lens[R.r0 + i];
-    q_first[i] = p.S_[i] + Tp; c_off[i] = (int)Mc;
+    c_off[i] = (int)Mc;
     for (int t = 0; t <= R.T[i]; ++t) {
       rows.push_back(p.seq_off[i] + q_first[i] + t);
       tg.push_back(t < R.T[i] ? R.code(i, t, 0) : EOS_ID);
     }
     Mc += R.T[i] + 1;
     trim_flops += 4.0 * (R.T[i] + 1) * (double)p.seq_len[i] * D_MODEL;
-    attn_flops += 4.0 * p.seq_len[i] * (double)p.seq_len[i] * D_MODEL;
   }
   const long o_qf = mb.add(q_first), o_co = mb.add(c_off), o_rows = mb.add(rows), o_tg = mb.add(tg);
   if (int e = upload_meta(c)) return e;
@@ -154,9 +176,7 @@ static int score_ar_once(vx_ctx* c, const ScoreRows& R, std::vector<float>& logp
   // every row and gather
   const Trim tr{Mc, mb.dev(o_qf), mb.dev(o_co), mb.dev(o_rows), trim_flops};
   for (int l = 0; l < NL; ++l)
-    if (int e = full_layer(c, c->ar[l], p.M, mb.dev(p.o_off), mb.dev(p.o_len), mb.dev(p.o_S), nb, p.max_len, nullptr, nullptr,
-                           nullptr, nullptr, nullptr, nullptr, attn_flops, (p.trim && l == NL - 1) ? &tr : nullptr))
-      return e;
+    if (int e = given_layer(c, p, mb, l, attn_flops, (p.trim && l == NL - 1) ? &tr : nullptr)) return e;
   // ar_decoder.norm on the kept rows, then ar_predict_layer on the fp32 GEMM (models/vallex.py:568)
   const float *ng = W(c, "ar_decoder.norm.weight"), *nbias = W(c, "ar_decoder.norm.bias");
   float* lg = c->sc_logits ? c->sc_logits : c->flogits;
@@ -223,9 +243,119 @@ static int score_nar_once(vx_ctx* c, const ScoreRows& R, std::vector<float>& log
   return sync_guarded(c);
 }
 
+// ---------------------------------------------------------------------------------------------
+// text alignment (vx_align): the AR pass above with align_rows_kernel (align.hip) tapping every weighted layer's q and k
+// ---------------------------------------------------------------------------------------------
+static int align_ld(const vx_ctx* c) { return (c->cfg.max_text + 3) / 4 * 4; }
+
+static int align_buffers(vx_ctx* c) {
+  if (c->al_out) return VX_OK;
+  float *out = nullptr, *w = nullptr;
+  if (int e = dev_alloc(c, &out, (size_t)c->mbr * c->cfg.max_new * align_ld(c))) return e;
+  if (int e = dev_alloc(c, &w, (size_t)c->NL * N_HEAD)) return e;
+  c->al_out = out; c->al_w = w;
+  return VX_OK;
+}
+
+// One group: attn [sum T_b][align_ld] = sum over the layers l and heads h of hw[l][h] x the probability the row that predicts frame t
+// puts on the text columns.  The accumulation buffer is zeroed HERE: a re-run in fp32 starts from zero, not from a half-finished
+// sum.  The pass ends behind the in_proj of the last weighted layer: no attention, FFN, final norm or predict layer there, no later layer.
+static int align_once(vx_ctx* c, const ScoreRows& R, const float* hw, std::vector<float>& attn) {
+  const int nb = R.nb, NL = c->NL, ld = align_ld(c);
+  PrefillPlan p;
+  MetaBuilder mb(c);
+  std::vector<int> q_first, tab;
+  double attn_flops = 0;
+  if (int e = given_tables(c, R, mb, p, q_first, attn_flops)) return e;
+  long sumT = 0;
+  int max_rows = 0;
+  for (int i = 0; i < nb; ++i) {
+    tab.insert(tab.end(), {p.seq_off[i], p.seq_len[i], p.S_[i], q_first[i], R.T[i], (int)sumT});
+    sumT += R.T[i];
+    max_rows = std::max(max_rows, R.T[i]);
+  }
+  const long o_tab = mb.add(tab);
+  if (int e = upload_meta(c)) return e;
+  auto weighted = [&](int l) { for (int h = 0; h < N_HEAD; ++h) if (hw[l * N_HEAD + h] > 0.f) return true; return false; };
+  int last = 0;
+  for (int l = 0; l < NL; ++l) if (weighted(l)) last = l;
+  H2D(c->al_w, hw, (size_t)NL * N_HEAD * sizeof(float));
+  HIPCHK(hipMemsetAsync(c->al_out, 0, (size_t)sumT * ld * sizeof(float), c->stream));
+  prefill_embed(c, p, mb);
+  for (int l = 0; l <= last; ++l) {
+    const AlignTap tap{mb.dev(o_tab), nb, max_rows, c->al_w + l * N_HEAD, c->al_out, ld, l == last};
+    if (int e = given_layer(c, p, mb, l, attn_flops, nullptr, weighted(l) ? &tap : nullptr)) return e;
+  }
+  HIPCHK(hipGetLastError());
+  attn.resize((size_t)sumT * ld);
+  D2H(attn.data(), c->al_out, attn.size() * sizeof(float));
+  return sync_guarded(c);           // the range flag rides on the sync that brings the result back
+}
+
 }  // namespace vxe
 
 extern "C" {
+
+int vx_align(vx_ctx* c, const vx_batch* b, const int64_t* codes, int32_t codes_stride, const int32_t* lens, const float* head_weights,
+             float* attn, int32_t out_stride, int32_t text_out_stride) {
+  if (!c) return VX_EINVAL;
+  if (c->serve) FAIL(VX_EINVAL, "vx_align: a serving session is open on this context (vx_serve_close it first)");
+  HIPCHK(hipSetDevice(c->dev));
+  if (int e = check_batch(c, b, c->cfg.max_batch)) return e;
+  if (!codes || !lens) FAIL(VX_EINVAL, "vx_align: null codes or lens");
+  if (!attn) FAIL(VX_EINVAL, "vx_align: null attn");
+  for (int i = 0; i < b->batch; ++i) {
+    const int T = lens[i];
+    if (T < 0 || T > c->cfg.max_new) FAIL(VX_EINVAL, "vx_align: row %d: lens %d outside 0 .. max_new (%d)", i, T, c->cfg.max_new);
+    if (T > codes_stride) FAIL(VX_EINVAL, "vx_align: row %d: codes_stride %d below lens %d", i, codes_stride, T);
+    if (T > out_stride) FAIL(VX_EINVAL, "vx_align: row %d: out_stride %d below lens %d", i, out_stride, T);
+    if (b->text_lens[i] > text_out_stride)
+      FAIL(VX_EINVAL, "vx_align: row %d: text_out_stride %d below the text length %d", i, text_out_stride, b->text_lens[i]);
+  }
+  for (int i = 0; i < b->batch; ++i)
+    for (int t = 0; t < lens[i]; ++t) {
+      const int64_t v = codes[((long)i * codes_stride + t) * N_Q];
+      if (v < 0 || v >= AUDIO_VOCAB) FAIL(VX_EINVAL, "vx_align: codes: row %d frame %d codebook 0: %lld outside 0 .. 1023", i, t, (long long)v);
+    }
+  std::vector<float> hw((size_t)c->NL * N_HEAD, 1.0f / (float)(N_HEAD * c->NL));
+  if (head_weights) {
+    bool any = false;
+    for (size_t i = 0; i < hw.size(); ++i) {
+      hw[i] = head_weights[i];
+      if (!std::isfinite(hw[i]) || hw[i] < 0.f)
+        FAIL(VX_EINVAL, "vx_align: head_weights[%d][%d] is negative or not finite", (int)(i / N_HEAD), (int)(i % N_HEAD));
+      any |= hw[i] > 0.f;
+    }
+    if (!any) FAIL(VX_EINVAL, "vx_align: head_weights are all zero");
+  }
+  if (int e = align_buffers(c)) return e;
+  reset_call_stats(c);
+  hipEvent_t e0 = c->ev_t[0], e1 = c->ev_t[1];
+  const int ld = align_ld(c);
+  for (int r0 = 0; r0 < b->batch; r0 += c->mbr) {
+    ScoreRows R{b, codes, codes_stride, r0, std::min(c->mbr, b->batch - r0), {}};
+    R.T.assign(lens + r0, lens + r0 + R.nb);
+    long sumT = 0;
+    for (int T : R.T) sumT += T;
+    if (sumT == 0) continue;                     // nothing to align in this group
+    std::vector<float> a;
+    HIPCHK(hipEventRecord(e0, c->stream));
+    if (int e = guarded(c, prefill_kind(c), [&] { return align_once(c, R, hw.data(), a); })) return e;
+    HIPCHK(hipEventRecord(e1, c->stream));
+    HIPCHK(hipEventSynchronize(e1));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1)); c->st_ar_ms += ms;
+    long off = 0;
+    for (int i = 0; i < R.nb; ++i) {
+      const int T = R.T[i], S = b->text_lens[r0 + i];
+      c->st_frames += T;
+      for (int t = 0; t < T; ++t)
+        memcpy(attn + ((long)(r0 + i) * out_stride + t) * text_out_stride, a.data() + (off + t) * ld, (size_t)S * sizeof(float));
+      off += T;
+    }
+  }
+  return VX_OK;
+}
 
 int vx_score(vx_ctx* c, const vx_batch* b, const int64_t* codes, int32_t codes_stride, const int32_t* lens, int32_t parts,
              float* logp, int32_t* rank, int32_t out_stride, float* eos_logp, int32_t* eos_rank) {

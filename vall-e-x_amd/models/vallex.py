@@ -312,6 +312,41 @@ class VALLE:
         res = self.engine.score(self.make_batch(rows), [_np(c, np.int64).reshape(-1, 8) for c in codes_list], parts)
         return [dict(logp=lp, rank=rk, eos_logp=el, eos_rank=er) for lp, rk, el, er in res]
 
+    # ---- text alignment (vx_align) -------------------------------------------------------------------------------
+    def align(self, x, x_lens, y, enroll_x_lens, codes, prompt_language: str = None,
+              text_language: Union[str, List[str]] = None, head_weights=None):
+        """Where in the text every frame of `codes` (1, T, 8), as `inference` returns them, came from: the attention of the AR row
+        that predicts frame t over the S text positions (the prompt's text included), summed over layers and heads with
+        head_weights (num_layers, 16); None: 1 / (16 num_layers) each.  Returns a dict: attn (T, S) float32; text_mass (T,), its row
+        sums (with uniform weights the text's share of the attention, at most 1); segments (S - enroll, 2) int32, first and last frame
+        of every token of the text that was synthesised (utils.alignment.monotonic_segments), or None when T < S - enroll.
+        The segments follow the documented rule whatever the weights are; how well they track the speech depends on which heads of a
+        trained checkpoint align -- that calibration is the caller's, through head_weights."""
+        xa, xl, ya, ca = _np(x), _np(x_lens), _np(y), _np(codes)
+        assert xa.ndim == 2, xa.shape                      # the checks of inference (models/vallex.py:488-493)
+        assert xl.ndim == 1, xl.shape
+        assert ya.ndim == 3, ya.shape
+        assert ya.shape[0] == 1, ya.shape
+        assert np.all(xl > 0)
+        assert ca.ndim == 3 and ca.shape[0] == 1 and ca.shape[2] == 8, ca.shape
+        S = int(xl.max())
+        row = dict(text=xa[0, :S], prompt=ya[0], enroll=int(_np(enroll_x_lens)), prompt_language=prompt_language,
+                   text_language=text_language)
+        return self.align_batch([row], [ca[0]], head_weights=head_weights)[0]
+
+    def align_batch(self, rows: Sequence[dict], codes_list: Sequence[np.ndarray], head_weights=None) -> List[dict]:
+        """`align` for the row dicts of `inference_batch`: codes_list[i] (T_i, 8) is aligned with the text of rows[i], one call."""
+        from ..utils.alignment import monotonic_segments
+        if len(rows) != len(codes_list):
+            raise ValueError(f"{len(codes_list)} code arrays for {len(rows)} rows")
+        res = self.engine.align(self.make_batch(rows), [_np(c, np.int64).reshape(-1, 8) for c in codes_list], head_weights)
+        out = []
+        for r, a in zip(rows, res):
+            enroll = int(r["enroll"])
+            seg = monotonic_segments(a, enroll) if a.shape[0] >= a.shape[1] - enroll else None
+            out.append(dict(attn=a, text_mass=a.sum(1), segments=seg))
+        return out
+
     def serve(self, top_k: int = -100, temperature: float = 1.0, sync_every: int = 8, force_eos_at=None, max_steps: int = 32,
               post=None, **kw) -> "Server":
         """A threaded serving front end (include/vallex_hip.h vx_serve_*): `Server.submit(row, best_of=..., seed=...)` may be called

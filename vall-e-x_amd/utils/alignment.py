@@ -1,0 +1,50 @@
+"""Frame-to-text segments from the attention `VALLE.align` returns (numpy only)."""
+from __future__ import annotations
+
+import numpy as np
+
+FLOOR = 1e-30      # attention below this counts as this (log of an exact zero)
+
+
+def monotonic_segments(attn: np.ndarray, enroll: int) -> np.ndarray:
+    """The best monotone path of the T frames through the text that was synthesised, columns enroll .. S-1 of attn (T, S).
+
+    The path s_0 .. s_{T-1} starts at column `enroll`, ends at column S - 1 and moves 0 or 1 columns per frame; it maximises
+    sum_t log(max(attn[t, s_t], 1e-30)) (Viterbi, float64).  Ties go to the smaller column: walking back from the last frame, a
+    frame whose two possible predecessors score the same takes the smaller one.  Returns (S - enroll, 2) int32, the first and the
+    last frame of every column.  Raises ValueError when T < S - enroll (no such path).
+
+    This is a rule, not a judgement: it is followed whatever attention it is given.  How well the segments track the speech depends
+    on which heads of a trained checkpoint align with it; that is the caller's calibration through `head_weights` of `VALLE.align`."""
+    a = np.asarray(attn, np.float64)
+    if a.ndim != 2:
+        raise ValueError(f"attn is (T, S), got shape {a.shape}")
+    T, S = a.shape
+    enroll = int(enroll)
+    if not 0 <= enroll <= S:
+        raise ValueError(f"enroll {enroll} outside 0 .. S = {S}")
+    n = S - enroll
+    if T < n:
+        raise ValueError(f"{T} frames cannot cover {n} text positions")
+    if n == 0:
+        return np.zeros((0, 2), np.int32)
+    lg = np.log(np.maximum(a[:, enroll:], FLOOR))
+    score = np.full(n, -np.inf)
+    score[0] = lg[0, 0]
+    moved = np.zeros((T, n), bool)               # moved[t, j]: the best path into (t, j) comes from column j - 1
+    for t in range(1, T):
+        stay, move = score, np.concatenate([[-np.inf], score[:-1]])
+        moved[t] = move >= stay                  # tie: the smaller predecessor
+        moved[t, 0] = False
+        score = np.where(moved[t], move, stay) + lg[t]
+    path = np.empty(T, np.int64)
+    j = n - 1
+    for t in range(T - 1, -1, -1):
+        path[t] = j
+        if moved[t, j]:
+            j -= 1
+    seg = np.empty((n, 2), np.int32)
+    for j in range(n):
+        frames = np.flatnonzero(path == j)
+        seg[j] = frames[0], frames[-1]
+    return seg
