@@ -255,6 +255,27 @@ int vx_encodec_decode(vx_ctx* ctx, const int64_t* codes, int32_t codes_stride, c
 int vx_encodec_encode(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t* lens, int32_t batch, int64_t* codes,
                       int32_t codes_stride, int32_t* out_lens);
 
+/* Sample-rate conversion of mono fp32 rows on the device: the other rates at both audio ends (everything above takes and gives
+ * 24 kHz).  replaces: convert_audio -> torchaudio.transforms.Resample(sr, 24000) with its defaults, data/tokenizer.py:105 -- restated
+ * from the package's published algorithm, unpinned (the package is not installed where this was written).
+ * With o, n = orig_rate, new_rate over their gcd: base = min(o, n) * 0.99, width = ceil(6 o / base), K = 2 width + o; n phase kernels
+ * of K Hann-windowed sinc taps, built on the host in double (the phase -p / n in fp32), rounded once to fp32 and cached per (o, n);
+ *   out[b][i n + p] = sum_j k_p[j] * x_b[i o + j - width],  x_b = 0 outside [0, lens[b]),  out_lens[b] = ceil(n lens[b] / o).
+ * Every element is one zero-initialised accumulator and K fmaf in tap order: its bits do not depend on the batch or on the windows.
+ *   wav [batch][wav_stride] fp32, lens [batch] samples (0 allowed: the row writes nothing); out [batch][out_stride] fp32; elements
+ *   behind out_lens[b] are not written.  orig_rate == new_rate copies the input bits.
+ * Needs no weights: it works on any created context, before vx_finalize_weights too, and while a serving session is open; it touches
+ * no decode state, no KV arena and no fallback counter.  The first call allocates its device buffers (vx_destroy frees them): one
+ * launch holds VX_RESAMPLE_WINDOW input samples (and twice as many output samples); the rows of a call are packed into launches in
+ * order and a row that does not fit is cut into windows, each with the real samples its taps reach on both sides -- by the rule above
+ * the result is bit-identical to a single pass.
+ * VX_EINVAL, nothing launched, the message naming the field: a NULL pointer; batch <= 0; a rate <= 0; a length negative or above
+ * wav_stride; out_stride below an output length; n K above 2^18 taps (1 MiB; e.g. 44101 -> 24000 -- every pair of the usual audio
+ * rates is below 52 000). */
+#define VX_RESAMPLE_WINDOW (1 << 23)
+int vx_resample(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t* lens, int32_t batch, int32_t orig_rate,
+                int32_t new_rate, float* out, int64_t out_stride, int32_t* out_lens);
+
 /* ---- step-level entries (kernel-level parity tests; same kernels as vx_infer) ---------------------------- */
 /* first ar_decoder.infer call (models/vallex.py:528-562): embeds, runs the prefix-LM prefill, fills the KV arena,
  * leaves the logits of the last row available.  batch <= 32. */

@@ -272,6 +272,18 @@ int vx_dev_align_rows(vx_ctx* ctx, int32_t M, int32_t nseq, const int32_t* tab, 
 int vx_dev_wave_op(vx_ctx* ctx, int32_t op, const int32_t* dims, const float* a, const float* b, const float* w, const float* bias,
                    const int32_t* ia, const int32_t* ib, float* out, float* out2, float* out3, int64_t* codes, int32_t* geom);
 
+/* The resampler's tap table (csrc/resample.hip, the kernel behind vx_resample), as the device holds it: geom = {o, n, width, K} of
+ * the pair, taps [n][K] = phase kernel p at taps + p K (NULL: the geometry alone, nothing is built).  The table is built and
+ * uploaded at the pair's first use and read back FROM THE DEVICE here, so the words a test sees are the words the kernel reads.
+ * VX_EINVAL: a rate <= 0, geom NULL, or more than 2^18 taps. */
+int vx_dev_resample_taps(vx_ctx* ctx, int32_t orig_rate, int32_t new_rate, float* taps, int32_t* geom);
+/* Input samples one launch of vx_resample holds, for later calls on this context: VX_DEV_RESAMPLE_WINDOW_MIN .. VX_RESAMPLE_WINDOW,
+ * or 0 for the default (VX_RESAMPLE_WINDOW).  A small window sends short rows through several windows and launches -- what the
+ * window tests need; the device buffers keep their size.  While a window below a pair's K is set, vx_resample refuses that pair
+ * (VX_EINVAL): a launch must hold one block's taps.  VX_EINVAL, nothing changed, for any other value. */
+#define VX_DEV_RESAMPLE_WINDOW_MIN 512
+int vx_dev_resample_window(vx_ctx* ctx, int32_t input_samples);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@ raise (VallexHipError / OSError); nothing here imports oracle/.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional, Sequence
 
@@ -80,11 +81,12 @@ SYMBOLS = ["vx_abi_version", "vx_create", "vx_destroy", "vx_last_error", "vx_syn
            "vx_infer", "vx_vocos_decode", "vx_encodec_decode", "vx_encodec_encode", "vx_ar_prefill", "vx_ar_logits", "vx_ar_step",
            "vx_nar", "vx_read_tap", "vx_last_stats", "vx_last_truncated", "vx_last_fallbacks", "vx_fallback_state",
            "vx_fallback_reset", "vx_arith_mode", "vx_infer_continuous", "vx_serve_open", "vx_serve_submit", "vx_serve_run",
-           "vx_serve_close", "vx_serve_submit_ex", "vx_serve_cancel", "vx_serve_submit_filtered", "vx_score", "vx_align"]
+           "vx_serve_close", "vx_serve_submit_ex", "vx_serve_cancel", "vx_serve_submit_filtered", "vx_score", "vx_align", "vx_resample"]
 # ... and include/vallex_hip_dev.h: measurement / kernel development, never called by the mirrors of the reference API
 DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kernel", "vx_bench_gemm", "vx_bench_attn",
                "vx_bench_gemm_clock", "vx_bench_gemm_epilogue", "vx_dev_sample", "vx_dev_attn", "vx_dev_sample_filtered",
-               "vx_dev_dec_attn", "vx_dev_dec_op", "vx_dev_gemm", "vx_dev_layernorm", "vx_dev_score_rows", "vx_dev_align_rows", "vx_dev_wave_op"]
+               "vx_dev_dec_attn", "vx_dev_dec_op", "vx_dev_gemm", "vx_dev_layernorm", "vx_dev_score_rows", "vx_dev_align_rows", "vx_dev_wave_op",
+               "vx_dev_resample_taps", "vx_dev_resample_window"]
 # sentinels the correctness entries pre-fill their outputs with (include/vallex_hip_dev.h)
 DEV_SENTINEL_I = -123456789
 DEV_SENTINEL_F = np.float32(-1.0e30)
@@ -106,6 +108,7 @@ DEV_SENTINEL_L = -1234567890123456789
 SCORE_AR, SCORE_NAR = 1, 2             # VX_SCORE_* of include/vallex_hip.h (parts of vx_score)
 SCORE_PARTS = {"ar": SCORE_AR, "nar": SCORE_NAR, "both": SCORE_AR | SCORE_NAR}
 DEV_ALIGN_ROW_TILE, DEV_ALIGN_KEY_TILE = 32, 32      # VX_DEV_ALIGN_* of include/vallex_hip_dev.h: tiles of align_rows_kernel
+RESAMPLE_WINDOW, DEV_RESAMPLE_WINDOW_MIN = 1 << 23, 512     # VX_RESAMPLE_WINDOW / VX_DEV_RESAMPLE_WINDOW_MIN: input samples per launch
 DEV_SAMPLE_CFG = ("kernel", "splitk", "top_k", "force_eos_at", "active", "n_gen", "cur_pos", "ctx_len", "text_len", "gen_stride")
 
 # vx_row_done_fn of vx_infer_continuous: (user, caller row, codes [frames][8] int64, frames)
@@ -129,7 +132,10 @@ def load_library() -> C.CDLL:
     # and of ROCr into the process (two runtimes driving one GPU address space).  The API mirrors import torch anyway (the
     # reference's signatures hand tensors in and out), so import it here, first: the library then resolves libamdhip64.so.7 to
     # the copy that is already loaded.  A C client (examples/*.c) has no torch and runs on the system runtime alone.
-    import torch  # noqa: F401
+    try:
+        import torch  # noqa: F401
+    except ImportError:      # a process without torch has one runtime anyway (the system's): the package runs on numpy alone
+        pass
     lib = C.CDLL(LIB_PATH)
     if LIB_OVERRIDDEN:
         import sys
@@ -205,6 +211,10 @@ def load_library() -> C.CDLL:
                                       C.c_int32]
     lib.vx_dev_wave_op.argtypes = [ctx, C.c_int32, P(C.c_int32), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_int32),
                                    P(C.c_int32), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_int64), P(C.c_int32)]
+    lib.vx_resample.argtypes = [ctx, P(C.c_float), C.c_int64, P(C.c_int32), C.c_int32, C.c_int32, C.c_int32, P(C.c_float), C.c_int64,
+                                P(C.c_int32)]
+    lib.vx_dev_resample_taps.argtypes = [ctx, C.c_int32, C.c_int32, P(C.c_float), P(C.c_int32)]
+    lib.vx_dev_resample_window.argtypes = [ctx, C.c_int32]
     lib.vx_last_stats.argtypes = [ctx, P(C.c_int64), P(C.c_int64), P(C.c_double), P(C.c_double)]
     lib.vx_last_truncated.argtypes = [ctx, P(C.c_int32)]
     lib.vx_last_fallbacks.argtypes = [ctx, P(C.c_int32), P(C.c_int32), P(C.c_int64)]
@@ -400,7 +410,49 @@ class Engine:
                               "phase is tried on f16x2 again and a clean pass leaves the mode, Engine.fallback_reset() leaves it at once",
                               RuntimeWarning, stacklevel=3)
 
-    def vocos_decode(self, codes: Sequence[np.ndarray], bandwidth_id: int = 2):
+    def resample(self, wavs: Sequence[np.ndarray], orig_rate: int, new_rate: int):
+        """vx_resample: mono fp32 waveforms (L_i,) at orig_rate -> a list of float32 arrays of ceil(n L_i / o) samples at new_rate
+        (o, n = the rates over their gcd): Hann-windowed sinc, utils.prompt_making.resample_sinc_hann's algorithm (torchaudio's
+        default, unpinned) on the device, all rows in one ragged launch.  Equal rates return the input bits."""
+        n = len(wavs)
+        if n == 0:
+            return []
+        ws = [np.ascontiguousarray(w, np.float32).reshape(-1) for w in wavs]
+        lens = np.array([len(w) for w in ws], np.int32)
+        stride = max(1, int(lens.max()))
+        if n == 1:
+            buf = ws[0] if len(ws[0]) else np.zeros(1, np.float32)        # no second copy of a single (long) row
+        else:
+            buf = np.zeros((n, stride), np.float32)
+            for i, w in enumerate(ws):
+                buf[i, : len(w)] = w
+        g = math.gcd(int(orig_rate), int(new_rate)) if int(orig_rate) > 0 and int(new_rate) > 0 else 1
+        ostride = max(1, -(-(int(new_rate) // g) * stride // max(1, int(orig_rate) // g)))
+        out = np.empty((n, ostride), np.float32)
+        out_lens = np.zeros(n, np.int32)
+        self._chk(self.lib.vx_resample(self.ctx, _ptr(buf, C.c_float), stride, _ptr(lens, C.c_int32), n, int(orig_rate), int(new_rate),
+                                       _ptr(out, C.c_float), ostride, _ptr(out_lens, C.c_int32)))
+        return [out[i, : out_lens[i]] for i in range(n)]
+
+    def dev_resample_taps(self, orig_rate: int, new_rate: int, taps: bool = True):
+        """vx_dev_resample_taps: ((o, n, width, K), the pair's tap table (n, K) float32 read back from the device -- None for
+        taps=False, which builds nothing)"""
+        geom = np.zeros(4, np.int32)
+        self._chk(self.lib.vx_dev_resample_taps(self.ctx, int(orig_rate), int(new_rate), None, _ptr(geom, C.c_int32)))
+        o, n, width, K = (int(v) for v in geom)
+        if not taps:
+            return (o, n, width, K), None
+        t = np.empty((n, K), np.float32)
+        self._chk(self.lib.vx_dev_resample_taps(self.ctx, int(orig_rate), int(new_rate), _ptr(t, C.c_float), _ptr(geom, C.c_int32)))
+        return (o, n, width, K), t
+
+    def dev_resample_window(self, input_samples: int = 0):
+        """vx_dev_resample_window: input samples one launch of `resample` holds from now on (DEV_RESAMPLE_WINDOW_MIN ..
+        RESAMPLE_WINDOW; 0 restores the default)"""
+        self._chk(self.lib.vx_dev_resample_window(self.ctx, int(input_samples)))
+
+    def vocos_decode(self, codes: Sequence[np.ndarray], bandwidth_id: int = 2, sample_rate: int = 24000):
+        """sample_rate other than 24000: the decoded rows go through `resample` (24000 -> sample_rate), one more launch"""
         n = len(codes)
         lens = np.array([c.shape[0] for c in codes], np.int32)
         stride = max(1, int(lens.max()))
@@ -412,9 +464,10 @@ class Engine:
         audio = np.empty((n, stride * 320), np.float32)
         self._chk(self.lib.vx_vocos_decode(self.ctx, _ptr(buf, C.c_int64), stride, _ptr(lens, C.c_int32), n,
                                            int(bandwidth_id), _ptr(audio, C.c_float), stride * 320))
-        return [audio[i, : lens[i] * 320] for i in range(n)]
+        rows = [audio[i, : lens[i] * 320] for i in range(n)]
+        return rows if int(sample_rate) == 24000 else self.resample(rows, 24000, int(sample_rate))
 
-    def encodec_decode(self, codes: Sequence[np.ndarray]):
+    def encodec_decode(self, codes: Sequence[np.ndarray], sample_rate: int = 24000):
         n = len(codes)
         lens = np.array([c.shape[0] for c in codes], np.int32)
         stride = max(1, int(lens.max()))
@@ -424,10 +477,15 @@ class Engine:
         audio = np.zeros((n, stride * 320), np.float32)
         self._chk(self.lib.vx_encodec_decode(self.ctx, _ptr(buf, C.c_int64), stride, _ptr(lens, C.c_int32), n,
                                              _ptr(audio, C.c_float), stride * 320))
+        if int(sample_rate) != 24000:
+            return self.resample([audio[i, : lens[i] * 320] for i in range(n)], 24000, int(sample_rate))
         return [audio[i, : lens[i] * 320].copy() for i in range(n)]
 
-    def encodec_encode(self, wavs: Sequence[np.ndarray]):
-        """mono 24 kHz fp32 waveforms (L_i,) -> codes (ceil(L_i / 320), 8) int64 per row (EnCodec encoder + RVQ, 6 kbps)."""
+    def encodec_encode(self, wavs: Sequence[np.ndarray], sample_rate: int = 24000):
+        """mono fp32 waveforms (L_i,) at sample_rate -> codes (ceil(L_i' / 320), 8) int64 per row (EnCodec encoder + RVQ, 6 kbps);
+        L_i' = L_i at 24 kHz, else the length after `resample` (sample_rate -> 24000), which runs first."""
+        if int(sample_rate) != 24000:
+            wavs = self.resample(wavs, int(sample_rate), 24000)
         n = len(wavs)
         lens = np.array([len(w) for w in wavs], np.int32)
         stride = max(1, int(lens.max()))
@@ -904,7 +962,7 @@ def _done_codes(codes, frames):
 class ServeSession:
     """A serving session of one Engine (vx_serve_open .. vx_serve_close).  Not thread-safe: every call from the thread that owns the
     engine (VALLE.serve wraps it in a worker thread).  While it is open, Engine.infer / nar / the step-level entries on the same
-    engine fail; vocos_decode / encodec_* stay available.  A request returns exactly what Engine.infer on it alone (batch 1, same
+    engine fail; vocos_decode / encodec_* / resample stay available.  A request returns exactly what Engine.infer on it alone (batch 1, same
     seed or draws, same best_of / length_penalty / return_worst, same top_k / temperature / force_eos_at) returns."""
 
     CANCEL_STATES = {0: None, 1: "waiting", 2: "decoding"}      # vx_serve_cancel's state

@@ -4,7 +4,7 @@
 // beams.hip: the best_of fan-out; admit.hip / serve.hip: admission kernels of the continuous schedule / the serving session;
 // serve_sample.hip: the serving session's per-row sampler;
 // bench_harness.hip: the measurement entries of include/vallex_hip_dev.h; score.hip: teacher-forced scoring, vx_score;
-// dev_wave.hip: vx_dev_wave_op, the correctness entry of the Vocos / EnCodec glue kernels).
+// dev_wave.hip: vx_dev_wave_op, the correctness entry of the Vocos / EnCodec glue kernels; resample.hip: vx_resample, kernel and driver).
 // Not part of the public C ABI.
 #pragma once
 
@@ -19,6 +19,7 @@
 #include <map>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/vallex_hip.h"
@@ -165,6 +166,11 @@ struct vx_ctx {
   // text alignment (vx_align, score.hip): allocated by the first vx_align
   float* al_out = nullptr;         // [mbr max_new][roundup(max_text, 4)] attention of the aligned frames over the text, summed over layers
   float* al_w = nullptr;           // [NL][16] head weights of the call
+  // sample-rate conversion (vx_resample, resample.hip): allocated by the first vx_resample; needs no weights
+  float *rs_in = nullptr, *rs_out = nullptr;      // input / output samples of one launch
+  int* rs_meta = nullptr;          // job records of one launch
+  long rs_window = 0;              // input samples per launch set by vx_dev_resample_window (0: the default, VX_RESAMPLE_WINDOW)
+  std::map<std::pair<int, int>, float*> rs_taps;  // (o, n) -> device tap table [K][n]
 
   // graph
   hipGraphExec_t graph_exec = nullptr, graph_exec_n = nullptr;   // one decode step / GRAPH_STEPS steps per launch

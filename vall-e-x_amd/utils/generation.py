@@ -182,6 +182,15 @@ def _detect(text, language):
     return language_detector(text)
 
 
+def _to_rate(wavs, sample_rate):
+    """the 24 kHz waveforms of a vocoder call at `sample_rate` (None / 24000: as they are): one vx_resample launch for the list"""
+    if sample_rate is None or int(sample_rate) == SAMPLE_RATE:
+        return wavs
+    if int(sample_rate) <= 0:
+        raise ValueError(f"sample_rate must be positive, got {sample_rate}")
+    return model.engine.resample(wavs, SAMPLE_RATE, int(sample_rate))
+
+
 def _infer_one(text, audio_prompts, text_prompts, lang_pr, language, accent, **kw):
     lang_token = lang2token[language]                                  # KeyError on unknown language (macros.py:8-13)
     lang = token2lang[lang_token]
@@ -200,7 +209,9 @@ def _infer_one(text, audio_prompts, text_prompts, lang_pr, language, accent, **k
     return out, phone_tokens
 
 
-def generate_audio(text, prompt=None, language="auto", accent="no-accent", **kw):
+def generate_audio(text, prompt=None, language="auto", accent="no-accent", sample_rate=None, **kw):
+    """utils/generation.py:92-152.  sample_rate (no reference counterpart; None = 24 kHz, the reference's): the waveform is resampled
+    on the device (Engine.resample, vx_resample) to that rate."""
     if model is None or vocos is None:
         raise RuntimeError("call preload_models() first")
     if isinstance(text, str):
@@ -219,10 +230,11 @@ def generate_audio(text, prompt=None, language="auto", accent="no-accent", **kw)
     features = vocos.codes_to_features(frames)
     samples = vocos.decode(features, bandwidth_id=np.array([2]))
     s = samples.squeeze()
-    return s.cpu().numpy() if torch is not None and isinstance(s, torch.Tensor) else np.asarray(s)
+    s = s.cpu().numpy() if torch is not None and isinstance(s, torch.Tensor) else np.asarray(s)
+    return s if sample_rate is None else _to_rate([s.reshape(-1)], sample_rate)[0]
 
 
-def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent", text_languages=None, **kw):
+def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent", text_languages=None, sample_rate=None, **kw):
     """Batch form of `generate_audio` (no reference equivalent: the reference synthesises one utterance per call,
     utils/generation.py:92-152): utterance i of the batch equals `generate_audio(texts[i], prompts[i], language[i], accent)`.
     `texts`: strings (need the tokenizer hook) or phoneme-id arrays; `prompts`: one preset name / path / None per utterance (or
@@ -230,7 +242,8 @@ def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent
     (what the tokenizer returned, `TextFrontendService`).  All utterances go through ONE `VALLE.inference_batch` call and ONE
     Vocos call.  `**kw` goes to `inference_batch`: `best_of`, `length_penalty` and `return_worst` apply to every utterance (best_of
     = N: N beams per utterance), injected `uniforms` are (steps, len(texts) x max(1, N)) with column i*N + j for beam j of
-    utterance i.  Returns a list of float32 waveforms."""
+    utterance i.  `sample_rate` (None = 24 kHz): the waveforms are resampled on the device in one more launch.  Returns a list of
+    float32 waveforms."""
     if model is None or vocos is None:
         raise RuntimeError("call preload_models() first")
     n = len(texts)
@@ -240,7 +253,7 @@ def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent
     rows = [_utterance_row(text, prompt, lang_in, accent, tl)
             for text, prompt, lang_in, tl in zip(texts, prompts, langs_in, text_languages)]
     codes = model.inference_batch(rows, top_k=-100, temperature=1, **kw)
-    return model.engine.vocos_decode(codes, 2)
+    return model.engine.vocos_decode(codes, 2, sample_rate=SAMPLE_RATE if sample_rate is None else int(sample_rate))
 
 
 def _utterance_row(text, prompt, lang_in, accent, tl=None) -> dict:
@@ -275,12 +288,18 @@ class AudioServer:
     Future of the float32 waveform.  Front-end work (tokenizer, prompt lookup, language detection) runs on the submitting thread;
     the codes of every group of completed requests go through Vocos on the server's worker thread.  Utterance i equals
     `generate_audio_batch([text], [prompt], language, accent, best_of=..., seed=...)[0]`.  `**serve_kw` goes to VALLE.serve
-    (sync_every, force_eos_at, max_steps)."""
+    (sync_every, force_eos_at, max_steps).  `sample_rate` (None = 24 kHz): ONE output rate for the server, applied to every delivered
+    waveform behind Vocos (vx_resample is allowed while the session is open)."""
 
-    def __init__(self, **serve_kw):
+    def __init__(self, sample_rate=None, **serve_kw):
         if model is None or vocos is None:
             raise RuntimeError("call preload_models() first")
-        self._server = model.serve(top_k=-100, temperature=1.0, post=lambda codes: model.engine.vocos_decode(codes, 2), **serve_kw)
+        rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
+        if rate <= 0:
+            raise ValueError(f"sample_rate must be positive, got {sample_rate}")
+        self.sample_rate = rate
+        self._server = model.serve(top_k=-100, temperature=1.0,
+                                   post=lambda codes: model.engine.vocos_decode(codes, 2, sample_rate=rate), **serve_kw)
 
     def submit(self, text, prompt=None, language="auto", accent="no-accent", best_of=1, seed=None, uniforms=None,
                length_penalty=1.0, return_worst=False, text_language=None, top_k=-100, temperature=1.0, top_p=1.0,
@@ -303,8 +322,9 @@ class AudioServer:
         self.close()
 
 
-def generate_audio_from_long_text(text, prompt=None, language="auto", accent="no-accent", mode="sliding-window", **kw):
-    """utils/generation.py:155-276.  `text` may also be a list of sentences / id arrays (pre-split)."""
+def generate_audio_from_long_text(text, prompt=None, language="auto", accent="no-accent", mode="sliding-window", sample_rate=None,
+                                  **kw):
+    """utils/generation.py:155-276.  `text` may also be a list of sentences / id arrays (pre-split).  sample_rate: as generate_audio."""
     if model is None or vocos is None:
         raise RuntimeError("call preload_models() first")
     if prompt is None or prompt == "":
@@ -352,4 +372,5 @@ def generate_audio_from_long_text(text, prompt=None, language="auto", accent="no
     features = vocos.codes_to_features(np.transpose(complete, (2, 0, 1)))
     samples = vocos.decode(features, bandwidth_id=np.array([2]))
     s = samples.squeeze()
-    return s.cpu().numpy() if torch is not None and isinstance(s, torch.Tensor) else np.asarray(s)
+    s = s.cpu().numpy() if torch is not None and isinstance(s, torch.Tensor) else np.asarray(s)
+    return s if sample_rate is None else _to_rate([s.reshape(-1)], sample_rate)[0]

@@ -7,8 +7,10 @@ What is NOT here (third-party CPU code outside the hot path, DESIGN.md section 8
 BPE tokenizer and langid (same pluggable hooks as `utils.generation`).  Audio at another sample rate is resampled to 24 kHz like the
 reference does (data/tokenizer.py:105 `convert_audio` = `torchaudio.transforms.Resample(sr, 24000)`): `resample_sinc_hann` below restates
 torchaudio's published default (Hann-windowed sinc, lowpass_filter_width 6, rolloff 0.99) -- torchaudio is not installed here, so this
-one piece is NOT pinned to the package; assign `resampler = lambda wav, sr, target_sr: ...` to plug in the real one.  Stereo is averaged
-like the reference does (utils/prompt_making.py:63-64).
+one piece is NOT pinned to the package; assign `resampler = lambda wav, sr, target_sr: ...` to plug in the real one.
+`device_resampler` is the same (unpinned) algorithm on the GPU (`vx_resample`): `resampler = device_resampler` plugs it in, and it is
+what a process WITHOUT torch gets on its own (the built-in needs torch).  Stereo is averaged like the reference does
+(utils/prompt_making.py:63-64).
 """
 from __future__ import annotations
 
@@ -60,6 +62,26 @@ def resample_sinc_hann(wav: np.ndarray, orig_freq: int, new_freq: int, lowpass_f
     return y.reshape(wav.shape[:-1] + (y.shape[-1],)).numpy()
 
 
+def device_resampler(wav: np.ndarray, sr: int, target_sr: int) -> np.ndarray:
+    """`resampler` hook on the device: (C, L) fp32 at sr -> (C, ceil(n L / o)) at target_sr through the loaded model's engine
+    (Engine.resample, vx_resample) -- resample_sinc_hann's taps and sums, K fmaf per sample, every channel a row of one launch."""
+    if G.model is None:
+        raise RuntimeError("call preload_models() first: the device resampler runs on the loaded model's engine")
+    wav = np.asarray(wav, np.float32)
+    rows = G.model.engine.resample(list(wav.reshape(-1, wav.shape[-1])), int(sr), int(target_sr))
+    return np.stack(rows).reshape(wav.shape[:-1] + (rows[0].shape[-1],))
+
+
+def _builtin_resampler() -> Callable[[np.ndarray, int, int], np.ndarray]:
+    """`resampler is None`: the torch restatement -- enrolment results do not change -- and, only where torch cannot be imported
+    (that case used to raise), the device path."""
+    try:
+        import torch  # noqa: F401
+    except ImportError:
+        return device_resampler
+    return resample_sinc_hann
+
+
 def _load_wav(path: str) -> Tuple[np.ndarray, int]:
     from scipy.io import wavfile                     # PCM / float WAV; the reference uses torchaudio.load
     sr, data = wavfile.read(path)
@@ -81,7 +103,7 @@ def tokenize_audio(tokenizer: AudioTokenizer, audio: Union[str, Tuple[np.ndarray
     if wav.shape[0] > 1:                                          # convert_audio(..., target_channels=1): channel mean, then resample
         wav = wav.mean(0, keepdims=True)
     if sr != tokenizer.sample_rate:
-        wav = np.asarray((resampler or resample_sinc_hann)(wav, int(sr), tokenizer.sample_rate), np.float32)
+        wav = np.asarray((resampler or _builtin_resampler())(wav, int(sr), tokenizer.sample_rate), np.float32)
     return tokenizer.encode(wav[None])                            # (1, 1, L)
 
 
