@@ -272,6 +272,91 @@ int vx_dev_align_rows(vx_ctx* ctx, int32_t M, int32_t nseq, const int32_t* tab, 
 int vx_dev_wave_op(vx_ctx* ctx, int32_t op, const int32_t* dims, const float* a, const float* b, const float* w, const float* bias,
                    const int32_t* ia, const int32_t* ib, float* out, float* out2, float* out3, int64_t* codes, int32_t* geom);
 
+/* ONE launch of a kernel of the seams between the phases -- the embedding gathers, the NAR arg-max, the prefill -> decode K / V
+ * hand-over and the AdaLN GEMV (csrc/rows.hip), the best_of fan-out (csrc/beams.hip), the admission kernels of the continuous
+ * schedule and the serving session (csrc/admit.hip, csrc/serve.hip), teacher forcing (csrc/decode.hip) -- through its product
+ * launcher on caller operands.  Everything the launch reads or writes is private scratch of the call: the context's arenas, decode
+ * state and KV cache are not touched, and the only context state read is what TABLES returns.  Every float output is pre-filled with
+ * VX_DEV_SENTINEL_F and every int output with VX_DEV_SENTINEL_I, and holds `extra` (0 .. 64) more rows or words than the launch may
+ * write; an IN / OUT operand carries the caller's contents in front of that sentinel tail.  Every index the kernel will form is
+ * checked on the host first.  dims is an int32 array whose meaning depends on op; arguments an op does not name may be NULL.  Rows
+ * are 1024 floats; "rows" counts are 1 .. 4096 unless stated.
+ *
+ *   EMBED_ROWS     dims {rows, extra, out_rows, rowsA, rowsB, pe_rows}; fa = tabA [rowsA][1024], fb = tabB [rowsB][1024] or NULL, fc =
+ *                  alpha [1], fd = pe [pe_rows][1024]; ia = idA [rows], ib = idB [rows] (-1: no add; NULL with tabB NULL and rowsB 0),
+ *                  ic = pos [rows], id = dst [rows] or NULL (the identity; then out_rows >= rows)
+ *                  out [out_rows + extra][1024]: out[dst[r]] = (tabA[idA[r]] + tabB[idB[r]]) + (alpha * pe[pos[r]]), every operation
+ *                  rounded to fp32 on its own (no fused multiply-add)
+ *   NAR_YEMB_INIT  dims {rows, extra, tab_rows}, tab_rows 1 .. 1024; fa = the 8 tables [8][tab_rows][1024] (the entry builds the device
+ *                  array of the 8 pointers); ia = codes [rows][8], all 8 inside the tables; ib = nj [rows], 1 .. 8
+ *                  out [rows + extra][1024]: out[r] = tab_0[codes[r][0]] + tab_1[codes[r][1]] + ... over j < nj[r], ascending
+ *   ADD_PE_SCATTER dims {rows, extra, out_rows, pe_rows}; fa = yemb [rows][1024], fc = alpha, fd = pe, ic = pos, id = dst (required)
+ *                  out [out_rows + extra][1024]: out[dst[r]] = yemb[r] + (alpha * pe[pos[r]])
+ *   EMBED_ACCUM    dims {n, extra, yrows, tab_rows}; fa = tab [tab_rows][1024]; ia = tok [n]; id = rowidx [n]
+ *                  out = yemb [yrows + extra][1024], IN / OUT: yemb[rowidx[i]] += tab[tok[i]]
+ *   ARGMAX_ROWS    dims {rows, extra, N, ldx}, 1 <= N <= ldx <= 8192; fa = x [rows][ldx]; iout = idx [rows + extra]: the lowest index
+ *                  of the largest of x[r][0 .. N-1] under `>` (so -0.0 and +0.0 tie and NaN is never chosen); a row without any
+ *                  value above -inf (all NaN, all -inf) gets 0
+ *   KV_SCATTER     dims {M, extra, Tmax, slots}, slots 1 .. 32; fa = qkv [M][3072]; ia = row_b [M] (slot), ib = row_t [M]
+ *                  out = kc, out2 = vc [slots][16][Tmax][64] + 64 extra floats: kc[row_b][h][row_t] = qkv[r][1024 + 64 h ..], vc from 2048
+ *   GEMV           dims {N, extra, K}, K % 4 == 0; fa = W [N][K], fb = e [K], fc = bias [N] or NULL; out [N + extra] = W e + bias
+ *   BEAM_FANOUT    dims {layers, extra, Tmax, slots, npairs, nrows, hrows}; layers 1 .. 64, slots 1 .. 32, npairs, nrows 0 .. 32 (not both
+ *                  0); ia = pairs [npairs][3] = {source slot, destination slot, cached rows 0 .. Tmax}; ib = hsrc_row [nrows];
+ *                  fa = hsrc [hrows][1024]; out = kc, out2 = vc [layers][slots][16][Tmax][64] + 64 extra floats, IN / OUT (may be NULL
+ *                  without pairs); out3 = dh [nrows + extra][1024]: dh[d] = hsrc[hsrc_row[d]]
+ *   ADMIT_ROWS     dims {n, extra, gen_stride, hrows}; ia = tab [n][5] (launch_admit_rows, csrc/engine_ctx.h); fa = hsrc [hrows][1024];
+ *                  out3 = hres [32 + extra][1024], IN / OUT; iout = the state block
+ *   ADMIT_MASK     dims {nrows, extra, gen_stride, phase}, nrows 1 .. 32, phase 0 | 1; ia = admitted [nrows]; iout = the state block
+ *   ADMIT_UNIFORMS dims {n, extra, steps, ncols, usteps, seed low word, seed high word}; ncols 1 .. 32, 1 <= steps <= usteps;
+ *                  ia = pairs [n][2] = {column d, caller row r}; fa = staged [n][steps] or NULL (the counter-based draws of `seed`);
+ *                  out = u [usteps][ncols] + extra floats, IN / OUT
+ *   SERVE_UNIFORMS dims {n, extra, gen_stride, ncols, usteps, nstaged}; ia = tab [n][13] (launch_serve_uniforms, csrc/engine_ctx.h:
+ *                  draws 0 .. usteps, staged offsets inside `staged`); fa = staged [nstaged] or NULL; out = u as ADMIT_UNIFORMS;
+ *                  out2 = sum_logp [32 + extra], IN / OUT; iout = the state block (row_smp, row_flt)
+ *   SERVE_CANCEL   dims {nrows, extra, gen_stride, row mask (the 32 bits of the word)}; iout = the state block
+ *   FORCE_TOKEN    dims {batch, extra, gen_stride}; ia = tok [batch]; iout = the state block (n_gen >= 0)
+ *   TABLES         no launch: out = the positional table [pe_rows][1024], out2 = the AdaLN table [7][2 NL + 1][2048] as the context holds
+ *                  them, iout = {pe_rows, NL, 2 NL + 1}; a NULL one is skipped
+ * The state block (IN / OUT, int32): every array a state kernel may read or write, at the word offsets VX_DEV_SEAM_ST_* -- 32 words each
+ * of cur_tok, cur_pos, ctx_len, n_gen, text_len, active, saved, slot_of (a permutation of 0 .. 31), then slot_meta [32][4], n_active
+ * (1 word + 3 of padding), row_smp [32][4], row_flt [32][4], and from VX_DEV_SEAM_ST_GEN gen [32][gen_stride] (gen_stride 1 .. 4096)
+ * and the `extra` sentinel words.
+ * VX_EINVAL, nothing launched and no output touched: anything outside the above -- an id outside its table, a dst / pos / slot / row
+ * index outside its operand, a duplicate in dst, rowidx, (row_b, row_t), the decode rows or columns of an admission table or the
+ * destinations of the fan-out pairs (two workgroups would write one row), a fan-out source that is also a destination, an operand of
+ * more than 2^24 elements.  VX_ESTATE while a serving session is open or before the weights are finalized. */
+#define VX_DEV_SEAM_EMBED_ROWS 0
+#define VX_DEV_SEAM_NAR_YEMB_INIT 1
+#define VX_DEV_SEAM_ADD_PE_SCATTER 2
+#define VX_DEV_SEAM_EMBED_ACCUM 3
+#define VX_DEV_SEAM_ARGMAX_ROWS 4
+#define VX_DEV_SEAM_KV_SCATTER 5
+#define VX_DEV_SEAM_GEMV 6
+#define VX_DEV_SEAM_BEAM_FANOUT 7
+#define VX_DEV_SEAM_ADMIT_ROWS 8
+#define VX_DEV_SEAM_ADMIT_MASK 9
+#define VX_DEV_SEAM_ADMIT_UNIFORMS 10
+#define VX_DEV_SEAM_SERVE_UNIFORMS 11
+#define VX_DEV_SEAM_SERVE_CANCEL 12
+#define VX_DEV_SEAM_FORCE_TOKEN 13
+#define VX_DEV_SEAM_TABLES 14
+#define VX_DEV_SEAM_ST_CUR_TOK 0
+#define VX_DEV_SEAM_ST_CUR_POS 32
+#define VX_DEV_SEAM_ST_CTX_LEN 64
+#define VX_DEV_SEAM_ST_N_GEN 96
+#define VX_DEV_SEAM_ST_TEXT_LEN 128
+#define VX_DEV_SEAM_ST_ACTIVE 160
+#define VX_DEV_SEAM_ST_SAVED 192
+#define VX_DEV_SEAM_ST_SLOT_OF 224
+#define VX_DEV_SEAM_ST_SLOT_META 256
+#define VX_DEV_SEAM_ST_N_ACTIVE 384
+#define VX_DEV_SEAM_ST_ROW_SMP 388
+#define VX_DEV_SEAM_ST_ROW_FLT 516
+#define VX_DEV_SEAM_ST_GEN 644
+int vx_dev_seam_op(vx_ctx* ctx, int32_t op, const int32_t* dims, const float* fa, const float* fb, const float* fc, const float* fd,
+                   const int32_t* ia, const int32_t* ib, const int32_t* ic, const int32_t* id, float* out, float* out2, float* out3,
+                   int32_t* iout);
+
 /* The resampler's tap table (csrc/resample.hip, the kernel behind vx_resample), as the device holds it: geom = {o, n, width, K} of
  * the pair, taps [n][K] = phase kernel p at taps + p K (NULL: the geometry alone, nothing is built).  The table is built and
  * uploaded at the pair's first use and read back FROM THE DEVICE here, so the words a test sees are the words the kernel reads.

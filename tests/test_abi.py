@@ -207,3 +207,20 @@ def test_dev_wave_op_prototype_matches_binding(lib):
     assert ops == _capi.DEV_WAVE_OPS and sorted(ops.values()) == list(range(12))
     assert int(re.search(r"#define VX_DEV_SENTINEL_L \((-\d+)LL\)", hdr).group(1)) == _capi.DEV_SENTINEL_L
     assert "vx_dev_wave_op" in _capi.DEV_SYMBOLS
+
+
+def test_dev_seam_op_prototype_matches_binding(lib):
+    """the header's prototype of vx_dev_seam_op and the ctypes signature agree argument by argument (15 of them); the op codes, the
+    word offsets of the state block and the int sentinel are the binding's"""
+    from vallex_amd import _capi
+    hdr = _proto_matches(lib, "vx_dev_seam_op", [
+        "vx_ctx* ctx", "int32_t op", "const int32_t* dims", "const float* fa", "const float* fb", "const float* fc", "const float* fd",
+        "const int32_t* ia", "const int32_t* ib", "const int32_t* ic", "const int32_t* id", "float* out", "float* out2", "float* out3",
+        "int32_t* iout"])
+    assert len(lib.vx_dev_seam_op.argtypes) == 15
+    st = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"#define VX_DEV_SEAM_ST_(\w+) (\d+)", hdr)}
+    assert st == _capi.DEV_SEAM_STATE
+    ops = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"#define VX_DEV_SEAM_(?!ST_)(\w+) (\d+)", hdr)}
+    assert ops == _capi.DEV_SEAM_OPS and sorted(ops.values()) == list(range(15))
+    assert int(re.search(r"#define VX_DEV_SENTINEL_I \((-\d+)\)", hdr).group(1)) == _capi.DEV_SENTINEL_I
+    assert "vx_dev_seam_op" in _capi.DEV_SYMBOLS

@@ -86,7 +86,7 @@ SYMBOLS = ["vx_abi_version", "vx_create", "vx_destroy", "vx_last_error", "vx_syn
 DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kernel", "vx_bench_gemm", "vx_bench_attn",
                "vx_bench_gemm_clock", "vx_bench_gemm_epilogue", "vx_dev_sample", "vx_dev_attn", "vx_dev_sample_filtered",
                "vx_dev_dec_attn", "vx_dev_dec_op", "vx_dev_gemm", "vx_dev_layernorm", "vx_dev_score_rows", "vx_dev_align_rows", "vx_dev_wave_op",
-               "vx_dev_resample_taps", "vx_dev_resample_window"]
+               "vx_dev_seam_op", "vx_dev_resample_taps", "vx_dev_resample_window"]
 # sentinels the correctness entries pre-fill their outputs with (include/vallex_hip_dev.h)
 DEV_SENTINEL_I = -123456789
 DEV_SENTINEL_F = np.float32(-1.0e30)
@@ -105,6 +105,12 @@ DEV_SENTINEL_H = 0xFBFF
 DEV_WAVE_OPS = {"codebook_sum": 0, "im2col7": 1, "dwconv7": 2, "istft_prep": 3, "overlap_add": 4, "im2col_seq": 5, "lstm_cell": 6,
                 "final_conv": 7, "enc_first_conv": 8, "enc_pad_elu": 9, "rvq_select": 10, "tables": 11}
 DEV_SENTINEL_L = -1234567890123456789
+# ops of vx_dev_seam_op (VX_DEV_SEAM_* of include/vallex_hip_dev.h) and the word offsets of its state block (VX_DEV_SEAM_ST_*)
+DEV_SEAM_OPS = {"embed_rows": 0, "nar_yemb_init": 1, "add_pe_scatter": 2, "embed_accum": 3, "argmax_rows": 4, "kv_scatter": 5, "gemv": 6,
+                "beam_fanout": 7, "admit_rows": 8, "admit_mask": 9, "admit_uniforms": 10, "serve_uniforms": 11, "serve_cancel": 12,
+                "force_token": 13, "tables": 14}
+DEV_SEAM_STATE = {"cur_tok": 0, "cur_pos": 32, "ctx_len": 64, "n_gen": 96, "text_len": 128, "active": 160, "saved": 192, "slot_of": 224,
+                  "slot_meta": 256, "n_active": 384, "row_smp": 388, "row_flt": 516, "gen": 644}
 SCORE_AR, SCORE_NAR = 1, 2             # VX_SCORE_* of include/vallex_hip.h (parts of vx_score)
 SCORE_PARTS = {"ar": SCORE_AR, "nar": SCORE_NAR, "both": SCORE_AR | SCORE_NAR}
 DEV_ALIGN_ROW_TILE, DEV_ALIGN_KEY_TILE = 32, 32      # VX_DEV_ALIGN_* of include/vallex_hip_dev.h: tiles of align_rows_kernel
@@ -211,6 +217,8 @@ def load_library() -> C.CDLL:
                                       C.c_int32]
     lib.vx_dev_wave_op.argtypes = [ctx, C.c_int32, P(C.c_int32), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_int32),
                                    P(C.c_int32), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_int64), P(C.c_int32)]
+    lib.vx_dev_seam_op.argtypes = [ctx, C.c_int32, P(C.c_int32), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_int32),
+                                   P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_int32)]
     lib.vx_resample.argtypes = [ctx, P(C.c_float), C.c_int64, P(C.c_int32), C.c_int32, C.c_int32, C.c_int32, P(C.c_float), C.c_int64,
                                 P(C.c_int32)]
     lib.vx_dev_resample_taps.argtypes = [ctx, C.c_int32, C.c_int32, P(C.c_float), P(C.c_int32)]
@@ -925,6 +933,24 @@ class Engine:
                                           pi(ia), pi(ib), pf(out), pf(out2), pf(out3),
                                           None if codes is None else _ptr(codes, C.c_int64), _ptr(geom, C.c_int32)))
         return geom
+
+    def dev_seam_op(self, op, dims, fa=None, fb=None, fc=None, fd=None, ia=None, ib=None, ic=None, id=None, out=None, out2=None, out3=None,
+                    iout=None):
+        """vx_dev_seam_op: one launch of a kernel of the seams between the phases (op: a key of DEV_SEAM_OPS or its code) on caller
+        operands; the meaning of dims and of the operands per op is documented in include/vallex_hip_dev.h.  fa .. fd are float32
+        inputs, ia .. id int32 inputs.  out, out2, out3 (float32) and iout (int32) are written IN PLACE and must be C-contiguous arrays
+        of the size the header states (IN / OUT operands are read, too)."""
+        f32 = lambda v: None if v is None else np.ascontiguousarray(v, np.float32)
+        i32 = lambda v: None if v is None else np.ascontiguousarray(v, np.int32)
+        fa, fb, fc, fd, ia, ib, ic, id = f32(fa), f32(fb), f32(fc), f32(fd), i32(ia), i32(ib), i32(ic), i32(id)
+        dims = np.ascontiguousarray(list(dims) + [0] * 8, np.int32)
+        for v, dt in ((out, np.float32), (out2, np.float32), (out3, np.float32), (iout, np.int32)):
+            if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.flags.c_contiguous and v.flags.writeable):
+                raise ValueError("out, out2, out3 are writeable C-contiguous float32 arrays, iout int32")
+        pf = lambda v: None if v is None else _ptr(v, C.c_float)
+        pi = lambda v: None if v is None else _ptr(v, C.c_int32)
+        self._chk(self.lib.vx_dev_seam_op(self.ctx, int(DEV_SEAM_OPS.get(op, op)), _ptr(dims, C.c_int32), pf(fa), pf(fb), pf(fc), pf(fd),
+                                          pi(ia), pi(ib), pi(ic), pi(id), pf(out), pf(out2), pf(out3), pi(iout)))
 
     def last_fallbacks(self):
         """phases of the last call that left the fp16 range of the f16x2 kernels and were re-run in fp32 (+ lifetime count)"""

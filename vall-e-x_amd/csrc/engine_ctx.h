@@ -4,7 +4,8 @@
 // beams.hip: the best_of fan-out; admit.hip / serve.hip: admission kernels of the continuous schedule / the serving session;
 // serve_sample.hip: the serving session's per-row sampler;
 // bench_harness.hip: the measurement entries of include/vallex_hip_dev.h; score.hip: teacher-forced scoring, vx_score;
-// dev_wave.hip: vx_dev_wave_op, the correctness entry of the Vocos / EnCodec glue kernels; resample.hip: vx_resample, kernel and driver).
+// dev_wave.hip: vx_dev_wave_op, the correctness entry of the Vocos / EnCodec glue kernels; dev_seam.hip: vx_dev_seam_op, the one of the
+// embedding / argmax / KV / admission kernels; resample.hip: vx_resample, kernel and driver).
 // Not part of the public C ABI.
 #pragma once
 
