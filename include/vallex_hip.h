@@ -276,6 +276,77 @@ int vx_encodec_encode(vx_ctx* ctx, const float* wav, int64_t wav_stride, const i
 int vx_resample(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t* lens, int32_t batch, int32_t orig_rate,
                 int32_t new_rate, float* out, int64_t out_stride, int32_t* out_lens);
 
+/* The output stage between a vocoder (or the resampler) and a sound device or file: trim, level, fade and 16-bit PCM of mono fp32
+ * rows on the device, with the measurements it rests on.  No reference counterpart: the reference hands back raw fp32.
+ * vx_finish measures every row (frame table -> vx_wave_info) and, when `out` is given, writes the kept span of every row, scaled,
+ * faded and in the asked format.  Every quantity is defined so that a plain numpy restatement reproduces it bit for bit:
+ *
+ * - Samples.  y[i] = isfinite(x[i]) ? x[i] : 0.  A non-finite sample never reaches an output.  It is counted in `nonfinite` (whole
+ *   row).
+ * - Frames.  Frame f covers samples [f F, min((f+1) F, L)); n_f is its count.  e_f is ONE LANE's sum in double of
+ *   (double)y * (double)y, taken in sample order from 0.0.  The square is exact in double, so contraction to an fma cannot change a
+ *   bit.  This equals np.cumsum(y.astype(f64) ** 2)[-1].  p_f = max |y|.  A frame's bits do not depend on the row, batch, tile or
+ *   window it lands in.
+ * - Active.  A frame is active iff e_f > thr2 * n_f, evaluated in double.  thr2 = pow(10.0, silence_db / 10.0) is computed once on
+ *   the host.  mean_square = (sum e_f) / (sum n_f) over the active frames, in frame order in double.
+ * - Span.  No active frame: begin = end = 0 on any trimmed side.  An untrimmed call keeps [0, L).  The gain is 1.  Otherwise, with
+ *   first and last active frames a and z: begin = (trim & 1) ? max(0, a F - keep) : 0 and
+ *   end = (trim & 2) ? min(L, (z + 1) F + keep) : L.
+ * - Gain.  The gain is computed on the host in double and rounded once to fp32.  t = pow(10, level_db / 20).  Peak mode:
+ *   g = t / peak.  RMS mode: g = t / sqrt(mean_square).  The result is min(g, pow(10, max_gain_db / 20)) (and at most FLT_MAX, so
+ *   that the fp32 gain is finite).  The gain is 1 when the denominator is 0.
+ * - Fades.  Two host-built fp32 tables use the smoothstep w(u) = u u (3 - 2u) with u = (j + 0.5) / n, evaluated in double with
+ *   + - * / only and rounded once.  No transcendental is used, so numpy reproduces every word.  Output sample i of n gets tab_in[i]
+ *   if i < fade_in, and tab_out[n - 1 - i] if n - 1 - i < fade_out.  It gets both where they overlap.  Rows shorter than a fade use
+ *   the part of the table they reach.
+ * - Apply.  The order is: v = y * g, then v *= tab_in[..] if it applies, then v *= tab_out[..] if it applies.  These are three
+ *   separately rounded fp32 multiplies.  VX_PCM_F32: out = v.  `clipped` counts |v| > 1.  VX_PCM_S16: r = rintf(v * 32768.0f)
+ *   (round half to even), stored as int16 clamped to [-32768, 32767].  `clipped` counts the samples the clamp changed.  Elements
+ *   behind out_lens[b] are not written.  A row of length 0 writes nothing.
+ * - Exactness and atomics.  The integer counts use integer atomics.  There are no floating-point atomics anywhere.  Two calls give
+ *   the same bits.
+ * - State.  As vx_resample: it needs no weights; it works on any created context, before vx_finalize_weights and while a serving
+ *   session is open; it touches no decode state, KV arena or fallback counter; the first call allocates its device buffers, which it
+ *   shares with the resampler's, since a context is single-threaded; vx_destroy frees them; all transfers go through the context's
+ *   pinned ring.
+ * - Windows.  One launch holds VX_FINISH_WINDOW (2^23) input samples.  Rows are packed into launches in order.  A longer row is cut at
+ *   frame multiples for the measure pass and anywhere for the apply pass.  By the rules above the result is bit-identical to a single
+ *   pass.
+ * - Refusals.  These return VX_EINVAL, launch nothing and write nothing, and the message names the field: NULL wav / lens / o / info;
+ *   out given without out_lens; batch <= 0; a wrong struct_size; every range above; a length negative or above wav_stride; out_stride
+ *   below a row's UNTRIMMED length, so that refusal never depends on the data.
+ *
+ *   wav [batch][wav_stride] fp32, lens [batch] samples; out [batch][out_stride] elements of `format` (float or int16_t), NULL:
+ *   measure only (info[b].clipped = 0); out_lens [batch] = end - begin (written when given); info [batch].  With `out` NULL the
+ *   fields trim .. format are still checked. */
+#define VX_PCM_F32 0
+#define VX_PCM_S16 1
+#define VX_LEVEL_NONE 0
+#define VX_LEVEL_PEAK 1
+#define VX_LEVEL_RMS  2
+#define VX_FINISH_WINDOW (1 << 23)
+typedef struct vx_finish_opts {
+  uint32_t struct_size;   /* = sizeof(vx_finish_opts) */
+  int32_t frame;          /* analysis frame in samples, 16 .. 4096 (10 ms = rate / 100) */
+  float silence_db;       /* finite, <= 0: a frame is ACTIVE iff its mean square exceeds 10^(silence_db / 10) */
+  int32_t trim;           /* bit 0: cut before the first active frame, bit 1: cut behind the last one */
+  int32_t keep;           /* >= 0: samples kept outside the active span on a trimmed side */
+  int32_t level_mode;     /* VX_LEVEL_* */
+  float level_db;         /* finite, <= 0: target dBFS of the peak / of the RMS over the active frames */
+  float max_gain_db;      /* finite, >= 0: cap of the gain */
+  int32_t fade_in, fade_out; /* >= 0 samples, <= 2^20 */
+  int32_t format;         /* VX_PCM_* : element type of out */
+} vx_finish_opts;
+typedef struct vx_wave_info {
+  int32_t begin, end;     /* the kept span [begin, end) in input samples; out_len = end - begin */
+  int32_t active_frames, nonfinite, clipped;
+  float peak;             /* max |y| over the frames that intersect [begin, end) */
+  float gain;             /* the linear gain that was applied (1 with VX_LEVEL_NONE) */
+  double mean_square;     /* over the active frames; 0 if there is none */
+} vx_wave_info;
+int vx_finish(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t* lens, int32_t batch, const vx_finish_opts* o,
+              void* out /* may be NULL: measure only */, int64_t out_stride /* in elements */, int32_t* out_lens, vx_wave_info* info);
+
 /* ---- step-level entries (kernel-level parity tests; same kernels as vx_infer) ---------------------------- */
 /* first ar_decoder.infer call (models/vallex.py:528-562): embeds, runs the prefix-LM prefill, fills the KV arena,
  * leaves the logits of the last row available.  batch <= 32. */

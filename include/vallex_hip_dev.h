@@ -369,6 +369,19 @@ int vx_dev_resample_taps(vx_ctx* ctx, int32_t orig_rate, int32_t new_rate, float
 #define VX_DEV_RESAMPLE_WINDOW_MIN 512
 int vx_dev_resample_window(vx_ctx* ctx, int32_t input_samples);
 
+/* The frame table of ONE row as wave_frames_kernel (csrc/finish.hip, the measure pass of vx_finish) writes it: frame f covers samples
+ * [f frame, min((f + 1) frame, len)); e[f] = one lane's sum in double of the squares of its samples (non-finite samples as 0) in
+ * sample order, p[f] = max |y|, z[f] = its non-finite samples.  e, p, z hold ceil(len / frame) entries each; len = 0 writes nothing.
+ * The row goes through the same planner and windows as vx_finish.  VX_EINVAL, nothing written: a NULL pointer, len < 0, frame
+ * outside 16 .. 4096. */
+int vx_dev_finish_frames(vx_ctx* ctx, const float* wav, int32_t len, int32_t frame, double* e, float* p, int32_t* z);
+/* Input samples one launch of vx_finish holds, for later calls on this context: VX_DEV_FINISH_WINDOW_MIN .. VX_FINISH_WINDOW, or 0
+ * for the default (VX_FINISH_WINDOW).  A small window sends short rows through several windows and launches of both passes -- what
+ * the window tests need; the device buffers keep their size.  A launch always holds at least one frame: a call whose frame exceeds
+ * the window runs with a window of one frame.  VX_EINVAL, nothing changed, for any other value. */
+#define VX_DEV_FINISH_WINDOW_MIN 512
+int vx_dev_finish_window(vx_ctx* ctx, int32_t input_samples);
+
 #ifdef __cplusplus
 }
 #endif

@@ -74,6 +74,19 @@ class vx_request_filters(C.Structure):
                 ("repetition_window", C.c_int32), ("min_frames", C.c_int32)]
 
 
+class vx_finish_opts(C.Structure):
+    """options of vx_finish (the output stage: trim, level, fades, PCM format)"""
+    _fields_ = [("struct_size", C.c_uint32), ("frame", C.c_int32), ("silence_db", C.c_float), ("trim", C.c_int32), ("keep", C.c_int32),
+                ("level_mode", C.c_int32), ("level_db", C.c_float), ("max_gain_db", C.c_float), ("fade_in", C.c_int32),
+                ("fade_out", C.c_int32), ("format", C.c_int32)]
+
+
+class vx_wave_info(C.Structure):
+    """what vx_finish measured of one row"""
+    _fields_ = [("begin", C.c_int32), ("end", C.c_int32), ("active_frames", C.c_int32), ("nonfinite", C.c_int32), ("clipped", C.c_int32),
+                ("peak", C.c_float), ("gain", C.c_float), ("mean_square", C.c_double)]
+
+
 # every symbol include/vallex_hip.h declares (tests/test_abi.py checks the library exports exactly these)
 ABI_VERSION = 6       # VX_ABI_VERSION of include/vallex_hip.h this binding was written against
 
@@ -81,12 +94,13 @@ SYMBOLS = ["vx_abi_version", "vx_create", "vx_destroy", "vx_last_error", "vx_syn
            "vx_infer", "vx_vocos_decode", "vx_encodec_decode", "vx_encodec_encode", "vx_ar_prefill", "vx_ar_logits", "vx_ar_step",
            "vx_nar", "vx_read_tap", "vx_last_stats", "vx_last_truncated", "vx_last_fallbacks", "vx_fallback_state",
            "vx_fallback_reset", "vx_arith_mode", "vx_infer_continuous", "vx_serve_open", "vx_serve_submit", "vx_serve_run",
-           "vx_serve_close", "vx_serve_submit_ex", "vx_serve_cancel", "vx_serve_submit_filtered", "vx_score", "vx_align", "vx_resample"]
+           "vx_serve_close", "vx_serve_submit_ex", "vx_serve_cancel", "vx_serve_submit_filtered", "vx_score", "vx_align", "vx_resample",
+           "vx_finish"]
 # ... and include/vallex_hip_dev.h: measurement / kernel development, never called by the mirrors of the reference API
 DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kernel", "vx_bench_gemm", "vx_bench_attn",
                "vx_bench_gemm_clock", "vx_bench_gemm_epilogue", "vx_dev_sample", "vx_dev_attn", "vx_dev_sample_filtered",
                "vx_dev_dec_attn", "vx_dev_dec_op", "vx_dev_gemm", "vx_dev_layernorm", "vx_dev_score_rows", "vx_dev_align_rows", "vx_dev_wave_op",
-               "vx_dev_seam_op", "vx_dev_resample_taps", "vx_dev_resample_window"]
+               "vx_dev_seam_op", "vx_dev_resample_taps", "vx_dev_resample_window", "vx_dev_finish_frames", "vx_dev_finish_window"]
 # sentinels the correctness entries pre-fill their outputs with (include/vallex_hip_dev.h)
 DEV_SENTINEL_I = -123456789
 DEV_SENTINEL_F = np.float32(-1.0e30)
@@ -115,6 +129,9 @@ SCORE_AR, SCORE_NAR = 1, 2             # VX_SCORE_* of include/vallex_hip.h (par
 SCORE_PARTS = {"ar": SCORE_AR, "nar": SCORE_NAR, "both": SCORE_AR | SCORE_NAR}
 DEV_ALIGN_ROW_TILE, DEV_ALIGN_KEY_TILE = 32, 32      # VX_DEV_ALIGN_* of include/vallex_hip_dev.h: tiles of align_rows_kernel
 RESAMPLE_WINDOW, DEV_RESAMPLE_WINDOW_MIN = 1 << 23, 512     # VX_RESAMPLE_WINDOW / VX_DEV_RESAMPLE_WINDOW_MIN: input samples per launch
+FINISH_WINDOW, DEV_FINISH_WINDOW_MIN = 1 << 23, 512         # VX_FINISH_WINDOW / VX_DEV_FINISH_WINDOW_MIN: input samples per launch
+PCM_F32, PCM_S16 = 0, 1                                      # VX_PCM_*
+LEVEL_NONE, LEVEL_PEAK, LEVEL_RMS = 0, 1, 2                  # VX_LEVEL_*
 DEV_SAMPLE_CFG = ("kernel", "splitk", "top_k", "force_eos_at", "active", "n_gen", "cur_pos", "ctx_len", "text_len", "gen_stride")
 
 # vx_row_done_fn of vx_infer_continuous: (user, caller row, codes [frames][8] int64, frames)
@@ -223,6 +240,10 @@ def load_library() -> C.CDLL:
                                 P(C.c_int32)]
     lib.vx_dev_resample_taps.argtypes = [ctx, C.c_int32, C.c_int32, P(C.c_float), P(C.c_int32)]
     lib.vx_dev_resample_window.argtypes = [ctx, C.c_int32]
+    lib.vx_finish.argtypes = [ctx, P(C.c_float), C.c_int64, P(C.c_int32), C.c_int32, P(vx_finish_opts), C.c_void_p, C.c_int64, P(C.c_int32),
+                              P(vx_wave_info)]
+    lib.vx_dev_finish_frames.argtypes = [ctx, P(C.c_float), C.c_int32, C.c_int32, P(C.c_double), P(C.c_float), P(C.c_int32)]
+    lib.vx_dev_finish_window.argtypes = [ctx, C.c_int32]
     lib.vx_last_stats.argtypes = [ctx, P(C.c_int64), P(C.c_int64), P(C.c_double), P(C.c_double)]
     lib.vx_last_truncated.argtypes = [ctx, P(C.c_int32)]
     lib.vx_last_fallbacks.argtypes = [ctx, P(C.c_int32), P(C.c_int32), P(C.c_int64)]
@@ -459,8 +480,75 @@ class Engine:
         RESAMPLE_WINDOW; 0 restores the default)"""
         self._chk(self.lib.vx_dev_resample_window(self.ctx, int(input_samples)))
 
-    def vocos_decode(self, codes: Sequence[np.ndarray], bandwidth_id: int = 2, sample_rate: int = 24000):
-        """sample_rate other than 24000: the decoded rows go through `resample` (24000 -> sample_rate), one more launch"""
+    def finish(self, wavs: Sequence[np.ndarray], frame: int, silence_db: float = -40.0, trim: int = 0, keep: int = 0, level_mode: int = 0,
+               level_db: float = -1.0, max_gain_db: float = 20.0, fade_in: int = 0, fade_out: int = 0, pcm16: bool = False):
+        """vx_finish, the output stage: mono fp32 waveforms (L_i,) -> (list of arrays, list of info dicts).  Every row is measured in
+        frames of `frame` samples (10 ms = rate // 100): a frame is active iff its mean square exceeds 10^(silence_db / 10).  trim bit 0 /
+        bit 1 cut before the first / behind the last active frame, keeping `keep` samples; level_mode LEVEL_PEAK / LEVEL_RMS brings the
+        peak / the RMS over the active frames to level_db dBFS with at most max_gain_db of gain; fade_in / fade_out samples of
+        smoothstep; pcm16: int16 (round half to even, clamped) instead of float32.  Non-finite samples count as 0.  info: begin, end,
+        active_frames, nonfinite, clipped, peak, gain, mean_square (include/vallex_hip.h: vx_wave_info)."""
+        return self._finish(wavs, frame, silence_db, trim, keep, level_mode, level_db, max_gain_db, fade_in, fade_out, pcm16, False)
+
+    def measure(self, wavs: Sequence[np.ndarray], frame: int, silence_db: float = -40.0):
+        """the info dicts of `finish` alone (vx_finish without an output: nothing is scaled or brought back): [begin, end) is the span
+        from the first to the last active frame (trim = 3, keep = 0; 0, 0 for an all-silent row), peak the peak inside it; active_frames,
+        nonfinite and mean_square say what the row holds; gain 1, clipped 0"""
+        return self._finish(wavs, frame, silence_db, 3, 0, 0, -1.0, 20.0, 0, 0, False, True)[1]
+
+    def _finish(self, wavs, frame, silence_db, trim, keep, level_mode, level_db, max_gain_db, fade_in, fade_out, pcm16, measure_only):
+        n = len(wavs)
+        if n == 0:
+            return [], []
+        ws = [np.ascontiguousarray(w, np.float32).reshape(-1) for w in wavs]
+        lens = np.array([len(w) for w in ws], np.int32)
+        stride = max(1, int(lens.max()))
+        if n == 1:
+            buf = ws[0] if len(ws[0]) else np.zeros(1, np.float32)        # no second copy of a single (long) row
+        else:
+            buf = np.zeros((n, stride), np.float32)
+            for i, w in enumerate(ws):
+                buf[i, : len(w)] = w
+        o = vx_finish_opts(C.sizeof(vx_finish_opts), int(frame), float(silence_db), int(trim), int(keep), int(level_mode), float(level_db),
+                           float(max_gain_db), int(fade_in), int(fade_out), PCM_S16 if pcm16 else PCM_F32)
+        info = (vx_wave_info * n)()
+        out = None if measure_only else np.empty((n, stride), np.int16 if pcm16 else np.float32)
+        out_lens = np.zeros(n, np.int32)
+        self._chk(self.lib.vx_finish(self.ctx, _ptr(buf, C.c_float), stride, _ptr(lens, C.c_int32), n, C.byref(o),
+                                     None if out is None else out.ctypes.data_as(C.c_void_p), stride, _ptr(out_lens, C.c_int32), info))
+        infos = [{f[0]: getattr(w, f[0]) for f in vx_wave_info._fields_} for w in info]
+        return ([] if out is None else [out[i, : out_lens[i]] for i in range(n)]), infos
+
+    def dev_finish_frames(self, wav: np.ndarray, frame: int):
+        """vx_dev_finish_frames: the frame table of one row as the measure kernel wrote it: (e float64, p float32, z int32)"""
+        w = np.ascontiguousarray(wav, np.float32).reshape(-1)
+        nf = -(-len(w) // int(frame)) if int(frame) > 0 else 0
+        e, p, z = np.zeros(max(nf, 1), np.float64), np.zeros(max(nf, 1), np.float32), np.zeros(max(nf, 1), np.int32)
+        buf = w if len(w) else np.zeros(1, np.float32)
+        self._chk(self.lib.vx_dev_finish_frames(self.ctx, _ptr(buf, C.c_float), len(w), int(frame), _ptr(e, C.c_double), _ptr(p, C.c_float),
+                                                _ptr(z, C.c_int32)))
+        return e[:nf], p[:nf], z[:nf]
+
+    def dev_finish_window(self, input_samples: int = 0):
+        """vx_dev_finish_window: input samples one launch of `finish` holds from now on (DEV_FINISH_WINDOW_MIN .. FINISH_WINDOW; 0
+        restores the default)"""
+        self._chk(self.lib.vx_dev_finish_window(self.ctx, int(input_samples)))
+
+    last_finish_info = None          # the info dicts of the last call that went through a `finish=` argument
+
+    def _finished(self, rows, finish, rate: int):
+        """the rows of a vocoder call through `finish` (an object with the fields of utils.generation.Finish; None: as they are) at the
+        output rate; the infos stay in `last_finish_info`"""
+        if finish is None:
+            return rows
+        frame = finish.frame if finish.frame is not None else int(rate) // 100
+        out, self.last_finish_info = self.finish(rows, frame, finish.silence_db, finish.trim, finish.keep, finish.level_mode, finish.level_db,
+                                                 finish.max_gain_db, finish.fade_in, finish.fade_out, finish.pcm16)
+        return out
+
+    def vocos_decode(self, codes: Sequence[np.ndarray], bandwidth_id: int = 2, sample_rate: int = 24000, finish=None):
+        """sample_rate other than 24000: the decoded rows go through `resample` (24000 -> sample_rate), one more launch; finish (a
+        utils.generation.Finish): then through `finish` at that rate"""
         n = len(codes)
         lens = np.array([c.shape[0] for c in codes], np.int32)
         stride = max(1, int(lens.max()))
@@ -473,9 +561,9 @@ class Engine:
         self._chk(self.lib.vx_vocos_decode(self.ctx, _ptr(buf, C.c_int64), stride, _ptr(lens, C.c_int32), n,
                                            int(bandwidth_id), _ptr(audio, C.c_float), stride * 320))
         rows = [audio[i, : lens[i] * 320] for i in range(n)]
-        return rows if int(sample_rate) == 24000 else self.resample(rows, 24000, int(sample_rate))
+        return self._finished(rows if int(sample_rate) == 24000 else self.resample(rows, 24000, int(sample_rate)), finish, sample_rate)
 
-    def encodec_decode(self, codes: Sequence[np.ndarray], sample_rate: int = 24000):
+    def encodec_decode(self, codes: Sequence[np.ndarray], sample_rate: int = 24000, finish=None):
         n = len(codes)
         lens = np.array([c.shape[0] for c in codes], np.int32)
         stride = max(1, int(lens.max()))
@@ -486,8 +574,8 @@ class Engine:
         self._chk(self.lib.vx_encodec_decode(self.ctx, _ptr(buf, C.c_int64), stride, _ptr(lens, C.c_int32), n,
                                              _ptr(audio, C.c_float), stride * 320))
         if int(sample_rate) != 24000:
-            return self.resample([audio[i, : lens[i] * 320] for i in range(n)], 24000, int(sample_rate))
-        return [audio[i, : lens[i] * 320].copy() for i in range(n)]
+            return self._finished(self.resample([audio[i, : lens[i] * 320] for i in range(n)], 24000, int(sample_rate)), finish, sample_rate)
+        return self._finished([audio[i, : lens[i] * 320].copy() for i in range(n)], finish, sample_rate)
 
     def encodec_encode(self, wavs: Sequence[np.ndarray], sample_rate: int = 24000):
         """mono fp32 waveforms (L_i,) at sample_rate -> codes (ceil(L_i' / 320), 8) int64 per row (EnCodec encoder + RVQ, 6 kbps);

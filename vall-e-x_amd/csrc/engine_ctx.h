@@ -5,7 +5,7 @@
 // serve_sample.hip: the serving session's per-row sampler;
 // bench_harness.hip: the measurement entries of include/vallex_hip_dev.h; score.hip: teacher-forced scoring, vx_score;
 // dev_wave.hip: vx_dev_wave_op, the correctness entry of the Vocos / EnCodec glue kernels; dev_seam.hip: vx_dev_seam_op, the one of the
-// embedding / argmax / KV / admission kernels; resample.hip: vx_resample, kernel and driver).
+// embedding / argmax / KV / admission kernels; resample.hip: vx_resample, kernel and driver; finish.hip: vx_finish, the output stage).
 // Not part of the public C ABI.
 #pragma once
 
@@ -172,6 +172,10 @@ struct vx_ctx {
   int* rs_meta = nullptr;          // job records of one launch
   long rs_window = 0;              // input samples per launch set by vx_dev_resample_window (0: the default, VX_RESAMPLE_WINDOW)
   std::map<std::pair<int, int>, float*> rs_taps;  // (o, n) -> device tap table [K][n]
+  // output stage (vx_finish, finish.hip): runs in the resampler's launch buffers (rs_buffers); needs no weights
+  float* fn_fade = nullptr;        // [2][2^20] the fade-in / fade-out tables, allocated by the first call with a fade
+  int fn_fade_n[2] = {0, 0};       // the lengths the two device tables were last built for
+  long fn_window = 0;              // input samples per launch set by vx_dev_finish_window (0: the default, VX_FINISH_WINDOW)
 
   // graph
   hipGraphExec_t graph_exec = nullptr, graph_exec_n = nullptr;   // one decode step / GRAPH_STEPS steps per launch
@@ -486,6 +490,13 @@ inline void reset_call_stats(vx_ctx* c) {      // what vx_last_stats / vx_last_t
 // schedule.hip: entry points that overwrite the decode state refuse to run while a serving session owns it; vx_destroy frees an open one
 int serve_busy(vx_ctx* c, const char* what);
 void serve_free(vx_serve* v);
+// resample.hip: the launch buffers of the waveform entries, allocated by the first call that needs them and shared by vx_resample and
+// vx_finish (a context is single-threaded): rs_in RS_IN_CAP floats, rs_out RS_OUT_CAP floats, rs_meta RS_MAX_JOBS records of RS_TAB ints
+constexpr int RS_TAB = 8;                  // ints of a job record
+constexpr int RS_MAX_JOBS = 4096;          // jobs per launch (grid.y)
+constexpr long RS_IN_CAP = VX_RESAMPLE_WINDOW;          // input samples per launch, default
+constexpr long RS_OUT_CAP = 2 * RS_IN_CAP;              // output samples per launch
+int rs_buffers(vx_ctx* c);
 // score.hip: (log-probability, rank) of targets[r] in logits[r][0 .. ncols-1], one wavefront per row
 void launch_score_rows(const float* logits, int ld, int rows, int ncols, const int* targets, float* logp, int* rank, hipStream_t s);
 

@@ -29,12 +29,9 @@
 
 namespace vxe {
 
-constexpr int RS_TAB = 8;                  // job record: {in_off, s_lo, in_cnt, L, blk0, nblk, out_off, out_cnt}
+// job record (RS_TAB ints, engine_ctx.h): {in_off, s_lo, in_cnt, L, blk0, nblk, out_off, out_cnt}
 constexpr int RS_LDS = 8192;               // floats of input span a workgroup stages
 constexpr int RS_TILE_OUT = 2048;          // outputs a workgroup aims at
-constexpr int RS_MAX_JOBS = 4096;          // jobs per launch (grid.y)
-constexpr long RS_IN_CAP = VX_RESAMPLE_WINDOW;          // input samples per launch, default
-constexpr long RS_OUT_CAP = 2 * RS_IN_CAP;              // output samples per launch
 static_assert(VX_DEV_RESAMPLE_WINDOW_MIN >= 256 && VX_DEV_RESAMPLE_WINDOW_MIN <= RS_IN_CAP, "window bounds of the dev header");
 
 // tab [njobs][8]:
@@ -104,7 +101,7 @@ static int rs_table(vx_ctx* c, const RsGeom& g, const float** dev) {
   return VX_OK;
 }
 
-static int rs_buffers(vx_ctx* c) {
+int rs_buffers(vx_ctx* c) {
   if (c->rs_in) return VX_OK;
   if (int e = dev_alloc(c, &c->rs_meta, (size_t)RS_MAX_JOBS * RS_TAB, false)) return e;
   if (int e = dev_alloc(c, &c->rs_out, (size_t)RS_OUT_CAP, false)) return e;

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import logging
 import os
+from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -182,6 +183,33 @@ def _detect(text, language):
     return language_detector(text)
 
 
+@dataclass(frozen=True)
+class Finish:
+    """The output stage of a waveform (Engine.finish, vx_finish), accepted as `finish=` wherever a waveform leaves: it is applied after
+    the resampler, at the output rate.  frame None = 10 ms at that rate (sample_rate // 100).  A frame is active iff its mean square
+    exceeds 10^(silence_db / 10); trim bit 0 / bit 1 cut before the first / behind the last active frame, `keep` samples stay;
+    level_mode 1 / 2 brings the peak / the RMS over the active frames to level_db dBFS with at most max_gain_db of gain; fade_in /
+    fade_out are samples of smoothstep; pcm16: int16 instead of float32.  The measurements of the last call stay in
+    `model.engine.last_finish_info`."""
+    frame: Optional[int] = None
+    silence_db: float = -40.0
+    trim: int = 0
+    keep: int = 0
+    level_mode: int = 0
+    level_db: float = -1.0
+    max_gain_db: float = 20.0
+    fade_in: int = 0
+    fade_out: int = 0
+    pcm16: bool = False
+
+
+def _finished(wavs, finish, sample_rate):
+    """the waveforms of a call, already at their output rate, through `finish` (None: as they are): one vx_finish call for the list"""
+    if finish is None:
+        return wavs
+    return model.engine._finished(wavs, finish, SAMPLE_RATE if sample_rate is None else int(sample_rate))
+
+
 def _to_rate(wavs, sample_rate):
     """the 24 kHz waveforms of a vocoder call at `sample_rate` (None / 24000: as they are): one vx_resample launch for the list"""
     if sample_rate is None or int(sample_rate) == SAMPLE_RATE:
@@ -209,9 +237,10 @@ def _infer_one(text, audio_prompts, text_prompts, lang_pr, language, accent, **k
     return out, phone_tokens
 
 
-def generate_audio(text, prompt=None, language="auto", accent="no-accent", sample_rate=None, **kw):
+def generate_audio(text, prompt=None, language="auto", accent="no-accent", sample_rate=None, finish=None, **kw):
     """utils/generation.py:92-152.  sample_rate (no reference counterpart; None = 24 kHz, the reference's): the waveform is resampled
-    on the device (Engine.resample, vx_resample) to that rate."""
+    on the device (Engine.resample, vx_resample) to that rate.  finish (a `Finish`; None = the raw fp32 of the reference): the output
+    stage behind it -- trim, level, fades, int16 with pcm16=True."""
     if model is None or vocos is None:
         raise RuntimeError("call preload_models() first")
     if isinstance(text, str):
@@ -231,10 +260,13 @@ def generate_audio(text, prompt=None, language="auto", accent="no-accent", sampl
     samples = vocos.decode(features, bandwidth_id=np.array([2]))
     s = samples.squeeze()
     s = s.cpu().numpy() if torch is not None and isinstance(s, torch.Tensor) else np.asarray(s)
+    if finish is not None:
+        return _finished(_to_rate([s.reshape(-1)], sample_rate), finish, sample_rate)[0]
     return s if sample_rate is None else _to_rate([s.reshape(-1)], sample_rate)[0]
 
 
-def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent", text_languages=None, sample_rate=None, **kw):
+def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent", text_languages=None, sample_rate=None, finish=None,
+                         **kw):
     """Batch form of `generate_audio` (no reference equivalent: the reference synthesises one utterance per call,
     utils/generation.py:92-152): utterance i of the batch equals `generate_audio(texts[i], prompts[i], language[i], accent)`.
     `texts`: strings (need the tokenizer hook) or phoneme-id arrays; `prompts`: one preset name / path / None per utterance (or
@@ -242,8 +274,8 @@ def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent
     (what the tokenizer returned, `TextFrontendService`).  All utterances go through ONE `VALLE.inference_batch` call and ONE
     Vocos call.  `**kw` goes to `inference_batch`: `best_of`, `length_penalty` and `return_worst` apply to every utterance (best_of
     = N: N beams per utterance), injected `uniforms` are (steps, len(texts) x max(1, N)) with column i*N + j for beam j of
-    utterance i.  `sample_rate` (None = 24 kHz): the waveforms are resampled on the device in one more launch.  Returns a list of
-    float32 waveforms."""
+    utterance i.  `sample_rate` (None = 24 kHz): the waveforms are resampled on the device in one more launch.  `finish` (a
+    `Finish`): the output stage behind it, one more call for the list.  Returns a list of float32 waveforms (int16 with pcm16=True)."""
     if model is None or vocos is None:
         raise RuntimeError("call preload_models() first")
     n = len(texts)
@@ -253,7 +285,7 @@ def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent
     rows = [_utterance_row(text, prompt, lang_in, accent, tl)
             for text, prompt, lang_in, tl in zip(texts, prompts, langs_in, text_languages)]
     codes = model.inference_batch(rows, top_k=-100, temperature=1, **kw)
-    return model.engine.vocos_decode(codes, 2, sample_rate=SAMPLE_RATE if sample_rate is None else int(sample_rate))
+    return model.engine.vocos_decode(codes, 2, sample_rate=SAMPLE_RATE if sample_rate is None else int(sample_rate), finish=finish)
 
 
 def _utterance_row(text, prompt, lang_in, accent, tl=None) -> dict:
@@ -289,17 +321,20 @@ class AudioServer:
     the codes of every group of completed requests go through Vocos on the server's worker thread.  Utterance i equals
     `generate_audio_batch([text], [prompt], language, accent, best_of=..., seed=...)[0]`.  `**serve_kw` goes to VALLE.serve
     (sync_every, force_eos_at, max_steps).  `sample_rate` (None = 24 kHz): ONE output rate for the server, applied to every delivered
-    waveform behind Vocos (vx_resample is allowed while the session is open)."""
+    waveform behind Vocos (vx_resample is allowed while the session is open).  `finish` (a `Finish`): ONE output stage for the server,
+    applied behind that (vx_finish is allowed as well)."""
 
-    def __init__(self, sample_rate=None, **serve_kw):
+    def __init__(self, sample_rate=None, finish=None, **serve_kw):
         if model is None or vocos is None:
             raise RuntimeError("call preload_models() first")
         rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
         if rate <= 0:
             raise ValueError(f"sample_rate must be positive, got {sample_rate}")
         self.sample_rate = rate
+        self.finish = finish
         self._server = model.serve(top_k=-100, temperature=1.0,
-                                   post=lambda codes: model.engine.vocos_decode(codes, 2, sample_rate=rate), **serve_kw)
+                                   post=lambda codes: model.engine.vocos_decode(codes, 2, sample_rate=rate, finish=finish),
+                                   **serve_kw)
 
     def submit(self, text, prompt=None, language="auto", accent="no-accent", best_of=1, seed=None, uniforms=None,
                length_penalty=1.0, return_worst=False, text_language=None, top_k=-100, temperature=1.0, top_p=1.0,
@@ -323,8 +358,9 @@ class AudioServer:
 
 
 def generate_audio_from_long_text(text, prompt=None, language="auto", accent="no-accent", mode="sliding-window", sample_rate=None,
-                                  **kw):
-    """utils/generation.py:155-276.  `text` may also be a list of sentences / id arrays (pre-split).  sample_rate: as generate_audio."""
+                                  finish=None, **kw):
+    """utils/generation.py:155-276.  `text` may also be a list of sentences / id arrays (pre-split).  sample_rate, finish: as
+    generate_audio (the output stage sees the concatenated waveform once)."""
     if model is None or vocos is None:
         raise RuntimeError("call preload_models() first")
     if prompt is None or prompt == "":
@@ -367,10 +403,12 @@ def generate_audio_from_long_text(text, prompt=None, language="auto", accent="no
             else:
                 audio_prompts, text_prompts = original                 # :268-269
     if not chunks:
-        return np.zeros(0, np.float32)
+        return np.zeros(0, np.int16 if finish is not None and finish.pcm16 else np.float32)
     complete = np.concatenate(chunks, axis=1)                          # (1, sum T, 8)
     features = vocos.codes_to_features(np.transpose(complete, (2, 0, 1)))
     samples = vocos.decode(features, bandwidth_id=np.array([2]))
     s = samples.squeeze()
     s = s.cpu().numpy() if torch is not None and isinstance(s, torch.Tensor) else np.asarray(s)
+    if finish is not None:
+        return _finished(_to_rate([s.reshape(-1)], sample_rate), finish, sample_rate)[0]
     return s if sample_rate is None else _to_rate([s.reshape(-1)], sample_rate)[0]

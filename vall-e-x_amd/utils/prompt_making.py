@@ -94,8 +94,24 @@ def _load_wav(path: str) -> Tuple[np.ndarray, int]:
     return wav, int(sr)
 
 
-def tokenize_audio(tokenizer: AudioTokenizer, audio: Union[str, Tuple[np.ndarray, int]]):
-    """data/tokenizer.py:99-111: (path | (wav (C, L), sr)) -> `tokenizer.encode(wav[None])` = [(codes (1, 8, T), None)]."""
+TRIM_FRAME, TRIM_KEEP = 240, 2400      # trim_db: 10 ms analysis frames at 24 kHz, 100 ms kept on both sides of the spoken span
+
+
+def trim_silence(wav: np.ndarray, trim_db: float) -> np.ndarray:
+    """(1, L) mono fp32 at 24 kHz -> (1, L') without the leading and trailing frames whose mean square is below 10^(trim_db / 10), on the
+    loaded model's engine (Engine.finish, vx_finish: trim both sides, keep TRIM_KEEP samples; level and format untouched).  Silence in
+    front of a prompt costs prompt frames of the KV arena on every request that uses it."""
+    if G.model is None:
+        raise RuntimeError("call preload_models() first: trim_db runs on the loaded model's engine")
+    rows, infos = G.model.engine.finish([wav.reshape(-1)], TRIM_FRAME, silence_db=float(trim_db), trim=3, keep=TRIM_KEEP)
+    if infos[0]["active_frames"] == 0:
+        raise ValueError(f"no 10 ms frame of the prompt is above trim_db = {trim_db} dB: the clip is silent")
+    return np.array(rows[0], np.float32)[None]
+
+
+def tokenize_audio(tokenizer: AudioTokenizer, audio: Union[str, Tuple[np.ndarray, int]], trim_db: Optional[float] = None):
+    """data/tokenizer.py:99-111: (path | (wav (C, L), sr)) -> `tokenizer.encode(wav[None])` = [(codes (1, 8, T), None)].
+    trim_db (no reference counterpart; None = the clip as it is): `trim_silence` on the 24 kHz mono clip before the encoder sees it."""
     wav, sr = _load_wav(audio) if isinstance(audio, str) else audio
     wav = np.asarray(wav.detach().cpu().numpy() if hasattr(wav, "detach") else wav, np.float32)
     if wav.ndim == 1:
@@ -104,6 +120,8 @@ def tokenize_audio(tokenizer: AudioTokenizer, audio: Union[str, Tuple[np.ndarray
         wav = wav.mean(0, keepdims=True)
     if sr != tokenizer.sample_rate:
         wav = np.asarray((resampler or _builtin_resampler())(wav, int(sr), tokenizer.sample_rate), np.float32)
+    if trim_db is not None:
+        wav = trim_silence(wav, trim_db)
     return tokenizer.encode(wav[None])                            # (1, 1, L)
 
 
@@ -125,8 +143,9 @@ def make_transcript(name, wav, sr, transcript: Optional[str] = None):
 
 
 def make_prompt(name: str, audio_prompt_path: Union[str, Tuple[np.ndarray, int]], transcript: Optional[str] = None,
-                save_dir: Optional[str] = None) -> str:
-    """utils/prompt_making.py:57-84.  `audio_prompt_path`: a WAV path or `(wav (C, L), sr)`.  Returns the path of the written .npz."""
+                save_dir: Optional[str] = None, trim_db: Optional[float] = None) -> str:
+    """utils/prompt_making.py:57-84.  `audio_prompt_path`: a WAV path or `(wav (C, L), sr)`.  Returns the path of the written .npz.
+    trim_db: as `tokenize_audio` (leading and trailing silence of the clip is cut before it is encoded)."""
     global codec
     if G.model is None:
         raise RuntimeError("call preload_models() first (with EnCodec weights: model.load_encodec_state_dict)")
@@ -141,7 +160,7 @@ def make_prompt(name: str, audio_prompt_path: Union[str, Tuple[np.ndarray, int]]
     if wav_pr.shape[0] == 2:                                      # :62-63
         wav_pr = wav_pr.mean(0, keepdims=True)
     text_pr, lang_pr = make_transcript(name, wav_pr, sr, transcript)
-    encoded_frames = tokenize_audio(codec, (wav_pr, sr))          # :67
+    encoded_frames = tokenize_audio(codec, (wav_pr, sr), trim_db=trim_db)          # :67
     codes = encoded_frames[0][0]
     codes = codes.numpy() if hasattr(codes, "numpy") else np.asarray(codes)
     audio_tokens = np.transpose(codes, (0, 2, 1))                 # (1, T, 8)   (:68)
