@@ -347,6 +347,53 @@ typedef struct vx_wave_info {
 int vx_finish(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t* lens, int32_t batch, const vx_finish_opts* o,
               void* out /* may be NULL: measure only */, int64_t out_stride /* in elements */, int32_t* out_lens, vx_wave_info* info);
 
+/* The speaking rate: a pitch-preserving time-stretch of mono fp32 rows on the device by WSOLA (waveform-similarity overlap-add).  No
+ * reference counterpart: the reference's pace is whatever the checkpoint and the prompt produce.  Each output hop is a crossfade
+ * between the continuation of the previous input segment and a new input segment, which is searched near its nominal position for the
+ * best match with that continuation.  The chosen positions are the exact map from output time to input time.  Inputs are a row x of
+ * length L and the options speed_num / speed_den, hop (H) and search (D).  The speed is reduced by its gcd and written num / den
+ * below.  Every quantity is defined so that a plain numpy restatement reproduces it bit for bit:
+ *
+ * - Samples.  y[i] = isfinite(x[i]) ? x[i] : 0.  Outside [0, L), y = 0.
+ * - Lengths.  Lout = ceil(L * den / num) in 64-bit integers.  The row has M = ceil(Lout / H) frames.  Frame k writes output samples
+ *   [k H, min((k + 1) H, Lout)).
+ * - Nominal positions.  n_k = floor(k * H * num / den) in 64-bit integers.
+ * - Frame 0.  p_0 = 0 and out[j] = y[j].
+ * - Search, for k >= 1.  The template is t[j] = y[p_{k-1} + H + j] for j in [0, H).  For every d in [-D, D], ONE LANE computes two
+ *   double sums from 0.0 in order j = 0 .. H-1: c_d = sum (double)y[n_k + d + j] * (double)t[j] and e_d = sum (double)y[n_k + d + j]^2.
+ *   Every product of two fp32 values is exact in double, so contraction to an fma cannot change a bit.  These sums equal
+ *   np.cumsum(...)[-1] in float64.  D_d = e_d - 2.0 * c_d in double: the squared distance to the template minus the template's own
+ *   energy.  2 c is exact, so it is again contraction-proof.  p_k = n_k + d*, where d* has the smallest D_d.  Ties go to the smallest
+ *   |d|, then to the negative d.  Consequence: an all-zero row keeps its nominal positions.
+ * - Crossfade.  w = the smoothstep table of H entries, w[j] = u u (3 - 2u) at u = (j + 0.5) / H, built in double and rounded once to
+ *   fp32 (the fade table of vx_finish).  For k >= 1: out[k H + j] = (float)((double)y[p_k + j] * (double)w[j] + (double)t[j] *
+ *   (double)w[H-1-j]).  That is two exact products, one double addition and one rounding to fp32.
+ * - Positions.  pos[b][k] = p_k (int32) is returned when `pos` is given.
+ * - Speed 1.  With num == den the input bits are copied and pos[k] = k H, as vx_resample does at equal rates.
+ * - Exactness.  No floating-point atomics.  Two calls give the same bits.  A row's bits do not depend on the batch or on the launch
+ *   windows.
+ * - State.  As vx_resample: it needs no weights and works before vx_finalize_weights; it works while a serving session is open; it
+ *   touches no decode state, KV arena or fallback counter; it runs in the resampler's launch buffers, with a small positions / cost
+ *   buffer of its own; transfers go through the pinned ring.
+ * - Windows.  One launch holds VX_STRETCH_WINDOW (2^23) input samples.  Rows are packed into launches in order.  A longer row is cut
+ *   at frame boundaries; its next window goes into the next launch and starts from the position found for the frame before it.
+ * - Refusals.  These return VX_EINVAL, launch nothing and write nothing, and the message names the field: hop outside 16 .. 2048;
+ *   search outside 0 .. 1024; speed_num or speed_den outside 1 .. 32767, or num / den outside 1/2 .. 2 (the output then fits the
+ *   resampler's two-to-one output buffer); a wrong struct_size; NULL wav / lens / o / out / out_lens; batch <= 0; a length negative
+ *   or above wav_stride; out_stride below a row's Lout; pos_stride below a row's M when pos is given.
+ *
+ *   wav [batch][wav_stride] fp32, lens [batch] samples (0 allowed: the row writes nothing); out [batch][out_stride] fp32, out_lens
+ *   [batch] = Lout; pos [batch][pos_stride] int32 or NULL.  Elements behind out_lens[b] and behind pos[b][M] are not written. */
+#define VX_STRETCH_WINDOW (1 << 23)
+typedef struct vx_stretch_opts {
+  uint32_t struct_size;   /* = sizeof(vx_stretch_opts) */
+  int32_t speed_num, speed_den; /* 1 .. 32767 each, 1/2 <= speed_num / speed_den <= 2: above 1 is faster (shorter) */
+  int32_t hop;            /* H, 16 .. 2048 samples (10 ms = rate / 100) */
+  int32_t search;         /* D, 0 .. 1024 samples on either side of the nominal position */
+} vx_stretch_opts;
+int vx_stretch(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t* lens, int32_t batch, const vx_stretch_opts* o,
+               float* out, int64_t out_stride, int32_t* out_lens, int32_t* pos /* may be NULL */, int64_t pos_stride);
+
 /* ---- step-level entries (kernel-level parity tests; same kernels as vx_infer) ---------------------------- */
 /* first ar_decoder.infer call (models/vallex.py:528-562): embeds, runs the prefix-LM prefill, fills the KV arena,
  * leaves the logits of the last row available.  batch <= 32. */

@@ -382,6 +382,19 @@ int vx_dev_finish_frames(vx_ctx* ctx, const float* wav, int32_t len, int32_t fra
 #define VX_DEV_FINISH_WINDOW_MIN 512
 int vx_dev_finish_window(vx_ctx* ctx, int32_t input_samples);
 
+/* Input samples one launch of vx_stretch holds, for later calls on this context: VX_DEV_STRETCH_WINDOW_MIN .. VX_STRETCH_WINDOW, or 0
+ * for the default (VX_STRETCH_WINDOW).  A small window sends short rows through several windows and launches -- what the window tests
+ * need; the device buffers keep their size.  One frame can read 2 search + 3 hop samples (its region and the template before it):
+ * the minimum holds that at hop 441, search 300; while a window below one frame's span is set, vx_stretch refuses those options
+ * (VX_EINVAL).  VX_EINVAL, nothing changed, for any other value. */
+#define VX_DEV_STRETCH_WINDOW_MIN 2048
+int vx_dev_stretch_window(vx_ctx* ctx, int32_t input_samples);
+/* stretch_rows_kernel (csrc/stretch.hip, the kernel behind vx_stretch) on ONE row, through the same planner and windows: out
+ * [ceil(len den / num)] and pos [M] as vx_stretch gives them, and cost [M] = the winning D_d of every frame as the kernel computed it,
+ * in double (cost[0] = 0: frame 0 is not searched).  At speed 1 the search runs as well (no copy): pos[k] = k hop then holds by the
+ * arithmetic, not by a shortcut.  VX_EINVAL, nothing written: a NULL pointer, len < 0, options out of range. */
+int vx_dev_stretch_costs(vx_ctx* ctx, const float* wav, int32_t len, const vx_stretch_opts* o, float* out, int32_t* pos, double* cost);
+
 #ifdef __cplusplus
 }
 #endif

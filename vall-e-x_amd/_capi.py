@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+from fractions import Fraction
 from typing import Optional, Sequence
 
 import numpy as np
@@ -81,6 +82,11 @@ class vx_finish_opts(C.Structure):
                 ("fade_out", C.c_int32), ("format", C.c_int32)]
 
 
+class vx_stretch_opts(C.Structure):
+    """options of vx_stretch (the speaking rate: speed as a fraction, hop and search radius of the WSOLA frames)"""
+    _fields_ = [("struct_size", C.c_uint32), ("speed_num", C.c_int32), ("speed_den", C.c_int32), ("hop", C.c_int32), ("search", C.c_int32)]
+
+
 class vx_wave_info(C.Structure):
     """what vx_finish measured of one row"""
     _fields_ = [("begin", C.c_int32), ("end", C.c_int32), ("active_frames", C.c_int32), ("nonfinite", C.c_int32), ("clipped", C.c_int32),
@@ -95,12 +101,13 @@ SYMBOLS = ["vx_abi_version", "vx_create", "vx_destroy", "vx_last_error", "vx_syn
            "vx_nar", "vx_read_tap", "vx_last_stats", "vx_last_truncated", "vx_last_fallbacks", "vx_fallback_state",
            "vx_fallback_reset", "vx_arith_mode", "vx_infer_continuous", "vx_serve_open", "vx_serve_submit", "vx_serve_run",
            "vx_serve_close", "vx_serve_submit_ex", "vx_serve_cancel", "vx_serve_submit_filtered", "vx_score", "vx_align", "vx_resample",
-           "vx_finish"]
+           "vx_finish", "vx_stretch"]
 # ... and include/vallex_hip_dev.h: measurement / kernel development, never called by the mirrors of the reference API
 DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kernel", "vx_bench_gemm", "vx_bench_attn",
                "vx_bench_gemm_clock", "vx_bench_gemm_epilogue", "vx_dev_sample", "vx_dev_attn", "vx_dev_sample_filtered",
                "vx_dev_dec_attn", "vx_dev_dec_op", "vx_dev_gemm", "vx_dev_layernorm", "vx_dev_score_rows", "vx_dev_align_rows", "vx_dev_wave_op",
-               "vx_dev_seam_op", "vx_dev_resample_taps", "vx_dev_resample_window", "vx_dev_finish_frames", "vx_dev_finish_window"]
+               "vx_dev_seam_op", "vx_dev_resample_taps", "vx_dev_resample_window", "vx_dev_finish_frames", "vx_dev_finish_window",
+               "vx_dev_stretch_window", "vx_dev_stretch_costs"]
 # sentinels the correctness entries pre-fill their outputs with (include/vallex_hip_dev.h)
 DEV_SENTINEL_I = -123456789
 DEV_SENTINEL_F = np.float32(-1.0e30)
@@ -130,6 +137,7 @@ SCORE_PARTS = {"ar": SCORE_AR, "nar": SCORE_NAR, "both": SCORE_AR | SCORE_NAR}
 DEV_ALIGN_ROW_TILE, DEV_ALIGN_KEY_TILE = 32, 32      # VX_DEV_ALIGN_* of include/vallex_hip_dev.h: tiles of align_rows_kernel
 RESAMPLE_WINDOW, DEV_RESAMPLE_WINDOW_MIN = 1 << 23, 512     # VX_RESAMPLE_WINDOW / VX_DEV_RESAMPLE_WINDOW_MIN: input samples per launch
 FINISH_WINDOW, DEV_FINISH_WINDOW_MIN = 1 << 23, 512         # VX_FINISH_WINDOW / VX_DEV_FINISH_WINDOW_MIN: input samples per launch
+STRETCH_WINDOW, DEV_STRETCH_WINDOW_MIN = 1 << 23, 2048      # VX_STRETCH_WINDOW / VX_DEV_STRETCH_WINDOW_MIN: input samples per launch
 PCM_F32, PCM_S16 = 0, 1                                      # VX_PCM_*
 LEVEL_NONE, LEVEL_PEAK, LEVEL_RMS = 0, 1, 2                  # VX_LEVEL_*
 DEV_SAMPLE_CFG = ("kernel", "splitk", "top_k", "force_eos_at", "active", "n_gen", "cur_pos", "ctx_len", "text_len", "gen_stride")
@@ -244,6 +252,10 @@ def load_library() -> C.CDLL:
                               P(vx_wave_info)]
     lib.vx_dev_finish_frames.argtypes = [ctx, P(C.c_float), C.c_int32, C.c_int32, P(C.c_double), P(C.c_float), P(C.c_int32)]
     lib.vx_dev_finish_window.argtypes = [ctx, C.c_int32]
+    lib.vx_stretch.argtypes = [ctx, P(C.c_float), C.c_int64, P(C.c_int32), C.c_int32, P(vx_stretch_opts), P(C.c_float), C.c_int64,
+                               P(C.c_int32), P(C.c_int32), C.c_int64]
+    lib.vx_dev_stretch_window.argtypes = [ctx, C.c_int32]
+    lib.vx_dev_stretch_costs.argtypes = [ctx, P(C.c_float), C.c_int32, P(vx_stretch_opts), P(C.c_float), P(C.c_int32), P(C.c_double)]
     lib.vx_last_stats.argtypes = [ctx, P(C.c_int64), P(C.c_int64), P(C.c_double), P(C.c_double)]
     lib.vx_last_truncated.argtypes = [ctx, P(C.c_int32)]
     lib.vx_last_fallbacks.argtypes = [ctx, P(C.c_int32), P(C.c_int32), P(C.c_int64)]
@@ -534,6 +546,78 @@ class Engine:
         restores the default)"""
         self._chk(self.lib.vx_dev_finish_window(self.ctx, int(input_samples)))
 
+    @staticmethod
+    def _stretch_opts(speed, hop, search, sample_rate) -> vx_stretch_opts:
+        """speed: a float (-> Fraction(speed).limit_denominator(1000)), a Fraction or a (num, den) pair; hop None = 10 ms
+        (sample_rate // 100), search None = 6.25 ms (sample_rate // 160)"""
+        if isinstance(speed, (tuple, list)):
+            num, den = int(speed[0]), int(speed[1])
+        else:
+            f = speed if isinstance(speed, Fraction) else Fraction(speed).limit_denominator(1000)
+            num, den = f.numerator, f.denominator
+        if not (-2 ** 31 <= num < 2 ** 31 and -2 ** 31 <= den < 2 ** 31):
+            raise ValueError(f"speed {speed!r} does not fit vx_stretch_opts")
+        return vx_stretch_opts(C.sizeof(vx_stretch_opts), num, den, int(sample_rate) // 100 if hop is None else int(hop),
+                               int(sample_rate) // 160 if search is None else int(search))
+
+    def stretch(self, wavs: Sequence[np.ndarray], speed, hop: Optional[int] = None, search: Optional[int] = None, sample_rate: int = 24000,
+                return_positions: bool = False):
+        """vx_stretch, the speaking rate: mono fp32 waveforms (L_i,) -> a list of float32 arrays of ceil(L_i den / num) samples, the same
+        pitch at speed = num / den times the pace (1/2 .. 2; above 1 is faster), by WSOLA on the device: every hop of `hop` output
+        samples is a smoothstep crossfade between the continuation of the previous input segment and the best-matching segment within
+        `search` samples of the nominal position.  return_positions: (waveforms, positions), positions[i] int32 (ceil(Lout_i / hop),) =
+        the input sample each output hop starts from -- the exact map from output to input time
+        (utils.alignment.stretched_sample).  Speed 1 returns the input bits.  Non-finite samples count as 0."""
+        n = len(wavs)
+        if n == 0:
+            return ([], []) if return_positions else []
+        o = self._stretch_opts(speed, hop, search, sample_rate)
+        ws = [np.ascontiguousarray(w, np.float32).reshape(-1) for w in wavs]
+        lens = np.array([len(w) for w in ws], np.int32)
+        stride = max(1, int(lens.max()))
+        if n == 1:
+            buf = ws[0] if len(ws[0]) else np.zeros(1, np.float32)        # no second copy of a single (long) row
+        else:
+            buf = np.zeros((n, stride), np.float32)
+            for i, w in enumerate(ws):
+                buf[i, : len(w)] = w
+        num, den = max(1, o.speed_num), max(1, o.speed_den)
+        ostride = max(1, -(-stride * den // num))
+        pstride = max(1, -(-ostride // max(1, o.hop)))
+        out = np.empty((n, ostride), np.float32)
+        out_lens = np.zeros(n, np.int32)
+        pos = np.zeros((n, pstride), np.int32) if return_positions else None
+        self._chk(self.lib.vx_stretch(self.ctx, _ptr(buf, C.c_float), stride, _ptr(lens, C.c_int32), n, C.byref(o), _ptr(out, C.c_float),
+                                      ostride, _ptr(out_lens, C.c_int32), None if pos is None else _ptr(pos, C.c_int32), pstride))
+        rows = [out[i, : out_lens[i]] for i in range(n)]
+        if not return_positions:
+            return rows
+        return rows, [pos[i, : -(-int(out_lens[i]) // o.hop)] for i in range(n)]
+
+    def dev_stretch_costs(self, wav: np.ndarray, speed, hop: int, search: int):
+        """vx_dev_stretch_costs: one row through the search kernel (also at speed 1): (out float32, pos int32, cost float64 = the
+        winning D of every frame as the kernel computed it, cost[0] = 0)"""
+        w = np.ascontiguousarray(wav, np.float32).reshape(-1)
+        o = self._stretch_opts(speed, hop, search, 24000)
+        g = math.gcd(o.speed_num, o.speed_den) if o.speed_num > 0 and o.speed_den > 0 else 1
+        num, den = max(1, o.speed_num // g), max(1, o.speed_den // g)
+        n_out = -(-len(w) * den // num)
+        M = -(-n_out // max(1, o.hop))
+        out, pos, cost = np.zeros(max(n_out, 1), np.float32), np.zeros(max(M, 1), np.int32), np.zeros(max(M, 1), np.float64)
+        buf = w if len(w) else np.zeros(1, np.float32)
+        self._chk(self.lib.vx_dev_stretch_costs(self.ctx, _ptr(buf, C.c_float), len(w), C.byref(o), _ptr(out, C.c_float), _ptr(pos, C.c_int32),
+                                                _ptr(cost, C.c_double)))
+        return out[:n_out], pos[:M], cost[:M]
+
+    def dev_stretch_window(self, input_samples: int = 0):
+        """vx_dev_stretch_window: input samples one launch of `stretch` holds from now on (DEV_STRETCH_WINDOW_MIN .. STRETCH_WINDOW; 0
+        restores the default)"""
+        self._chk(self.lib.vx_dev_stretch_window(self.ctx, int(input_samples)))
+
+    def _stretched(self, rows, speed):
+        """the 24 kHz rows of a vocoder call at `speed` (None: as they are), before the resampler and the output stage"""
+        return rows if speed is None else self.stretch(rows, speed)
+
     last_finish_info = None          # the info dicts of the last call that went through a `finish=` argument
 
     def _finished(self, rows, finish, rate: int):
@@ -546,9 +630,9 @@ class Engine:
                                                  finish.max_gain_db, finish.fade_in, finish.fade_out, finish.pcm16)
         return out
 
-    def vocos_decode(self, codes: Sequence[np.ndarray], bandwidth_id: int = 2, sample_rate: int = 24000, finish=None):
-        """sample_rate other than 24000: the decoded rows go through `resample` (24000 -> sample_rate), one more launch; finish (a
-        utils.generation.Finish): then through `finish` at that rate"""
+    def vocos_decode(self, codes: Sequence[np.ndarray], bandwidth_id: int = 2, sample_rate: int = 24000, finish=None, speed=None):
+        """speed (None: nothing runs): the decoded rows go through `stretch` at 24 kHz first; sample_rate other than 24000: then through
+        `resample` (24000 -> sample_rate), one more launch; finish (a utils.generation.Finish): then through `finish` at that rate"""
         n = len(codes)
         lens = np.array([c.shape[0] for c in codes], np.int32)
         stride = max(1, int(lens.max()))
@@ -560,10 +644,11 @@ class Engine:
         audio = np.empty((n, stride * 320), np.float32)
         self._chk(self.lib.vx_vocos_decode(self.ctx, _ptr(buf, C.c_int64), stride, _ptr(lens, C.c_int32), n,
                                            int(bandwidth_id), _ptr(audio, C.c_float), stride * 320))
-        rows = [audio[i, : lens[i] * 320] for i in range(n)]
+        rows = self._stretched([audio[i, : lens[i] * 320] for i in range(n)], speed)
         return self._finished(rows if int(sample_rate) == 24000 else self.resample(rows, 24000, int(sample_rate)), finish, sample_rate)
 
-    def encodec_decode(self, codes: Sequence[np.ndarray], sample_rate: int = 24000, finish=None):
+    def encodec_decode(self, codes: Sequence[np.ndarray], sample_rate: int = 24000, finish=None, speed=None):
+        """speed, sample_rate, finish: as vocos_decode (stretch at 24 kHz, then resample, then finish)"""
         n = len(codes)
         lens = np.array([c.shape[0] for c in codes], np.int32)
         stride = max(1, int(lens.max()))
@@ -573,6 +658,9 @@ class Engine:
         audio = np.zeros((n, stride * 320), np.float32)
         self._chk(self.lib.vx_encodec_decode(self.ctx, _ptr(buf, C.c_int64), stride, _ptr(lens, C.c_int32), n,
                                              _ptr(audio, C.c_float), stride * 320))
+        if speed is not None:
+            rows = self.stretch([audio[i, : lens[i] * 320] for i in range(n)], speed)
+            return self._finished(rows if int(sample_rate) == 24000 else self.resample(rows, 24000, int(sample_rate)), finish, sample_rate)
         if int(sample_rate) != 24000:
             return self._finished(self.resample([audio[i, : lens[i] * 320] for i in range(n)], 24000, int(sample_rate)), finish, sample_rate)
         return self._finished([audio[i, : lens[i] * 320].copy() for i in range(n)], finish, sample_rate)

@@ -176,6 +176,12 @@ struct vx_ctx {
   float* fn_fade = nullptr;        // [2][2^20] the fade-in / fade-out tables, allocated by the first call with a fade
   int fn_fade_n[2] = {0, 0};       // the lengths the two device tables were last built for
   long fn_window = 0;              // input samples per launch set by vx_dev_finish_window (0: the default, VX_FINISH_WINDOW)
+  // time-stretch (vx_stretch, stretch.hip): runs in the resampler's launch buffers (rs_buffers); needs no weights
+  float* st_fade = nullptr;        // [2048] the crossfade table of the hop it was last built for (st_fade_n)
+  int st_fade_n = 0;
+  int* st_pos = nullptr;           // [ST_FRAME_CAP] positions of one launch's frames
+  double* st_cost = nullptr;       // [ST_FRAME_CAP] winning costs of one launch's frames
+  long st_window = 0;              // input samples per launch set by vx_dev_stretch_window (0: the default, VX_STRETCH_WINDOW)
 
   // graph
   hipGraphExec_t graph_exec = nullptr, graph_exec_n = nullptr;   // one decode step / GRAPH_STEPS steps per launch

@@ -1,0 +1,287 @@
+// The speaking rate (vx_stretch, include/vallex_hip.h): a pitch-preserving time-stretch of mono fp32 rows by WSOLA.
+//
+// Frame k of a row writes the output hop [k H, (k + 1) H): a crossfade between the continuation of the previous input segment (the
+// template t[j] = y[p_{k-1} + H + j]) and a new segment y[p_k + j], where p_k = n_k + d* is searched in [n_k - D, n_k + D] around the
+// nominal position n_k = floor(k H num / den) for the smallest D_d = e_d - 2 c_d (the squared distance to the template minus the
+// template's energy).  The contract -- sums, tie rule, crossfade, every rounding -- is in the header; stretch_host.h has the integers.
+//
+// Arithmetic (the contract the tests rest on): candidate d is summed by ONE lane in double in sample order from 0.0, every product
+// of two fp32 values is exact in double, the winner is a total order on (D, |d|, d), an output is two exact products, one double
+// addition and one rounding.  The bits therefore depend neither on the lane, the wave, the job, the window nor the launch a frame
+// lands in.  No atomics, no inline assembly.
+//
+// Work decomposition: frame k needs p_{k-1}, so a row is a serial walk.  A launch covers a ragged list of JOBS (the frames [k0, k1)
+// of one row: a whole row, or one window of a long one), grid (job): one 256-thread workgroup walks its job's frames in order, the
+// rows of a batch run side by side on different CUs.  Everything frame k reads -- the search region, the new segment and the NEXT
+// frame's template -- lies in y[n_k - D, n_k + D + 2H), which is staged into LDS as fp32 with zeros outside the row (the padding
+// never exists in HBM).  That span depends on n_k alone, not on p_{k-1}: the region of frame k + 1 is loaded into registers before
+// frame k is searched and stored into the other LDS buffer behind the search.  Candidate c = d + D belongs to lane c mod 256; the
+// lanes of a wavefront read reg[c + j] at stride 1 (conflict-free) and t[j] as a broadcast.  Each lane keeps its best (D, d); six
+// shuffle steps reduce a wavefront, one LDS step the four of them.
+// LDS: 2 (2D + 2H) + H floats and 48 bytes -- 57 392 bytes at the largest options, 6.7 KiB at hop 240, search 150.
+#include "engine_ctx.h"
+#include "finish_host.h"
+#include "stretch_host.h"
+
+#include "../../include/vallex_hip_dev.h"
+
+namespace vxe {
+
+constexpr int ST_TAB = 16;                                   // ints of a job record
+constexpr int ST_MAX_JOBS = RS_MAX_JOBS * RS_TAB / ST_TAB;   // the records of a launch fill rs_meta
+constexpr long ST_FRAME_CAP = 1L << 18;                      // frames of a launch: the position / cost tables
+constexpr int ST_NONE = 0x3fffffff;                          // the offset of a lane that saw no candidate: loses every tie
+static_assert(VX_STRETCH_WINDOW == RS_IN_CAP, "vx_stretch runs in the resampler's launch buffers");
+static_assert(VX_DEV_STRETCH_WINDOW_MIN >= 2 * 300 + 3 * 441 && VX_DEV_STRETCH_WINDOW_MIN <= VX_STRETCH_WINDOW, "window bounds of the dev header");
+static_assert(2 * ST_SEARCH_MAX + 3 * ST_HOP_MAX <= VX_STRETCH_WINDOW, "one frame fits the default window");
+static_assert((2 * ST_SEARCH_MAX + 2 * ST_HOP_MAX + 255) / 256 <= 24, "the prefetch registers hold the largest region");
+static_assert(48 + (2 * (2 * ST_SEARCH_MAX + 2 * ST_HOP_MAX) + ST_HOP_MAX) * sizeof(float) <= 65536, "LDS of the largest options");
+
+// the total order of the search: smaller D, then smaller |d|, then the negative d
+__device__ __forceinline__ bool st_better(double Da, int da, double Db, int db) {
+  if (Da != Db) return Da < Db;
+  const int aa = da < 0 ? -da : da, ab = db < 0 ? -db : db;
+  return aa != ab ? aa < ab : da < db;
+}
+
+// tab [njobs][ST_TAB]:
+//   0 in_off   first float of the job's staged samples in `in`
+//   1 s_lo     row sample index of that float;  2 in_cnt  staged samples: the job's span cut to [0, L)
+//   3 k0, 4 k1 frames of the job;  5 p_prev  p_{k0-1} (k0 >= 1)
+//   6 out_off  first float of the job's outputs in `out` (output sample k0 H of the row);  7 Lout  output samples of the ROW
+//   8 f_off    first record of the job in `pos` / `cost`
+// NPRE: registers of the prefetch, 256 NPRE >= 2D + 2H
+template <int NPRE>
+__global__ __launch_bounds__(256) void stretch_rows_kernel(const float* __restrict__ in, const int* __restrict__ tab,
+                                                           const float* __restrict__ w, float* __restrict__ out, int* __restrict__ pos,
+                                                           double* __restrict__ cost, int H, int D, int num, int den) {
+  extern __shared__ double st_lds[];
+  double* redD = st_lds;                                         // [4] the wavefronts' winners
+  int* redd = reinterpret_cast<int*>(st_lds + 4);                // [4]
+  float* reg = reinterpret_cast<float*>(st_lds + 6);             // [2][S] the regions of this frame and the next
+  const int S = 2 * D + 2 * H, ncand = 2 * D + 1;
+  float* t = reg + 2 * S;                                        // [H] the template
+  const int* tb = tab + blockIdx.x * ST_TAB;
+  const long in_off = tb[0], s_lo = tb[1], in_cnt = tb[2], out_off = tb[6], Lout = tb[7], f_off = tb[8];
+  const int k0 = tb[3], k1 = tb[4], tid = threadIdx.x;
+  // sample s of the row: 0 outside the row and where it is not finite; the job holds every sample of the row its frames can read
+  // (stretch_host.h: st_span) -- the range test keeps a wrong table inside the buffer
+  auto y_at = [&](long s) -> float {
+    const long r = s - s_lo;
+    if (r < 0 || r >= in_cnt) return 0.f;
+    const float x = in[in_off + r];
+    return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u ? x : 0.f;
+  };
+  long p_prev = tb[5];
+  int ks = k0;
+  if (k0 == 0) {                                                 // frame 0: p_0 = 0, the input itself
+    for (int j = tid; j < H && j < Lout; j += 256) out[out_off + j] = y_at(j);
+    if (tid == 0) { pos[f_off] = 0; cost[f_off] = 0.0; }
+    p_prev = 0;
+    ks = 1;
+  }
+  if (ks >= k1) return;                                          // block-uniform
+  for (int j = tid; j < H; j += 256) t[j] = y_at(p_prev + H + j);
+  {
+    const long base = (long)ks * H * num / den - D;
+    for (int i = tid; i < S; i += 256) reg[i] = y_at(base + i);
+  }
+  for (int k = ks; k < k1; ++k) {
+    float* cur = reg + ((k - ks) & 1) * S;
+    float* oth = reg + (((k - ks) & 1) ^ 1) * S;
+    const long nk = (long)k * H * num / den;                     // cur holds y[n_k - D, n_k - D + S)
+    __syncthreads();                                             // cur and t are written; nobody reads oth or red* any more
+    const bool more = k + 1 < k1;
+    float pre[NPRE];
+    if (more) {
+      const long nbase = (long)(k + 1) * H * num / den - D;
+#pragma unroll
+      for (int i = 0; i < NPRE; ++i) pre[i] = tid + 256 * i < S ? y_at(nbase + tid + 256 * i) : 0.f;
+    }
+    double bD = __builtin_inf();
+    int bd = ST_NONE;
+    for (int cd = tid; cd < ncand; cd += 256) {
+      const float* rp = cur + cd;
+      double cs = 0.0, es = 0.0;
+#pragma unroll 16
+      for (int j = 0; j < H; ++j) {
+        const double a = (double)rp[j], b = (double)t[j];
+        cs += a * b;                                             // both products are exact in double: an fma gives the same bits
+        es += a * a;
+      }
+      const double Dd = es - 2.0 * cs;                           // 2 c is exact
+      if (st_better(Dd, cd - D, bD, bd)) { bD = Dd; bd = cd - D; }
+    }
+    for (int off = 32; off; off >>= 1) {
+      const double oD = __shfl_xor(bD, off, 64);
+      const int od = __shfl_xor(bd, off, 64);
+      if (st_better(oD, od, bD, bd)) { bD = oD; bd = od; }
+    }
+    if ((tid & 63) == 0) { redD[tid >> 6] = bD; redd[tid >> 6] = bd; }
+    if (more) {
+#pragma unroll
+      for (int i = 0; i < NPRE; ++i)
+        if (tid + 256 * i < S) oth[tid + 256 * i] = pre[i];
+    }
+    __syncthreads();
+    bD = redD[0]; bd = redd[0];
+#pragma unroll
+    for (int v = 1; v < 4; ++v)
+      if (st_better(redD[v], redd[v], bD, bd)) { bD = redD[v]; bd = redd[v]; }
+    const int r0 = bd + D;                                       // p_k - base, 0 .. 2D
+    const long o0 = (long)k * H;
+    for (int j = tid; j < H; j += 256) {
+      const float a = cur[r0 + j], tt = t[j];
+      const float v = (float)((double)a * (double)w[j] + (double)tt * (double)w[H - 1 - j]);
+      if (o0 + j < Lout) out[out_off + (o0 - (long)k0 * H) + j] = v;
+      t[j] = cur[r0 + H + j];                                    // the next frame's template; lane j alone touches t[j] here
+    }
+    if (tid == 0) { pos[f_off + (k - k0)] = (int)(nk + bd); cost[f_off + (k - k0)] = bD; }
+  }
+}
+
+// the crossfade table, rebuilt when the hop changes, and the position / cost tables of a launch
+static int st_tables(vx_ctx* c, int H) {
+  if (!c->st_fade) {
+    if (int e = dev_alloc(c, &c->st_fade, (size_t)ST_HOP_MAX, false)) return e;
+    if (int e = dev_alloc(c, &c->st_pos, (size_t)ST_FRAME_CAP, false)) return e;
+    if (int e = dev_alloc(c, &c->st_cost, (size_t)ST_FRAME_CAP, false)) return e;
+  }
+  if (c->st_fade_n != H) {
+    std::vector<float> t;
+    fn_fade_table(H, t);
+    H2D(c->st_fade, t.data(), t.size() * sizeof(float));
+    c->st_fade_n = H;
+  }
+  return VX_OK;
+}
+
+// every check of vx_stretch behind the pointers: options, lengths, strides.  olen [batch] = Lout of every row.
+static int st_check(vx_ctx* c, const char* who, int64_t wav_stride, const int32_t* lens, int batch, const vx_stretch_opts* o,
+                    int64_t out_stride, bool has_pos, int64_t pos_stride, StGeom* g, std::vector<long>* olen) {
+  CHECK_STRUCT(*o, vx_stretch_opts);
+  char why[160];
+  if (st_check_opts(*o, why, sizeof why)) FAIL(VX_EINVAL, "%s: %s", who, why);
+  *g = st_geometry(*o);
+  olen->resize((size_t)batch);
+  for (int i = 0; i < batch; ++i) {
+    const long L = lens[i];
+    if (L < 0 || L > wav_stride) FAIL(VX_EINVAL, "%s: lens[%d] = %ld outside 0 .. wav_stride %ld", who, i, L, (long)wav_stride);
+    const long n = st_out_len(*g, L), M = st_frames(*g, L);
+    if (n > 0x7fffffffL || (M > 0 && st_nominal(*g, M - 1) + g->D > 0x7fffffffL))
+      FAIL(VX_EINVAL, "%s: lens[%d] = %ld gives %ld output samples or a position above what out_lens / pos hold", who, i, L, n);
+    if (n > out_stride) FAIL(VX_EINVAL, "%s: out_stride %ld below the %ld output samples of row %d", who, (long)out_stride, n, i);
+    if (has_pos && M > pos_stride) FAIL(VX_EINVAL, "%s: pos_stride %ld below the %ld frames of row %d", who, (long)pos_stride, M, i);
+    (*olen)[(size_t)i] = n;
+  }
+  return VX_OK;
+}
+
+// the general path: plan, then one launch per group of jobs, everything of a launch behind one stream sync.  cost: one row only.
+static int st_run(vx_ctx* c, const char* who, const float* wav, int64_t wav_stride, const int32_t* lens, int batch, const StGeom& g,
+                  float* out, int64_t out_stride, int32_t* pos, int64_t pos_stride, double* cost) {
+  const long win = c->st_window ? c->st_window : (long)VX_STRETCH_WINDOW;
+  std::vector<StJob> jobs;
+  if (!st_plan(g, lens, batch, win, RS_OUT_CAP, ST_FRAME_CAP, ST_MAX_JOBS, &jobs))
+    FAIL(VX_EINVAL, "%s: the window of %ld input samples (vx_dev_stretch_window) is below one frame's span at hop %d, search %d", who, win, g.H, g.D);
+  if (jobs.empty()) return VX_OK;
+  HIPCHK(hipSetDevice(c->dev));
+  if (int e = rs_buffers(c)) return e;
+  if (int e = st_tables(c, g.H)) return e;
+  const int S = 2 * g.D + 2 * g.H;
+  const size_t lds = 48 + (size_t)(2 * S + g.H) * sizeof(float);
+  std::vector<long> p_last((size_t)batch, 0);                    // p of the last frame a launch has walked, per row
+  std::vector<int> tab, last;
+  for (size_t j0 = 0; j0 < jobs.size();) {
+    size_t j1 = j0;
+    while (j1 < jobs.size() && jobs[j1].launch == jobs[j0].launch) ++j1;
+    tab.clear();
+    last.assign(j1 - j0, 0);
+    for (size_t k = j0; k < j1; ++k) {
+      const StJob& j = jobs[k];
+      for (long v : {j.in_off, j.s_lo, j.s_hi - j.s_lo, j.k0, j.k1, p_last[(size_t)j.row], j.out_off, st_out_len(g, lens[j.row]), j.f_off,
+                     0L, 0L, 0L, 0L, 0L, 0L, 0L})
+        tab.push_back((int)v);
+      if (j.s_hi > j.s_lo)
+        H2D(c->rs_in + j.in_off, wav + (long)j.row * wav_stride + j.s_lo, (size_t)(j.s_hi - j.s_lo) * sizeof(float));
+    }
+    H2D(c->rs_meta, tab.data(), tab.size() * sizeof(int));
+    const dim3 grid((unsigned)(j1 - j0));
+    if (S <= 8 * 256)
+      hipLaunchKernelGGL(stretch_rows_kernel<8>, grid, dim3(256), lds, c->stream, c->rs_in, c->rs_meta, c->st_fade, c->rs_out, c->st_pos,
+                         c->st_cost, g.H, g.D, (int)g.num, (int)g.den);
+    else
+      hipLaunchKernelGGL(stretch_rows_kernel<24>, grid, dim3(256), lds, c->stream, c->rs_in, c->rs_meta, c->st_fade, c->rs_out, c->st_pos,
+                         c->st_cost, g.H, g.D, (int)g.num, (int)g.den);
+    for (size_t k = j0; k < j1; ++k) {
+      const StJob& j = jobs[k];
+      const long nf = j.k1 - j.k0;
+      if (j.out_cnt > 0) D2H(out + (long)j.row * out_stride + j.k0 * g.H, c->rs_out + j.out_off, (size_t)j.out_cnt * sizeof(float));
+      if (pos) D2H(pos + (long)j.row * pos_stride + j.k0, c->st_pos + j.f_off, (size_t)nf * sizeof(int));
+      if (cost) D2H(cost + j.k0, c->st_cost + j.f_off, (size_t)nf * sizeof(double));
+      D2H(&last[k - j0], c->st_pos + j.f_off + nf - 1, sizeof(int));
+    }
+    SYNC();
+    HIPCHK(hipGetLastError());
+    for (size_t k = j0; k < j1; ++k) p_last[(size_t)jobs[k].row] = last[k - j0];
+    j0 = j1;
+  }
+  return VX_OK;
+}
+
+}  // namespace vxe
+
+extern "C" {
+
+int vx_stretch(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_t* lens, int32_t batch, const vx_stretch_opts* o, float* out,
+               int64_t out_stride, int32_t* out_lens, int32_t* pos, int64_t pos_stride) {
+  using namespace vxe;
+  if (!c) return VX_EINVAL;
+  if (!wav) FAIL(VX_EINVAL, "vx_stretch: wav is NULL");
+  if (!lens) FAIL(VX_EINVAL, "vx_stretch: lens is NULL");
+  if (!o) FAIL(VX_EINVAL, "vx_stretch: o is NULL");
+  if (!out) FAIL(VX_EINVAL, "vx_stretch: out is NULL");
+  if (!out_lens) FAIL(VX_EINVAL, "vx_stretch: out_lens is NULL");
+  if (batch <= 0) FAIL(VX_EINVAL, "vx_stretch: batch %d below 1", batch);
+  StGeom g;
+  std::vector<long> olen;
+  if (int e = st_check(c, "vx_stretch", wav_stride, lens, batch, o, out_stride, pos != nullptr, pos_stride, &g, &olen)) return e;
+  if (g.num == g.den) {                                          // nothing to stretch: the input bits
+    for (int i = 0; i < batch; ++i) {
+      if (olen[(size_t)i]) memmove(out + (long)i * out_stride, wav + (long)i * wav_stride, (size_t)olen[(size_t)i] * sizeof(float));
+      if (pos)
+        for (long k = 0, M = st_frames(g, lens[i]); k < M; ++k) pos[(long)i * pos_stride + k] = (int32_t)(k * g.H);
+      out_lens[i] = (int32_t)olen[(size_t)i];
+    }
+    return VX_OK;
+  }
+  if (int e = st_run(c, "vx_stretch", wav, wav_stride, lens, batch, g, out, out_stride, pos, pos_stride, nullptr)) return e;
+  for (int i = 0; i < batch; ++i) out_lens[i] = (int32_t)olen[(size_t)i];
+  return VX_OK;
+}
+
+int vx_dev_stretch_costs(vx_ctx* c, const float* wav, int32_t len, const vx_stretch_opts* o, float* out, int32_t* pos, double* cost) {
+  using namespace vxe;
+  if (!c) return VX_EINVAL;
+  if (!wav) FAIL(VX_EINVAL, "vx_dev_stretch_costs: wav is NULL");
+  if (!o) FAIL(VX_EINVAL, "vx_dev_stretch_costs: o is NULL");
+  if (!out || !pos || !cost) FAIL(VX_EINVAL, "vx_dev_stretch_costs: out, pos or cost is NULL");
+  if (len < 0) FAIL(VX_EINVAL, "vx_dev_stretch_costs: len %d below 0", len);
+  StGeom g;
+  std::vector<long> olen;
+  const int64_t big = 0x7fffffffL;
+  if (int e = st_check(c, "vx_dev_stretch_costs", len, &len, 1, o, big, true, big, &g, &olen)) return e;
+  return st_run(c, "vx_dev_stretch_costs", wav, len, &len, 1, g, out, big, pos, big, cost);
+}
+
+int vx_dev_stretch_window(vx_ctx* c, int32_t input_samples) {
+  using namespace vxe;
+  if (!c) return VX_EINVAL;
+  if (input_samples != 0 && (input_samples < VX_DEV_STRETCH_WINDOW_MIN || input_samples > VX_STRETCH_WINDOW))
+    FAIL(VX_EINVAL, "vx_dev_stretch_window: input_samples %d outside %d .. %d (0 restores the default)", input_samples,
+         VX_DEV_STRETCH_WINDOW_MIN, VX_STRETCH_WINDOW);
+  c->st_window = input_samples;
+  return VX_OK;
+}
+
+}  // extern "C"

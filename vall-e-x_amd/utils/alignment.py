@@ -48,3 +48,24 @@ def monotonic_segments(attn: np.ndarray, enroll: int) -> np.ndarray:
         frames = np.flatnonzero(path == j)
         seg[j] = frames[0], frames[-1]
     return seg
+
+
+def stretched_sample(positions, hop: int, s, out_len=None):
+    """Where input sample `s` is heard after `Engine.stretch(..., return_positions=True)`: positions[k] is the input sample output hop k
+    starts from, so the answer is k * hop + (s - positions[k]) for the largest k with positions[k] <= s (k = 0 when there is none),
+    clamped to the output, [0, out_len - 1] (out_len None: len(positions) * hop, the whole last hop).  `s` may be an array -- the
+    frames of `monotonic_segments` times 320, say -- and the result has its shape (int64); a scalar gives an int."""
+    p = np.asarray(positions, np.int64).reshape(-1)
+    hop = int(hop)
+    if hop <= 0:
+        raise ValueError(f"hop {hop} below 1")
+    sa = np.asarray(s, np.int64)
+    if p.size == 0:
+        out = np.zeros(sa.shape, np.int64)
+    else:
+        # positions need not rise; the largest k with positions[k] <= s is the largest k whose SUFFIX minimum is <= s, and those rise
+        suffix_min = np.minimum.accumulate(p[::-1])[::-1]
+        k = np.maximum(np.searchsorted(suffix_min, sa, side="right") - 1, 0)
+        n = p.size * hop if out_len is None else int(out_len)
+        out = np.clip(k * hop + (sa - p[k]), 0, max(n - 1, 0))
+    return int(out) if np.ndim(s) == 0 else out

@@ -210,6 +210,13 @@ def _finished(wavs, finish, sample_rate):
     return model.engine._finished(wavs, finish, SAMPLE_RATE if sample_rate is None else int(sample_rate))
 
 
+def _at_speed(wavs, speed):
+    """the 24 kHz waveforms of a vocoder call at `speed` (None: as they are): one vx_stretch call for the list, before the resampler"""
+    if speed is None:
+        return wavs
+    return model.engine.stretch(wavs, speed)
+
+
 def _to_rate(wavs, sample_rate):
     """the 24 kHz waveforms of a vocoder call at `sample_rate` (None / 24000: as they are): one vx_resample launch for the list"""
     if sample_rate is None or int(sample_rate) == SAMPLE_RATE:
@@ -237,10 +244,12 @@ def _infer_one(text, audio_prompts, text_prompts, lang_pr, language, accent, **k
     return out, phone_tokens
 
 
-def generate_audio(text, prompt=None, language="auto", accent="no-accent", sample_rate=None, finish=None, **kw):
+def generate_audio(text, prompt=None, language="auto", accent="no-accent", sample_rate=None, finish=None, speed=None, **kw):
     """utils/generation.py:92-152.  sample_rate (no reference counterpart; None = 24 kHz, the reference's): the waveform is resampled
     on the device (Engine.resample, vx_resample) to that rate.  finish (a `Finish`; None = the raw fp32 of the reference): the output
-    stage behind it -- trim, level, fades, int16 with pcm16=True."""
+    stage behind it -- trim, level, fades, int16 with pcm16=True.  speed (a float, a Fraction or a (num, den) pair in 1/2 .. 2; None =
+    the pace the model produced): the speaking rate, a pitch-preserving time-stretch on the device (Engine.stretch, vx_stretch) at
+    24 kHz, before the resampler."""
     if model is None or vocos is None:
         raise RuntimeError("call preload_models() first")
     if isinstance(text, str):
@@ -260,13 +269,15 @@ def generate_audio(text, prompt=None, language="auto", accent="no-accent", sampl
     samples = vocos.decode(features, bandwidth_id=np.array([2]))
     s = samples.squeeze()
     s = s.cpu().numpy() if torch is not None and isinstance(s, torch.Tensor) else np.asarray(s)
+    if speed is not None:
+        return _finished(_to_rate(_at_speed([s.reshape(-1)], speed), sample_rate), finish, sample_rate)[0]
     if finish is not None:
         return _finished(_to_rate([s.reshape(-1)], sample_rate), finish, sample_rate)[0]
     return s if sample_rate is None else _to_rate([s.reshape(-1)], sample_rate)[0]
 
 
 def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent", text_languages=None, sample_rate=None, finish=None,
-                         **kw):
+                         speed=None, **kw):
     """Batch form of `generate_audio` (no reference equivalent: the reference synthesises one utterance per call,
     utils/generation.py:92-152): utterance i of the batch equals `generate_audio(texts[i], prompts[i], language[i], accent)`.
     `texts`: strings (need the tokenizer hook) or phoneme-id arrays; `prompts`: one preset name / path / None per utterance (or
@@ -275,7 +286,8 @@ def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent
     Vocos call.  `**kw` goes to `inference_batch`: `best_of`, `length_penalty` and `return_worst` apply to every utterance (best_of
     = N: N beams per utterance), injected `uniforms` are (steps, len(texts) x max(1, N)) with column i*N + j for beam j of
     utterance i.  `sample_rate` (None = 24 kHz): the waveforms are resampled on the device in one more launch.  `finish` (a
-    `Finish`): the output stage behind it, one more call for the list.  Returns a list of float32 waveforms (int16 with pcm16=True)."""
+    `Finish`): the output stage behind it, one more call for the list.  `speed` (None = as produced): the speaking rate, one vx_stretch
+    call for the list before both.  Returns a list of float32 waveforms (int16 with pcm16=True)."""
     if model is None or vocos is None:
         raise RuntimeError("call preload_models() first")
     n = len(texts)
@@ -285,7 +297,8 @@ def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent
     rows = [_utterance_row(text, prompt, lang_in, accent, tl)
             for text, prompt, lang_in, tl in zip(texts, prompts, langs_in, text_languages)]
     codes = model.inference_batch(rows, top_k=-100, temperature=1, **kw)
-    return model.engine.vocos_decode(codes, 2, sample_rate=SAMPLE_RATE if sample_rate is None else int(sample_rate), finish=finish)
+    return model.engine.vocos_decode(codes, 2, sample_rate=SAMPLE_RATE if sample_rate is None else int(sample_rate), finish=finish,
+                                     speed=speed)
 
 
 def _utterance_row(text, prompt, lang_in, accent, tl=None) -> dict:
@@ -322,9 +335,10 @@ class AudioServer:
     `generate_audio_batch([text], [prompt], language, accent, best_of=..., seed=...)[0]`.  `**serve_kw` goes to VALLE.serve
     (sync_every, force_eos_at, max_steps).  `sample_rate` (None = 24 kHz): ONE output rate for the server, applied to every delivered
     waveform behind Vocos (vx_resample is allowed while the session is open).  `finish` (a `Finish`): ONE output stage for the server,
-    applied behind that (vx_finish is allowed as well)."""
+    applied behind that (vx_finish is allowed as well).  `speed` (None = as produced): ONE speaking rate for the server, applied to
+    every delivered waveform between Vocos and the resampler (vx_stretch is allowed as well)."""
 
-    def __init__(self, sample_rate=None, finish=None, **serve_kw):
+    def __init__(self, sample_rate=None, finish=None, speed=None, **serve_kw):
         if model is None or vocos is None:
             raise RuntimeError("call preload_models() first")
         rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
@@ -332,8 +346,9 @@ class AudioServer:
             raise ValueError(f"sample_rate must be positive, got {sample_rate}")
         self.sample_rate = rate
         self.finish = finish
+        self.speed = speed
         self._server = model.serve(top_k=-100, temperature=1.0,
-                                   post=lambda codes: model.engine.vocos_decode(codes, 2, sample_rate=rate, finish=finish),
+                                   post=lambda codes: model.engine.vocos_decode(codes, 2, sample_rate=rate, finish=finish, speed=speed),
                                    **serve_kw)
 
     def submit(self, text, prompt=None, language="auto", accent="no-accent", best_of=1, seed=None, uniforms=None,
@@ -358,9 +373,9 @@ class AudioServer:
 
 
 def generate_audio_from_long_text(text, prompt=None, language="auto", accent="no-accent", mode="sliding-window", sample_rate=None,
-                                  finish=None, **kw):
-    """utils/generation.py:155-276.  `text` may also be a list of sentences / id arrays (pre-split).  sample_rate, finish: as
-    generate_audio (the output stage sees the concatenated waveform once)."""
+                                  finish=None, speed=None, **kw):
+    """utils/generation.py:155-276.  `text` may also be a list of sentences / id arrays (pre-split).  sample_rate, finish, speed: as
+    generate_audio (the stretch and the output stage see the concatenated waveform once)."""
     if model is None or vocos is None:
         raise RuntimeError("call preload_models() first")
     if prompt is None or prompt == "":
@@ -409,6 +424,8 @@ def generate_audio_from_long_text(text, prompt=None, language="auto", accent="no
     samples = vocos.decode(features, bandwidth_id=np.array([2]))
     s = samples.squeeze()
     s = s.cpu().numpy() if torch is not None and isinstance(s, torch.Tensor) else np.asarray(s)
+    if speed is not None:
+        return _finished(_to_rate(_at_speed([s.reshape(-1)], speed), sample_rate), finish, sample_rate)[0]
     if finish is not None:
         return _finished(_to_rate([s.reshape(-1)], sample_rate), finish, sample_rate)[0]
     return s if sample_rate is None else _to_rate([s.reshape(-1)], sample_rate)[0]
