@@ -394,6 +394,77 @@ typedef struct vx_stretch_opts {
 int vx_stretch(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t* lens, int32_t batch, const vx_stretch_opts* o,
                float* out, int64_t out_stride, int32_t* out_lens, int32_t* pos /* may be NULL */, int64_t pos_stride);
 
+/* Programme loudness after ITU-R BS.1770 (the quantity of EBU R 128 and of every delivery specification in LUFS) of mono fp32 rows on
+ * the device, and vx_finish with its level step replaced by a loudness target.  No reference counterpart.  All arithmetic is double
+ * unless stated.  Every operation named is separately rounded.  A plain numpy restatement reproduces every quantity bit for bit, given
+ * the ten coefficients the library reports.
+ *
+ * - Samples.  y[i] = isfinite(x[i]) ? x[i] : 0, counted in `nonfinite` (over the measured span).
+ * - Rate and steps.  sample_rate is in 8000 .. 192000.  Step S = sample_rate / 10 by integer division (100 ms).  A block is 4 steps.
+ *   The block hop is 1 step.  This is the standard's 75 % overlap.  The warm-up is W = 2 S.
+ * - Coefficients.  vx_loudness_coeffs(rate, double c[10]) is a pure host function and needs no context.  It fills
+ *   c = {b0, b1, b2, a1, a2} of the shelf, then the same five of the high-pass.  Shelf: K = tan(pi * 1681.974450955533 / fs),
+ *   Vh = 10^(3.999843853973347 / 20), Vb = Vh^0.4996667741545416, Q = 0.7071752369554196, a0 = 1 + K/Q + K K,
+ *   b = {(Vh + Vb K/Q + K K)/a0, 2 (K K - Vh)/a0, (Vh - Vb K/Q + K K)/a0}, a1 = 2 (K K - 1)/a0, a2 = (1 - K/Q + K K)/a0.  High-pass:
+ *   K = tan(pi * 38.13547087602444 / fs), Q = 0.5003270373238773, b = {1, -2, 1}, a1 and a2 formed as for the shelf.  At 48 kHz this
+ *   is the standard's table.  tan and pow may differ by an ulp between libraries.  Everything downstream is therefore defined on the
+ *   coefficients the call reports.
+ * - Filter.  Each stage is transposed direct form II, in exactly this order and association.  Shelf: u = b0 x + s1,
+ *   s1 = (b1 x - a1 u) + s2, s2 = b2 x - a2 u.  High-pass, on u with t1, t2, giving v: the same three lines.  No step is contracted
+ *   to an fma.
+ * - Step energies.  z_j covers samples [j S, min((j+1) S, n)) of the measured span.  ONE lane starts both stages from rest
+ *   (s1 = s2 = t1 = t2 = 0) at sample j S - W.  Samples before the span count as 0.  It runs to the end of the step.  Over the step's
+ *   own samples it accumulates z = z + v v from 0.0 in sample order.  The largest pole radius is sqrt(a2) of the high-pass, between
+ *   0.9705 at 8 kHz and 0.99875 at 192 kHz, so W rho^W is 2.5e-18 .. 6.1e-17: starting from rest instead of from the true history is
+ *   below one rounding error.  In exchange a step's bits depend on nothing but the W + S samples it reads: not the row, batch, job,
+ *   tile or window.
+ * - Blocks.  For a span of n >= 4 S samples the blocks are k = 0 .. (n - 4 S) / S, complete blocks only, and
+ *   m_k = (((z_k + z_{k+1}) + z_{k+2}) + z_{k+3}) / (4 S).  For 1 <= n < 4 S there is one block over the whole span:
+ *   m_0 = (sum of z_j in order) / n.  This departs from the standard: an utterance shorter than 400 ms must still be levelled.
+ *   n = 0: no block.
+ * - Gates.  They run on the host, in energy, in block order.  Absolute gate: m_k > A, with A = pow(10, (-70 + 0.691) / 10) computed
+ *   once (`above_abs` blocks).  Relative gate: among those, m_k > 0.1 * (sum m_k / count) (`gated` blocks).  mean_square is the mean of
+ *   m_k over the blocks passing both gates, summed in block order.  loudness = -0.691 + 10 log10(mean_square).  max_momentary is the
+ *   same formula on the largest m_k of all blocks.  No block at all gives loudness = max_momentary = -HUGE_VAL.  Blocks of which none
+ *   passes the gates give loudness = -HUGE_VAL and mean_square = 0.  In either case the gain is 1.
+ * - Gain of vx_finish_loud.  t = pow(10, (target_lufs - loudness) / 20).
+ *   g = min(t, pow(10, max_gain_db / 20), pow(10, ceiling_db / 20) / peak, FLT_MAX), rounded once to fp32.  peak is vx_wave_info.peak
+ *   over the kept span.  The ceiling term is dropped when peak is 0.  max_gain_db comes from the vx_finish_opts.
+ * - Span.  vx_finish_loud measures loudness over the kept span [begin, end), with step 0 starting at begin.  The loudness it reports
+ *   is therefore bit-equal to vx_loudness on the slice, and the delivered audio has the target loudness, not the untrimmed row.
+ * - vx_finish_loud is vx_finish with the level step replaced: o->level_mode must be VX_LEVEL_NONE.  Trim, keep, fades, format,
+ *   refusals, sentinels and out == NULL (measure only) are as in vx_finish.  The order is: frames pass, span, steps pass over the
+ *   span, gates and gain, apply.  A call that fits one launch uploads its samples once.
+ * - State.  As vx_finish: no weights, no decode state, allowed while a serving session is open; it runs in the resampler's launch
+ *   buffers plus a step table; transfers go through the pinned ring.
+ * - Windows.  One launch holds VX_LOUDNESS_WINDOW (2^23) samples.  Rows are packed into launches in order.  A longer row is cut at
+ *   step multiples, and a later part carries the W samples in front of its first step.  By the rules above no cut changes a bit.
+ * - Refusals.  These return VX_EINVAL, launch nothing and write nothing, and the message names the field: NULL wav / lens / info
+ *   (vx_finish_loud: o / lo / linfo as well); batch <= 0; a length negative or above wav_stride; sample_rate outside 8000 .. 192000;
+ *   vx_finish_loud: everything vx_finish refuses, a wrong struct_size of either struct, level_mode other than VX_LEVEL_NONE,
+ *   target_lufs not finite or outside -70 .. 0, ceiling_db not finite or above 0.  vx_loudness_coeffs returns VX_EINVAL for a NULL c
+ *   or a rate out of range.
+ * Not covered: true peak (4x oversampling), loudness range, short-term loudness, channel weights of more than one channel. */
+#define VX_LOUDNESS_WINDOW (1 << 23)
+typedef struct vx_loudness_opts {
+  uint32_t struct_size;   /* = sizeof(vx_loudness_opts) */
+  int32_t sample_rate;    /* 8000 .. 192000 */
+  float target_lufs;      /* finite, -70 .. 0 */
+  float ceiling_db;       /* finite, <= 0: dBFS the sample peak may reach after the gain */
+} vx_loudness_opts;
+typedef struct vx_loudness_info {
+  double loudness;        /* LUFS of the gated blocks; -HUGE_VAL when none passes */
+  double mean_square;     /* mean K-weighted energy of the gated blocks; 0 when none passes */
+  double max_momentary;   /* LUFS of the loudest block; -HUGE_VAL without a block */
+  int32_t blocks, above_abs, gated, nonfinite;
+} vx_loudness_info;
+int vx_loudness_coeffs(int32_t sample_rate, double c[10]);
+int vx_loudness(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t* lens, int32_t batch, int32_t sample_rate,
+                vx_loudness_info* info);
+int vx_finish_loud(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t* lens, int32_t batch, const vx_finish_opts* o,
+                   const vx_loudness_opts* lo, void* out /* may be NULL: measure only */, int64_t out_stride, int32_t* out_lens,
+                   vx_wave_info* info, vx_loudness_info* linfo);
+
 /* ---- step-level entries (kernel-level parity tests; same kernels as vx_infer) ---------------------------- */
 /* first ar_decoder.infer call (models/vallex.py:528-562): embeds, runs the prefix-LM prefill, fills the KV arena,
  * leaves the logits of the last row available.  batch <= 32. */

@@ -395,6 +395,19 @@ int vx_dev_stretch_window(vx_ctx* ctx, int32_t input_samples);
  * arithmetic, not by a shortcut.  VX_EINVAL, nothing written: a NULL pointer, len < 0, options out of range. */
 int vx_dev_stretch_costs(vx_ctx* ctx, const float* wav, int32_t len, const vx_stretch_opts* o, float* out, int32_t* pos, double* cost);
 
+/* The step table of ONE row as loudness_steps_kernel (csrc/loudness.hip, the steps pass of vx_loudness and vx_finish_loud) writes it:
+ * z [ceil(n / S)], S = sample_rate / 10, z_j = the K-weighted energy of samples [j S, min((j + 1) S, n)) as include/vallex_hip.h
+ * defines it.  The row goes through the same planner and windows as vx_loudness.  VX_EINVAL, nothing written: a NULL pointer, n < 0,
+ * sample_rate outside 8000 .. 192000, a window (below) under 3 S. */
+int vx_dev_loudness_steps(vx_ctx* ctx, const float* wav, int32_t n, int32_t sample_rate, double* z);
+/* Samples one launch of the steps pass holds (warm-ups included), for later calls on this context: VX_DEV_LOUDNESS_WINDOW_MIN ..
+ * VX_LOUDNESS_WINDOW, or 0 for the default (VX_LOUDNESS_WINDOW).  A small window sends short rows through several jobs and launches --
+ * what the window tests need; the device buffers keep their size.  A launch must hold a warm-up and one step: while a window below
+ * 3 S of a call's rate is set, that call is refused (VX_EINVAL), not run with a larger window.  With a window set, vx_finish_loud
+ * uploads the kept spans again for the steps pass.  VX_EINVAL, nothing changed, for any other value. */
+#define VX_DEV_LOUDNESS_WINDOW_MIN 4096
+int vx_dev_loudness_window(vx_ctx* ctx, int32_t samples);
+
 #ifdef __cplusplus
 }
 #endif

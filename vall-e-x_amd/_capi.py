@@ -93,6 +93,17 @@ class vx_wave_info(C.Structure):
                 ("peak", C.c_float), ("gain", C.c_float), ("mean_square", C.c_double)]
 
 
+class vx_loudness_opts(C.Structure):
+    """the loudness target of vx_finish_loud (BS.1770: LUFS at a sample rate, under a sample-peak ceiling)"""
+    _fields_ = [("struct_size", C.c_uint32), ("sample_rate", C.c_int32), ("target_lufs", C.c_float), ("ceiling_db", C.c_float)]
+
+
+class vx_loudness_info(C.Structure):
+    """what vx_loudness measured of one row"""
+    _fields_ = [("loudness", C.c_double), ("mean_square", C.c_double), ("max_momentary", C.c_double), ("blocks", C.c_int32),
+                ("above_abs", C.c_int32), ("gated", C.c_int32), ("nonfinite", C.c_int32)]
+
+
 # every symbol include/vallex_hip.h declares (tests/test_abi.py checks the library exports exactly these)
 ABI_VERSION = 6       # VX_ABI_VERSION of include/vallex_hip.h this binding was written against
 
@@ -101,13 +112,13 @@ SYMBOLS = ["vx_abi_version", "vx_create", "vx_destroy", "vx_last_error", "vx_syn
            "vx_nar", "vx_read_tap", "vx_last_stats", "vx_last_truncated", "vx_last_fallbacks", "vx_fallback_state",
            "vx_fallback_reset", "vx_arith_mode", "vx_infer_continuous", "vx_serve_open", "vx_serve_submit", "vx_serve_run",
            "vx_serve_close", "vx_serve_submit_ex", "vx_serve_cancel", "vx_serve_submit_filtered", "vx_score", "vx_align", "vx_resample",
-           "vx_finish", "vx_stretch"]
+           "vx_finish", "vx_stretch", "vx_loudness_coeffs", "vx_loudness", "vx_finish_loud"]
 # ... and include/vallex_hip_dev.h: measurement / kernel development, never called by the mirrors of the reference API
 DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kernel", "vx_bench_gemm", "vx_bench_attn",
                "vx_bench_gemm_clock", "vx_bench_gemm_epilogue", "vx_dev_sample", "vx_dev_attn", "vx_dev_sample_filtered",
                "vx_dev_dec_attn", "vx_dev_dec_op", "vx_dev_gemm", "vx_dev_layernorm", "vx_dev_score_rows", "vx_dev_align_rows", "vx_dev_wave_op",
                "vx_dev_seam_op", "vx_dev_resample_taps", "vx_dev_resample_window", "vx_dev_finish_frames", "vx_dev_finish_window",
-               "vx_dev_stretch_window", "vx_dev_stretch_costs"]
+               "vx_dev_stretch_window", "vx_dev_stretch_costs", "vx_dev_loudness_steps", "vx_dev_loudness_window"]
 # sentinels the correctness entries pre-fill their outputs with (include/vallex_hip_dev.h)
 DEV_SENTINEL_I = -123456789
 DEV_SENTINEL_F = np.float32(-1.0e30)
@@ -138,6 +149,7 @@ DEV_ALIGN_ROW_TILE, DEV_ALIGN_KEY_TILE = 32, 32      # VX_DEV_ALIGN_* of include
 RESAMPLE_WINDOW, DEV_RESAMPLE_WINDOW_MIN = 1 << 23, 512     # VX_RESAMPLE_WINDOW / VX_DEV_RESAMPLE_WINDOW_MIN: input samples per launch
 FINISH_WINDOW, DEV_FINISH_WINDOW_MIN = 1 << 23, 512         # VX_FINISH_WINDOW / VX_DEV_FINISH_WINDOW_MIN: input samples per launch
 STRETCH_WINDOW, DEV_STRETCH_WINDOW_MIN = 1 << 23, 2048      # VX_STRETCH_WINDOW / VX_DEV_STRETCH_WINDOW_MIN: input samples per launch
+LOUDNESS_WINDOW, DEV_LOUDNESS_WINDOW_MIN = 1 << 23, 4096    # VX_LOUDNESS_WINDOW / VX_DEV_LOUDNESS_WINDOW_MIN: samples per launch
 PCM_F32, PCM_S16 = 0, 1                                      # VX_PCM_*
 LEVEL_NONE, LEVEL_PEAK, LEVEL_RMS = 0, 1, 2                  # VX_LEVEL_*
 DEV_SAMPLE_CFG = ("kernel", "splitk", "top_k", "force_eos_at", "active", "n_gen", "cur_pos", "ctx_len", "text_len", "gen_stride")
@@ -255,6 +267,12 @@ def load_library() -> C.CDLL:
     lib.vx_stretch.argtypes = [ctx, P(C.c_float), C.c_int64, P(C.c_int32), C.c_int32, P(vx_stretch_opts), P(C.c_float), C.c_int64,
                                P(C.c_int32), P(C.c_int32), C.c_int64]
     lib.vx_dev_stretch_window.argtypes = [ctx, C.c_int32]
+    lib.vx_loudness_coeffs.argtypes = [C.c_int32, P(C.c_double)]
+    lib.vx_loudness.argtypes = [ctx, P(C.c_float), C.c_int64, P(C.c_int32), C.c_int32, C.c_int32, P(vx_loudness_info)]
+    lib.vx_finish_loud.argtypes = [ctx, P(C.c_float), C.c_int64, P(C.c_int32), C.c_int32, P(vx_finish_opts), P(vx_loudness_opts), C.c_void_p,
+                                   C.c_int64, P(C.c_int32), P(vx_wave_info), P(vx_loudness_info)]
+    lib.vx_dev_loudness_steps.argtypes = [ctx, P(C.c_float), C.c_int32, C.c_int32, P(C.c_double)]
+    lib.vx_dev_loudness_window.argtypes = [ctx, C.c_int32]
     lib.vx_dev_stretch_costs.argtypes = [ctx, P(C.c_float), C.c_int32, P(vx_stretch_opts), P(C.c_float), P(C.c_int32), P(C.c_double)]
     lib.vx_last_stats.argtypes = [ctx, P(C.c_int64), P(C.c_int64), P(C.c_double), P(C.c_double)]
     lib.vx_last_truncated.argtypes = [ctx, P(C.c_int32)]
@@ -614,6 +632,80 @@ class Engine:
         restores the default)"""
         self._chk(self.lib.vx_dev_stretch_window(self.ctx, int(input_samples)))
 
+    @staticmethod
+    def _packed(wavs):
+        """(buf (n, stride) or the single row itself, lens, stride) of mono fp32 rows"""
+        ws = [np.ascontiguousarray(w, np.float32).reshape(-1) for w in wavs]
+        lens = np.array([len(w) for w in ws], np.int32)
+        stride = max(1, int(lens.max()))
+        if len(ws) == 1:
+            return (ws[0] if len(ws[0]) else np.zeros(1, np.float32)), lens, stride      # no second copy of a single (long) row
+        buf = np.zeros((len(ws), stride), np.float32)
+        for i, w in enumerate(ws):
+            buf[i, : len(w)] = w
+        return buf, lens, stride
+
+    def loudness_coeffs(self, sample_rate: int) -> np.ndarray:
+        """vx_loudness_coeffs: the ten K-weighting coefficients the library filters with at `sample_rate` ({b0, b1, b2, a1, a2} of the
+        shelf, then of the high-pass), float64"""
+        c = np.zeros(10, np.float64)
+        if self.lib.vx_loudness_coeffs(int(sample_rate), _ptr(c, C.c_double)) != 0:
+            raise ValueError(f"sample_rate {sample_rate} outside 8000 .. 192000")
+        return c
+
+    last_loudness_info = None        # the loudness dicts of the last `finish_loud` (also through a `finish=` argument with lufs set)
+
+    def loudness(self, wavs: Sequence[np.ndarray], sample_rate: int):
+        """vx_loudness, ITU-R BS.1770 programme loudness of mono fp32 waveforms (L_i,) at `sample_rate`: a list of dicts -- loudness
+        (LUFS; -inf when no block passes the gates), mean_square, max_momentary, blocks, above_abs, gated, nonfinite
+        (include/vallex_hip.h: vx_loudness_info).  K-weighting, 400 ms blocks at 75 % overlap, the -70 LUFS and the -10 LU gate; a row
+        shorter than 400 ms is one block.  Non-finite samples count as 0."""
+        n = len(wavs)
+        if n == 0:
+            return []
+        buf, lens, stride = self._packed(wavs)
+        info = (vx_loudness_info * n)()
+        self._chk(self.lib.vx_loudness(self.ctx, _ptr(buf, C.c_float), stride, _ptr(lens, C.c_int32), n, int(sample_rate), info))
+        return [{f[0]: getattr(w, f[0]) for f in vx_loudness_info._fields_} for w in info]
+
+    def finish_loud(self, wavs: Sequence[np.ndarray], sample_rate: int, lufs: float, ceiling_db: float = -1.0, frame: Optional[int] = None,
+                    silence_db: float = -40.0, trim: int = 0, keep: int = 0, max_gain_db: float = 20.0, fade_in: int = 0, fade_out: int = 0,
+                    pcm16: bool = False):
+        """vx_finish_loud, `finish` with the level step replaced by a loudness target: the kept span of every row is brought to `lufs`
+        LUFS (BS.1770, measured over that span at `sample_rate`) with at most max_gain_db of gain and a sample peak of at most
+        ceiling_db dBFS.  frame None = 10 ms (sample_rate // 100); trim, keep, fades and pcm16 as in `finish`.  Returns (list of arrays,
+        list of info dicts); the loudness dicts of the rows (as `loudness` on the kept spans) stay in `last_loudness_info`."""
+        n = len(wavs)
+        if n == 0:
+            self.last_loudness_info = []
+            return [], []
+        buf, lens, stride = self._packed(wavs)
+        o = vx_finish_opts(C.sizeof(vx_finish_opts), int(sample_rate) // 100 if frame is None else int(frame), float(silence_db), int(trim),
+                           int(keep), LEVEL_NONE, -1.0, float(max_gain_db), int(fade_in), int(fade_out), PCM_S16 if pcm16 else PCM_F32)
+        lo = vx_loudness_opts(C.sizeof(vx_loudness_opts), int(sample_rate), float(lufs), float(ceiling_db))
+        info, linfo = (vx_wave_info * n)(), (vx_loudness_info * n)()
+        out = np.empty((n, stride), np.int16 if pcm16 else np.float32)
+        out_lens = np.zeros(n, np.int32)
+        self._chk(self.lib.vx_finish_loud(self.ctx, _ptr(buf, C.c_float), stride, _ptr(lens, C.c_int32), n, C.byref(o), C.byref(lo),
+                                          out.ctypes.data_as(C.c_void_p), stride, _ptr(out_lens, C.c_int32), info, linfo))
+        self.last_loudness_info = [{f[0]: getattr(w, f[0]) for f in vx_loudness_info._fields_} for w in linfo]
+        return [out[i, : out_lens[i]] for i in range(n)], [{f[0]: getattr(w, f[0]) for f in vx_wave_info._fields_} for w in info]
+
+    def dev_loudness_steps(self, wav: np.ndarray, sample_rate: int) -> np.ndarray:
+        """vx_dev_loudness_steps: the step table of one row as the steps kernel wrote it (float64, one K-weighted energy per 100 ms)"""
+        w = np.ascontiguousarray(wav, np.float32).reshape(-1)
+        S = int(sample_rate) // 10
+        ns = -(-len(w) // S) if S > 0 else 0
+        z = np.zeros(max(ns, 1), np.float64)
+        buf = w if len(w) else np.zeros(1, np.float32)
+        self._chk(self.lib.vx_dev_loudness_steps(self.ctx, _ptr(buf, C.c_float), len(w), int(sample_rate), _ptr(z, C.c_double)))
+        return z[:ns]
+
+    def dev_loudness_window(self, samples: int = 0):
+        """vx_dev_loudness_window: samples one launch of the steps pass holds from now on (DEV_LOUDNESS_WINDOW_MIN .. LOUDNESS_WINDOW; 0
+        restores the default); a call whose 3 S exceeds it is refused"""
+        self._chk(self.lib.vx_dev_loudness_window(self.ctx, int(samples)))
+
     def _stretched(self, rows, speed):
         """the 24 kHz rows of a vocoder call at `speed` (None: as they are), before the resampler and the output stage"""
         return rows if speed is None else self.stretch(rows, speed)
@@ -626,6 +718,12 @@ class Engine:
         if finish is None:
             return rows
         frame = finish.frame if finish.frame is not None else int(rate) // 100
+        if getattr(finish, "lufs", None) is not None:
+            if finish.level_mode != LEVEL_NONE:
+                raise ValueError("Finish: lufs and level_mode != 0 both set a level; give one")
+            out, self.last_finish_info = self.finish_loud(rows, int(rate), finish.lufs, finish.ceiling_db, frame, finish.silence_db, finish.trim,
+                                                          finish.keep, finish.max_gain_db, finish.fade_in, finish.fade_out, finish.pcm16)
+            return out
         out, self.last_finish_info = self.finish(rows, frame, finish.silence_db, finish.trim, finish.keep, finish.level_mode, finish.level_db,
                                                  finish.max_gain_db, finish.fade_in, finish.fade_out, finish.pcm16)
         return out

@@ -182,6 +182,10 @@ struct vx_ctx {
   int* st_pos = nullptr;           // [ST_FRAME_CAP] positions of one launch's frames
   double* st_cost = nullptr;       // [ST_FRAME_CAP] winning costs of one launch's frames
   long st_window = 0;              // input samples per launch set by vx_dev_stretch_window (0: the default, VX_STRETCH_WINDOW)
+  // loudness (vx_loudness / vx_finish_loud, loudness.hip): runs in the resampler's launch buffers (rs_buffers); needs no weights
+  double* ln_z = nullptr;          // [LN_Z_CAP] step energies of one launch
+  int* ln_nonf = nullptr;          // [LN_Z_CAP] non-finite samples of one launch's steps
+  long ln_window = 0;              // samples per launch set by vx_dev_loudness_window (0: the default, VX_LOUDNESS_WINDOW)
 
   // graph
   hipGraphExec_t graph_exec = nullptr, graph_exec_n = nullptr;   // one decode step / GRAPH_STEPS steps per launch

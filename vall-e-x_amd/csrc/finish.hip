@@ -111,8 +111,8 @@ __global__ __launch_bounds__(256) void wave_apply_kernel(const float* __restrict
 static long fn_win(const vx_ctx* c, int F) { return std::max<long>(c->fn_window ? c->fn_window : (long)VX_FINISH_WINDOW, F); }
 
 // the measure pass: the frame table of every row, row i at table[f0[i] ..).  resident: the whole batch went through ONE launch, and
-// row i's samples still lie at rs_in + base[i]
-static int fn_measure(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_t* lens, int batch, int F, std::vector<FnFrame>& table,
+// row i's samples still lie at rs_in + base[i].  (fn_measure and fn_apply are shared with vx_finish_loud, loudness.hip.)
+int fn_measure(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_t* lens, int batch, int F, std::vector<FnFrame>& table,
                       std::vector<long>& f0, bool* resident, std::vector<long>& base) {
   std::vector<long> lo(batch, 0), hi(batch);
   f0.assign(batch + 1, 0);
@@ -170,7 +170,7 @@ static int fn_fades(vx_ctx* c, int fade_in, int fade_out) {
   return VX_OK;
 }
 
-static int fn_apply(vx_ctx* c, const float* wav, int64_t wav_stride, int batch, const vx_finish_opts& o, bool resident,
+int fn_apply(vx_ctx* c, const float* wav, int64_t wav_stride, int batch, const vx_finish_opts& o, bool resident,
                     const std::vector<long>& base, void* out, int64_t out_stride, vx_wave_info* info) {
   if (int e = fn_fades(c, o.fade_in, o.fade_out)) return e;
   const bool s16 = o.format == VX_PCM_S16;

@@ -190,7 +190,9 @@ class Finish:
     exceeds 10^(silence_db / 10); trim bit 0 / bit 1 cut before the first / behind the last active frame, `keep` samples stay;
     level_mode 1 / 2 brings the peak / the RMS over the active frames to level_db dBFS with at most max_gain_db of gain; fade_in /
     fade_out are samples of smoothstep; pcm16: int16 instead of float32.  The measurements of the last call stay in
-    `model.engine.last_finish_info`."""
+    `model.engine.last_finish_info`.  lufs (None: the level is level_mode's): the kept span is brought to that BS.1770 loudness instead
+    (Engine.finish_loud, vx_finish_loud) under max_gain_db and a sample peak of ceiling_db dBFS; level_mode must then be 0.  The
+    loudness measurements stay in `model.engine.last_loudness_info`."""
     frame: Optional[int] = None
     silence_db: float = -40.0
     trim: int = 0
@@ -201,6 +203,12 @@ class Finish:
     fade_in: int = 0
     fade_out: int = 0
     pcm16: bool = False
+    lufs: Optional[float] = None
+    ceiling_db: float = -1.0
+
+    def __post_init__(self):
+        if self.lufs is not None and self.level_mode != 0:
+            raise ValueError("Finish: lufs and level_mode != 0 both set a level; give one")
 
 
 def _finished(wavs, finish, sample_rate):

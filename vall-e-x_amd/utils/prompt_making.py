@@ -109,9 +109,24 @@ def trim_silence(wav: np.ndarray, trim_db: float) -> np.ndarray:
     return np.array(rows[0], np.float32)[None]
 
 
-def tokenize_audio(tokenizer: AudioTokenizer, audio: Union[str, Tuple[np.ndarray, int]], trim_db: Optional[float] = None):
+PROMPT_CEILING_DB = -1.0               # lufs: the sample peak of a levelled clip stays below this
+
+
+def level_loudness(wav: np.ndarray, lufs: float, sample_rate: int) -> np.ndarray:
+    """(1, L) mono fp32 at sample_rate -> the clip at `lufs` LUFS (BS.1770), on the loaded model's engine (Engine.finish_loud,
+    vx_finish_loud: no trim, fp32 out, sample peak at most PROMPT_CEILING_DB dBFS).  The loudness of a cloned voice follows the
+    loudness of its enrolment clip."""
+    if G.model is None:
+        raise RuntimeError("call preload_models() first: lufs runs on the loaded model's engine")
+    rows, _ = G.model.engine.finish_loud([wav.reshape(-1)], int(sample_rate), float(lufs), PROMPT_CEILING_DB)
+    return np.array(rows[0], np.float32)[None]
+
+
+def tokenize_audio(tokenizer: AudioTokenizer, audio: Union[str, Tuple[np.ndarray, int]], trim_db: Optional[float] = None,
+                   lufs: Optional[float] = None):
     """data/tokenizer.py:99-111: (path | (wav (C, L), sr)) -> `tokenizer.encode(wav[None])` = [(codes (1, 8, T), None)].
-    trim_db (no reference counterpart; None = the clip as it is): `trim_silence` on the 24 kHz mono clip before the encoder sees it."""
+    trim_db (no reference counterpart; None = the clip as it is): `trim_silence` on the 24 kHz mono clip before the encoder sees it.
+    lufs (no reference counterpart; None = the clip's own level): `level_loudness` on that clip, after the trim."""
     wav, sr = _load_wav(audio) if isinstance(audio, str) else audio
     wav = np.asarray(wav.detach().cpu().numpy() if hasattr(wav, "detach") else wav, np.float32)
     if wav.ndim == 1:
@@ -122,6 +137,8 @@ def tokenize_audio(tokenizer: AudioTokenizer, audio: Union[str, Tuple[np.ndarray
         wav = np.asarray((resampler or _builtin_resampler())(wav, int(sr), tokenizer.sample_rate), np.float32)
     if trim_db is not None:
         wav = trim_silence(wav, trim_db)
+    if lufs is not None:
+        wav = level_loudness(wav, lufs, tokenizer.sample_rate)
     return tokenizer.encode(wav[None])                            # (1, 1, L)
 
 
@@ -143,9 +160,10 @@ def make_transcript(name, wav, sr, transcript: Optional[str] = None):
 
 
 def make_prompt(name: str, audio_prompt_path: Union[str, Tuple[np.ndarray, int]], transcript: Optional[str] = None,
-                save_dir: Optional[str] = None, trim_db: Optional[float] = None) -> str:
+                save_dir: Optional[str] = None, trim_db: Optional[float] = None, lufs: Optional[float] = None) -> str:
     """utils/prompt_making.py:57-84.  `audio_prompt_path`: a WAV path or `(wav (C, L), sr)`.  Returns the path of the written .npz.
-    trim_db: as `tokenize_audio` (leading and trailing silence of the clip is cut before it is encoded)."""
+    trim_db: as `tokenize_audio` (leading and trailing silence of the clip is cut before it is encoded); lufs: as `tokenize_audio`
+    (the clip is brought to that loudness, after the trim, before it is encoded)."""
     global codec
     if G.model is None:
         raise RuntimeError("call preload_models() first (with EnCodec weights: model.load_encodec_state_dict)")
@@ -160,7 +178,7 @@ def make_prompt(name: str, audio_prompt_path: Union[str, Tuple[np.ndarray, int]]
     if wav_pr.shape[0] == 2:                                      # :62-63
         wav_pr = wav_pr.mean(0, keepdims=True)
     text_pr, lang_pr = make_transcript(name, wav_pr, sr, transcript)
-    encoded_frames = tokenize_audio(codec, (wav_pr, sr), trim_db=trim_db)          # :67
+    encoded_frames = tokenize_audio(codec, (wav_pr, sr), trim_db=trim_db, lufs=lufs)          # :67
     codes = encoded_frames[0][0]
     codes = codes.numpy() if hasattr(codes, "numpy") else np.asarray(codes)
     audio_tokens = np.transpose(codes, (0, 2, 1))                 # (1, T, 8)   (:68)
