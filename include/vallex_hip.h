@@ -444,7 +444,7 @@ int vx_stretch(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t*
  *   vx_finish_loud: everything vx_finish refuses, a wrong struct_size of either struct, level_mode other than VX_LEVEL_NONE,
  *   target_lufs not finite or outside -70 .. 0, ceiling_db not finite or above 0.  vx_loudness_coeffs returns VX_EINVAL for a NULL c
  *   or a rate out of range.
- * Not covered: true peak (4x oversampling), loudness range, short-term loudness, channel weights of more than one channel. */
+ * Not covered: loudness range, short-term loudness, channel weights of more than one channel.  True peak: vx_limit below. */
 #define VX_LOUDNESS_WINDOW (1 << 23)
 typedef struct vx_loudness_opts {
   uint32_t struct_size;   /* = sizeof(vx_loudness_opts) */
@@ -464,6 +464,77 @@ int vx_loudness(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t
 int vx_finish_loud(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t* lens, int32_t batch, const vx_finish_opts* o,
                    const vx_loudness_opts* lo, void* out /* may be NULL: measure only */, int64_t out_stride, int32_t* out_lens,
                    vx_wave_info* info, vx_loudness_info* linfo);
+
+/* A true-peak look-ahead limiter of mono fp32 rows on the device (vx_limit), and vx_finish_loud with its sample-peak ceiling term
+ * replaced by that limiter (vx_finish_limited): the gain is set by the loudness target alone and the limiter holds the ceiling.  No
+ * reference counterpart.  A plain numpy restatement reproduces every quantity bit for bit, given the taps and the ceiling the library
+ * reports, independent of the batch and of the windows.
+ *
+ * Inputs: a row x of length L; pre_gain gs (fp32, finite, > 0); ceiling_db (finite, <= 0); lookahead Wn (1 .. 1024 samples), with
+ * N = 2 Wn + 1; oversample n in {1, 2, 4, 8}.
+ *
+ * - Samples.  y[i] = isfinite(x[i]) ? x[i] : 0.  Non-finite samples are counted in `nonfinite`.  y = 0 outside [0, L).
+ * - Taps.  These are the resampler's own table for the pair (o, n) = (1, n): width 7 and K = 15, k_p[j] for p < n, j < 15, in fp32.
+ *   vx_limit_taps(oversample, float* taps) is a pure host function (taps is [n][15]).  It needs no context and reports the taps.
+ *   Everything downstream is defined on the reported taps, as vx_loudness_coeffs does for its coefficients.  n = 1 has no taps.
+ * - Detector.  For n > 1: d_p[i] = sum_j (double)k_p[j] * (double)y[i + j - 7].  The sum runs in tap order j = 0 .. 14 from 0.0 in
+ *   double.  The product of two fp32 values is exact in double.  Contraction to an fma therefore changes no bit.
+ *   P[i] = (float) max(|y[i]|, |d_0[i]|, .., |d_{n-1}[i]|).  A max is exact in any order.  For n = 1: P[i] = |y[i]|.
+ * - Demand.  c = (float) pow(10, ceiling_db / 20).  It is computed once on the host and reported in the info.
+ *   den = (double)P[i] * (double)gs.  This product is exact.  r = den > (double)c ? (double)c / den : 1.0.  This is one correctly
+ *   rounded double division.  q[i] = (int64) floor(r * 16777216.0), an integer in [0, 2^24].  q = 2^24 outside [0, L).
+ * - Hold and smooth.  Both are defined for every integer i, and both are integer arithmetic.  m[i] = min_{|k - i| <= Wn} q[k].
+ *   s[i] = sum_{|k - i| <= Wn} m[k], which is below 2^36.  Being integers, they are exact in any order, so no decomposition and no
+ *   cut can change a bit.
+ * - Gain and output.  g[i] = (float)((double)s[i] / (double)(N * 16777216)).  This is one double division and one rounding.
+ *   out[i] = (y[i] * gs) * g[i].  These are two separately rounded fp32 multiplies, so nothing can be contracted.
+ * - Consequences.  m[k] <= q[i] whenever |k - i| <= Wn.  Hence s[i] <= N q[i], and g[i] <= q[i] / 2^24, which is exact in fp32, and
+ *   that is <= r.  So |out[i]| <= c (1 + 2^-22).  Where nothing within 2 Wn exceeds the ceiling, g = 1.0 exactly.  With gs = 1 the
+ *   output then has the bits of y.  An isolated over-ceiling sample at k0 with demand q0 gives the trapezoid
+ *   s[i] = N 2^24 - max(0, N - |i - k0|) (2^24 - q0).
+ * - Info per row.  peak = max_i P[i].  This is the true peak of the input at n-times oversampling, linear, before pre_gain.  It is 0
+ *   for an empty row.  min_gain = min_i g[i].  It is 1 for an empty row.  reduced = #{i : g[i] < 1}.  nonfinite.  ceiling = c.
+ *   With out == NULL (measure only) peak, nonfinite and ceiling are measured; min_gain is 1 and reduced is 0.
+ * - Exactness.  No floating-point atomics, and no atomics at all in the kernel.  Two calls give the same bits.  A row's bits depend
+ *   on neither the batch nor the windows.
+ * - State.  As vx_finish: no weights; works before vx_finalize_weights and while a serving session is open; touches no decode state,
+ *   KV arena or fallback counter; runs in the resampler's launch buffers plus what it allocates at first use, which vx_destroy
+ *   frees; transfers go through the pinned ring.
+ * - Windows.  One launch holds VX_LIMIT_WINDOW (2^23) samples.  Rows are packed in order.  A longer row is cut anywhere.  A part
+ *   carries the 2 Wn + 7 real samples its outputs reach on either side.  Zeros exist only outside the row.
+ * - vx_finish_limited is vx_finish_loud with two changes.  The gain: the ceiling term is dropped,
+ *   g = min(10^((target - loudness) / 20), 10^(max_gain_db / 20), FLT_MAX), rounded once; it is 1 when nothing passes the gates.  The
+ *   limiter runs between the gain and the fades: it limits the kept span [begin, end) as a row of its own, with zeros outside, with
+ *   pre_gain = g and ceiling_db = lo->ceiling_db.  The existing apply pass then runs over the limited samples at gain 1, which is
+ *   exact: fades and format as before.  The output is therefore bit-equal to vx_finish(vx_limit(x[begin:end], g, ceiling),
+ *   VX_LEVEL_NONE, no trim, same fades and format).  level_mode must be VX_LEVEL_NONE.  out == NULL measures only, giving
+ *   liminfo.peak of the span.  vx_wave_info.gain reports g.  A call that fits one launch uploads its samples once.
+ * - Refusals.  These return VX_EINVAL, launch nothing and write nothing, and the message names the field: NULL wav, lens, o or info;
+ *   batch <= 0; a wrong struct_size; a length negative or above wav_stride; out_stride below a length when out is given; pre_gain
+ *   not finite or <= 0; ceiling_db not finite or > 0; lookahead outside 1 .. 1024; oversample not one of 1, 2, 4, 8.
+ *   vx_finish_limited: every refusal of vx_finish_loud and of vx_limit (lim and liminfo NULL as well).  vx_limit_taps returns
+ *   VX_EINVAL for a NULL taps or an oversample that is not one of 1, 2, 4, 8.
+ * Not covered: the true peak after the time-varying gain is close to the ceiling but not bounded by it; the loudness after limiting
+ * is slightly below the target; loudness range and short-term loudness remain unbuilt. */
+#define VX_LIMIT_WINDOW (1 << 23)
+typedef struct vx_limit_opts {
+  uint32_t struct_size;   /* = sizeof(vx_limit_opts) */
+  int32_t lookahead;      /* Wn, 1 .. 1024 samples */
+  int32_t oversample;     /* n: 1, 2, 4 or 8 */
+} vx_limit_opts;
+typedef struct vx_limit_info {
+  float peak;             /* max P: the true peak of the input, linear, before pre_gain */
+  float min_gain;         /* min g; 1 for an empty row */
+  float ceiling;          /* c */
+  int32_t reduced;        /* samples with g < 1 */
+  int32_t nonfinite;
+} vx_limit_info;
+int vx_limit_taps(int32_t oversample, float* taps /* [oversample][15]; untouched for oversample 1 */);
+int vx_limit(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t* lens, int32_t batch, float pre_gain, float ceiling_db,
+             const vx_limit_opts* o, float* out /* NULL: measure only -> peak, nonfinite */, int64_t out_stride, vx_limit_info* info);
+int vx_finish_limited(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t* lens, int32_t batch, const vx_finish_opts* o,
+                      const vx_loudness_opts* lo, const vx_limit_opts* lim, void* out /* may be NULL: measure only */, int64_t out_stride,
+                      int32_t* out_lens, vx_wave_info* info, vx_loudness_info* linfo, vx_limit_info* liminfo);
 
 /* ---- step-level entries (kernel-level parity tests; same kernels as vx_infer) ---------------------------- */
 /* first ar_decoder.infer call (models/vallex.py:528-562): embeds, runs the prefix-LM prefill, fills the KV arena,

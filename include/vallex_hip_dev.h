@@ -408,6 +408,19 @@ int vx_dev_loudness_steps(vx_ctx* ctx, const float* wav, int32_t n, int32_t samp
 #define VX_DEV_LOUDNESS_WINDOW_MIN 4096
 int vx_dev_loudness_window(vx_ctx* ctx, int32_t samples);
 
+/* The detector readings and the gains of ONE row as limit_rows_kernel (csrc/limit.hip, the kernel behind vx_limit and
+ * vx_finish_limited) writes them: P [len] and g [len] as include/vallex_hip.h defines them.  The row goes through the same planner and
+ * windows as vx_limit.  VX_EINVAL, nothing written: a NULL pointer, len < 0, anything vx_limit refuses. */
+int vx_dev_limit_gain(vx_ctx* ctx, const float* wav, int32_t len, float pre_gain, float ceiling_db, const vx_limit_opts* o, float* P,
+                      float* g);
+/* Samples one launch of the limiter holds (halos included), for later calls on this context: VX_DEV_LIMIT_WINDOW_MIN ..
+ * VX_LIMIT_WINDOW, or 0 for the default (VX_LIMIT_WINDOW).  A small window sends short rows through several parts and launches -- what
+ * the window tests need; the device buffers keep their size.  A window that cannot hold a part's two halos of 2 Wn + 7 samples plus
+ * one sample is refused by the call (VX_EINVAL), not enlarged.  With a window set, vx_finish_limited brings the limited samples to the
+ * host between the limiter and the apply pass.  VX_EINVAL, nothing changed, for any other value. */
+#define VX_DEV_LIMIT_WINDOW_MIN 8192
+int vx_dev_limit_window(vx_ctx* ctx, int32_t samples);
+
 #ifdef __cplusplus
 }
 #endif

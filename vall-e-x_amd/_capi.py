@@ -104,6 +104,16 @@ class vx_loudness_info(C.Structure):
                 ("above_abs", C.c_int32), ("gated", C.c_int32), ("nonfinite", C.c_int32)]
 
 
+class vx_limit_opts(C.Structure):
+    """options of vx_limit / vx_finish_limited (the look-ahead in samples, the detector's oversampling)"""
+    _fields_ = [("struct_size", C.c_uint32), ("lookahead", C.c_int32), ("oversample", C.c_int32)]
+
+
+class vx_limit_info(C.Structure):
+    """what vx_limit measured of one row"""
+    _fields_ = [("peak", C.c_float), ("min_gain", C.c_float), ("ceiling", C.c_float), ("reduced", C.c_int32), ("nonfinite", C.c_int32)]
+
+
 # every symbol include/vallex_hip.h declares (tests/test_abi.py checks the library exports exactly these)
 ABI_VERSION = 6       # VX_ABI_VERSION of include/vallex_hip.h this binding was written against
 
@@ -112,13 +122,15 @@ SYMBOLS = ["vx_abi_version", "vx_create", "vx_destroy", "vx_last_error", "vx_syn
            "vx_nar", "vx_read_tap", "vx_last_stats", "vx_last_truncated", "vx_last_fallbacks", "vx_fallback_state",
            "vx_fallback_reset", "vx_arith_mode", "vx_infer_continuous", "vx_serve_open", "vx_serve_submit", "vx_serve_run",
            "vx_serve_close", "vx_serve_submit_ex", "vx_serve_cancel", "vx_serve_submit_filtered", "vx_score", "vx_align", "vx_resample",
-           "vx_finish", "vx_stretch", "vx_loudness_coeffs", "vx_loudness", "vx_finish_loud"]
+           "vx_finish", "vx_stretch", "vx_loudness_coeffs", "vx_loudness", "vx_finish_loud", "vx_limit_taps", "vx_limit",
+           "vx_finish_limited"]
 # ... and include/vallex_hip_dev.h: measurement / kernel development, never called by the mirrors of the reference API
 DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kernel", "vx_bench_gemm", "vx_bench_attn",
                "vx_bench_gemm_clock", "vx_bench_gemm_epilogue", "vx_dev_sample", "vx_dev_attn", "vx_dev_sample_filtered",
                "vx_dev_dec_attn", "vx_dev_dec_op", "vx_dev_gemm", "vx_dev_layernorm", "vx_dev_score_rows", "vx_dev_align_rows", "vx_dev_wave_op",
                "vx_dev_seam_op", "vx_dev_resample_taps", "vx_dev_resample_window", "vx_dev_finish_frames", "vx_dev_finish_window",
-               "vx_dev_stretch_window", "vx_dev_stretch_costs", "vx_dev_loudness_steps", "vx_dev_loudness_window"]
+               "vx_dev_stretch_window", "vx_dev_stretch_costs", "vx_dev_loudness_steps", "vx_dev_loudness_window",
+               "vx_dev_limit_gain", "vx_dev_limit_window"]
 # sentinels the correctness entries pre-fill their outputs with (include/vallex_hip_dev.h)
 DEV_SENTINEL_I = -123456789
 DEV_SENTINEL_F = np.float32(-1.0e30)
@@ -150,6 +162,7 @@ RESAMPLE_WINDOW, DEV_RESAMPLE_WINDOW_MIN = 1 << 23, 512     # VX_RESAMPLE_WINDOW
 FINISH_WINDOW, DEV_FINISH_WINDOW_MIN = 1 << 23, 512         # VX_FINISH_WINDOW / VX_DEV_FINISH_WINDOW_MIN: input samples per launch
 STRETCH_WINDOW, DEV_STRETCH_WINDOW_MIN = 1 << 23, 2048      # VX_STRETCH_WINDOW / VX_DEV_STRETCH_WINDOW_MIN: input samples per launch
 LOUDNESS_WINDOW, DEV_LOUDNESS_WINDOW_MIN = 1 << 23, 4096    # VX_LOUDNESS_WINDOW / VX_DEV_LOUDNESS_WINDOW_MIN: samples per launch
+LIMIT_WINDOW, DEV_LIMIT_WINDOW_MIN = 1 << 23, 8192          # VX_LIMIT_WINDOW / VX_DEV_LIMIT_WINDOW_MIN: samples per launch
 PCM_F32, PCM_S16 = 0, 1                                      # VX_PCM_*
 LEVEL_NONE, LEVEL_PEAK, LEVEL_RMS = 0, 1, 2                  # VX_LEVEL_*
 DEV_SAMPLE_CFG = ("kernel", "splitk", "top_k", "force_eos_at", "active", "n_gen", "cur_pos", "ctx_len", "text_len", "gen_stride")
@@ -273,6 +286,14 @@ def load_library() -> C.CDLL:
                                    C.c_int64, P(C.c_int32), P(vx_wave_info), P(vx_loudness_info)]
     lib.vx_dev_loudness_steps.argtypes = [ctx, P(C.c_float), C.c_int32, C.c_int32, P(C.c_double)]
     lib.vx_dev_loudness_window.argtypes = [ctx, C.c_int32]
+    lib.vx_limit_taps.argtypes = [C.c_int32, P(C.c_float)]
+    lib.vx_limit.argtypes = [ctx, P(C.c_float), C.c_int64, P(C.c_int32), C.c_int32, C.c_float, C.c_float, P(vx_limit_opts), P(C.c_float),
+                             C.c_int64, P(vx_limit_info)]
+    lib.vx_finish_limited.argtypes = [ctx, P(C.c_float), C.c_int64, P(C.c_int32), C.c_int32, P(vx_finish_opts), P(vx_loudness_opts),
+                                      P(vx_limit_opts), C.c_void_p, C.c_int64, P(C.c_int32), P(vx_wave_info), P(vx_loudness_info),
+                                      P(vx_limit_info)]
+    lib.vx_dev_limit_gain.argtypes = [ctx, P(C.c_float), C.c_int32, C.c_float, C.c_float, P(vx_limit_opts), P(C.c_float), P(C.c_float)]
+    lib.vx_dev_limit_window.argtypes = [ctx, C.c_int32]
     lib.vx_dev_stretch_costs.argtypes = [ctx, P(C.c_float), C.c_int32, P(vx_stretch_opts), P(C.c_float), P(C.c_int32), P(C.c_double)]
     lib.vx_last_stats.argtypes = [ctx, P(C.c_int64), P(C.c_int64), P(C.c_double), P(C.c_double)]
     lib.vx_last_truncated.argtypes = [ctx, P(C.c_int32)]
@@ -706,6 +727,92 @@ class Engine:
         restores the default); a call whose 3 S exceeds it is refused"""
         self._chk(self.lib.vx_dev_loudness_window(self.ctx, int(samples)))
 
+    def limit_taps(self, oversample: int) -> np.ndarray:
+        """vx_limit_taps: the taps the detector of `limit` interpolates with, (oversample, 15) float32 -- the resampler's table of the
+        pair (1, oversample); (0, 15) at oversample 1"""
+        n = int(oversample)
+        t = np.zeros((max(n, 1), 15), np.float32)
+        if self.lib.vx_limit_taps(n, _ptr(t, C.c_float)) != 0:
+            raise ValueError(f"oversample {oversample} is not one of 1, 2, 4, 8")
+        return t[: n if n > 1 else 0]
+
+    last_limit_info = None           # the limiter dicts of the last `finish_limited` (also through a `finish=` LimitedFinish)
+
+    @staticmethod
+    def _limit_dicts(info):
+        return [{f[0]: getattr(w, f[0]) for f in vx_limit_info._fields_} for w in info]
+
+    def limit(self, wavs: Sequence[np.ndarray], ceiling_db: float = -1.0, pre_gain: float = 1.0, lookahead: int = 120, oversample: int = 4):
+        """vx_limit, a true-peak look-ahead limiter of mono fp32 waveforms (L_i,): every row times pre_gain, then held under ceiling_db
+        dBTP by a gain that follows the detector's `oversample`-times interpolated peak, `lookahead` samples ahead, and is smoothed
+        over 2 lookahead + 1 samples.  Returns (list of float32 arrays, list of dicts -- peak, min_gain, ceiling, reduced, nonfinite:
+        include/vallex_hip.h, vx_limit_info).  Where nothing within 2 lookahead exceeds the ceiling the gain is exactly 1.  Non-finite
+        samples count as 0."""
+        n = len(wavs)
+        if n == 0:
+            return [], []
+        buf, lens, stride = self._packed(wavs)
+        o = vx_limit_opts(C.sizeof(vx_limit_opts), int(lookahead), int(oversample))
+        info = (vx_limit_info * n)()
+        out = np.empty((n, stride), np.float32)
+        self._chk(self.lib.vx_limit(self.ctx, _ptr(buf, C.c_float), stride, _ptr(lens, C.c_int32), n, float(pre_gain), float(ceiling_db),
+                                    C.byref(o), _ptr(out, C.c_float), stride, info))
+        return [out[i, : lens[i]] for i in range(n)], self._limit_dicts(info)
+
+    def true_peak(self, wavs: Sequence[np.ndarray], oversample: int = 4):
+        """the measure-only call of vx_limit: a list of dicts with peak = the `oversample`-times interpolated (true) peak of every row,
+        linear, and nonfinite; nothing is limited (min_gain 1, reduced 0)"""
+        n = len(wavs)
+        if n == 0:
+            return []
+        buf, lens, stride = self._packed(wavs)
+        o = vx_limit_opts(C.sizeof(vx_limit_opts), 1, int(oversample))
+        info = (vx_limit_info * n)()
+        self._chk(self.lib.vx_limit(self.ctx, _ptr(buf, C.c_float), stride, _ptr(lens, C.c_int32), n, 1.0, 0.0, C.byref(o), None, 0, info))
+        return self._limit_dicts(info)
+
+    def finish_limited(self, wavs: Sequence[np.ndarray], sample_rate: int, lufs: float, ceiling_db: float = -1.0, lookahead: Optional[int] = None,
+                       oversample: int = 4, frame: Optional[int] = None, silence_db: float = -40.0, trim: int = 0, keep: int = 0,
+                       max_gain_db: float = 20.0, fade_in: int = 0, fade_out: int = 0, pcm16: bool = False, measure_only: bool = False):
+        """vx_finish_limited, `finish_loud` with the sample-peak ceiling term of its gain replaced by the limiter: the kept span of every
+        row is brought to `lufs` LUFS with at most max_gain_db of gain, then held under ceiling_db dBTP by `limit` (lookahead None = 5 ms,
+        sample_rate // 200), then faded and formatted.  Returns (list of arrays, list of info dicts; `gain` is the loudness gain); the
+        loudness dicts stay in `last_loudness_info`, the limiter dicts in `last_limit_info`.  measure_only: no output, ([], infos)."""
+        n = len(wavs)
+        if n == 0:
+            self.last_loudness_info, self.last_limit_info = [], []
+            return [], []
+        buf, lens, stride = self._packed(wavs)
+        o = vx_finish_opts(C.sizeof(vx_finish_opts), int(sample_rate) // 100 if frame is None else int(frame), float(silence_db), int(trim),
+                           int(keep), LEVEL_NONE, -1.0, float(max_gain_db), int(fade_in), int(fade_out), PCM_S16 if pcm16 else PCM_F32)
+        lo = vx_loudness_opts(C.sizeof(vx_loudness_opts), int(sample_rate), float(lufs), float(ceiling_db))
+        lim = vx_limit_opts(C.sizeof(vx_limit_opts), int(sample_rate) // 200 if lookahead is None else int(lookahead), int(oversample))
+        info, linfo, minfo = (vx_wave_info * n)(), (vx_loudness_info * n)(), (vx_limit_info * n)()
+        out = None if measure_only else np.empty((n, stride), np.int16 if pcm16 else np.float32)
+        out_lens = np.zeros(n, np.int32)
+        self._chk(self.lib.vx_finish_limited(self.ctx, _ptr(buf, C.c_float), stride, _ptr(lens, C.c_int32), n, C.byref(o), C.byref(lo),
+                                             C.byref(lim), None if out is None else out.ctypes.data_as(C.c_void_p), stride,
+                                             _ptr(out_lens, C.c_int32), info, linfo, minfo))
+        self.last_loudness_info = [{f[0]: getattr(w, f[0]) for f in vx_loudness_info._fields_} for w in linfo]
+        self.last_limit_info = self._limit_dicts(minfo)
+        rows = [] if out is None else [out[i, : out_lens[i]] for i in range(n)]
+        return rows, [{f[0]: getattr(w, f[0]) for f in vx_wave_info._fields_} for w in info]
+
+    def dev_limit_gain(self, wav: np.ndarray, pre_gain: float = 1.0, ceiling_db: float = -1.0, lookahead: int = 120, oversample: int = 4):
+        """vx_dev_limit_gain: (P, g) of one row as the limiter kernel wrote them (float32: the detector readings and the gains)"""
+        w = np.ascontiguousarray(wav, np.float32).reshape(-1)
+        P, g = np.zeros(max(len(w), 1), np.float32), np.zeros(max(len(w), 1), np.float32)
+        buf = w if len(w) else np.zeros(1, np.float32)
+        o = vx_limit_opts(C.sizeof(vx_limit_opts), int(lookahead), int(oversample))
+        self._chk(self.lib.vx_dev_limit_gain(self.ctx, _ptr(buf, C.c_float), len(w), float(pre_gain), float(ceiling_db), C.byref(o),
+                                             _ptr(P, C.c_float), _ptr(g, C.c_float)))
+        return P[: len(w)], g[: len(w)]
+
+    def dev_limit_window(self, samples: int = 0):
+        """vx_dev_limit_window: samples one launch of the limiter holds from now on (DEV_LIMIT_WINDOW_MIN .. LIMIT_WINDOW; 0 restores
+        the default)"""
+        self._chk(self.lib.vx_dev_limit_window(self.ctx, int(samples)))
+
     def _stretched(self, rows, speed):
         """the 24 kHz rows of a vocoder call at `speed` (None: as they are), before the resampler and the output stage"""
         return rows if speed is None else self.stretch(rows, speed)
@@ -721,6 +828,11 @@ class Engine:
         if getattr(finish, "lufs", None) is not None:
             if finish.level_mode != LEVEL_NONE:
                 raise ValueError("Finish: lufs and level_mode != 0 both set a level; give one")
+            if hasattr(finish, "oversample"):        # a utils.generation.LimitedFinish: the limiter holds the ceiling
+                out, self.last_finish_info = self.finish_limited(rows, int(rate), finish.lufs, finish.ceiling_db, finish.lookahead,
+                                                                 finish.oversample, frame, finish.silence_db, finish.trim, finish.keep,
+                                                                 finish.max_gain_db, finish.fade_in, finish.fade_out, finish.pcm16)
+                return out
             out, self.last_finish_info = self.finish_loud(rows, int(rate), finish.lufs, finish.ceiling_db, frame, finish.silence_db, finish.trim,
                                                           finish.keep, finish.max_gain_db, finish.fade_in, finish.fade_out, finish.pcm16)
             return out

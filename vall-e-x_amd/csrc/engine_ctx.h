@@ -186,6 +186,11 @@ struct vx_ctx {
   double* ln_z = nullptr;          // [LN_Z_CAP] step energies of one launch
   int* ln_nonf = nullptr;          // [LN_Z_CAP] non-finite samples of one launch's steps
   long ln_window = 0;              // samples per launch set by vx_dev_loudness_window (0: the default, VX_LOUDNESS_WINDOW)
+  // limiter (vx_limit / vx_finish_limited, limit.hip): runs in the resampler's launch buffers (rs_buffers); needs no weights
+  double* lm_taps = nullptr;       // [8][15] the detector's taps, widened, of the oversampling they were last built for (lm_taps_n)
+  int lm_taps_n = 0;
+  float* lm_rec = nullptr;         // [LM_REC_CAP][4] tile records of one launch: {peak, min gain, reduced, non-finite}
+  long lm_window = 0;              // samples per launch set by vx_dev_limit_window (0: the default, VX_LIMIT_WINDOW)
 
   // graph
   hipGraphExec_t graph_exec = nullptr, graph_exec_n = nullptr;   // one decode step / GRAPH_STEPS steps per launch

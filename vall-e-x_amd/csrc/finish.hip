@@ -111,7 +111,7 @@ __global__ __launch_bounds__(256) void wave_apply_kernel(const float* __restrict
 static long fn_win(const vx_ctx* c, int F) { return std::max<long>(c->fn_window ? c->fn_window : (long)VX_FINISH_WINDOW, F); }
 
 // the measure pass: the frame table of every row, row i at table[f0[i] ..).  resident: the whole batch went through ONE launch, and
-// row i's samples still lie at rs_in + base[i].  (fn_measure and fn_apply are shared with vx_finish_loud, loudness.hip.)
+// row i's samples still lie at rs_in + base[i].  (fn_measure and fn_apply are shared with vx_finish_loud, loudness.hip, and vx_finish_limited, limit.hip.)
 int fn_measure(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_t* lens, int batch, int F, std::vector<FnFrame>& table,
                       std::vector<long>& f0, bool* resident, std::vector<long>& base) {
   std::vector<long> lo(batch, 0), hi(batch);
@@ -170,9 +170,11 @@ static int fn_fades(vx_ctx* c, int fade_in, int fade_out) {
   return VX_OK;
 }
 
+// src (with resident): the device buffer the rows lie in, row i's sample 0 at src + base[i]; nullptr: rs_in
 int fn_apply(vx_ctx* c, const float* wav, int64_t wav_stride, int batch, const vx_finish_opts& o, bool resident,
-                    const std::vector<long>& base, void* out, int64_t out_stride, vx_wave_info* info) {
+                    const std::vector<long>& base, void* out, int64_t out_stride, vx_wave_info* info, const float* src) {
   if (int e = fn_fades(c, o.fade_in, o.fade_out)) return e;
+  const float* in = resident && src ? src : c->rs_in;
   const bool s16 = o.format == VX_PCM_S16;
   const size_t es = s16 ? sizeof(short) : sizeof(float);
   std::vector<long> lo(batch), hi(batch);
@@ -200,10 +202,10 @@ int fn_apply(vx_ctx* c, const float* wav, int64_t wav_stride, int batch, const v
     H2D(c->rs_meta, tab.data(), tab.size() * sizeof(int));
     const dim3 grid((unsigned)((max_cnt + FN_TILE - 1) / FN_TILE), (unsigned)(j1 - j0));
     if (s16)
-      hipLaunchKernelGGL(wave_apply_kernel<true>, grid, dim3(256), 0, c->stream, c->rs_in, c->rs_meta, tab_in, tab_out, o.fade_in, o.fade_out,
+      hipLaunchKernelGGL(wave_apply_kernel<true>, grid, dim3(256), 0, c->stream, in, c->rs_meta, tab_in, tab_out, o.fade_in, o.fade_out,
                          (void*)c->rs_out);
     else
-      hipLaunchKernelGGL(wave_apply_kernel<false>, grid, dim3(256), 0, c->stream, c->rs_in, c->rs_meta, tab_in, tab_out, o.fade_in, o.fade_out,
+      hipLaunchKernelGGL(wave_apply_kernel<false>, grid, dim3(256), 0, c->stream, in, c->rs_meta, tab_in, tab_out, o.fade_in, o.fade_out,
                          (void*)c->rs_out);
     for (size_t k = j0; k < j1; ++k) {
       const FnJob& j = jobs[k];
@@ -252,7 +254,7 @@ int vx_finish(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_t* le
   std::vector<vx_wave_info> w((size_t)batch);
   for (int i = 0; i < batch; ++i) fn_reduce(table.data() + f0[i], lens[i], *o, thr2, &w[(size_t)i]);
   if (out)
-    if (int e = fn_apply(c, wav, wav_stride, batch, *o, resident, base, out, out_stride, w.data())) return e;
+    if (int e = fn_apply(c, wav, wav_stride, batch, *o, resident, base, out, out_stride, w.data(), nullptr)) return e;
   for (int i = 0; i < batch; ++i) {
     info[i] = w[(size_t)i];
     if (out_lens) out_lens[i] = w[(size_t)i].end - w[(size_t)i].begin;

@@ -39,7 +39,7 @@ struct LnCoef { double c[10]; };
 int fn_measure(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_t* lens, int batch, int F, std::vector<FnFrame>& table,
                std::vector<long>& f0, bool* resident, std::vector<long>& base);
 int fn_apply(vx_ctx* c, const float* wav, int64_t wav_stride, int batch, const vx_finish_opts& o, bool resident, const std::vector<long>& base,
-             void* out, int64_t out_stride, vx_wave_info* info);
+             void* out, int64_t out_stride, vx_wave_info* info, const float* src);
 
 // tab [njobs][RS_TAB]: {in_off, pre, cnt, z_off}: the job's steps cover in[in_off + pre .. in_off + pre + cnt), the `pre` samples in
 // front are its warm-up (what a lane would read in front of in_off lies before the span: 0).  Step t of the job -> z[z_off + t],
@@ -112,7 +112,8 @@ __global__ __launch_bounds__(LN_LANES) void loudness_steps_kernel(const float* _
 
 static long ln_win(const vx_ctx* c) { return c->ln_window ? c->ln_window : (long)VX_LOUDNESS_WINDOW; }
 
-static int ln_buffers(vx_ctx* c) {
+// (ln_buffers, ln_steps and ln_check_rows are shared with vx_finish_limited, limit.hip)
+int ln_buffers(vx_ctx* c) {
   if (int e = rs_buffers(c)) return e;
   if (!c->ln_z) {
     if (int e = dev_alloc(c, &c->ln_z, (size_t)LN_Z_CAP, false)) return e;
@@ -123,7 +124,7 @@ static int ln_buffers(vx_ctx* c) {
 
 // the steps pass over the spans [lo[i], hi[i]) of the rows: the step table of row i at z[z0[i] ..), its non-finite samples in nonf[i].
 // resident: the rows already lie in rs_in, row i's sample 0 at rs_in + base[i]; nothing is uploaded and one launch takes all of them.
-static int ln_steps(vx_ctx* c, const char* who, const float* wav, int64_t wav_stride, const long* lo, const long* hi, int batch, int rate,
+int ln_steps(vx_ctx* c, const char* who, const float* wav, int64_t wav_stride, const long* lo, const long* hi, int batch, int rate,
                     bool resident, const std::vector<long>& base, std::vector<double>& z, std::vector<long>& z0, std::vector<int>& nonf) {
   const int S = ln_step(rate);
   LnCoef k;
@@ -174,7 +175,7 @@ static int ln_steps(vx_ctx* c, const char* who, const float* wav, int64_t wav_st
   return VX_OK;
 }
 
-static int ln_check_rows(vx_ctx* c, const char* who, const float* wav, int64_t wav_stride, const int32_t* lens, int batch) {
+int ln_check_rows(vx_ctx* c, const char* who, const float* wav, int64_t wav_stride, const int32_t* lens, int batch) {
   if (!wav) FAIL(VX_EINVAL, "%s: wav is NULL", who);
   if (!lens) FAIL(VX_EINVAL, "%s: lens is NULL", who);
   if (batch <= 0) FAIL(VX_EINVAL, "%s: batch %d below 1", who, batch);
@@ -265,7 +266,7 @@ int vx_finish_loud(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_
     w[(size_t)i].gain = ln_gain(li[(size_t)i].loudness, lo_->target_lufs, lo_->ceiling_db, o->max_gain_db, w[(size_t)i].peak);
   }
   if (out)
-    if (int e = fn_apply(c, wav, wav_stride, batch, *o, resident, base, out, out_stride, w.data())) return e;
+    if (int e = fn_apply(c, wav, wav_stride, batch, *o, resident, base, out, out_stride, w.data(), nullptr)) return e;
   for (int i = 0; i < batch; ++i) {
     info[i] = w[(size_t)i];
     linfo[i] = li[(size_t)i];

@@ -211,6 +211,22 @@ class Finish:
             raise ValueError("Finish: lufs and level_mode != 0 both set a level; give one")
 
 
+@dataclass(frozen=True)
+class LimitedFinish(Finish):
+    """A `Finish` whose loudness target is held under ceiling_db dBTP by a true-peak look-ahead limiter (Engine.finish_limited,
+    vx_finish_limited) instead of by a smaller gain: the gain is set by lufs and max_gain_db alone, so a loud sample no longer makes
+    the whole utterance quieter than the target.  lufs must be set.  lookahead None = 5 ms at the output rate (sample_rate // 200),
+    1 .. 1024 samples; oversample 1, 2, 4 or 8: the detector's interpolation.  The limiter's measurements stay in
+    `model.engine.last_limit_info`."""
+    lookahead: Optional[int] = None
+    oversample: int = 4
+
+    def __post_init__(self):
+        super().__post_init__()
+        if self.lufs is None:
+            raise ValueError("LimitedFinish: lufs must be set (the limiter sits behind the loudness target)")
+
+
 def _finished(wavs, finish, sample_rate):
     """the waveforms of a call, already at their output rate, through `finish` (None: as they are): one vx_finish call for the list"""
     if finish is None:
