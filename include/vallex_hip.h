@@ -536,6 +536,60 @@ int vx_finish_limited(vx_ctx* ctx, const float* wav, int64_t wav_stride, const i
                       const vx_loudness_opts* lo, const vx_limit_opts* lim, void* out /* may be NULL: measure only */, int64_t out_stride,
                       int32_t* out_lens, vx_wave_info* info, vx_loudness_info* linfo, vx_limit_info* liminfo);
 
+/* The fundamental frequency: F0 per frame of mono fp32 rows on the device by YIN (de Cheveigne & Kawahara 2002: the difference
+ * function, its cumulative-mean normalisation, the absolute threshold, parabolic refinement).  No reference counterpart.  It is the
+ * measurement behind the pitch control: a pitch shift by p / q is vx_stretch at speed q / p followed by vx_resample with orig_rate = p,
+ * new_rate = q, and vx_f0 is what shows that the result moved by p / q.  Inputs are a row x of length L and the
+ * options sample_rate, hop (H), window (W), lag_min, lag_max and threshold.  All arithmetic is double and every named operation is
+ * rounded on its own (no contraction), so that a plain numpy restatement reproduces every output word for word:
+ *
+ * - Samples.  y[i] = isfinite(x[i]) ? x[i] : 0.  Outside [0, L), y = 0.  `nonfinite` counts the non-finite samples of the row.
+ * - Frames.  M = ceil(L / H); a row with L = 0 has no frame.  Frame k is centred on k H + H/2: its first sample is
+ *   s_k = k H + H/2 - (W + lag_max)/2 in 64-bit integers with integer division (it may be negative), and it reads
+ *   y[s_k .. s_k + W + lag_max).
+ * - Difference.  For every t in [0, lag_max] ONE LANE computes d(t) = the sum from 0.0, in order j = 0 .. W-1, of e * e with
+ *   e = (double)y[s_k + j] - (double)y[s_k + j + t].  The subtraction, the product and the addition are three roundings: an fma of
+ *   e * e + acc would change bits.  This equals np.cumsum(e * e)[-1] in float64.
+ * - Normalisation.  c(t) = d(1) + .. + d(t), added in lag order (a serial prefix: double addition is not associative).  d'(0) = 1 and
+ *   d'(t) = c(t) > 0 ? (d(t) * (double)t) / c(t) : 1.
+ * - Pick.  The first u in [lag_min, lag_max] with d'(u) < (double)threshold, then t = u stepped upward while t + 1 <= lag_max and
+ *   d'(t + 1) < d'(t): the frame is voiced.  Without such a u, t = the arg-min of d' over [lag_min, lag_max], ties to the smallest lag:
+ *   the frame is unvoiced.
+ * - Refinement.  With a, b, c = d'(t - 1), d'(t), d'(t + 1): if t + 1 <= lag_max, b <= a, b <= c and den = (a - 2.0 * b) + c > 0, then
+ *   off = (0.5 * (a - c)) / den, else off = 0.  f0 = (float)((double)sample_rate / ((double)t + off)).
+ * - Outputs per frame.  f0[b][k] = that candidate, always written; lag[b][k] = +t of a voiced and -t of an unvoiced frame;
+ *   ap[b][k] = (float)d'(t), the aperiodicity.  An all-zero frame gives lag = -lag_min, ap = 1, f0 = sample_rate / lag_min.
+ * - Info.  Plain host code over the voiced frames of the row: f0_median = the lower median of the fp32 values (element (n - 1) / 2 of
+ *   the n sorted values), f0_min and f0_max over the same frames; all three 0 without a voiced frame.
+ * - Exactness.  No floating-point atomics.  Two calls give the same bits.  A row's bits depend neither on the batch nor on the launch
+ *   windows: frames are independent.
+ * - State.  As vx_stretch: it needs no weights, works while a serving session is open, touches no decode state, and runs in the
+ *   resampler's launch buffers; transfers go through the pinned ring.
+ * - Windows.  One launch holds VX_F0_WINDOW (2^23) samples.  Rows are packed into launches in order.  A longer row is cut at frame
+ *   boundaries, and every part is staged with all the samples its frames reach.
+ * - Refusals.  These return VX_EINVAL, launch nothing and write nothing, and the message names the field: sample_rate outside
+ *   8000 .. 192000; hop outside 16 .. 4096; window outside 16 .. 2048; lag_min or lag_max outside 2 <= lag_min < lag_max <= 1024;
+ *   threshold not finite or outside (0, 1]; a wrong struct_size; NULL wav / lens / o / f0 / lag / info; batch <= 0; a length negative
+ *   or above wav_stride; frame_stride below a row's M.
+ *
+ *   wav [batch][wav_stride] fp32, lens [batch] samples (0 allowed: the row writes nothing but its info); f0, lag and ap (when given)
+ *   [batch][frame_stride]; info [batch].  Elements behind M of a row are not written. */
+#define VX_F0_WINDOW (1 << 23)
+typedef struct vx_f0_opts {
+  uint32_t struct_size;     /* = sizeof(vx_f0_opts) */
+  int32_t sample_rate;      /* 8000 .. 192000: only turns lags into Hz */
+  int32_t hop;              /* H, 16 .. 4096 */
+  int32_t window;           /* W, 16 .. 2048: samples summed per lag */
+  int32_t lag_min, lag_max; /* 2 <= lag_min < lag_max <= 1024 */
+  float threshold;          /* finite, in (0, 1] */
+} vx_f0_opts;
+typedef struct vx_f0_info {
+  int32_t frames, voiced_frames, nonfinite;
+  float f0_median, f0_min, f0_max;
+} vx_f0_info;
+int vx_f0(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t* lens, int32_t batch, const vx_f0_opts* o, float* f0,
+          int32_t* lag, float* ap /* may be NULL */, int64_t frame_stride, vx_f0_info* info);
+
 /* ---- step-level entries (kernel-level parity tests; same kernels as vx_infer) ---------------------------- */
 /* first ar_decoder.infer call (models/vallex.py:528-562): embeds, runs the prefix-LM prefill, fills the KV arena,
  * leaves the logits of the last row available.  batch <= 32. */

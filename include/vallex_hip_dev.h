@@ -421,6 +421,18 @@ int vx_dev_limit_gain(vx_ctx* ctx, const float* wav, int32_t len, float pre_gain
 #define VX_DEV_LIMIT_WINDOW_MIN 8192
 int vx_dev_limit_window(vx_ctx* ctx, int32_t samples);
 
+/* The difference and its normalisation of ONE row as f0_frames_kernel (csrc/f0.hip, the kernel behind vx_f0) computes them: d and dp
+ * [M][lag_max + 1] doubles, M = ceil(len / hop), d[k][t] = d(t) and dp[k][t] = d'(t) of frame k as include/vallex_hip.h defines
+ * them.  The row goes through the same planner and windows as vx_f0 (fewer frames per launch: the tables take their room).
+ * VX_EINVAL, nothing written: a NULL pointer, len < 0, options out of range. */
+int vx_dev_f0_table(vx_ctx* ctx, const float* wav, int32_t len, const vx_f0_opts* o, double* d, double* dp);
+/* Samples one launch of vx_f0 holds, for later calls on this context: VX_DEV_F0_WINDOW_MIN .. VX_F0_WINDOW, or 0 for the default
+ * (VX_F0_WINDOW).  A small window sends short rows through several parts and launches -- what the window tests need; the device
+ * buffers keep their size.  One frame reaches window + lag_max samples: the minimum holds that at the largest options (window 2048,
+ * lag_max 1024), so no call is refused for its window.  VX_EINVAL, nothing changed, for any other value. */
+#define VX_DEV_F0_WINDOW_MIN 3072
+int vx_dev_f0_window(vx_ctx* ctx, int32_t samples);
+
 #ifdef __cplusplus
 }
 #endif

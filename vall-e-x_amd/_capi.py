@@ -114,6 +114,18 @@ class vx_limit_info(C.Structure):
     _fields_ = [("peak", C.c_float), ("min_gain", C.c_float), ("ceiling", C.c_float), ("reduced", C.c_int32), ("nonfinite", C.c_int32)]
 
 
+class vx_f0_opts(C.Structure):
+    """options of vx_f0 (the pitch tracker: rate, hop, window and lag range of the YIN frames, the voicing threshold)"""
+    _fields_ = [("struct_size", C.c_uint32), ("sample_rate", C.c_int32), ("hop", C.c_int32), ("window", C.c_int32), ("lag_min", C.c_int32),
+                ("lag_max", C.c_int32), ("threshold", C.c_float)]
+
+
+class vx_f0_info(C.Structure):
+    """what vx_f0 measured of one row"""
+    _fields_ = [("frames", C.c_int32), ("voiced_frames", C.c_int32), ("nonfinite", C.c_int32), ("f0_median", C.c_float),
+                ("f0_min", C.c_float), ("f0_max", C.c_float)]
+
+
 # every symbol include/vallex_hip.h declares (tests/test_abi.py checks the library exports exactly these)
 ABI_VERSION = 6       # VX_ABI_VERSION of include/vallex_hip.h this binding was written against
 
@@ -131,6 +143,10 @@ DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kerne
                "vx_dev_seam_op", "vx_dev_resample_taps", "vx_dev_resample_window", "vx_dev_finish_frames", "vx_dev_finish_window",
                "vx_dev_stretch_window", "vx_dev_stretch_costs", "vx_dev_loudness_steps", "vx_dev_loudness_window",
                "vx_dev_limit_gain", "vx_dev_limit_window"]
+# the pitch tracker's entries, one of vallex_hip.h and two of vallex_hip_dev.h, in a list of their own: the header scan of
+# tests/test_abi.py matches names of letters and underscores, and these carry a digit (tests/test_f0_refs.py checks them)
+F0_SYMBOLS = ["vx_f0"]
+F0_DEV_SYMBOLS = ["vx_dev_f0_table", "vx_dev_f0_window"]
 # sentinels the correctness entries pre-fill their outputs with (include/vallex_hip_dev.h)
 DEV_SENTINEL_I = -123456789
 DEV_SENTINEL_F = np.float32(-1.0e30)
@@ -163,6 +179,7 @@ FINISH_WINDOW, DEV_FINISH_WINDOW_MIN = 1 << 23, 512         # VX_FINISH_WINDOW /
 STRETCH_WINDOW, DEV_STRETCH_WINDOW_MIN = 1 << 23, 2048      # VX_STRETCH_WINDOW / VX_DEV_STRETCH_WINDOW_MIN: input samples per launch
 LOUDNESS_WINDOW, DEV_LOUDNESS_WINDOW_MIN = 1 << 23, 4096    # VX_LOUDNESS_WINDOW / VX_DEV_LOUDNESS_WINDOW_MIN: samples per launch
 LIMIT_WINDOW, DEV_LIMIT_WINDOW_MIN = 1 << 23, 8192          # VX_LIMIT_WINDOW / VX_DEV_LIMIT_WINDOW_MIN: samples per launch
+F0_WINDOW, DEV_F0_WINDOW_MIN = 1 << 23, 3072                # VX_F0_WINDOW / VX_DEV_F0_WINDOW_MIN: samples per launch
 PCM_F32, PCM_S16 = 0, 1                                      # VX_PCM_*
 LEVEL_NONE, LEVEL_PEAK, LEVEL_RMS = 0, 1, 2                  # VX_LEVEL_*
 DEV_SAMPLE_CFG = ("kernel", "splitk", "top_k", "force_eos_at", "active", "n_gen", "cur_pos", "ctx_len", "text_len", "gen_stride")
@@ -294,6 +311,10 @@ def load_library() -> C.CDLL:
                                       P(vx_limit_info)]
     lib.vx_dev_limit_gain.argtypes = [ctx, P(C.c_float), C.c_int32, C.c_float, C.c_float, P(vx_limit_opts), P(C.c_float), P(C.c_float)]
     lib.vx_dev_limit_window.argtypes = [ctx, C.c_int32]
+    lib.vx_f0.argtypes = [ctx, P(C.c_float), C.c_int64, P(C.c_int32), C.c_int32, P(vx_f0_opts), P(C.c_float), P(C.c_int32), P(C.c_float),
+                          C.c_int64, P(vx_f0_info)]
+    lib.vx_dev_f0_table.argtypes = [ctx, P(C.c_float), C.c_int32, P(vx_f0_opts), P(C.c_double), P(C.c_double)]
+    lib.vx_dev_f0_window.argtypes = [ctx, C.c_int32]
     lib.vx_dev_stretch_costs.argtypes = [ctx, P(C.c_float), C.c_int32, P(vx_stretch_opts), P(C.c_float), P(C.c_int32), P(C.c_double)]
     lib.vx_last_stats.argtypes = [ctx, P(C.c_int64), P(C.c_int64), P(C.c_double), P(C.c_double)]
     lib.vx_last_truncated.argtypes = [ctx, P(C.c_int32)]
@@ -301,7 +322,7 @@ def load_library() -> C.CDLL:
     lib.vx_fallback_state.argtypes = [ctx, P(C.c_int32), P(C.c_int32), P(C.c_int64)]
     lib.vx_fallback_reset.argtypes = [ctx]
     lib.vx_arith_mode.argtypes = [ctx, P(C.c_int32), P(C.c_int32)]
-    for name in SYMBOLS + DEV_SYMBOLS:
+    for name in SYMBOLS + DEV_SYMBOLS + F0_SYMBOLS + F0_DEV_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("vx_destroy", "vx_last_error", "vx_read_tap", "vx_abi_version"):
             fn.restype = C.c_int
@@ -813,8 +834,124 @@ class Engine:
         the default)"""
         self._chk(self.lib.vx_dev_limit_window(self.ctx, int(samples)))
 
-    def _stretched(self, rows, speed):
-        """the 24 kHz rows of a vocoder call at `speed` (None: as they are), before the resampler and the output stage"""
+    @staticmethod
+    def _f0_opts(sample_rate, hop, window, fmin, fmax, threshold) -> vx_f0_opts:
+        """hop None = 10 ms (sample_rate // 100), window None = 25 ms (sample_rate // 40); the lags are lag_min = floor(rate / fmax) ..
+        lag_max = ceil(rate / fmin)"""
+        rate = int(sample_rate)
+        if not (math.isfinite(fmin) and math.isfinite(fmax) and 0 < fmin < fmax):
+            raise ValueError(f"f0: fmin {fmin!r}, fmax {fmax!r} must be finite with 0 < fmin < fmax")
+        lag_min, lag_max = math.floor(rate / fmax), math.ceil(rate / fmin)
+        if not (-2 ** 31 <= lag_min < 2 ** 31 and -2 ** 31 <= lag_max < 2 ** 31 and -2 ** 31 <= rate < 2 ** 31):
+            raise ValueError(f"f0: sample_rate {sample_rate!r}, fmin {fmin!r}, fmax {fmax!r} do not fit vx_f0_opts")
+        return vx_f0_opts(C.sizeof(vx_f0_opts), rate, rate // 100 if hop is None else int(hop), rate // 40 if window is None else int(window),
+                          lag_min, lag_max, float(threshold))
+
+    def f0(self, wavs: Sequence[np.ndarray], sample_rate: int = 24000, hop: Optional[int] = None, window: Optional[int] = None,
+           fmin: float = 60.0, fmax: float = 500.0, threshold: float = 0.15):
+        """vx_f0, the pitch tracker: mono fp32 waveforms (L_i,) -> (f0, voiced, ap, info), a list per row each.  YIN on the device, one
+        frame per `hop` samples (ceil(L_i / hop) frames, frame k centred on k hop + hop / 2): f0 float32 = the candidate in Hz of
+        every frame, voiced bool = its normalised difference dipped under `threshold`, ap float32 = that difference at the chosen lag
+        (0 = periodic, 1 = noise), info = a dict with frames, voiced_frames, nonfinite and f0_median / f0_min / f0_max over the voiced
+        frames (include/vallex_hip.h: vx_f0_info).  The search covers fmin .. fmax; `window` samples are summed per lag (it should
+        hold two periods of fmin).  Non-finite samples count as 0."""
+        f, lag, ap, info = self.f0_lags(wavs, self._f0_opts(sample_rate, hop, window, fmin, fmax, threshold))
+        return f, [l > 0 for l in lag], ap, info
+
+    def f0_lags(self, wavs: Sequence[np.ndarray], o: vx_f0_opts):
+        """vx_f0 with the options as the C struct: (f0, lag, ap, info) per row; lag int32 = +t of a voiced, -t of an unvoiced frame"""
+        n = len(wavs)
+        if n == 0:
+            return [], [], [], []
+        buf, lens, stride = self._packed(wavs)
+        fstride = max(1, -(-stride // max(1, o.hop)))
+        f = np.zeros((n, fstride), np.float32)
+        lag = np.zeros((n, fstride), np.int32)
+        ap = np.zeros((n, fstride), np.float32)
+        info = (vx_f0_info * n)()
+        self._chk(self.lib.vx_f0(self.ctx, _ptr(buf, C.c_float), stride, _ptr(lens, C.c_int32), n, C.byref(o), _ptr(f, C.c_float),
+                                 _ptr(lag, C.c_int32), _ptr(ap, C.c_float), fstride, info))
+        ms = [-(-int(L) // o.hop) for L in lens]
+        infos = [{fl[0]: getattr(w, fl[0]) for fl in vx_f0_info._fields_} for w in info]
+        return [f[i, :m] for i, m in enumerate(ms)], [lag[i, :m] for i, m in enumerate(ms)], [ap[i, :m] for i, m in enumerate(ms)], infos
+
+    def dev_f0_table(self, wav: np.ndarray, o: vx_f0_opts):
+        """vx_dev_f0_table: the difference d and its normalisation d' of one row as the kernel computed them, (M, lag_max + 1) float64
+        each"""
+        w = np.ascontiguousarray(wav, np.float32).reshape(-1)
+        M = -(-len(w) // o.hop) if o.hop > 0 else 0
+        T1 = max(1, o.lag_max + 1)
+        d, dp = np.zeros((max(M, 1), T1), np.float64), np.zeros((max(M, 1), T1), np.float64)
+        buf = w if len(w) else np.zeros(1, np.float32)
+        self._chk(self.lib.vx_dev_f0_table(self.ctx, _ptr(buf, C.c_float), len(w), C.byref(o), _ptr(d, C.c_double), _ptr(dp, C.c_double)))
+        return d[:M], dp[:M]
+
+    def dev_f0_window(self, samples: int = 0):
+        """vx_dev_f0_window: samples one launch of `f0` holds from now on (DEV_F0_WINDOW_MIN .. F0_WINDOW; 0 restores the default)"""
+        self._chk(self.lib.vx_dev_f0_window(self.ctx, int(samples)))
+
+    @staticmethod
+    def pitch_ratio(pitch) -> Fraction:
+        """the pitch ratio p / q of a `pitch` argument: a float is semitones (-> Fraction(2 ** (st / 12)).limit_denominator(256): within
+        3 cents of the request), a Fraction or a (num, den) pair is the ratio itself, both terms at most 512.  1/2 .. 2 (an octave
+        either way), else ValueError."""
+        if isinstance(pitch, (tuple, list)):
+            if len(pitch) != 2 or int(pitch[1]) == 0:
+                raise ValueError(f"pitch {pitch!r}: a (num, den) pair with den != 0")
+            r = Fraction(int(pitch[0]), int(pitch[1]))
+        elif isinstance(pitch, Fraction):
+            r = pitch
+        else:
+            st = float(pitch)
+            if not math.isfinite(st) or abs(st) > 12.0:
+                raise ValueError(f"pitch {pitch!r}: semitones outside -12 .. 12")
+            r = Fraction(2.0 ** (st / 12.0)).limit_denominator(256)
+        if r.numerator < 1 or r.numerator > 512 or r.denominator > 512:
+            raise ValueError(f"pitch {pitch!r}: the terms of {r} are outside 1 .. 512")
+        if 2 * r.numerator < r.denominator or r.numerator > 2 * r.denominator:
+            raise ValueError(f"pitch {pitch!r}: the ratio {r} is outside 1/2 .. 2")
+        return r
+
+    @classmethod
+    def _shift_plan(cls, pitch, speed):
+        """(p / q, the combined speed of the stretch, the speed itself) of a `shift` call; every ValueError of it, before any launch"""
+        r = cls.pitch_ratio(pitch)
+        if speed is None:
+            sp = Fraction(1)
+        elif isinstance(speed, (tuple, list)):
+            if int(speed[1]) == 0:
+                raise ValueError(f"speed {speed!r}: a (num, den) pair with den != 0")
+            sp = Fraction(int(speed[0]), int(speed[1]))
+        else:
+            sp = speed if isinstance(speed, Fraction) else Fraction(speed).limit_denominator(1000)
+        comb = sp / r
+        if sp <= 0 or 2 * sp < 1 or sp > 2:
+            raise ValueError(f"speed {speed!r} outside 1/2 .. 2")
+        if 2 * comb < 1 or comb > 2:
+            raise ValueError(f"speed {sp} with pitch ratio {r}: the stretch would run at {comb}, outside 1/2 .. 2")
+        if comb.numerator > 32767 or comb.denominator > 32767:
+            raise ValueError(f"speed {sp} with pitch ratio {r}: {comb} does not fit vx_stretch_opts (terms above 32767)")
+        return r, comb, sp
+
+    def shift(self, wavs: Sequence[np.ndarray], pitch, speed=None):
+        """the pitch control: mono fp32 waveforms (L_i,) at 24 kHz -> a list of float32 arrays of ceil(L_i / speed) samples (exactly L_i
+        with speed=None) whose pitch is p / q = pitch_ratio(pitch) times the input's.  One `stretch` at (speed or 1) q / p (the
+        duration grows by p / q at the same pitch), then one `resample` with orig_rate = p, new_rate = q (duration and pitch go
+        back by q / p and up by p / q), cut to the length.  Ratio 1 with speed=None returns the input bits.  The formants move with
+        the pitch: meant for a few semitones.  ValueError before any launch: a ratio, a speed or their quotient outside 1/2 .. 2."""
+        r, comb, sp = self._shift_plan(pitch, speed)
+        ws = [np.ascontiguousarray(w, np.float32).reshape(-1) for w in wavs]
+        if not ws:
+            return []
+        want = [-(-len(w) * sp.denominator // sp.numerator) for w in ws]
+        rows = self.stretch(ws, comb)
+        rows = self.resample(rows, r.numerator, r.denominator)
+        return [y[:m] for y, m in zip(rows, want)]
+
+    def _stretched(self, rows, speed, pitch=None):
+        """the 24 kHz rows of a vocoder call at `speed` and `pitch` (None: as they are), before the resampler and the output stage"""
+        if pitch is not None:
+            return self.shift(rows, pitch, speed)
         return rows if speed is None else self.stretch(rows, speed)
 
     last_finish_info = None          # the info dicts of the last call that went through a `finish=` argument
@@ -840,9 +977,12 @@ class Engine:
                                                  finish.max_gain_db, finish.fade_in, finish.fade_out, finish.pcm16)
         return out
 
-    def vocos_decode(self, codes: Sequence[np.ndarray], bandwidth_id: int = 2, sample_rate: int = 24000, finish=None, speed=None):
-        """speed (None: nothing runs): the decoded rows go through `stretch` at 24 kHz first; sample_rate other than 24000: then through
-        `resample` (24000 -> sample_rate), one more launch; finish (a utils.generation.Finish): then through `finish` at that rate"""
+    def vocos_decode(self, codes: Sequence[np.ndarray], bandwidth_id: int = 2, sample_rate: int = 24000, finish=None, speed=None, pitch=None):
+        """speed (None: nothing runs): the decoded rows go through `stretch` at 24 kHz first; pitch (None: nothing runs): through `shift`
+        instead, which takes the speed along; sample_rate other than 24000: then through `resample` (24000 -> sample_rate), one more
+        launch; finish (a utils.generation.Finish): then through `finish` at that rate"""
+        if pitch is not None:
+            self._shift_plan(pitch, speed)                                # a ValueError comes before the vocoder runs
         n = len(codes)
         lens = np.array([c.shape[0] for c in codes], np.int32)
         stride = max(1, int(lens.max()))
@@ -854,11 +994,13 @@ class Engine:
         audio = np.empty((n, stride * 320), np.float32)
         self._chk(self.lib.vx_vocos_decode(self.ctx, _ptr(buf, C.c_int64), stride, _ptr(lens, C.c_int32), n,
                                            int(bandwidth_id), _ptr(audio, C.c_float), stride * 320))
-        rows = self._stretched([audio[i, : lens[i] * 320] for i in range(n)], speed)
+        rows = self._stretched([audio[i, : lens[i] * 320] for i in range(n)], speed, pitch)
         return self._finished(rows if int(sample_rate) == 24000 else self.resample(rows, 24000, int(sample_rate)), finish, sample_rate)
 
-    def encodec_decode(self, codes: Sequence[np.ndarray], sample_rate: int = 24000, finish=None, speed=None):
-        """speed, sample_rate, finish: as vocos_decode (stretch at 24 kHz, then resample, then finish)"""
+    def encodec_decode(self, codes: Sequence[np.ndarray], sample_rate: int = 24000, finish=None, speed=None, pitch=None):
+        """speed, pitch, sample_rate, finish: as vocos_decode (stretch or shift at 24 kHz, then resample, then finish)"""
+        if pitch is not None:
+            self._shift_plan(pitch, speed)                                # a ValueError comes before the vocoder runs
         n = len(codes)
         lens = np.array([c.shape[0] for c in codes], np.int32)
         stride = max(1, int(lens.max()))
@@ -868,8 +1010,8 @@ class Engine:
         audio = np.zeros((n, stride * 320), np.float32)
         self._chk(self.lib.vx_encodec_decode(self.ctx, _ptr(buf, C.c_int64), stride, _ptr(lens, C.c_int32), n,
                                              _ptr(audio, C.c_float), stride * 320))
-        if speed is not None:
-            rows = self.stretch([audio[i, : lens[i] * 320] for i in range(n)], speed)
+        if speed is not None or pitch is not None:
+            rows = self._stretched([audio[i, : lens[i] * 320] for i in range(n)], speed, pitch)
             return self._finished(rows if int(sample_rate) == 24000 else self.resample(rows, 24000, int(sample_rate)), finish, sample_rate)
         if int(sample_rate) != 24000:
             return self._finished(self.resample([audio[i, : lens[i] * 320] for i in range(n)], 24000, int(sample_rate)), finish, sample_rate)

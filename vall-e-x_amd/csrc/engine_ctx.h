@@ -191,6 +191,8 @@ struct vx_ctx {
   int lm_taps_n = 0;
   float* lm_rec = nullptr;         // [LM_REC_CAP][4] tile records of one launch: {peak, min gain, reduced, non-finite}
   long lm_window = 0;              // samples per launch set by vx_dev_limit_window (0: the default, VX_LIMIT_WINDOW)
+  // pitch tracker (vx_f0, f0.hip): runs in the resampler's launch buffers (rs_buffers) alone; needs no weights
+  long f0_window = 0;              // samples per launch set by vx_dev_f0_window (0: the default, VX_F0_WINDOW)
 
   // graph
   hipGraphExec_t graph_exec = nullptr, graph_exec_n = nullptr;   // one decode step / GRAPH_STEPS steps per launch

@@ -69,3 +69,27 @@ def stretched_sample(positions, hop: int, s, out_len=None):
         n = p.size * hop if out_len is None else int(out_len)
         out = np.clip(k * hop + (sa - p[k]), 0, max(n - 1, 0))
     return int(out) if np.ndim(s) == 0 else out
+
+
+def token_pitch(segments, f0, voiced, hop: int, frame: int = 320) -> np.ndarray:
+    """The pitch of every text token: `segments` (n, 2) are the first and the last codec frame of each token as `monotonic_segments`
+    returns them (a codec frame is `frame` samples: 320 at 24 kHz), f0 / voiced the per-frame output of `Engine.f0` on the SAME
+    waveform at hop `hop` (F0 frame k is centred on sample k hop + hop // 2).  Token j covers the samples
+    [first_j frame, (last_j + 1) frame); its pitch is the lower median (element (m - 1) // 2 of the m sorted values, as
+    vx_f0_info.f0_median) of f0 over the voiced F0 frames whose centre lies in that span.  Returns (n,) float64, NaN for a token
+    without a voiced frame.  Host numpy."""
+    seg = np.asarray(segments, np.int64).reshape(-1, 2)
+    f = np.asarray(f0, np.float64).reshape(-1)
+    v = np.asarray(voiced, bool).reshape(-1)
+    hop, frame = int(hop), int(frame)
+    if hop <= 0 or frame <= 0:
+        raise ValueError(f"hop {hop} and frame {frame} must be positive")
+    if f.shape != v.shape:
+        raise ValueError(f"f0 has {f.size} frames, voiced {v.size}")
+    centre = np.arange(f.size, dtype=np.int64) * hop + hop // 2
+    out = np.full(len(seg), np.nan, np.float64)
+    for j, (a, b) in enumerate(seg):
+        vals = np.sort(f[v & (centre >= a * frame) & (centre < (b + 1) * frame)])
+        if vals.size:
+            out[j] = vals[(vals.size - 1) // 2]
+    return out

@@ -234,11 +234,20 @@ def _finished(wavs, finish, sample_rate):
     return model.engine._finished(wavs, finish, SAMPLE_RATE if sample_rate is None else int(sample_rate))
 
 
-def _at_speed(wavs, speed):
-    """the 24 kHz waveforms of a vocoder call at `speed` (None: as they are): one vx_stretch call for the list, before the resampler"""
+def _at_speed(wavs, speed, pitch=None):
+    """the 24 kHz waveforms of a vocoder call at `speed` (None: as they are): one vx_stretch call for the list, before the resampler;
+    with `pitch` (None: as they are): Engine.shift, the stretch at the combined speed and the p -> q resample, for the list"""
+    if pitch is not None:
+        return model.engine.shift(wavs, pitch, speed)
     if speed is None:
         return wavs
     return model.engine.stretch(wavs, speed)
+
+
+def _check_pitch(pitch, speed):
+    """the ValueError of a `pitch` / `speed` pair that Engine.shift would refuse, before anything is synthesised"""
+    if pitch is not None:
+        model.engine._shift_plan(pitch, speed)
 
 
 def _to_rate(wavs, sample_rate):
@@ -268,14 +277,17 @@ def _infer_one(text, audio_prompts, text_prompts, lang_pr, language, accent, **k
     return out, phone_tokens
 
 
-def generate_audio(text, prompt=None, language="auto", accent="no-accent", sample_rate=None, finish=None, speed=None, **kw):
+def generate_audio(text, prompt=None, language="auto", accent="no-accent", sample_rate=None, finish=None, speed=None, pitch=None, **kw):
     """utils/generation.py:92-152.  sample_rate (no reference counterpart; None = 24 kHz, the reference's): the waveform is resampled
     on the device (Engine.resample, vx_resample) to that rate.  finish (a `Finish`; None = the raw fp32 of the reference): the output
     stage behind it -- trim, level, fades, int16 with pcm16=True.  speed (a float, a Fraction or a (num, den) pair in 1/2 .. 2; None =
     the pace the model produced): the speaking rate, a pitch-preserving time-stretch on the device (Engine.stretch, vx_stretch) at
-    24 kHz, before the resampler."""
+    24 kHz, before the resampler.  pitch (a float in semitones, -12 .. 12, or the ratio as a Fraction or a (num, den) pair in
+    1/2 .. 2; None = the pitch the model produced): a pitch shift that keeps the duration (Engine.shift: the stretch at speed / ratio,
+    then a resample by the ratio), in place of the stretch.  It moves the formants with the pitch: meant for a few semitones."""
     if model is None or vocos is None:
         raise RuntimeError("call preload_models() first")
+    _check_pitch(pitch, speed)
     if isinstance(text, str):
         text = text.replace("\n", "").strip(" ")
     language = _detect(text, language)
@@ -293,15 +305,15 @@ def generate_audio(text, prompt=None, language="auto", accent="no-accent", sampl
     samples = vocos.decode(features, bandwidth_id=np.array([2]))
     s = samples.squeeze()
     s = s.cpu().numpy() if torch is not None and isinstance(s, torch.Tensor) else np.asarray(s)
-    if speed is not None:
-        return _finished(_to_rate(_at_speed([s.reshape(-1)], speed), sample_rate), finish, sample_rate)[0]
+    if speed is not None or pitch is not None:
+        return _finished(_to_rate(_at_speed([s.reshape(-1)], speed, pitch), sample_rate), finish, sample_rate)[0]
     if finish is not None:
         return _finished(_to_rate([s.reshape(-1)], sample_rate), finish, sample_rate)[0]
     return s if sample_rate is None else _to_rate([s.reshape(-1)], sample_rate)[0]
 
 
 def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent", text_languages=None, sample_rate=None, finish=None,
-                         speed=None, **kw):
+                         speed=None, pitch=None, **kw):
     """Batch form of `generate_audio` (no reference equivalent: the reference synthesises one utterance per call,
     utils/generation.py:92-152): utterance i of the batch equals `generate_audio(texts[i], prompts[i], language[i], accent)`.
     `texts`: strings (need the tokenizer hook) or phoneme-id arrays; `prompts`: one preset name / path / None per utterance (or
@@ -311,9 +323,11 @@ def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent
     = N: N beams per utterance), injected `uniforms` are (steps, len(texts) x max(1, N)) with column i*N + j for beam j of
     utterance i.  `sample_rate` (None = 24 kHz): the waveforms are resampled on the device in one more launch.  `finish` (a
     `Finish`): the output stage behind it, one more call for the list.  `speed` (None = as produced): the speaking rate, one vx_stretch
-    call for the list before both.  Returns a list of float32 waveforms (int16 with pcm16=True)."""
+    call for the list before both.  `pitch` (None = as produced): the pitch shift of `generate_audio`, Engine.shift for the list in
+    place of the stretch.  Returns a list of float32 waveforms (int16 with pcm16=True)."""
     if model is None or vocos is None:
         raise RuntimeError("call preload_models() first")
+    _check_pitch(pitch, speed)
     n = len(texts)
     prompts = list(prompts) if isinstance(prompts, (list, tuple)) else [prompts] * n
     langs_in = list(language) if isinstance(language, (list, tuple)) else [language] * n
@@ -322,7 +336,7 @@ def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent
             for text, prompt, lang_in, tl in zip(texts, prompts, langs_in, text_languages)]
     codes = model.inference_batch(rows, top_k=-100, temperature=1, **kw)
     return model.engine.vocos_decode(codes, 2, sample_rate=SAMPLE_RATE if sample_rate is None else int(sample_rate), finish=finish,
-                                     speed=speed)
+                                     speed=speed, pitch=pitch)
 
 
 def _utterance_row(text, prompt, lang_in, accent, tl=None) -> dict:
@@ -360,9 +374,10 @@ class AudioServer:
     (sync_every, force_eos_at, max_steps).  `sample_rate` (None = 24 kHz): ONE output rate for the server, applied to every delivered
     waveform behind Vocos (vx_resample is allowed while the session is open).  `finish` (a `Finish`): ONE output stage for the server,
     applied behind that (vx_finish is allowed as well).  `speed` (None = as produced): ONE speaking rate for the server, applied to
-    every delivered waveform between Vocos and the resampler (vx_stretch is allowed as well)."""
+    every delivered waveform between Vocos and the resampler (vx_stretch is allowed as well).  `pitch` (None = as produced): ONE pitch
+    shift for the server (generate_audio's `pitch`), applied there in place of the stretch."""
 
-    def __init__(self, sample_rate=None, finish=None, speed=None, **serve_kw):
+    def __init__(self, sample_rate=None, finish=None, speed=None, pitch=None, **serve_kw):
         if model is None or vocos is None:
             raise RuntimeError("call preload_models() first")
         rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
@@ -371,8 +386,11 @@ class AudioServer:
         self.sample_rate = rate
         self.finish = finish
         self.speed = speed
+        _check_pitch(pitch, speed)
+        self.pitch = pitch
         self._server = model.serve(top_k=-100, temperature=1.0,
-                                   post=lambda codes: model.engine.vocos_decode(codes, 2, sample_rate=rate, finish=finish, speed=speed),
+                                   post=lambda codes: model.engine.vocos_decode(codes, 2, sample_rate=rate, finish=finish, speed=speed,
+                                                                                pitch=pitch),
                                    **serve_kw)
 
     def submit(self, text, prompt=None, language="auto", accent="no-accent", best_of=1, seed=None, uniforms=None,
@@ -397,11 +415,12 @@ class AudioServer:
 
 
 def generate_audio_from_long_text(text, prompt=None, language="auto", accent="no-accent", mode="sliding-window", sample_rate=None,
-                                  finish=None, speed=None, **kw):
-    """utils/generation.py:155-276.  `text` may also be a list of sentences / id arrays (pre-split).  sample_rate, finish, speed: as
-    generate_audio (the stretch and the output stage see the concatenated waveform once)."""
+                                  finish=None, speed=None, pitch=None, **kw):
+    """utils/generation.py:155-276.  `text` may also be a list of sentences / id arrays (pre-split).  sample_rate, finish, speed,
+    pitch: as generate_audio (the stretch or the shift and the output stage see the concatenated waveform once)."""
     if model is None or vocos is None:
         raise RuntimeError("call preload_models() first")
+    _check_pitch(pitch, speed)
     if prompt is None or prompt == "":
         prompt = None
         mode = "sliding-window"                                        # :162-163: overrides ANY mode, also an unknown one
@@ -448,8 +467,8 @@ def generate_audio_from_long_text(text, prompt=None, language="auto", accent="no
     samples = vocos.decode(features, bandwidth_id=np.array([2]))
     s = samples.squeeze()
     s = s.cpu().numpy() if torch is not None and isinstance(s, torch.Tensor) else np.asarray(s)
-    if speed is not None:
-        return _finished(_to_rate(_at_speed([s.reshape(-1)], speed), sample_rate), finish, sample_rate)[0]
+    if speed is not None or pitch is not None:
+        return _finished(_to_rate(_at_speed([s.reshape(-1)], speed, pitch), sample_rate), finish, sample_rate)[0]
     if finish is not None:
         return _finished(_to_rate([s.reshape(-1)], sample_rate), finish, sample_rate)[0]
     return s if sample_rate is None else _to_rate([s.reshape(-1)], sample_rate)[0]
