@@ -590,6 +590,70 @@ typedef struct vx_f0_info {
 int vx_f0(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t* lens, int32_t batch, const vx_f0_opts* o, float* f0,
           int32_t* lag, float* ap /* may be NULL */, int64_t frame_stride, vx_f0_info* info);
 
+/* The formant-preserving pitch shift: time-domain PSOLA of mono fp32 rows on the device, from the lags vx_f0 gives.  No reference
+ * counterpart.  Pitch marks are walked along the waveform one period apart, and two-period grains around them are laid down again
+ * at a new spacing: every grain keeps its shape, and with it the spectral envelope, while the spacing sets the pitch.  Inputs are a
+ * row x of length L, the signed lags lag[0 .. Mf) of that row at hop Hf (Mf = ceil(L / Hf); lag > 0 is voiced), the options
+ * period_min, period_max, unvoiced_period (U) and the pitch ratio ratio_q16 (Q16), and optionally a per-frame array ratio[b][k]
+ * (Q16) that replaces ratio_q16 frame by frame.  All floating-point arithmetic is double and every named operation is rounded on
+ * its own, so that a plain numpy restatement reproduces marks, grain table and output word for word:
+ *
+ * - Samples.  y[i] = isfinite(x[i]) ? x[i] : 0, and 0 outside [0, L).  `nonfinite` counts the non-finite samples of the row.
+ * - Period at a position.  For a sample index a, k = min(a / Hf, Mf - 1) by integer division.  The position is VOICED iff
+ *   period_min <= lag[k] <= period_max; P = lag[k] where voiced, else U.  A lag outside the bounds is unvoiced, not an error.
+ * - Analysis marks, a serial walk per row.  a_0 = 0.  Given a_i with its P and voicing: unvoiced, a_{i+1} = a_i + U.  Voiced:
+ *   D = P / 8 by integer division and the template is t[j] = y[a_i + j], j in [0, P).  For every d in [-D, D] ONE LANE computes two
+ *   double sums from 0.0 in order j = 0 .. P-1: c_d = sum (double)y[a_i + P + d + j] * (double)t[j] and
+ *   e_d = sum (double)y[a_i + P + d + j]^2 (products of two fp32 values are exact in double: contraction-proof, the rule of
+ *   vx_stretch).  cost_d = e_d - 2.0 * c_d; d* has the smallest cost, ties go to the smallest |d|, then to the negative d;
+ *   a_{i+1} = a_i + P + d*.  N is the number of marks below L; the first mark at or above L is kept as a_N, it closes the last
+ *   period.  An all-zero row steps by exactly P.
+ * - Synthesis marks, serial integer arithmetic.  Time is an int64 in units of 2^-16 sample: S_0 = 0, s_j = (S_j + 32768) >> 16.
+ *   While s_j < L: i(j) is the index in [0, N-1] of the analysis mark nearest to s_j, ties to the lower index; g = a_{i+1} - a_i at
+ *   i = i(j); r is the ratio of frame min(a_i / Hf, Mf - 1) if mark i is voiced, else 65536; S_{j+1} = S_j + floor((g << 32) / r).
+ *   J is the number of grains.  The duration is kept: the output has L samples; unvoiced stretches are re-laid at their own spacing.
+ *   Grains stop at s_j < L: at a ratio below 1 the last grain may end up to half an output period before L, and those samples
+ *   are gaps.
+ * - Grain j.  Centre s_j, source centre a = a_{i(j)}, right width Wr = a_{i+1} - a_i, left width Wl = a_i - a_{i-1} (for i = 0,
+ *   a_1 - a_0).  For rr in [-Wl, Wr): u = ((double)(rr + Wl) + 0.5) / (double)Wl if rr < 0, else
+ *   u = ((double)(Wr - rr) - 0.5) / (double)Wr; w = (float)((u * u) * (3.0 - 2.0 * u)), every operation rounded on its own, no fma:
+ *   the smoothstep of vx_finish and vx_stretch.  Every weight is positive.
+ * - Output.  For every n in [0, L) ONE LANE walks the grains that cover n in order of j: num += (double)y[a + (n - s_j)] * (double)w
+ *   (an exact product and one addition), den += (double)w; out[n] = den > 0 ? (float)(num / den) : 0.  `gaps` counts the samples
+ *   with den == 0.  With every ratio at 65536 the output equals y bit for bit (a -0.0 comes out as +0.0: num starts from +0.0).
+ * - Info.  marks = N, voiced_marks = the voiced ones of a_0 .. a_{N-1}, grains = J, gaps, nonfinite.
+ * - Exactness.  No floating-point atomics.  Two calls give the same bits.  A row's bits depend neither on the batch nor on the launch
+ *   windows.
+ * - State.  As vx_f0 / vx_stretch: it needs no weights, works while a serving session is open, touches no decode state, and runs in
+ *   the resampler's launch buffers, whose upper half holds the lags, the marks and the grain table; transfers go through the pinned
+ *   ring.
+ * - Windows.  One launch holds VX_PSOLA_WINDOW (2^23) samples.  Rows are packed into launches in order.  A row is not cut across
+ *   launches: a longer row is refused (349 s at 24 kHz).
+ * - Refusals.  These return VX_EINVAL, launch nothing (the mark walk aside, where marks_stride is judged) and write nothing, and the
+ *   message names the field: hop outside 16 .. 4096; period_min / period_max outside 16 <= period_min <= period_max <= 1024;
+ *   unvoiced_period outside [period_min, period_max]; ratio_q16, or any element of ratio within a row's Mf, outside 43691 .. 131072
+ *   (2/3 .. 2: below 2/3 the grains no longer overlap); a wrong struct_size; NULL wav / lens / lag / o / out / info; batch <= 0; a
+ *   length negative, above wav_stride or above VX_PSOLA_WINDOW; lag_stride below a row's Mf; out_stride below L; marks_stride below
+ *   N + 1 when marks is given (the library knows N after the walk and before anything is written to the caller).
+ *
+ *   wav [batch][wav_stride] fp32, lens [batch]; lag and ratio (when given) [batch][lag_stride] int32; out [batch][out_stride] fp32,
+ *   L samples per row; marks (when given) [batch][marks_stride] int32 = a_0 .. a_N; info [batch].  Elements behind a row's end are
+ *   not written. */
+#define VX_PSOLA_WINDOW (1 << 23)
+typedef struct vx_psola_opts {
+  uint32_t struct_size;     /* = sizeof(vx_psola_opts) */
+  int32_t hop;              /* Hf, 16 .. 4096: the hop the lags were measured at */
+  int32_t period_min, period_max; /* 16 <= period_min <= period_max <= 1024 */
+  int32_t unvoiced_period;  /* U, period_min .. period_max */
+  int32_t ratio_q16;        /* 43691 .. 131072: the pitch ratio, 65536 = 1 */
+} vx_psola_opts;
+typedef struct vx_psola_info {
+  int32_t marks, voiced_marks, grains, gaps, nonfinite;
+} vx_psola_info;
+int vx_psola(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t* lens, int32_t batch, const int32_t* lag, int64_t lag_stride,
+             const int32_t* ratio /* may be NULL */, const vx_psola_opts* o, float* out, int64_t out_stride,
+             int32_t* marks /* may be NULL */, int64_t marks_stride, vx_psola_info* info);
+
 /* ---- step-level entries (kernel-level parity tests; same kernels as vx_infer) ---------------------------- */
 /* first ar_decoder.infer call (models/vallex.py:528-562): embeds, runs the prefix-LM prefill, fills the KV arena,
  * leaves the logits of the last row available.  batch <= 32. */

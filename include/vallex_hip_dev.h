@@ -433,6 +433,22 @@ int vx_dev_f0_table(vx_ctx* ctx, const float* wav, int32_t len, const vx_f0_opts
 #define VX_DEV_F0_WINDOW_MIN 3072
 int vx_dev_f0_window(vx_ctx* ctx, int32_t samples);
 
+/* The mark costs and the grain table of ONE row as the kernels behind vx_psola (csrc/psola.hip) saw them: cost [N + 1] doubles, the
+ * winning cost of every voiced mark below len as psola_marks_kernel wrote it and 0 for the unvoiced marks and the closing one;
+ * grains [J][4] int32 = (s_j, a, Wl, Wr) of every grain, read back from the table psola_synth_kernel walked.  *n_marks = N and
+ * *n_grains = J are always written on success.  The row goes through the same planner and window as vx_psola.  VX_EINVAL, nothing
+ * written: a NULL pointer, len < 0, options or ratios out of range, cost_cap below N + 1 or grain_cap below J
+ * (len / 14 + 2 and len / 7 + 2 always suffice). */
+int vx_dev_psola_table(vx_ctx* ctx, const float* wav, int32_t len, const int32_t* lag, const int32_t* ratio /* may be NULL */,
+                       const vx_psola_opts* o, double* cost, int32_t cost_cap, int32_t* grains, int32_t grain_cap, int32_t* n_marks,
+                       int32_t* n_grains);
+/* Samples one launch of vx_psola holds, for later calls on this context: VX_DEV_PSOLA_WINDOW_MIN .. VX_PSOLA_WINDOW, or 0 for the
+ * default (VX_PSOLA_WINDOW).  A small window sends a ragged batch of short rows through several launches -- what the window tests
+ * need; the device buffers keep their size.  A row is never cut, so a row above the window is refused (VX_EINVAL naming lens).
+ * VX_EINVAL, nothing changed, for any other value. */
+#define VX_DEV_PSOLA_WINDOW_MIN 1024
+int vx_dev_psola_window(vx_ctx* ctx, int32_t samples);
+
 #ifdef __cplusplus
 }
 #endif

@@ -126,6 +126,17 @@ class vx_f0_info(C.Structure):
                 ("f0_min", C.c_float), ("f0_max", C.c_float)]
 
 
+class vx_psola_opts(C.Structure):
+    """options of vx_psola (the formant-preserving pitch shift: the hop of the lags, the period bounds, the unvoiced period, the ratio)"""
+    _fields_ = [("struct_size", C.c_uint32), ("hop", C.c_int32), ("period_min", C.c_int32), ("period_max", C.c_int32),
+                ("unvoiced_period", C.c_int32), ("ratio_q16", C.c_int32)]
+
+
+class vx_psola_info(C.Structure):
+    """what vx_psola did to one row"""
+    _fields_ = [("marks", C.c_int32), ("voiced_marks", C.c_int32), ("grains", C.c_int32), ("gaps", C.c_int32), ("nonfinite", C.c_int32)]
+
+
 # every symbol include/vallex_hip.h declares (tests/test_abi.py checks the library exports exactly these)
 ABI_VERSION = 6       # VX_ABI_VERSION of include/vallex_hip.h this binding was written against
 
@@ -135,14 +146,14 @@ SYMBOLS = ["vx_abi_version", "vx_create", "vx_destroy", "vx_last_error", "vx_syn
            "vx_fallback_reset", "vx_arith_mode", "vx_infer_continuous", "vx_serve_open", "vx_serve_submit", "vx_serve_run",
            "vx_serve_close", "vx_serve_submit_ex", "vx_serve_cancel", "vx_serve_submit_filtered", "vx_score", "vx_align", "vx_resample",
            "vx_finish", "vx_stretch", "vx_loudness_coeffs", "vx_loudness", "vx_finish_loud", "vx_limit_taps", "vx_limit",
-           "vx_finish_limited"]
+           "vx_finish_limited", "vx_psola"]
 # ... and include/vallex_hip_dev.h: measurement / kernel development, never called by the mirrors of the reference API
 DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kernel", "vx_bench_gemm", "vx_bench_attn",
                "vx_bench_gemm_clock", "vx_bench_gemm_epilogue", "vx_dev_sample", "vx_dev_attn", "vx_dev_sample_filtered",
                "vx_dev_dec_attn", "vx_dev_dec_op", "vx_dev_gemm", "vx_dev_layernorm", "vx_dev_score_rows", "vx_dev_align_rows", "vx_dev_wave_op",
                "vx_dev_seam_op", "vx_dev_resample_taps", "vx_dev_resample_window", "vx_dev_finish_frames", "vx_dev_finish_window",
                "vx_dev_stretch_window", "vx_dev_stretch_costs", "vx_dev_loudness_steps", "vx_dev_loudness_window",
-               "vx_dev_limit_gain", "vx_dev_limit_window"]
+               "vx_dev_limit_gain", "vx_dev_limit_window", "vx_dev_psola_table", "vx_dev_psola_window"]
 # the pitch tracker's entries, one of vallex_hip.h and two of vallex_hip_dev.h, in a list of their own: the header scan of
 # tests/test_abi.py matches names of letters and underscores, and these carry a digit (tests/test_f0_refs.py checks them)
 F0_SYMBOLS = ["vx_f0"]
@@ -180,6 +191,8 @@ STRETCH_WINDOW, DEV_STRETCH_WINDOW_MIN = 1 << 23, 2048      # VX_STRETCH_WINDOW 
 LOUDNESS_WINDOW, DEV_LOUDNESS_WINDOW_MIN = 1 << 23, 4096    # VX_LOUDNESS_WINDOW / VX_DEV_LOUDNESS_WINDOW_MIN: samples per launch
 LIMIT_WINDOW, DEV_LIMIT_WINDOW_MIN = 1 << 23, 8192          # VX_LIMIT_WINDOW / VX_DEV_LIMIT_WINDOW_MIN: samples per launch
 F0_WINDOW, DEV_F0_WINDOW_MIN = 1 << 23, 3072                # VX_F0_WINDOW / VX_DEV_F0_WINDOW_MIN: samples per launch
+PSOLA_WINDOW, DEV_PSOLA_WINDOW_MIN = 1 << 23, 1024          # VX_PSOLA_WINDOW / VX_DEV_PSOLA_WINDOW_MIN: samples per launch
+PSOLA_RATIO_MIN, PSOLA_RATIO_MAX = 43691, 131072            # the Q16 ratios vx_psola takes: 2/3 .. 2
 PCM_F32, PCM_S16 = 0, 1                                      # VX_PCM_*
 LEVEL_NONE, LEVEL_PEAK, LEVEL_RMS = 0, 1, 2                  # VX_LEVEL_*
 DEV_SAMPLE_CFG = ("kernel", "splitk", "top_k", "force_eos_at", "active", "n_gen", "cur_pos", "ctx_len", "text_len", "gen_stride")
@@ -315,6 +328,11 @@ def load_library() -> C.CDLL:
                           C.c_int64, P(vx_f0_info)]
     lib.vx_dev_f0_table.argtypes = [ctx, P(C.c_float), C.c_int32, P(vx_f0_opts), P(C.c_double), P(C.c_double)]
     lib.vx_dev_f0_window.argtypes = [ctx, C.c_int32]
+    lib.vx_psola.argtypes = [ctx, P(C.c_float), C.c_int64, P(C.c_int32), C.c_int32, P(C.c_int32), C.c_int64, P(C.c_int32), P(vx_psola_opts),
+                             P(C.c_float), C.c_int64, P(C.c_int32), C.c_int64, P(vx_psola_info)]
+    lib.vx_dev_psola_table.argtypes = [ctx, P(C.c_float), C.c_int32, P(C.c_int32), P(C.c_int32), P(vx_psola_opts), P(C.c_double), C.c_int32,
+                                       P(C.c_int32), C.c_int32, P(C.c_int32), P(C.c_int32)]
+    lib.vx_dev_psola_window.argtypes = [ctx, C.c_int32]
     lib.vx_dev_stretch_costs.argtypes = [ctx, P(C.c_float), C.c_int32, P(vx_stretch_opts), P(C.c_float), P(C.c_int32), P(C.c_double)]
     lib.vx_last_stats.argtypes = [ctx, P(C.c_int64), P(C.c_int64), P(C.c_double), P(C.c_double)]
     lib.vx_last_truncated.argtypes = [ctx, P(C.c_int32)]
@@ -912,10 +930,124 @@ class Engine:
             raise ValueError(f"pitch {pitch!r}: the ratio {r} is outside 1/2 .. 2")
         return r
 
+    @staticmethod
+    def psola_q16(ratio) -> int:
+        """the Q16 word of a pitch ratio for `psola` (a float, a Fraction or a (num, den) pair): round(ratio 65536); outside
+        43691 .. 131072 (2/3 .. 2) a ValueError"""
+        if isinstance(ratio, (tuple, list)):
+            if len(ratio) != 2 or int(ratio[1]) == 0:
+                raise ValueError(f"ratio {ratio!r}: a (num, den) pair with den != 0")
+            ratio = Fraction(int(ratio[0]), int(ratio[1]))
+        if not isinstance(ratio, Fraction):
+            if not math.isfinite(float(ratio)):
+                raise ValueError(f"ratio {ratio!r} is not finite")
+            ratio = Fraction(float(ratio))
+        q = int(round(ratio * 65536))
+        if q < PSOLA_RATIO_MIN or q > PSOLA_RATIO_MAX:
+            raise ValueError(f"ratio {ratio!r}: {q} / 65536 is outside {PSOLA_RATIO_MIN} .. {PSOLA_RATIO_MAX} (2/3 .. 2)")
+        return q
+
     @classmethod
-    def _shift_plan(cls, pitch, speed):
-        """(p / q, the combined speed of the stretch, the speed itself) of a `shift` call; every ValueError of it, before any launch"""
+    def _psola_plan(cls, wavs, lags, hop, ratio, contour, period_min, period_max, unvoiced_period):
+        """(rows, lag (n, stride) int32, ratio (n, stride) int32 or None, options) of a `psola` call; every ValueError of it, before
+        any launch"""
+        ws = [np.ascontiguousarray(w, np.float32).reshape(-1) for w in wavs]
+        hop = int(hop)
+        if hop < 16 or hop > 4096:
+            raise ValueError(f"psola: hop {hop} outside 16 .. 4096")
+        if len(lags) != len(ws) or (contour is not None and len(contour) != len(ws)):
+            raise ValueError(f"psola: {len(ws)} rows, {len(lags)} lag arrays" + ("" if contour is None else f", {len(contour)} contours"))
+        o = vx_psola_opts(C.sizeof(vx_psola_opts), hop, int(period_min), int(period_max), int(unvoiced_period), cls.psola_q16(ratio))
+        if not 16 <= o.period_min <= o.period_max <= 1024:
+            raise ValueError(f"psola: period_min {o.period_min}, period_max {o.period_max} outside 16 <= period_min <= period_max <= 1024")
+        if not o.period_min <= o.unvoiced_period <= o.period_max:
+            raise ValueError(f"psola: unvoiced_period {o.unvoiced_period} outside period_min {o.period_min} .. period_max {o.period_max}")
+        ms = [-(-len(w) // hop) for w in ws]
+        stride = max([1] + ms)
+        lag = np.zeros((len(ws), stride), np.int32)
+        rat = None if contour is None else np.full((len(ws), stride), 65536, np.int32)
+        for i, m in enumerate(ms):
+            row = np.asarray(lags[i]).reshape(-1)
+            if len(row) != m:
+                raise ValueError(f"psola: row {i} has {len(ws[i])} samples, {m} frames at hop {hop}, and {len(row)} lags")
+            lag[i, :m] = row
+            if rat is not None:
+                cr = np.asarray(contour[i]).reshape(-1)
+                if len(cr) != m:
+                    raise ValueError(f"psola: row {i} has {m} frames at hop {hop}, its contour {len(cr)}")
+                if m and (cr.min() < PSOLA_RATIO_MIN or cr.max() > PSOLA_RATIO_MAX):
+                    raise ValueError(f"psola: the contour of row {i} leaves {PSOLA_RATIO_MIN} .. {PSOLA_RATIO_MAX} (Q16, 2/3 .. 2)")
+                rat[i, :m] = cr
+        return ws, lag, rat, o
+
+    def psola(self, wavs: Sequence[np.ndarray], lags: Sequence[np.ndarray], hop: int, ratio=1.0, contour=None, period_min: int = 48,
+              period_max: int = 400, unvoiced_period: int = 120, return_marks: bool = False):
+        """vx_psola, the formant-preserving pitch shift: mono fp32 waveforms (L_i,) and their signed lags (ceil(L_i / hop),) as
+        `f0_lags` gives them at `hop` -> (rows, infos), rows float32 of L_i samples whose pitch is `ratio` times the input's at the
+        same duration and the same spectral envelope, infos dicts with marks, voiced_marks, grains, gaps and nonfinite
+        (include/vallex_hip.h: vx_psola_info).  Time-domain PSOLA on the device: pitch marks one period apart along the waveform,
+        two-period grains around them laid down again at period / ratio.  ratio: a float, a Fraction or a (num, den) pair in
+        2/3 .. 2; contour: per row the Q16 ratio of every frame (int, 43691 .. 131072: utils.alignment.range_contour), which replaces
+        `ratio` frame by frame.  A lag outside period_min .. period_max counts as unvoiced; unvoiced stretches are re-laid at their own
+        spacing of `unvoiced_period`.  The defaults are those of `f0` at 24 kHz.  return_marks: (rows, infos, marks), marks int32
+        a_0 .. a_N per row.  Ratio 1 returns the input bits (non-finite samples as 0)."""
+        ws, lag, rat, o = self._psola_plan(wavs, lags, hop, ratio, contour, period_min, period_max, unvoiced_period)
+        n = len(ws)
+        if n == 0:
+            return ([], [], []) if return_marks else ([], [])
+        buf, lens, stride = self._packed(ws)
+        out = np.zeros((n, stride), np.float32)
+        mstride = stride // 14 + 2
+        marks = np.zeros((n, mstride), np.int32) if return_marks else None
+        info = (vx_psola_info * n)()
+        self._chk(self.lib.vx_psola(self.ctx, _ptr(buf, C.c_float), stride, _ptr(lens, C.c_int32), n, _ptr(lag, C.c_int32), lag.shape[1],
+                                    None if rat is None else _ptr(rat, C.c_int32), C.byref(o), _ptr(out, C.c_float), stride,
+                                    None if marks is None else _ptr(marks, C.c_int32), mstride, info))
+        rows = [out[i, :L] for i, L in enumerate(lens)]
+        infos = [{fl[0]: getattr(w, fl[0]) for fl in vx_psola_info._fields_} for w in info]
+        if return_marks:
+            return rows, infos, [marks[i, : infos[i]["marks"] + 1] for i in range(n)]
+        return rows, infos
+
+    def dev_psola_table(self, wav: np.ndarray, lag: np.ndarray, o: vx_psola_opts, ratio: Optional[np.ndarray] = None):
+        """vx_dev_psola_table: (cost (N + 1,) float64, grains (J, 4) int32 = (s, a, Wl, Wr)) of one row as the kernels saw them"""
+        w = np.ascontiguousarray(wav, np.float32).reshape(-1)
+        lg = np.ascontiguousarray(lag, np.int32).reshape(-1)
+        rt = None if ratio is None else np.ascontiguousarray(ratio, np.int32).reshape(-1)
+        ccap, gcap = len(w) // 14 + 2, len(w) // 7 + 2
+        cost, grains = np.zeros(ccap, np.float64), np.zeros((gcap, 4), np.int32)
+        nm, ng = C.c_int32(0), C.c_int32(0)
+        one = np.zeros(1, np.int32)
+        self._chk(self.lib.vx_dev_psola_table(self.ctx, _ptr(w if len(w) else np.zeros(1, np.float32), C.c_float), len(w),
+                                              _ptr(lg if len(lg) else one, C.c_int32), None if rt is None else _ptr(rt if len(rt) else one, C.c_int32),
+                                              C.byref(o), _ptr(cost, C.c_double), ccap, _ptr(grains, C.c_int32), gcap, C.byref(nm), C.byref(ng)))
+        return cost[: nm.value + 1], grains[: ng.value]
+
+    def dev_psola_window(self, samples: int = 0):
+        """vx_dev_psola_window: samples one launch of `psola` holds from now on (DEV_PSOLA_WINDOW_MIN .. PSOLA_WINDOW; 0 restores the
+        default)"""
+        self._chk(self.lib.vx_dev_psola_window(self.ctx, int(samples)))
+
+    @staticmethod
+    def _pitch_parts(pitch, formants=False, range=None):
+        """(pitch, formants, range) of a `pitch=` argument: an object with the fields of utils.generation.Pitch carries all three"""
+        if hasattr(pitch, "pitch") and hasattr(pitch, "formants"):
+            return pitch.pitch, bool(pitch.formants), getattr(pitch, "range", None)
+        return pitch, bool(formants), range
+
+    @classmethod
+    def _shift_plan(cls, pitch, speed, formants=False, range=None):
+        """(p / q, the combined speed of the stretch, the speed itself) of a `shift` call; every ValueError of it, before any launch.
+        `pitch` may be a utils.generation.Pitch.  With formants the stretch runs at the speed alone and the ratio goes to `psola`."""
+        pitch, formants, range = cls._pitch_parts(pitch, formants, range)
         r = cls.pitch_ratio(pitch)
+        if range is not None:
+            if not formants:
+                raise ValueError("pitch: range= needs formants=True (the contour is applied by psola)")
+            if not (math.isfinite(float(range)) and 0.0 <= float(range) <= 4.0):
+                raise ValueError(f"pitch: range {range!r} outside 0 .. 4")
+        if formants and (3 * r.numerator < 2 * r.denominator):
+            raise ValueError(f"pitch {pitch!r}: the ratio {r} is below 2/3, where the grains of the formant-preserving shift no longer overlap")
         if speed is None:
             sp = Fraction(1)
         elif isinstance(speed, (tuple, list)):
@@ -924,7 +1056,7 @@ class Engine:
             sp = Fraction(int(speed[0]), int(speed[1]))
         else:
             sp = speed if isinstance(speed, Fraction) else Fraction(speed).limit_denominator(1000)
-        comb = sp / r
+        comb = sp if formants else sp / r
         if sp <= 0 or 2 * sp < 1 or sp > 2:
             raise ValueError(f"speed {speed!r} outside 1/2 .. 2")
         if 2 * comb < 1 or comb > 2:
@@ -933,16 +1065,32 @@ class Engine:
             raise ValueError(f"speed {sp} with pitch ratio {r}: {comb} does not fit vx_stretch_opts (terms above 32767)")
         return r, comb, sp
 
-    def shift(self, wavs: Sequence[np.ndarray], pitch, speed=None):
+    def shift(self, wavs: Sequence[np.ndarray], pitch, speed=None, formants: bool = False, range=None):
         """the pitch control: mono fp32 waveforms (L_i,) at 24 kHz -> a list of float32 arrays of ceil(L_i / speed) samples (exactly L_i
         with speed=None) whose pitch is p / q = pitch_ratio(pitch) times the input's.  One `stretch` at (speed or 1) q / p (the
         duration grows by p / q at the same pitch), then one `resample` with orig_rate = p, new_rate = q (duration and pitch go
         back by q / p and up by p / q), cut to the length.  Ratio 1 with speed=None returns the input bits.  The formants move with
-        the pitch: meant for a few semitones.  ValueError before any launch: a ratio, a speed or their quotient outside 1/2 .. 2."""
-        r, comb, sp = self._shift_plan(pitch, speed)
+        the pitch: meant for a few semitones.  ValueError before any launch: a ratio, a speed or their quotient outside 1/2 .. 2.
+        formants=True (or a utils.generation.Pitch as `pitch`) keeps the formants instead: `stretch` at `speed` if given, then
+        `f0_lags` with the defaults of `f0`, then `psola` at round(p / q 65536) -- ratios 2/3 .. 2; ratio 1 with speed=None returns
+        the input bits.  range (with formants only): the intonation is scaled around its median by that factor on the way
+        (utils.alignment.range_contour; 0 flattens it, above 1 widens it)."""
+        pitch, formants, range = self._pitch_parts(pitch, formants, range)
+        r, comb, sp = self._shift_plan(pitch, speed, formants, range)
         ws = [np.ascontiguousarray(w, np.float32).reshape(-1) for w in wavs]
         if not ws:
             return []
+        if formants:
+            if r == 1 and speed is None and range is None:
+                return [w.copy() for w in ws]
+            rows = ws if speed is None else self.stretch(ws, sp)
+            o = self._f0_opts(24000, None, None, 60.0, 500.0, 0.15)
+            f, lag, _, _ = self.f0_lags(rows, o)
+            contour = None
+            if range is not None:
+                from .utils.alignment import range_contour
+                contour = [range_contour(fi, li, r, range) for fi, li in zip(f, lag)]
+            return self.psola(rows, lag, o.hop, r, contour, o.lag_min, o.lag_max, 120)[0]
         want = [-(-len(w) * sp.denominator // sp.numerator) for w in ws]
         rows = self.stretch(ws, comb)
         rows = self.resample(rows, r.numerator, r.denominator)

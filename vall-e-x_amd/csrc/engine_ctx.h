@@ -193,6 +193,8 @@ struct vx_ctx {
   long lm_window = 0;              // samples per launch set by vx_dev_limit_window (0: the default, VX_LIMIT_WINDOW)
   // pitch tracker (vx_f0, f0.hip): runs in the resampler's launch buffers (rs_buffers) alone; needs no weights
   long f0_window = 0;              // samples per launch set by vx_dev_f0_window (0: the default, VX_F0_WINDOW)
+  // formant-preserving pitch shift (vx_psola, psola.hip): runs in the resampler's launch buffers (rs_buffers) alone; needs no weights
+  long ps_window = 0;              // samples per launch set by vx_dev_psola_window (0: the default, VX_PSOLA_WINDOW)
 
   // graph
   hipGraphExec_t graph_exec = nullptr, graph_exec_n = nullptr;   // one decode step / GRAPH_STEPS steps per launch

@@ -93,3 +93,25 @@ def token_pitch(segments, f0, voiced, hop: int, frame: int = 320) -> np.ndarray:
         if vals.size:
             out[j] = vals[(vals.size - 1) // 2]
     return out
+
+
+def range_contour(f0, lag, ratio, scale) -> np.ndarray:
+    """The per-frame pitch ratios that scale the intonation of one row around its median: f0 / lag are the per-frame output of
+    `Engine.f0_lags` (lag > 0 is voiced), `ratio` the overall pitch ratio, `scale` the factor on the intonation's range (in the log
+    domain): voiced frame k gets ratio * (f0_k / median) ** (scale - 1), so that its pitch lands on ratio * median *
+    (f0_k / median) ** scale -- scale 0 flattens the contour to the median, 1 leaves it, above 1 widens it.  The median is the lower
+    median of f0 over the voiced frames (vx_f0_info.f0_median).  Unvoiced frames get `ratio`.  Returns (M,) int32 in Q16, rounded
+    to nearest and clipped to 43691 .. 131072, what `Engine.psola` takes as a row's `contour`.  Host numpy."""
+    f = np.asarray(f0, np.float64).reshape(-1)
+    v = np.asarray(lag).reshape(-1) > 0
+    if f.shape != v.shape:
+        raise ValueError(f"f0 has {f.size} frames, lag {v.size}")
+    ratio, scale = float(ratio), float(scale)
+    if not (np.isfinite(ratio) and ratio > 0 and np.isfinite(scale)):
+        raise ValueError(f"ratio {ratio!r} must be positive and scale {scale!r} finite")
+    out = np.full(f.size, ratio, np.float64)
+    if v.any():
+        vals = np.sort(f[v])
+        med = vals[(vals.size - 1) // 2]
+        out[v] = ratio * (f[v] / med) ** (scale - 1.0)
+    return np.clip(np.rint(out * 65536.0), 43691, 131072).astype(np.int32)

@@ -234,6 +234,22 @@ def _finished(wavs, finish, sample_rate):
     return model.engine._finished(wavs, finish, SAMPLE_RATE if sample_rate is None else int(sample_rate))
 
 
+class Pitch:
+    """A pitch request with its method, accepted wherever `pitch=` is: `pitch` as there (a float in semitones, or the ratio as a
+    Fraction or a (num, den) pair).  formants=True keeps the spectral envelope, and with it the speaker: Engine.shift runs the pitch
+    tracker and the PSOLA shift (vx_f0, then vx_psola) in place of the stretch-and-resample shift; the ratio must lie in 2/3 .. 2.
+    formants=False is the plain `pitch=`.  range (None: as spoken; needs formants=True): the intonation is scaled around its median by
+    that factor (utils.alignment.range_contour): 0 flattens it, above 1 widens it, 0 .. 4.  Every ValueError is raised here."""
+
+    def __init__(self, pitch, formants: bool = True, range=None):
+        self.pitch, self.formants, self.range = pitch, bool(formants), range
+        from .._capi import Engine
+        Engine._shift_plan(self, None)
+
+    def __repr__(self):
+        return f"Pitch({self.pitch!r}, formants={self.formants}, range={self.range!r})"
+
+
 def _at_speed(wavs, speed, pitch=None):
     """the 24 kHz waveforms of a vocoder call at `speed` (None: as they are): one vx_stretch call for the list, before the resampler;
     with `pitch` (None: as they are): Engine.shift, the stretch at the combined speed and the p -> q resample, for the list"""
@@ -284,7 +300,9 @@ def generate_audio(text, prompt=None, language="auto", accent="no-accent", sampl
     the pace the model produced): the speaking rate, a pitch-preserving time-stretch on the device (Engine.stretch, vx_stretch) at
     24 kHz, before the resampler.  pitch (a float in semitones, -12 .. 12, or the ratio as a Fraction or a (num, den) pair in
     1/2 .. 2; None = the pitch the model produced): a pitch shift that keeps the duration (Engine.shift: the stretch at speed / ratio,
-    then a resample by the ratio), in place of the stretch.  It moves the formants with the pitch: meant for a few semitones."""
+    then a resample by the ratio), in place of the stretch.  It moves the formants with the pitch: meant for a few semitones.  A
+    `Pitch` (pitch, formants=True, range=None) keeps the formants instead (the pitch tracker, then the PSOLA shift: vx_f0, vx_psola)
+    and can scale the intonation's range; it is accepted wherever `pitch=` is."""
     if model is None or vocos is None:
         raise RuntimeError("call preload_models() first")
     _check_pitch(pitch, speed)

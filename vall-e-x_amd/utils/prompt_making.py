@@ -125,7 +125,8 @@ def level_loudness(wav: np.ndarray, lufs: float, sample_rate: int) -> np.ndarray
 def shift_pitch(wav: np.ndarray, pitch) -> np.ndarray:
     """(1, L) mono fp32 at 24 kHz -> the clip at `pitch` (semitones, or the ratio as a Fraction or a (num, den) pair) with the same
     length, on the loaded model's engine (Engine.shift: vx_stretch, then vx_resample).  The pitch of a cloned voice follows the pitch
-    of its enrolment clip; the formants move along, so this is meant for a few semitones."""
+    of its enrolment clip; the formants move along, so this is meant for a few semitones -- a utils.generation.Pitch as `pitch` keeps
+    them (vx_f0, then vx_psola)."""
     if G.model is None:
         raise RuntimeError("call preload_models() first: pitch runs on the loaded model's engine")
     return np.array(G.model.engine.shift([wav.reshape(-1)], pitch)[0], np.float32)[None]
