@@ -86,13 +86,30 @@ int vx_dev_sample_filtered(vx_ctx* ctx, int32_t n, const int32_t* cfg, const flo
  * nothing is written behind them).  *range_flag = the f16x2 range flag after the launch (0 for the other variants). */
 int vx_dev_attn(vx_ctx* ctx, int32_t variant, int32_t planes, int32_t batch, const float* qkv, const int32_t* seq_len,
                 const int32_t* prefix_len, const int32_t* q_first, float* out, int64_t out_rows, int32_t* range_flag);
+/* The kernel-selection fields a context read from its configuration and the environment when its weights were finalized, so that
+ * a measurement or a test that sets a switch can show that the context took it.  out[0 .. 13], in this order:
+ *    0 sb_fuse           VX_SB_FUSE (1; 0: no small-batch chain)       7 balance_rows  VX_BALANCE_ROWS (1)
+ *    1 sb_qkv_rows       VX_SB_QKV (4: the fused QKV up to 4 rows)      8 nar_trim      VX_NAR_TRIM (1)
+ *    2 sb_qkv_nsplit     VX_SB_QKV_NSPLIT (0: the rule's count)         9 graph_multi   VX_GRAPH_MULTI (1)
+ *    3 qkv_bal           VX_QKV_BALANCED (1)                           10 gemm_mode     0 f16x2, 1 bf16x3 (VX_GEMM_X3), 2 fp32 (VX_GEMM_F32)
+ *    4 fuse_out          VX_FUSE_OUT (1), 0 whenever Tmax < 128        11 attn_x3       0: exact-fp32 full-sequence attention (VX_ATTN_F32)
+ *    5 fuse_split        VX_FUSE_SPLIT (1)                             12 attn_h2       0: bf16x3 full-sequence attention (VX_ATTN_X3)
+ *    6 att_nsplit_force  VX_ATT_NSPLIT (0: the rule; at most 16)       13 Tmax          arena rows per (slot, head)
+ * VX_EINVAL for a null out or n < 14 (VX_DEV_SWITCHES), VX_ESTATE before vx_finalize_weights. */
+#define VX_DEV_SWITCHES 14
+int vx_dev_switches(vx_ctx* ctx, int32_t* out, int32_t n);
 /* The attention block of ONE decode step on nrows (1 .. 32) chosen rows: the launches of the engine's step from the attention launch
  * to the launch behind which the out_proj result exists, with the chain and the context splits the engine's own rule picks for nrows
- * rows (reported in geom[3] = {nsplit, sb_qkv, split_fused}):
+ * rows under the context's switches (reported in geom[4] = {nsplit, sb_qkv, split_fused, sb_chain}).  With the default switches:
  *   1 .. 4 rows        dec_attn_qkv (norm1 + in_proj + split attention) | out_proj GEMM with the combine as prologue
  *   5 .. 7 rows        dec_attn | dec_attn_combine | out_proj GEMM | reduce + LayerNorm
  *   8 .. 16 rows       dec_attn with out_proj folded in, context splits | reduce (weighs the slabs by e^(m_s - M) / L) + LayerNorm
  *   17 .. 32 rows      dec_attn with out_proj folded in, one split | reduce + LayerNorm
+ * and under a switch whatever decode_geometry (engine.hip) makes of it, at any row count: the unfused chain with 1 .. 16 splits (one
+ * split: no combine launch, no (m, l)), the split-fused one with 2 .. 4, the fused one, and
+ *   1 .. 4 rows, sb_chain without sb_qkv (VX_SB_QKV below the row count, or a VX_SB_QKV_NSPLIT that is not instantiated):
+ *                      dec_attn (unfused, 16 | 8 splits) | out_proj GEMM with the combine as prologue
+ * A combination a launcher does not instantiate is VX_EINVAL ("a launcher refused this configuration"), nothing launched.
  * The weights are the context's layer 0 (in_proj, out_proj, norm1, norm2, and linear2's bias for skp 8); everything else is private
  * scratch of the call, pre-filled with the sentinel -- the K / V arena too, which has nrows slots of [16][Tmax][64] for a Tmax of the
  * caller's (128 .. 4096).  The context's decode state is not touched.
@@ -100,16 +117,18 @@ int vx_dev_attn(vx_ctx* ctx, int32_t variant, int32_t planes, int32_t batch, con
  *   slot_order [nrows]: slot_order[y] = the row in launch slot y, a permutation (the identity for nrows <= 4)
  *   kc, vc [nrows][16][Tmax][64], in and out, indexed by ROW (the entry moves row r's stream into its slot and back): the cached rows
  *       0 .. ctx - 2 and whatever the caller wants a reused slot to hold behind them; out: the whole stream after the launch
- *   qkv (the dec_attn chains): the in_proj split-K slabs [4][nrows][3072], or for qkv_balanced != 0 [8][nrows][3072] with q in all
- *       eight and k, v in the first four (columns 1024 .. 3071 of slabs 4 .. 7 are not read)
- *   x_in (the 1 .. 4-row chain): skp 0: [nrows][1024], norm1(h) as the sampler leaves it (packed by the entry); skp 8: [9][nrows][1024],
+ *   qkv (the dec_attn chains, sb_chain without sb_qkv included): the in_proj split-K slabs [4][nrows][3072], or for qkv_balanced != 0
+ *       [8][nrows][3072] with q in all eight and k, v in the first four (columns 1024 .. 3071 of slabs 4 .. 7 are not read); sb_chain
+ *       without sb_qkv reads four slabs only, as the engine's QKV GEMM of that chain writes them: qkv_balanced != 0 is VX_EINVAL there
+ *   x_in (the sb_qkv chain): skp 0: [nrows][1024], norm1(h) as the sampler leaves it (packed by the entry); skp 8: [9][nrows][1024],
  *       eight linear2 slabs and the residual row: x = norm1(resid + sum of the slabs + linear2 bias)
- *   resid [nrows][1024] (the dec_attn chains): the residual rows the closing reduce + LayerNorm adds
- *   out [4][nrows][1024]: the 1 .. 4-row chain: the four split-K slabs of out_proj (bias not added); the other chains: out[0] = h =
+ *   resid [nrows][1024] (the dec_attn chains; sb_chain without sb_qkv does not read it and takes NULL): the residual rows the closing
+ *       reduce + LayerNorm adds
+ *   out [4][nrows][1024]: sb_chain, with or without sb_qkv: the four split-K slabs of out_proj (bias not added); the other chains: out[0] = h =
  *       resid + out_proj(attention) (every row: the reduce kernels do not look at the active flag), out[1 .. 3] keep the sentinel
- *   xp_att [nrows][1024]: the attention output in front of out_proj where a chain stores it (5 .. 7 rows), un-packed
- *   part_ml [nrows][16][17][2]: (m, l) of partial s < nsplit of every (row, head) where the chain has context splits; the 1 .. 4-row
- *       chain's partial `nsplit` (the new token's) has no (m, l): the consumer forms it
+ *   xp_att [nrows][1024]: the attention output in front of out_proj where a chain stores it (the unfused chain), un-packed
+ *   part_ml [nrows][16][17][2]: (m, l) of partial s < nsplit of every (row, head) where the chain has context splits (nsplit >= 2, or
+ *       sb_chain); the sb_qkv chain's partial `nsplit` (the new token's) has no (m, l): the consumer forms it
  * VX_ESTATE while a serving session is open; VX_EINVAL for Tmax < 128, a context beyond Tmax, a slot order that is no permutation. */
 int vx_dev_dec_attn(vx_ctx* ctx, int32_t nrows, int32_t Tmax, int32_t qkv_balanced, int32_t skp, const int32_t* ctx_len,
                     const int32_t* active, const int32_t* slot_order, float* kc, float* vc, const float* qkv, const float* x_in,

@@ -212,15 +212,82 @@ DEC_CTX = (300, 1, 257, 2, 130, 16, 129, 17, 128, 18, 127, 33)
 DEC_KINDS = ("uniform", "model", "sharp", "new_heavy", "new_light")
 
 
-def dec_geometry(nrows):
-    """(chain, context splits) the engine's rule picks with its default switches (engine.hip decode_geometry)"""
-    if nrows <= 4:
-        return "sb_qkv", (16, 8, 4, 4)[nrows - 1]
-    if nrows <= 7:
-        return "unfused", max(2, 256 // (nrows * 16))
-    if nrows <= 16:
-        return "split_fused", min(4, 256 // (16 * ((nrows + 1) // 2)))
-    return "fused", 1
+def dec_geometry(nrows, identity=True, sb_fuse=1, sb_qkv_rows=4, sb_qkv_nsplit=0, fuse_out=1, fuse_split=1, att_nsplit_force=0):
+    """(chain, context splits) the engine's rule picks (engine.hip decode_geometry), restated statement by statement with the switches
+    a context reads (weights.hip; the names are the fields vx_dev_switches reports, fuse_out after the Tmax rule).  With no switch: the
+    default table.  Chains: 'sb_qkv' (norm1 + QKV inside the attention launch, <= 4 rows), 'sb' (the small-batch chain without the fused
+    QKV: unfused dec_attn, the combine in the prologue of out_proj), 'unfused' (dec_attn | combine if there are splits | out_proj),
+    'split_fused' (out_proj inside dec_attn, 2 .. 4 context splits), 'fused' (out_proj inside dec_attn, one split)."""
+    nsplit = max(1, min(16, 512 // (nrows * 16)))
+    if 4 < nrows <= 16:
+        nsplit = max(2, 256 // (nrows * 16))
+    split_fused = False
+    if fuse_out and fuse_split == 1 and 8 <= nrows <= 16:
+        ns = min(4, 256 // (16 * ((nrows + 1) // 2)))
+        if ns >= 2:
+            nsplit, split_fused = ns, True
+    if att_nsplit_force > 0:
+        nsplit = att_nsplit_force
+        split_fused = bool(fuse_out) and fuse_split != 0 and nrows > 4 and 2 <= nsplit <= 4       # any non-zero fuse_split, as the code has it
+    sb_chain = sb_qkv = False
+    if sb_fuse and nrows <= 4 and identity:
+        nsplit, sb_chain = (16 if nrows <= 2 else 8), True              # sb_chain_supported: 16 and 8 splits are instantiated
+        if nrows <= sb_qkv_rows:
+            ns2 = sb_qkv_nsplit if sb_qkv_nsplit > 0 else (16, 8, 4, 4)[nrows - 1]
+            if ns2 in (16, 8, 4):                                       # sb_qkv_chain_supported
+                nsplit, sb_qkv = ns2, True
+    chain = "sb_qkv" if sb_qkv else "sb" if sb_chain else "split_fused" if split_fused else "fused" if fuse_out and nsplit == 1 else "unfused"
+    return chain, nsplit
+
+
+# the switched chains (tests/test_gpu_kernel_dec_attn_switches.py): environment of a line -> {rows: (chain, context splits)}, pinned by
+# hand in tests/test_kernel_refs.py; `fields`: what vx_dev_switches must report for the line (the other fields keep their defaults)
+DEC_SWITCH_DEFAULTS = dict(sb_fuse=1, sb_qkv_rows=4, sb_qkv_nsplit=0, qkv_bal=1, fuse_out=1, fuse_split=1, att_nsplit_force=0, balance_rows=1,
+                           nar_trim=1, graph_multi=1, gemm_mode=0, attn_x3=1, attn_h2=1)
+DEC_SWITCH_LINES = {
+    "sb_qkv_0": dict(env={"VX_SB_QKV": "0"}, fields=dict(sb_qkv_rows=0), rows=(1, 2, 3, 4)),
+    "sb_qkv_2": dict(env={"VX_SB_QKV": "2"}, fields=dict(sb_qkv_rows=2), rows=(2, 3)),
+    "sb_qkv_nsplit_4": dict(env={"VX_SB_QKV_NSPLIT": "4"}, fields=dict(sb_qkv_nsplit=4), rows=(1, 2)),
+    "sb_qkv_nsplit_8": dict(env={"VX_SB_QKV_NSPLIT": "8"}, fields=dict(sb_qkv_nsplit=8), rows=(1, 2)),
+    "sb_qkv_nsplit_16": dict(env={"VX_SB_QKV_NSPLIT": "16"}, fields=dict(sb_qkv_nsplit=16), rows=(1, 2)),
+    "sb_qkv_nsplit_5": dict(env={"VX_SB_QKV_NSPLIT": "5"}, fields=dict(sb_qkv_nsplit=5), rows=(1,)),
+    "sb_fuse_0": dict(env={"VX_SB_FUSE": "0"}, fields=dict(sb_fuse=0), rows=(1, 2, 3, 4)),
+    "fuse_out_0": dict(env={"VX_FUSE_OUT": "0"}, fields=dict(fuse_out=0), rows=(8, 9, 16, 17, 32)),
+    "fuse_split_0": dict(env={"VX_FUSE_SPLIT": "0"}, fields=dict(fuse_split=0), rows=(8, 11), geometry_only=(17,)),
+    "att_nsplit_1": dict(env={"VX_ATT_NSPLIT": "1"}, fields=dict(att_nsplit_force=1), rows=(5, 8)),
+    "att_nsplit_2": dict(env={"VX_ATT_NSPLIT": "2"}, fields=dict(att_nsplit_force=2), rows=(5, 7, 17, 32)),
+    "att_nsplit_4": dict(env={"VX_ATT_NSPLIT": "4"}, fields=dict(att_nsplit_force=4), rows=(5, 7, 17, 32)),
+    "att_nsplit_8": dict(env={"VX_ATT_NSPLIT": "8"}, fields=dict(att_nsplit_force=8), rows=(8, 32)),
+    "att_nsplit_16": dict(env={"VX_ATT_NSPLIT": "16"}, fields=dict(att_nsplit_force=16), rows=(8, 32)),
+    "att_nsplit_3_fuse_split_0": dict(env={"VX_ATT_NSPLIT": "3", "VX_FUSE_SPLIT": "0"}, fields=dict(att_nsplit_force=3, fuse_split=0), rows=(9,)),
+}
+_GEOM_ARGS = ("sb_fuse", "sb_qkv_rows", "sb_qkv_nsplit", "fuse_out", "fuse_split", "att_nsplit_force")
+
+
+def dec_switch_geometry(line, nrows, identity=True):
+    """(chain, context splits) of a line of DEC_SWITCH_LINES at a row count, by the restated rule"""
+    f = DEC_SWITCH_LINES[line]["fields"]
+    return dec_geometry(nrows, identity, **{k: v for k, v in f.items() if k in _GEOM_ARGS})
+
+
+def dec_switch_launches(nrows):
+    """[(contexts, finished row or None)] of the launches a switched chain is tested with: the launches of dec_launch_contexts, each with
+    ONE finished row (active 0) from 3 rows up -- row (3 j + 1) mod nrows of launch j below 8 rows; from 8 rows up, where launch slots y
+    and y + ceil(nrows / 2) share a workgroup on the fused chains, a row of the first half in even launches and of the second half in
+    odd ones --, then launches in which every row is live that hold the contexts the finished rows had (filled up from DEC_CTX in order),
+    so that every context of DEC_CTX still meets every split count in a live row"""
+    base = dec_launch_contexts(nrows)
+    if nrows < 3:
+        return [(c, None) for c in base]
+    gy = (nrows + 1) // 2
+    fin = (lambda j: (3 * j + 1) % nrows) if nrows < 8 else (lambda j: gy + j % (nrows - gy) if j % 2 else (j + 1) % gy)
+    out = [(c, fin(j)) for j, c in enumerate(base)]
+    lost = [c[f] for c, f in out]
+    lost += [c for c in DEC_CTX if c not in lost]
+    nmore = -(-len(out) // nrows)
+    for j in range(nmore):
+        out.append(([lost[(j * nrows + i) % len(lost)] for i in range(nrows)], None))
+    return out
 
 
 def dec_split_bounds(npast, nsplit):

@@ -36,6 +36,45 @@ def get_model(num_layers, seed, eos_gain=1.0, vocos=False, debug_taps=False, max
     return _MODELS[key]
 
 
+_SWITCHED = []
+_SWITCHED_SD = {}
+
+
+def drop_switched():
+    """drop the engine of the switched context, as get_model drops its own"""
+    while _SWITCHED:
+        _SWITCHED.pop().__dict__.pop("_engine", None)
+
+
+def switched_model(monkeypatch, env, fields, num_layers, seed, eos_gain=1.0, max_new=320, max_prompt=400, max_text=256, max_batch=32):
+    """A FRESH context created under the kernel-selection switches `env` ({name: value}, set through monkeypatch).  It never enters
+    get_model's cache -- a switched context must never be handed to another test --, its engine is created here, while the variables
+    are set (the environment is read at finalize), and at most one switched context is alive: the previous one is dropped first, and
+    the caller drops this one at teardown (drop_switched).  `fields`: what vx_dev_switches must report besides the defaults
+    (tests/_kernel_refs.py DEC_SWITCH_DEFAULTS; Tmax follows from the geometry) -- asserted here, before anything runs on the
+    context: a test that sets a switch and cannot show that the context read it proves nothing."""
+    from tests._kernel_refs import DEC_SWITCH_DEFAULTS
+    drop_switched()
+    for k in [k for k in os.environ if k.startswith("VX_") and k not in ("VX_DEV", "VX_LIB", "VX_FORCE_BUILD", "VX_PIN_MB")]:
+        monkeypatch.delenv(k)                  # a switch of the caller's shell is not part of the line under test
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    m = VALLE(1024, 16, num_layers, norm_first=True, add_prenet=False, prefix_mode=1, share_embedding=True, nar_scale_factor=1.0,
+              prepend_bos=True, num_quantizers=8, engine_max_new=max_new, engine_max_prompt=max_prompt, engine_max_text=max_text,
+              engine_max_batch=max_batch)
+    key = (num_layers, seed, eos_gain)
+    if key not in _SWITCHED_SD:                # one weight set at a time: the lines of a file share theirs
+        _SWITCHED_SD.clear()
+        _SWITCHED_SD[key] = synth.vallex_state_dict(num_layers, seed, eos_gain)
+    m.to("cuda:0").load_state_dict(_SWITCHED_SD[key], strict=True)
+    _SWITCHED.append(m)
+    got = m.engine.dev_switches()
+    want = dict(DEC_SWITCH_DEFAULTS, Tmax=max_text + 1 + max_prompt + max_new + 1)
+    want.update(fields)
+    assert got == want, ("the context did not read the switches", env, {k: (got[k], want[k]) for k in want if got[k] != want[k]})
+    return m
+
+
 _SDS = {}
 
 

@@ -203,6 +203,109 @@ def test_dec_attn_launch_plans_cover_the_edges():
                       ("split_fused", 2), ("fused", 1)}
 
 
+# the switched chains (tests/test_gpu_kernel_dec_attn_switches.py), written down by hand from the switch table of docs/log_r28.md:
+# line -> {rows: (chain, context splits)}
+SWITCH_TABLE = {
+    "sb_qkv_0": {1: ("sb", 16), 2: ("sb", 16), 3: ("sb", 8), 4: ("sb", 8)},
+    "sb_qkv_2": {2: ("sb_qkv", 8), 3: ("sb", 8)},
+    "sb_qkv_nsplit_4": {1: ("sb_qkv", 4), 2: ("sb_qkv", 4)},
+    "sb_qkv_nsplit_8": {1: ("sb_qkv", 8), 2: ("sb_qkv", 8)},
+    "sb_qkv_nsplit_16": {1: ("sb_qkv", 16), 2: ("sb_qkv", 16)},
+    "sb_qkv_nsplit_5": {1: ("sb", 16)},                                    # 5 splits are not instantiated
+    "sb_fuse_0": {1: ("unfused", 16), 2: ("unfused", 16), 3: ("unfused", 10), 4: ("unfused", 8)},
+    "fuse_out_0": {8: ("unfused", 2), 9: ("unfused", 2), 16: ("unfused", 2), 17: ("unfused", 1), 32: ("unfused", 1)},
+    "fuse_split_0": {8: ("unfused", 2), 11: ("unfused", 2), 17: ("fused", 1)},
+    "att_nsplit_1": {5: ("fused", 1), 8: ("fused", 1)},
+    "att_nsplit_2": {5: ("split_fused", 2), 7: ("split_fused", 2), 17: ("split_fused", 2), 32: ("split_fused", 2)},
+    "att_nsplit_4": {5: ("split_fused", 4), 7: ("split_fused", 4), 17: ("split_fused", 4), 32: ("split_fused", 4)},
+    "att_nsplit_8": {8: ("unfused", 8), 32: ("unfused", 8)},
+    "att_nsplit_16": {8: ("unfused", 16), 32: ("unfused", 16)},
+    "att_nsplit_3_fuse_split_0": {9: ("unfused", 3)},
+}
+
+
+def test_dec_geometry_without_switches_is_the_default_table():
+    want = {1: ("sb_qkv", 16), 2: ("sb_qkv", 8), 3: ("sb_qkv", 4), 4: ("sb_qkv", 4), 5: ("unfused", 3), 6: ("unfused", 2), 7: ("unfused", 2),
+            8: ("split_fused", 4), 9: ("split_fused", 3), 10: ("split_fused", 3), 11: ("split_fused", 2), 16: ("split_fused", 2),
+            17: ("fused", 1), 32: ("fused", 1)}
+    for n, g in want.items():
+        assert R.dec_geometry(n) == g, n
+    # a launch order that is not the identity never takes a small-batch chain; any non-zero fuse_split fuses under a forced count
+    assert R.dec_geometry(3, identity=False) == ("unfused", 10)
+    assert R.dec_geometry(9, fuse_split=2, att_nsplit_force=2) == ("split_fused", 2)
+    assert R.dec_geometry(9, fuse_split=2) == ("unfused", 2)               # ... but the 8 .. 16-row rule itself asks for 1
+    assert R.dec_geometry(20, fuse_out=0) == ("unfused", 1)
+
+
+def test_dec_switch_table_is_pinned_and_its_launch_plans_cover_the_edges():
+    assert set(SWITCH_TABLE) == set(R.DEC_SWITCH_LINES)
+    for line, rows in SWITCH_TABLE.items():
+        spec = R.DEC_SWITCH_LINES[line]
+        assert set(rows) == set(spec["rows"]) | set(spec.get("geometry_only", ())), line
+        assert set(spec["fields"]) <= set(R.DEC_SWITCH_DEFAULTS) and all(R.DEC_SWITCH_DEFAULTS[k] != v for k, v in spec["fields"].items()), line
+        for n, want in rows.items():
+            assert R.dec_switch_geometry(line, n) == want, (line, n)
+        for n in spec["rows"]:
+            chain, ns = rows[n]
+            plans = R.dec_switch_launches(n)
+            assert all(len(c) == n for c, _ in plans) and len(plans) <= 14
+            assert all(f is None or 0 <= f < n for _, f in plans)
+            assert n < 3 or sum(f is not None for _, f in plans) == len(R.dec_launch_contexts(n))
+            live = [c for p, f in plans for r, c in enumerate(p) if r != f]
+            assert set(live) == set(R.DEC_CTX) and max(live) <= R.DEC_TMAX, (line, n)
+            empty = exact = past1 = False
+            for c in live:
+                b = R.dec_split_bounds(c - 1, ns)
+                filled = [t1 - t0 for t0, t1 in b if t1 > t0]
+                assert sum(filled) == c - 1
+                empty |= len(filled) < ns
+                exact |= bool(filled) and filled[-1] % 16 == 0
+                past1 |= bool(filled) and filled[-1] % 16 == 1
+            assert (empty or ns == 1) and exact and past1, (line, n, ns, empty, exact, past1)
+            if ns == 16:                # the longest context, 300, has chunks of 32 rows and six empty splits; 257 fills all sixteen
+                assert sum(t1 > t0 for t0, t1 in R.dec_split_bounds(299, 16)) == 10 and all(t1 > t0 for t0, t1 in R.dec_split_bounds(256, 16))
+            if n >= 8:                  # two rows per workgroup on the fused chains: a finished row in a first and in a second half
+                gy = (n + 1) // 2
+                fin = [f for _, f in plans if f is not None]
+                assert (any(f < gy for f in fin) and any(f >= gy for f in fin)) or len(fin) == 1, (n, fin)
+
+
+def test_every_switch_the_sources_read_is_documented_and_every_per_context_switch_has_a_test_line():
+    """The README's switch paragraph names every VX_* variable the library reads (outside the VX_DEV_PROBES tool builds and the
+    VX_BENCH_* measurement entries), and every one of them that a CONTEXT reads (weights.hip, at finalize) has a line in the switch
+    table of tests/test_gpu_switches.py, which creates a context under it."""
+    import glob
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    readme = open(os.path.join(root, "README.md")).read()
+    para = re.search(r"Kernel-selection switches \(environment.*?\n\n", readme, re.S).group(0)
+    documented = set(re.findall(r"`(VX_[A-Z0-9_]+)", para))
+    read, per_context = set(), set()
+    for f in glob.glob(os.path.join(root, "vall-e-x_amd", "csrc", "*.hip")):
+        src = re.sub(r"#ifdef VX_DEV_PROBES.*?#endif", "", open(f).read(), flags=re.S)
+        names = {n for n in re.findall(r'getenv\("(VX_[A-Z0-9_]+)"\)', src) if not n.startswith("VX_BENCH_")}
+        read |= names
+        if os.path.basename(f) == "weights.hip":
+            per_context |= names
+    assert len(per_context) >= 14 and "VX_SB_QKV_NSPLIT" in per_context and "VX_GEMM_W128" in read - per_context
+    assert read <= documented, ("read by the library, missing in the README's switch paragraph", sorted(read - documented))
+    table = re.search(r"^SWITCH_LINES = \{.*?^\}", open(os.path.join(root, "tests", "test_gpu_switches.py")).read(), re.S | re.M).group(0)
+    tested = set(re.findall(r'"(VX_[A-Z0-9_]+)"', table))
+    assert per_context <= tested, ("per-context switches without a line in tests/test_gpu_switches.py", sorted(per_context - tested))
+    assert tested <= per_context, ("a line for a switch no context reads", sorted(tested - per_context))
+    # ... and the kernel-level table knows no switch the model-level one does not
+    assert {k for spec in R.DEC_SWITCH_LINES.values() for k in spec["env"]} <= tested
+    # the words of vx_dev_switches: the header's order is the binding's, and the defaults the tests assert name every word but Tmax
+    from vallex_amd._capi import DEV_SWITCHES
+    hdr = open(os.path.join(root, "include", "vallex_hip_dev.h")).read()
+    block = hdr[:hdr.index("int vx_dev_switches(")][-2200:]
+    assert int(re.search(r"#define VX_DEV_SWITCHES (\d+)", block).group(1)) == len(DEV_SWITCHES) == 14
+    for i, name in enumerate(DEV_SWITCHES):
+        assert re.search(rf"(?<!\d){i} {name}\b", block), (i, name)
+    assert set(R.DEC_SWITCH_DEFAULTS) == set(DEV_SWITCHES) - {"Tmax"}
+
+
 # ---- the GEMM / FFN / LayerNorm half of the decode step (tests/test_gpu_kernel_dec_ffn.py) ------------------------------------------
 @pytest.fixture(scope="module")
 def ffn_sd():

@@ -9,7 +9,8 @@
 #   devices                        GPUs visible to torch / rocminfo
 #   suite                          the whole GPU test suite (what the driver runs at round end)
 #   golden [ENV=V ...]             the golden parity subset (parity, full-length, batch-32, long-context, trained-like) under env switches
-#   switches                       `golden` under every runtime switch of the library, one by one, then the C client and smoke()
+#   switches                       the two switch test files of the suite (every per-context switch against the oracle and against float64),
+#                                  then the C client and smoke()
 #   smoke                          __graft_entry__.smoke()
 #   bench LABEL [bench.py args]    one `bench.py --full` line -> <tag>_bench_LABEL.json (+ .err)
 #   cbench LABEL [ENV=V ...] -- [c_bench args]      one run of the torch-free C client (examples/c_bench.c) -> <tag>_cbench.jsonl
@@ -56,9 +57,10 @@ step_golden() {
   env "$@" timeout 600 python -m pytest $GOLDEN -m gpu -q -x 2>&1 | tail -3 | tee -a gpurun_out/${TAG}_golden.log
 }
 step_switches() {
-  for sw in VX_SB_QKV=0 VX_SB_FUSE=0 VX_FUSE_OUT=0 VX_FUSE_SPLIT=0 VX_BALANCE_ROWS=0 VX_NAR_TRIM=0 VX_GEMM_X3=1 VX_ATTN_X3=1 VX_GEMM_F32=1 VX_ATTN_F32=1; do
-    step_golden $sw
-  done
+  # the per-context switches are part of the suite: every line against the oracle and, one launch at a time, against float64
+  # (step_golden on these two files: its result lines go to the golden log of the tag)
+  local GOLDEN="tests/test_gpu_switches.py tests/test_gpu_kernel_dec_attn_switches.py"
+  step_golden
   gcc -std=c99 -Wall -Wextra -Werror -pedantic -Iinclude examples/c_client.c $LF -o /tmp/c_client && /tmp/c_client --run 2>&1 | tail -4 | tee -a gpurun_out/${TAG}_golden.log
   step_smoke
 }

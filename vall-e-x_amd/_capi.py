@@ -153,7 +153,7 @@ DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kerne
                "vx_dev_dec_attn", "vx_dev_dec_op", "vx_dev_gemm", "vx_dev_layernorm", "vx_dev_score_rows", "vx_dev_align_rows", "vx_dev_wave_op",
                "vx_dev_seam_op", "vx_dev_resample_taps", "vx_dev_resample_window", "vx_dev_finish_frames", "vx_dev_finish_window",
                "vx_dev_stretch_window", "vx_dev_stretch_costs", "vx_dev_loudness_steps", "vx_dev_loudness_window",
-               "vx_dev_limit_gain", "vx_dev_limit_window", "vx_dev_psola_table", "vx_dev_psola_window"]
+               "vx_dev_limit_gain", "vx_dev_limit_window", "vx_dev_psola_table", "vx_dev_psola_window", "vx_dev_switches"]
 # the pitch tracker's entries, one of vallex_hip.h and two of vallex_hip_dev.h, in a list of their own: the header scan of
 # tests/test_abi.py matches names of letters and underscores, and these carry a digit (tests/test_f0_refs.py checks them)
 F0_SYMBOLS = ["vx_f0"]
@@ -161,6 +161,9 @@ F0_DEV_SYMBOLS = ["vx_dev_f0_table", "vx_dev_f0_window"]
 # sentinels the correctness entries pre-fill their outputs with (include/vallex_hip_dev.h)
 DEV_SENTINEL_I = -123456789
 DEV_SENTINEL_F = np.float32(-1.0e30)
+# the words of vx_dev_switches, in its order (include/vallex_hip_dev.h)
+DEV_SWITCHES = ("sb_fuse", "sb_qkv_rows", "sb_qkv_nsplit", "qkv_bal", "fuse_out", "fuse_split", "att_nsplit_force", "balance_rows",
+                "nar_trim", "graph_multi", "gemm_mode", "attn_x3", "attn_h2", "Tmax")
 # ops and weights of vx_dev_dec_op (VX_DEV_OP_* / VX_DEV_W_* of include/vallex_hip_dev.h)
 DEV_OPS = {"embed": 0, "gemm": 1, "qkv_bal": 2, "linear1": 3, "reduce_ln": 4, "sb_ln_gemm": 5, "sb_linear1": 6}
 DEV_WEIGHTS = {"in_proj": 0, "out_proj": 1, "linear2": 2, "predict": 3}
@@ -281,6 +284,7 @@ def load_library() -> C.CDLL:
     lib.vx_dev_dec_attn.argtypes = [ctx, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_float),
                                     P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
                                     P(C.c_int32)]
+    lib.vx_dev_switches.argtypes = [ctx, P(C.c_int32), C.c_int32]
     lib.vx_dev_dec_op.argtypes = [ctx, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_int32), P(C.c_int32), P(C.c_float), P(C.c_float),
                                   P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float)]
     lib.vx_dev_gemm.argtypes = [ctx, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), C.c_int32, C.c_int32, P(C.c_int32),
@@ -1411,13 +1415,21 @@ class Engine:
                                        _ptr(out, C.c_float), rows, C.byref(flag)))
         return out, flag.value
 
+    def dev_switches(self, n: int = None):
+        """vx_dev_switches: {name: value} of the kernel-selection fields the context read when it was finalized (DEV_SWITCHES;
+        include/vallex_hip_dev.h).  n: the words offered to the entry (default: as many as it reports)."""
+        n = len(DEV_SWITCHES) if n is None else int(n)
+        out = np.full(max(n, 1), DEV_SENTINEL_I, np.int32)
+        self._chk(self.lib.vx_dev_switches(self.ctx, _ptr(out, C.c_int32), n))
+        return {k: int(v) for k, v in zip(DEV_SWITCHES, out)}
+
     def dev_dec_attn(self, ctx_len, k_rows, v_rows, tmax: int, qkv=None, x_in=None, resid=None, active=None, slot_order=None,
                      qkv_balanced: bool = False, skp: int = 0, k_fill=0.0, v_fill=0.0):
         """vx_dev_dec_attn: the attention block of one decode step of layer 0 on chosen rows (include/vallex_hip_dev.h).
         ctx_len (n,): cached rows including the new token; k_rows / v_rows: per row the cached rows (ctx - 1, 16, 64) float32;
         k_fill / v_fill: what the rest of the row's arena stream, rows ctx - 1 .. tmax - 1, holds before the launch -- a scalar or per
         row an array that broadcasts to (16, tmax - ctx + 1, 64).  qkv (4 | 8, n, 3072) for the dec_attn chains, x_in (n, 1024) or
-        (9, n, 1024) for the 1 .. 4-row chain, resid (n, 1024).  Returns a dict: nsplit, sb_qkv, split_fused, out (4, n, 1024), xp_att
+        (9, n, 1024) for the sb_qkv chain, resid (n, 1024).  Returns a dict: nsplit, sb_qkv, split_fused, sb_chain, out (4, n, 1024), xp_att
         (n, 1024), part_ml (n, 16, 17, 2), k / v (n, 16, tmax, 64) after the launch and k0 / v0, the same streams before it."""
         cl = np.ascontiguousarray(ctx_len, np.int32)
         n = len(cl)
@@ -1453,11 +1465,11 @@ class Engine:
         out = np.empty((4, n, 1024), np.float32)
         xp_att = np.empty((n, 1024), np.float32)
         part_ml = np.empty((n, 16, 17, 2), np.float32)
-        geom = np.zeros(3, np.int32)
+        geom = np.zeros(4, np.int32)
         self._chk(self.lib.vx_dev_dec_attn(self.ctx, n, int(tmax), int(bool(qkv_balanced)), int(skp), _ptr(cl, C.c_int32), _ptr(act, C.c_int32),
                                            _ptr(order, C.c_int32), _ptr(k, C.c_float), _ptr(v, C.c_float), pq, px, pr, _ptr(out, C.c_float),
                                            _ptr(xp_att, C.c_float), _ptr(part_ml, C.c_float), _ptr(geom, C.c_int32)))
-        return dict(nsplit=int(geom[0]), sb_qkv=bool(geom[1]), split_fused=bool(geom[2]), out=out, xp_att=xp_att, part_ml=part_ml,
+        return dict(nsplit=int(geom[0]), sb_qkv=bool(geom[1]), split_fused=bool(geom[2]), sb_chain=bool(geom[3]), out=out, xp_att=xp_att, part_ml=part_ml,
                     k=k, v=v, k0=k0, v0=v0)
 
     def dev_dec_op(self, op: str, nrows: int, layer: int = 0, weight: str = None, sk: int = None, tok=None, pos=None, x=None,

@@ -773,8 +773,20 @@ int vx_dev_attn(vx_ctx* c, int32_t variant, int32_t planes, int32_t batch, const
   return VX_OK;
 }
 
+// vx_dev_switches: the kernel-selection fields finalize_weights read (weights.hip), in the order include/vallex_hip_dev.h documents
+int vx_dev_switches(vx_ctx* c, int32_t* out, int32_t n) {
+  if (!c) return VX_EINVAL;
+  if (!out || n < VX_DEV_SWITCHES) FAIL(VX_EINVAL, "vx_dev_switches: out must hold %d words", VX_DEV_SWITCHES);
+  if (!c->finalized) FAIL(VX_ESTATE, "vx_dev_switches: weights not finalized");
+  const int32_t v[VX_DEV_SWITCHES] = {c->sb_fuse, c->sb_qkv_rows, c->sb_qkv_nsplit, c->qkv_bal, c->fuse_out, c->fuse_split, c->att_nsplit_force,
+                                      c->balance_rows, c->nar_trim, c->graph_multi, c->gemm_mode, c->attn_x3, c->attn_h2, c->Tmax};
+  memcpy(out, v, sizeof v);
+  return VX_OK;
+}
+
 // vx_dev_dec_attn: the attention block of ONE decode step of layer 0 on caller-chosen operands -- the launch sequence of ar_step_launches
-// from the attention launch to the launch behind which the out_proj result exists, with the geometry decode_geometry picks for `nrows`.
+// from the attention launch to the launch behind which the out_proj result exists, with the geometry decode_geometry picks for `nrows`
+// under the context's switches (every chain of ar_step_launches: sb_qkv, the small-batch chain without the fused QKV, and the general one).
 // Everything the launches touch is private scratch pre-filled with the sentinels (the K / V arena included: [nrows slots][16][Tmax][64]);
 // the context only lends its layer-0 weights and its geometry switches, and the four geometry fields decode_geometry sets are put
 // back, so the decode state of the context is not touched.
@@ -811,10 +823,12 @@ int vx_dev_dec_attn(vx_ctx* c, int32_t nrows, int32_t Tmax, int32_t qkv_balanced
   const int nsplit = c->nsplit;
   const bool split_fused = c->split_fused, sb_chain = c->sb_chain, sb_qkv = c->sb_qkv;
   c->nsplit = k_nsplit; c->split_fused = k_sf; c->sb_chain = k_sbc; c->sb_qkv = k_sbq;
-  geom[0] = nsplit; geom[1] = sb_qkv; geom[2] = split_fused;
-  if (sb_chain && !sb_qkv) FAIL(VX_ESTATE, "vx_dev_dec_attn: the small-batch chain without the fused QKV (VX_SB_QKV) is not covered by this entry");
+  geom[0] = nsplit; geom[1] = sb_qkv; geom[2] = split_fused; geom[3] = sb_chain;
+  const bool sb_plain = sb_chain && !sb_qkv;                              // QKV GEMM | dec_attn partials | out_proj with the combine as prologue
   const bool fused = !sb_chain && c->fuse_out && (nsplit == 1 || split_fused);
-  if (sb_qkv ? !x_in : (!qkv || !resid)) FAIL(VX_EINVAL, "vx_dev_dec_attn: %s", sb_qkv ? "this chain reads x_in" : "this chain reads qkv and resid");
+  if (sb_qkv ? !x_in : (!qkv || (!resid && !sb_plain)))
+    FAIL(VX_EINVAL, "vx_dev_dec_attn: %s", sb_qkv ? "this chain reads x_in" : sb_plain ? "this chain reads qkv" : "this chain reads qkv and resid");
+  if (sb_plain && qkv_balanced) FAIL(VX_EINVAL, "vx_dev_dec_attn: the small-batch chain without the fused QKV reads four in_proj slabs, not the balanced layout");
   const LayerW& L = c->ar[0];
   if (fused && !L.out_wh) FAIL(VX_ESTATE, "vx_dev_dec_attn: the context has no head-major W_o");
   if ((split_fused && nsplit > 4) || nsplit > 16) FAIL(VX_ESTATE, "vx_dev_dec_attn: %d context splits exceed the scratch slabs", nsplit);
@@ -845,7 +859,7 @@ int vx_dev_dec_attn(vx_ctx* c, int32_t nrows, int32_t Tmax, int32_t qkv_balanced
       if (!sb_qkv) {
         const int slabs = qkv_balanced ? SK_QKV_BAL_Q : SK_QKV;
         for (int ks = 0; ks < slabs; ++ks) memcpy(&hf[f_qkv + ((size_t)ks * MB + r) * NP], qkv + ((size_t)ks * nrows + r) * NP, NP * 4);
-        memcpy(&hf[f_dh + (size_t)r * d], resid + (size_t)r * d, d * 4);
+        if (resid) memcpy(&hf[f_dh + (size_t)r * d], resid + (size_t)r * d, d * 4);
       } else if (skp == 0) {
         // the packed-x image (decode.hip ln_pack_row): float4 column c4 of row r at ((c4 >> 1) * 64 + r + 32 * (c4 & 1)) * 4
         for (int c4 = 0; c4 < d / 4; ++c4) memcpy(&hf[f_xp + (((size_t)(c4 >> 1) * 64) + r + 32 * (c4 & 1)) * 4], x_in + (size_t)r * d + 4 * c4, 16);
@@ -877,6 +891,10 @@ int vx_dev_dec_attn(vx_ctx* c, int32_t nrows, int32_t Tmax, int32_t qkv_balanced
     ok = launch_dec_attn_qkv(L.in_w, L.in_b, dk, dv, Tmax, d_meta, pt_o, pt_ml, qk_new, nsplit, nrows, skp ? p_o : nullptr, skp,
                              skp ? L.l2_b : nullptr, dh, dh2, L.n1_w, L.n1_b, xp, st);
     ok = ok && launch_skinny_gemm_sb_combine(L.out_wp, p_o, D_MODEL, SK_OUT, pt_o, pt_ml, nsplit + 1, nrows, st, qk_new);
+  } else if (sb_plain) {
+    // the engine's layer-0 sequence of this chain behind its QKV GEMM (ar_step_launches): the unfused kernel's nsplit partials, no qk_new
+    ok = launch_dec_attn(p_qkv, SK_QKV, L.in_b, dk, dv, Tmax, d_meta, xpa, pt_o, pt_ml, nsplit, nrows, nullptr, p_oh, st);
+    ok = ok && launch_skinny_gemm_sb_combine(L.out_wp, p_o, D_MODEL, SK_OUT, pt_o, pt_ml, nsplit, nrows, st, nullptr);
   } else if (!launch_dec_attn(p_qkv, qkv_balanced ? SK_QKV_BALANCED : SK_QKV, L.in_b, dk, dv, Tmax, d_meta, xpa, pt_o, pt_ml, nsplit, nrows,
                               fused ? L.out_wh : nullptr, p_oh, st)) {
     ok = false;
@@ -902,12 +920,12 @@ int vx_dev_dec_attn(vx_ctx* c, int32_t nrows, int32_t Tmax, int32_t qkv_balanced
   }
   TRYX(xfer_sync(c));
   TRY(hipGetLastError());
-  // outputs, indexed by row.  out [SK_OUT][nrows][1024]: the out_proj slabs of the small-batch chain; the other chains: out[0] = h
+  // outputs, indexed by row.  out [SK_OUT][nrows][1024]: the out_proj slabs of the small-batch chains; the other chains: out[0] = h
   const int np = sb_qkv ? nsplit + 1 : nsplit;
   for (size_t i = 0; i < (size_t)SK_OUT * nrows * d; ++i) out[i] = VX_DEV_SENTINEL_F;
   for (size_t i = 0; i < (size_t)nrows * N_HEAD * NPART * 2; ++i) part_ml[i] = VX_DEV_SENTINEL_F;
   for (int r = 0; r < nrows; ++r) {
-    if (sb_qkv)
+    if (sb_chain)
       for (int ks = 0; ks < SK_OUT; ++ks) memcpy(out + ((size_t)ks * nrows + r) * d, &of[f_po + ((size_t)ks * MB + r) * d], d * 4);
     else memcpy(out + (size_t)r * d, &of[f_dh + (size_t)r * d], d * 4);
     for (int c4 = 0; c4 < d / 4; ++c4) memcpy(xp_att + (size_t)r * d + 4 * c4, &of[f_xpa + (((size_t)(c4 >> 1) * 64) + r + 32 * (c4 & 1)) * 4], 16);
