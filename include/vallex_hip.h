@@ -654,6 +654,67 @@ int vx_psola(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t* l
              const int32_t* ratio /* may be NULL */, const vx_psola_opts* o, float* out, int64_t out_stride,
              int32_t* marks /* may be NULL */, int64_t marks_stride, vx_psola_info* info);
 
+/* Spectral noise suppression of mono fp32 rows on the device: an enrolment clip with hiss or fan noise is cleaned before it is
+ * cloned.  No reference counterpart.  A short-time Fourier analysis (frame N = 512, hop H = 128, B = 257 bins, square-root Hann
+ * window on both sides), a noise profile taken from the quietest frames of the row (or given by the caller), a floored spectral
+ * subtraction gain on a five-frame power average, and overlap-add.  All arithmetic is IEEE double and every named operation is
+ * rounded on its own (no fma), so that a plain numpy restatement reproduces every word:
+ *
+ * - Tables, built once on the host in double.  Window w[n] = sqrt(0.5 - 0.5 cos(2 pi n / N)), n = 0 .. 511.  Twiddles
+ *   c[k] = cos(2 pi k / N), s[k] = -sin(2 pi k / N), k = 0 .. 255.  vx_denoise_tables(double t[1024]) is a pure host function, needs
+ *   no context and reports the words the library uses: w [512], c [256], s [256].  Everything downstream is defined on these words.
+ * - Samples.  y[i] = isfinite(x[i]) ? x[i] : 0, and 0 outside [0, L).  `nonfinite` counts the non-finite samples of the row.
+ * - Frames.  A row of L samples has T = ceil(L / H) + 3 frames.  Frame t covers samples [(t - 3) H, (t - 3) H + N); every sample
+ *   lies in exactly four frames.  A frame is FULL if it lies wholly inside the row: t = 3 .. floor(L / H) - 1, F of them.
+ * - FFT.  Radix-2 decimation in time over 512 complex doubles, in place.  The input (double)y[(t - 3) H + n] * w[n], imaginary part
+ *   +0.0, is loaded in bit-reversed order.  Stages m = 2, 4 .. 512 with h = m / 2; butterfly j = 0 .. 255 has g = j / h, p = j % h,
+ *   i0 = g m + p, i1 = i0 + h, q = p (N / m), and computes tr = c[q] re[i1] - s[q] im[i1], ti = c[q] im[i1] + s[q] re[i1],
+ *   (re, im)[i0] = a + t, (re, im)[i1] = a - t, a the old value at i0: two products and one sum per component, each rounded.  The
+ *   inverse is the same network with s negated, then the real part times 1 / N.
+ * - Power and energy.  P[t][k] = re re + im im for k = 0 .. 256; E[t] is ONE LANE's sum of P[t][0 .. 256] from 0.0 in bin order.
+ * - Noise profile Nz [257].  noise_psd given: Nz = noise_psd, and K = 0 is reported.  Otherwise
+ *   K = min(max(kmin, floor((double)frac * (double)F)), F); the host chooses the K full frames smallest in the total order
+ *   (E[t], t); Nz[k] = (sum of P[t][k] over the chosen frames from 0.0 in ascending t) / (double)K.  With K = 0 (no full frame, or
+ *   kmin = 0 under a small frac) the profile is all zero.
+ * - Gain.  S[t][k] = ((((P[a][k] + P[b][k]) + P[t][k]) + P[d][k]) + P[e][k]) / 5.0 with a, b, d, e = t - 2, t - 1, t + 1, t + 2 clamped
+ *   to [0, T - 1].  g = S > 0 ? 1.0 - ((double)alpha * Nz[k]) / S : (double)floor; then g = g > floor ? g : floor.  Bin k > 256 takes
+ *   g[N - k]; both components of the spectrum are multiplied by g.
+ * - Synthesis.  y_t[n] = (re'[n] * (1.0 / N)) * w[n], re' the inverse network's real part.  For output sample i, acc = 0.0 and its
+ *   four frames are added in ascending t; out[i] = (float)(0.5 * acc).  With alpha = 0 the output is the input within one fp32 ulp.
+ * - Exactness.  No atomics.  Two calls give the same bits.  A row's bits depend neither on the batch nor on the launch windows.
+ *   Double division on the device is correctly rounded (vx_dev_denoise_div probes it); sqrt runs on the host alone.
+ * - State.  As vx_psola: it needs no weights, works while a serving session is open and touches no decode state.  Samples go
+ *   through the resampler's launch buffers and the pinned ring; the power table of one window (about 68 MB) is the stage's own
+ *   allocation, made by the first call and freed by vx_destroy.
+ * - Windows.  One launch holds VX_DENOISE_WINDOW (2^22) samples and at most 256 rows.  Rows are packed into launches in order.  A row
+ *   is not cut across launches: a longer row is refused (174 s at 24 kHz).
+ * - Refusals.  These return VX_EINVAL, launch nothing and write nothing, and the message names the field: a wrong struct_size;
+ *   alpha not finite or below 0; floor outside (0, 1]; frac outside [0, 1]; kmin below 0; NULL wav / lens / o / out / info;
+ *   batch <= 0; a length negative, above wav_stride, above out_stride or above VX_DENOISE_WINDOW; a noise_psd word that is not finite
+ *   or below 0.
+ *
+ *   wav [batch][wav_stride] fp32, lens [batch]; noise_psd (when given) [257] doubles, one profile for every row; out
+ *   [batch][out_stride] fp32, L samples per row; psd_out (when given) [batch][257] doubles, the profile every row was cleaned with;
+ *   info [batch].  Elements behind a row's end are not written. */
+#define VX_DENOISE_WINDOW (1 << 22)
+#define VX_DENOISE_N 512
+#define VX_DENOISE_HOP 128
+#define VX_DENOISE_BINS 257
+typedef struct vx_denoise_opts {
+  uint32_t struct_size;     /* = sizeof(vx_denoise_opts) */
+  float alpha;              /* over-subtraction factor, finite and >= 0 (0: the identity) */
+  float floor;              /* smallest gain, in (0, 1] */
+  float frac;               /* share of the full frames taken as noise, in [0, 1] */
+  int32_t kmin;             /* ... and at least this many of them, >= 0 */
+} vx_denoise_opts;
+typedef struct vx_denoise_info {
+  int32_t frames, full_frames, k, nonfinite;
+} vx_denoise_info;
+int vx_denoise_tables(double t[1024]);
+int vx_denoise(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t* lens, int32_t batch, const vx_denoise_opts* o,
+               const double* noise_psd /* may be NULL */, float* out, int64_t out_stride, double* psd_out /* may be NULL */,
+               vx_denoise_info* info);
+
 /* ---- step-level entries (kernel-level parity tests; same kernels as vx_infer) ---------------------------- */
 /* first ar_decoder.infer call (models/vallex.py:528-562): embeds, runs the prefix-LM prefill, fills the KV arena,
  * leaves the logits of the last row available.  batch <= 32. */

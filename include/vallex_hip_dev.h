@@ -468,6 +468,30 @@ int vx_dev_psola_table(vx_ctx* ctx, const float* wav, int32_t len, const int32_t
 #define VX_DEV_PSOLA_WINDOW_MIN 1024
 int vx_dev_psola_window(vx_ctx* ctx, int32_t samples);
 
+/* The FFT network of vx_denoise (csrc/denoise.hip: the device function both of its kernels run) on caller frames: re / im
+ * [nframes][512] doubles in natural order, loaded in bit-reversed order as the contract states; out_re / out_im [nframes][512].
+ * inverse = 0: the forward network.  inverse = 1: the network with s negated and both components times 1 / 512.  No window, no
+ * cleaning of the input words.  VX_EINVAL: a NULL pointer, nframes outside 1 .. VX_DEV_DENOISE_FFT_MAX, inverse not 0 or 1. */
+#define VX_DEV_DENOISE_FFT_MAX 1024
+int vx_dev_denoise_fft(vx_ctx* ctx, const double* re, const double* im, int32_t nframes, int32_t inverse, double* out_re, double* out_im);
+/* What the kernels behind vx_denoise computed of ONE row: P [T][257] and E [T] as denoise_power_kernel wrote them, sel [K] the chosen
+ * frames in ascending t as the profile kernel walked them (*n_sel = K; nothing with a noise_psd), gain [T][257] from the device
+ * function the synthesis kernel runs, read from the same P and profile.  T = ceil(len / 128) + 3; sel_cap must hold K (T always
+ * suffices).  The row goes through the same planner and window as vx_denoise.  VX_EINVAL, nothing written: a NULL pointer other than
+ * noise_psd, len < 0 or above VX_DEV_DENOISE_TABLE_MAX, options out of range, sel_cap below K. */
+#define VX_DEV_DENOISE_TABLE_MAX (1 << 20)
+int vx_dev_denoise_table(vx_ctx* ctx, const float* wav, int32_t len, const vx_denoise_opts* o, const double* noise_psd /* may be NULL */,
+                         double* P, double* E, int32_t* sel, int32_t sel_cap, int32_t* n_sel, double* gain);
+/* Samples one launch of vx_denoise holds, for later calls on this context: VX_DEV_DENOISE_WINDOW_MIN .. VX_DENOISE_WINDOW, or 0 for
+ * the default (VX_DENOISE_WINDOW).  A small window sends a ragged batch of short rows through several launches; the device buffers
+ * keep their size.  A row is never cut, so a row above the window is refused (VX_EINVAL naming lens).  VX_EINVAL, nothing changed,
+ * for any other value. */
+#define VX_DEV_DENOISE_WINDOW_MIN 3072
+int vx_dev_denoise_window(vx_ctx* ctx, int32_t samples);
+/* q[i] = a[i] / b[i], i in [0, n), by a kernel of csrc/denoise.hip under the flags of its gain: the probe of the contract's claim
+ * that double division on the device is correctly rounded.  VX_EINVAL: a NULL pointer, n outside 1 .. 65536. */
+int vx_dev_denoise_div(vx_ctx* ctx, const double* a, const double* b, int32_t n, double* q);
+
 #ifdef __cplusplus
 }
 #endif

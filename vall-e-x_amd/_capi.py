@@ -137,6 +137,16 @@ class vx_psola_info(C.Structure):
     _fields_ = [("marks", C.c_int32), ("voiced_marks", C.c_int32), ("grains", C.c_int32), ("gaps", C.c_int32), ("nonfinite", C.c_int32)]
 
 
+class vx_denoise_opts(C.Structure):
+    """options of vx_denoise (the noise suppression: over-subtraction, gain floor, share and least count of the noise frames)"""
+    _fields_ = [("struct_size", C.c_uint32), ("alpha", C.c_float), ("floor", C.c_float), ("frac", C.c_float), ("kmin", C.c_int32)]
+
+
+class vx_denoise_info(C.Structure):
+    """what vx_denoise did to one row"""
+    _fields_ = [("frames", C.c_int32), ("full_frames", C.c_int32), ("k", C.c_int32), ("nonfinite", C.c_int32)]
+
+
 # every symbol include/vallex_hip.h declares (tests/test_abi.py checks the library exports exactly these)
 ABI_VERSION = 6       # VX_ABI_VERSION of include/vallex_hip.h this binding was written against
 
@@ -146,14 +156,15 @@ SYMBOLS = ["vx_abi_version", "vx_create", "vx_destroy", "vx_last_error", "vx_syn
            "vx_fallback_reset", "vx_arith_mode", "vx_infer_continuous", "vx_serve_open", "vx_serve_submit", "vx_serve_run",
            "vx_serve_close", "vx_serve_submit_ex", "vx_serve_cancel", "vx_serve_submit_filtered", "vx_score", "vx_align", "vx_resample",
            "vx_finish", "vx_stretch", "vx_loudness_coeffs", "vx_loudness", "vx_finish_loud", "vx_limit_taps", "vx_limit",
-           "vx_finish_limited", "vx_psola"]
+           "vx_finish_limited", "vx_psola", "vx_denoise_tables", "vx_denoise"]
 # ... and include/vallex_hip_dev.h: measurement / kernel development, never called by the mirrors of the reference API
 DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kernel", "vx_bench_gemm", "vx_bench_attn",
                "vx_bench_gemm_clock", "vx_bench_gemm_epilogue", "vx_dev_sample", "vx_dev_attn", "vx_dev_sample_filtered",
                "vx_dev_dec_attn", "vx_dev_dec_op", "vx_dev_gemm", "vx_dev_layernorm", "vx_dev_score_rows", "vx_dev_align_rows", "vx_dev_wave_op",
                "vx_dev_seam_op", "vx_dev_resample_taps", "vx_dev_resample_window", "vx_dev_finish_frames", "vx_dev_finish_window",
                "vx_dev_stretch_window", "vx_dev_stretch_costs", "vx_dev_loudness_steps", "vx_dev_loudness_window",
-               "vx_dev_limit_gain", "vx_dev_limit_window", "vx_dev_psola_table", "vx_dev_psola_window", "vx_dev_switches"]
+               "vx_dev_limit_gain", "vx_dev_limit_window", "vx_dev_psola_table", "vx_dev_psola_window", "vx_dev_switches",
+               "vx_dev_denoise_fft", "vx_dev_denoise_table", "vx_dev_denoise_window", "vx_dev_denoise_div"]
 # the pitch tracker's entries, one of vallex_hip.h and two of vallex_hip_dev.h, in a list of their own: the header scan of
 # tests/test_abi.py matches names of letters and underscores, and these carry a digit (tests/test_f0_refs.py checks them)
 F0_SYMBOLS = ["vx_f0"]
@@ -196,6 +207,8 @@ LIMIT_WINDOW, DEV_LIMIT_WINDOW_MIN = 1 << 23, 8192          # VX_LIMIT_WINDOW / 
 F0_WINDOW, DEV_F0_WINDOW_MIN = 1 << 23, 3072                # VX_F0_WINDOW / VX_DEV_F0_WINDOW_MIN: samples per launch
 PSOLA_WINDOW, DEV_PSOLA_WINDOW_MIN = 1 << 23, 1024          # VX_PSOLA_WINDOW / VX_DEV_PSOLA_WINDOW_MIN: samples per launch
 PSOLA_RATIO_MIN, PSOLA_RATIO_MAX = 43691, 131072            # the Q16 ratios vx_psola takes: 2/3 .. 2
+DENOISE_WINDOW, DEV_DENOISE_WINDOW_MIN = 1 << 22, 3072      # VX_DENOISE_WINDOW / VX_DEV_DENOISE_WINDOW_MIN: samples per launch
+DENOISE_N, DENOISE_HOP, DENOISE_BINS = 512, 128, 257        # VX_DENOISE_N / _HOP / _BINS: frame, hop and bins of vx_denoise
 PCM_F32, PCM_S16 = 0, 1                                      # VX_PCM_*
 LEVEL_NONE, LEVEL_PEAK, LEVEL_RMS = 0, 1, 2                  # VX_LEVEL_*
 DEV_SAMPLE_CFG = ("kernel", "splitk", "top_k", "force_eos_at", "active", "n_gen", "cur_pos", "ctx_len", "text_len", "gen_stride")
@@ -337,6 +350,14 @@ def load_library() -> C.CDLL:
     lib.vx_dev_psola_table.argtypes = [ctx, P(C.c_float), C.c_int32, P(C.c_int32), P(C.c_int32), P(vx_psola_opts), P(C.c_double), C.c_int32,
                                        P(C.c_int32), C.c_int32, P(C.c_int32), P(C.c_int32)]
     lib.vx_dev_psola_window.argtypes = [ctx, C.c_int32]
+    lib.vx_denoise_tables.argtypes = [P(C.c_double)]
+    lib.vx_denoise.argtypes = [ctx, P(C.c_float), C.c_int64, P(C.c_int32), C.c_int32, P(vx_denoise_opts), P(C.c_double), P(C.c_float),
+                               C.c_int64, P(C.c_double), P(vx_denoise_info)]
+    lib.vx_dev_denoise_fft.argtypes = [ctx, P(C.c_double), P(C.c_double), C.c_int32, C.c_int32, P(C.c_double), P(C.c_double)]
+    lib.vx_dev_denoise_table.argtypes = [ctx, P(C.c_float), C.c_int32, P(vx_denoise_opts), P(C.c_double), P(C.c_double), P(C.c_double),
+                                         P(C.c_int32), C.c_int32, P(C.c_int32), P(C.c_double)]
+    lib.vx_dev_denoise_window.argtypes = [ctx, C.c_int32]
+    lib.vx_dev_denoise_div.argtypes = [ctx, P(C.c_double), P(C.c_double), C.c_int32, P(C.c_double)]
     lib.vx_dev_stretch_costs.argtypes = [ctx, P(C.c_float), C.c_int32, P(vx_stretch_opts), P(C.c_float), P(C.c_int32), P(C.c_double)]
     lib.vx_last_stats.argtypes = [ctx, P(C.c_int64), P(C.c_int64), P(C.c_double), P(C.c_double)]
     lib.vx_last_truncated.argtypes = [ctx, P(C.c_int32)]
@@ -1033,6 +1054,122 @@ class Engine:
         self._chk(self.lib.vx_dev_psola_window(self.ctx, int(samples)))
 
     @staticmethod
+    def denoise_tables() -> np.ndarray:
+        """vx_denoise_tables: the words the noise suppression computes with, float64 (1024,): the window w [512], then the twiddles
+        c [256] and s [256]"""
+        t = np.zeros(2 * DENOISE_N, np.float64)
+        load_library().vx_denoise_tables(_ptr(t, C.c_double))
+        return t
+
+    @staticmethod
+    def _denoise_opts(strength_db=None, floor_db=-18.0, frac=0.1, kmin=8, profile=None):
+        """(vx_denoise_opts, profile (257,) float64 or None) of a `denoise` call; every ValueError of it, before any launch.
+        alpha = 10^(strength_db / 10) (None: 2.0), floor = 10^(floor_db / 20)."""
+        try:
+            alpha = 2.0 if strength_db is None else 10.0 ** (float(strength_db) / 10.0)
+            fl = 10.0 ** (float(floor_db) / 20.0)
+        except OverflowError:
+            alpha = fl = math.inf
+        if not (math.isfinite(alpha) and 0.0 <= alpha <= 1e30):
+            raise ValueError(f"denoise: strength_db {strength_db!r} gives no finite over-subtraction factor")
+        if not (math.isfinite(fl) and float(np.float32(fl)) > 0.0 and fl <= 1.0):
+            raise ValueError(f"denoise: floor_db {floor_db!r} above 0 dB or too low for fp32 (the gain floor must lie in (0, 1])")
+        if not (math.isfinite(float(frac)) and 0.0 <= float(frac) <= 1.0):
+            raise ValueError(f"denoise: frac {frac!r} outside 0 .. 1")
+        if not 0 <= int(kmin) < 2 ** 31:
+            raise ValueError(f"denoise: kmin {kmin!r} below 0")
+        psd = None
+        if profile is not None:
+            psd = np.ascontiguousarray(profile, np.float64).reshape(-1)
+            if len(psd) != DENOISE_BINS or not np.isfinite(psd).all() or (psd < 0).any():
+                raise ValueError(f"denoise: a profile is {DENOISE_BINS} finite powers, none below 0 (Engine.noise_profile)")
+        return vx_denoise_opts(C.sizeof(vx_denoise_opts), alpha, fl, float(frac), int(kmin)), psd
+
+    @classmethod
+    def _denoise_parts(cls, denoise):
+        """the keyword arguments of `denoise` of a `denoise=` argument: True is the defaults, an object with the fields of
+        utils.generation.Denoise carries its own"""
+        if denoise is True:
+            return {}
+        if all(hasattr(denoise, f) for f in ("strength_db", "floor_db", "frac", "kmin", "profile")):
+            return dict(strength_db=denoise.strength_db, floor_db=denoise.floor_db, frac=denoise.frac, kmin=denoise.kmin,
+                        profile=denoise.profile)
+        raise ValueError(f"denoise {denoise!r}: None, True or a utils.generation.Denoise")
+
+    last_denoise_info = None         # the info dicts of the last `denoise` (also through a `denoise=` argument)
+
+    def denoise(self, wavs: Sequence[np.ndarray], strength_db=None, floor_db: float = -18.0, frac: float = 0.1, kmin: int = 8,
+                profile=None, return_profiles: bool = False):
+        """vx_denoise, spectral noise suppression of mono fp32 waveforms (L_i,) -> (rows, infos): rows float32 of L_i samples, infos
+        dicts with frames, full_frames, k and nonfinite (include/vallex_hip.h: vx_denoise_info).  Frames of 512 samples at a hop of
+        128; the noise profile of a row is the mean power of its k = max(kmin, frac * full_frames) quietest full frames, the gain of
+        a bin 1 - alpha * noise / (five-frame mean power), not below the floor.  strength_db: the over-subtraction alpha in dB of
+        power (None: alpha = 2); floor_db: the smallest gain.  profile (257 powers, `noise_profile`): used for every row in place of
+        the row's own -- what continuous speech needs, which has no quiet frames.  Steady noise (hiss, a fan) is assumed.
+        return_profiles: (rows, infos, profiles), the profile every row was cleaned with, float64 (257,)."""
+        o, psd = self._denoise_opts(strength_db, floor_db, frac, kmin, profile)
+        n = len(wavs)
+        if n == 0:
+            self.last_denoise_info = []
+            return ([], [], []) if return_profiles else ([], [])
+        buf, lens, stride = self._packed(wavs)
+        out = np.zeros((n, stride), np.float32)
+        prof = np.zeros((n, DENOISE_BINS), np.float64)
+        info = (vx_denoise_info * n)()
+        self._chk(self.lib.vx_denoise(self.ctx, _ptr(buf, C.c_float), stride, _ptr(lens, C.c_int32), n, C.byref(o),
+                                      None if psd is None else _ptr(psd, C.c_double), _ptr(out, C.c_float), stride, _ptr(prof, C.c_double),
+                                      info))
+        rows = [out[i, :L] for i, L in enumerate(lens)]
+        infos = [{fl[0]: getattr(w, fl[0]) for fl in vx_denoise_info._fields_} for w in info]
+        self.last_denoise_info = infos
+        return (rows, infos, [prof[i] for i in range(n)]) if return_profiles else (rows, infos)
+
+    def noise_profile(self, wav: np.ndarray, frac: float = 0.1, kmin: int = 8) -> np.ndarray:
+        """the noise profile `denoise` would take from this clip, float64 (257,): the mean power of its quietest full frames.  Taken
+        once from a clip with pauses (or, with frac=1.0, from a recording of the room alone), it is what `profile=` accepts."""
+        return self.denoise([wav], frac=frac, kmin=kmin, return_profiles=True)[2][0].copy()
+
+    def _denoised(self, rows, denoise):
+        """the rows of a `denoise=` argument (None: as they are)"""
+        if denoise is None:
+            return rows
+        return self.denoise(rows, **self._denoise_parts(denoise))[0]
+
+    def dev_denoise_fft(self, re: np.ndarray, im: np.ndarray, inverse: bool = False):
+        """vx_dev_denoise_fft: the network of the noise suppression on frames (n, 512) float64 -> (re, im); the inverse is scaled by
+        1 / 512"""
+        r = np.ascontiguousarray(re, np.float64).reshape(-1, DENOISE_N)
+        i = np.ascontiguousarray(im, np.float64).reshape(-1, DENOISE_N)
+        orr, oi = np.zeros_like(r), np.zeros_like(i)
+        self._chk(self.lib.vx_dev_denoise_fft(self.ctx, _ptr(r, C.c_double), _ptr(i, C.c_double), len(r), int(bool(inverse)),
+                                              _ptr(orr, C.c_double), _ptr(oi, C.c_double)))
+        return orr, oi
+
+    def dev_denoise_table(self, wav: np.ndarray, o: vx_denoise_opts, profile: Optional[np.ndarray] = None):
+        """vx_dev_denoise_table: (P (T, 257), E (T,), sel (K,) int32, gain (T, 257)) of one row as the kernels computed them"""
+        w = np.ascontiguousarray(wav, np.float32).reshape(-1)
+        T = -(-len(w) // DENOISE_HOP) + 3
+        P, E, g = np.zeros((T, DENOISE_BINS), np.float64), np.zeros(T, np.float64), np.zeros((T, DENOISE_BINS), np.float64)
+        sel, ns = np.zeros(T, np.int32), C.c_int32(0)
+        psd = None if profile is None else np.ascontiguousarray(profile, np.float64).reshape(-1)
+        self._chk(self.lib.vx_dev_denoise_table(self.ctx, _ptr(w if len(w) else np.zeros(1, np.float32), C.c_float), len(w), C.byref(o),
+                                                None if psd is None else _ptr(psd, C.c_double), _ptr(P, C.c_double), _ptr(E, C.c_double),
+                                                _ptr(sel, C.c_int32), T, C.byref(ns), _ptr(g, C.c_double)))
+        return P, E, sel[: ns.value], g
+
+    def dev_denoise_window(self, samples: int = 0):
+        """vx_dev_denoise_window: samples one launch of `denoise` holds from now on (DEV_DENOISE_WINDOW_MIN .. DENOISE_WINDOW; 0
+        restores the default)"""
+        self._chk(self.lib.vx_dev_denoise_window(self.ctx, int(samples)))
+
+    def dev_denoise_div(self, a: np.ndarray, b: np.ndarray) -> np.ndarray:
+        """vx_dev_denoise_div: a / b element by element, float64, by a kernel compiled with the noise suppression's"""
+        a, b = np.ascontiguousarray(a, np.float64).reshape(-1), np.ascontiguousarray(b, np.float64).reshape(-1)
+        q = np.zeros_like(a)
+        self._chk(self.lib.vx_dev_denoise_div(self.ctx, _ptr(a, C.c_double), _ptr(b, C.c_double), len(a), _ptr(q, C.c_double)))
+        return q
+
+    @staticmethod
     def _pitch_parts(pitch, formants=False, range=None):
         """(pitch, formants, range) of a `pitch=` argument: an object with the fields of utils.generation.Pitch carries all three"""
         if hasattr(pitch, "pitch") and hasattr(pitch, "formants"):
@@ -1129,12 +1266,16 @@ class Engine:
                                                  finish.max_gain_db, finish.fade_in, finish.fade_out, finish.pcm16)
         return out
 
-    def vocos_decode(self, codes: Sequence[np.ndarray], bandwidth_id: int = 2, sample_rate: int = 24000, finish=None, speed=None, pitch=None):
-        """speed (None: nothing runs): the decoded rows go through `stretch` at 24 kHz first; pitch (None: nothing runs): through `shift`
+    def vocos_decode(self, codes: Sequence[np.ndarray], bandwidth_id: int = 2, sample_rate: int = 24000, finish=None, speed=None, pitch=None,
+                     denoise=None):
+        """denoise (None: nothing runs; True or a utils.generation.Denoise): the decoded rows go through `denoise` first of all, directly
+        behind the vocoder.  speed (None: nothing runs): the decoded rows go through `stretch` at 24 kHz first; pitch (None: nothing runs): through `shift`
         instead, which takes the speed along; sample_rate other than 24000: then through `resample` (24000 -> sample_rate), one more
         launch; finish (a utils.generation.Finish): then through `finish` at that rate"""
         if pitch is not None:
             self._shift_plan(pitch, speed)                                # a ValueError comes before the vocoder runs
+        if denoise is not None:
+            self._denoise_opts(**self._denoise_parts(denoise))
         n = len(codes)
         lens = np.array([c.shape[0] for c in codes], np.int32)
         stride = max(1, int(lens.max()))
@@ -1146,13 +1287,15 @@ class Engine:
         audio = np.empty((n, stride * 320), np.float32)
         self._chk(self.lib.vx_vocos_decode(self.ctx, _ptr(buf, C.c_int64), stride, _ptr(lens, C.c_int32), n,
                                            int(bandwidth_id), _ptr(audio, C.c_float), stride * 320))
-        rows = self._stretched([audio[i, : lens[i] * 320] for i in range(n)], speed, pitch)
+        rows = self._stretched(self._denoised([audio[i, : lens[i] * 320] for i in range(n)], denoise), speed, pitch)
         return self._finished(rows if int(sample_rate) == 24000 else self.resample(rows, 24000, int(sample_rate)), finish, sample_rate)
 
-    def encodec_decode(self, codes: Sequence[np.ndarray], sample_rate: int = 24000, finish=None, speed=None, pitch=None):
-        """speed, pitch, sample_rate, finish: as vocos_decode (stretch or shift at 24 kHz, then resample, then finish)"""
+    def encodec_decode(self, codes: Sequence[np.ndarray], sample_rate: int = 24000, finish=None, speed=None, pitch=None, denoise=None):
+        """speed, pitch, sample_rate, finish, denoise: as vocos_decode (denoise, stretch or shift at 24 kHz, then resample, then finish)"""
         if pitch is not None:
             self._shift_plan(pitch, speed)                                # a ValueError comes before the vocoder runs
+        if denoise is not None:
+            self._denoise_opts(**self._denoise_parts(denoise))
         n = len(codes)
         lens = np.array([c.shape[0] for c in codes], np.int32)
         stride = max(1, int(lens.max()))
@@ -1162,8 +1305,8 @@ class Engine:
         audio = np.zeros((n, stride * 320), np.float32)
         self._chk(self.lib.vx_encodec_decode(self.ctx, _ptr(buf, C.c_int64), stride, _ptr(lens, C.c_int32), n,
                                              _ptr(audio, C.c_float), stride * 320))
-        if speed is not None or pitch is not None:
-            rows = self._stretched([audio[i, : lens[i] * 320] for i in range(n)], speed, pitch)
+        if speed is not None or pitch is not None or denoise is not None:
+            rows = self._stretched(self._denoised([audio[i, : lens[i] * 320] for i in range(n)], denoise), speed, pitch)
             return self._finished(rows if int(sample_rate) == 24000 else self.resample(rows, 24000, int(sample_rate)), finish, sample_rate)
         if int(sample_rate) != 24000:
             return self._finished(self.resample([audio[i, : lens[i] * 320] for i in range(n)], 24000, int(sample_rate)), finish, sample_rate)

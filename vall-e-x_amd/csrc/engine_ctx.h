@@ -195,6 +195,9 @@ struct vx_ctx {
   long f0_window = 0;              // samples per launch set by vx_dev_f0_window (0: the default, VX_F0_WINDOW)
   // formant-preserving pitch shift (vx_psola, psola.hip): runs in the resampler's launch buffers (rs_buffers) alone; needs no weights
   long ps_window = 0;              // samples per launch set by vx_dev_psola_window (0: the default, VX_PSOLA_WINDOW)
+  // noise suppression (vx_denoise, denoise.hip): samples in the resampler's launch buffers (rs_buffers); needs no weights
+  double* dn_buf = nullptr;        // the stage's own tables, allocated by the first call: w, stage twiddles, P, E, profiles, chosen frames
+  long dn_window = 0;              // samples per launch set by vx_dev_denoise_window (0: the default, VX_DENOISE_WINDOW)
 
   // graph
   hipGraphExec_t graph_exec = nullptr, graph_exec_n = nullptr;   // one decode step / GRAPH_STEPS steps per launch

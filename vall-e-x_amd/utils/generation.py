@@ -250,6 +250,40 @@ class Pitch:
         return f"Pitch({self.pitch!r}, formants={self.formants}, range={self.range!r})"
 
 
+@dataclass(eq=False)
+class Denoise:
+    """A noise-suppression request with chosen values, accepted wherever `denoise=` is (True there means these defaults):
+    strength_db, the over-subtraction in dB of power (None: a factor of 2); floor_db, the smallest gain; frac and kmin, the share and
+    the least count of a clip's quietest full frames its noise profile is taken from; profile, a stored profile (257 powers,
+    Engine.noise_profile) used in place of the clip's own -- what continuous speech needs, which has no quiet frames.  Every
+    ValueError is raised here."""
+
+    strength_db: Optional[float] = None
+    floor_db: float = -18.0
+    frac: float = 0.1
+    kmin: int = 8
+    profile: Optional[np.ndarray] = None
+
+    def __post_init__(self):
+        if self.profile is not None:
+            self.profile = np.array(self.profile, np.float64).reshape(-1)
+        from .._capi import Engine
+        Engine._denoise_opts(self.strength_db, self.floor_db, self.frac, self.kmin, self.profile)
+
+
+def _denoised(wavs, denoise):
+    """the 24 kHz waveforms of a vocoder call through `denoise` (None: as they are), directly behind the vocoder"""
+    if denoise is None:
+        return wavs
+    return model.engine._denoised(wavs, denoise)
+
+
+def _check_denoise(denoise):
+    """the ValueError of a `denoise` argument that Engine.denoise would refuse, before anything is synthesised"""
+    if denoise is not None:
+        model.engine._denoise_opts(**model.engine._denoise_parts(denoise))
+
+
 def _at_speed(wavs, speed, pitch=None):
     """the 24 kHz waveforms of a vocoder call at `speed` (None: as they are): one vx_stretch call for the list, before the resampler;
     with `pitch` (None: as they are): Engine.shift, the stretch at the combined speed and the p -> q resample, for the list"""
@@ -293,7 +327,8 @@ def _infer_one(text, audio_prompts, text_prompts, lang_pr, language, accent, **k
     return out, phone_tokens
 
 
-def generate_audio(text, prompt=None, language="auto", accent="no-accent", sample_rate=None, finish=None, speed=None, pitch=None, **kw):
+def generate_audio(text, prompt=None, language="auto", accent="no-accent", sample_rate=None, finish=None, speed=None, pitch=None,
+                   denoise=None, **kw):
     """utils/generation.py:92-152.  sample_rate (no reference counterpart; None = 24 kHz, the reference's): the waveform is resampled
     on the device (Engine.resample, vx_resample) to that rate.  finish (a `Finish`; None = the raw fp32 of the reference): the output
     stage behind it -- trim, level, fades, int16 with pcm16=True.  speed (a float, a Fraction or a (num, den) pair in 1/2 .. 2; None =
@@ -302,10 +337,13 @@ def generate_audio(text, prompt=None, language="auto", accent="no-accent", sampl
     1/2 .. 2; None = the pitch the model produced): a pitch shift that keeps the duration (Engine.shift: the stretch at speed / ratio,
     then a resample by the ratio), in place of the stretch.  It moves the formants with the pitch: meant for a few semitones.  A
     `Pitch` (pitch, formants=True, range=None) keeps the formants instead (the pitch tracker, then the PSOLA shift: vx_f0, vx_psola)
-    and can scale the intonation's range; it is accepted wherever `pitch=` is."""
+    and can scale the intonation's range; it is accepted wherever `pitch=` is.  denoise (None = the waveform as the vocoder gave it;
+    True or a `Denoise`): spectral noise suppression on the device (Engine.denoise, vx_denoise) directly behind the vocoder, before
+    speed, pitch, resample and finish -- for a preset that was enrolled from a noisy clip."""
     if model is None or vocos is None:
         raise RuntimeError("call preload_models() first")
     _check_pitch(pitch, speed)
+    _check_denoise(denoise)
     if isinstance(text, str):
         text = text.replace("\n", "").strip(" ")
     language = _detect(text, language)
@@ -323,6 +361,8 @@ def generate_audio(text, prompt=None, language="auto", accent="no-accent", sampl
     samples = vocos.decode(features, bandwidth_id=np.array([2]))
     s = samples.squeeze()
     s = s.cpu().numpy() if torch is not None and isinstance(s, torch.Tensor) else np.asarray(s)
+    if denoise is not None:
+        s = _denoised([s.reshape(-1)], denoise)[0]
     if speed is not None or pitch is not None:
         return _finished(_to_rate(_at_speed([s.reshape(-1)], speed, pitch), sample_rate), finish, sample_rate)[0]
     if finish is not None:
@@ -331,7 +371,7 @@ def generate_audio(text, prompt=None, language="auto", accent="no-accent", sampl
 
 
 def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent", text_languages=None, sample_rate=None, finish=None,
-                         speed=None, pitch=None, **kw):
+                         speed=None, pitch=None, denoise=None, **kw):
     """Batch form of `generate_audio` (no reference equivalent: the reference synthesises one utterance per call,
     utils/generation.py:92-152): utterance i of the batch equals `generate_audio(texts[i], prompts[i], language[i], accent)`.
     `texts`: strings (need the tokenizer hook) or phoneme-id arrays; `prompts`: one preset name / path / None per utterance (or
@@ -342,10 +382,12 @@ def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent
     utterance i.  `sample_rate` (None = 24 kHz): the waveforms are resampled on the device in one more launch.  `finish` (a
     `Finish`): the output stage behind it, one more call for the list.  `speed` (None = as produced): the speaking rate, one vx_stretch
     call for the list before both.  `pitch` (None = as produced): the pitch shift of `generate_audio`, Engine.shift for the list in
-    place of the stretch.  Returns a list of float32 waveforms (int16 with pcm16=True)."""
+    place of the stretch.  `denoise` (None = as produced): the noise suppression of `generate_audio`, one Engine.denoise call for the
+    list directly behind Vocos.  Returns a list of float32 waveforms (int16 with pcm16=True)."""
     if model is None or vocos is None:
         raise RuntimeError("call preload_models() first")
     _check_pitch(pitch, speed)
+    _check_denoise(denoise)
     n = len(texts)
     prompts = list(prompts) if isinstance(prompts, (list, tuple)) else [prompts] * n
     langs_in = list(language) if isinstance(language, (list, tuple)) else [language] * n
@@ -354,7 +396,7 @@ def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent
             for text, prompt, lang_in, tl in zip(texts, prompts, langs_in, text_languages)]
     codes = model.inference_batch(rows, top_k=-100, temperature=1, **kw)
     return model.engine.vocos_decode(codes, 2, sample_rate=SAMPLE_RATE if sample_rate is None else int(sample_rate), finish=finish,
-                                     speed=speed, pitch=pitch)
+                                     speed=speed, pitch=pitch, denoise=denoise)
 
 
 def _utterance_row(text, prompt, lang_in, accent, tl=None) -> dict:
@@ -393,9 +435,10 @@ class AudioServer:
     waveform behind Vocos (vx_resample is allowed while the session is open).  `finish` (a `Finish`): ONE output stage for the server,
     applied behind that (vx_finish is allowed as well).  `speed` (None = as produced): ONE speaking rate for the server, applied to
     every delivered waveform between Vocos and the resampler (vx_stretch is allowed as well).  `pitch` (None = as produced): ONE pitch
-    shift for the server (generate_audio's `pitch`), applied there in place of the stretch."""
+    shift for the server (generate_audio's `pitch`), applied there in place of the stretch.  `denoise` (None = as produced): ONE noise
+    suppression for the server (generate_audio's `denoise`), applied directly behind Vocos (vx_denoise is allowed as well)."""
 
-    def __init__(self, sample_rate=None, finish=None, speed=None, pitch=None, **serve_kw):
+    def __init__(self, sample_rate=None, finish=None, speed=None, pitch=None, denoise=None, **serve_kw):
         if model is None or vocos is None:
             raise RuntimeError("call preload_models() first")
         rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
@@ -406,9 +449,11 @@ class AudioServer:
         self.speed = speed
         _check_pitch(pitch, speed)
         self.pitch = pitch
+        _check_denoise(denoise)
+        self.denoise = denoise
         self._server = model.serve(top_k=-100, temperature=1.0,
                                    post=lambda codes: model.engine.vocos_decode(codes, 2, sample_rate=rate, finish=finish, speed=speed,
-                                                                                pitch=pitch),
+                                                                                pitch=pitch, denoise=denoise),
                                    **serve_kw)
 
     def submit(self, text, prompt=None, language="auto", accent="no-accent", best_of=1, seed=None, uniforms=None,
@@ -433,12 +478,14 @@ class AudioServer:
 
 
 def generate_audio_from_long_text(text, prompt=None, language="auto", accent="no-accent", mode="sliding-window", sample_rate=None,
-                                  finish=None, speed=None, pitch=None, **kw):
+                                  finish=None, speed=None, pitch=None, denoise=None, **kw):
     """utils/generation.py:155-276.  `text` may also be a list of sentences / id arrays (pre-split).  sample_rate, finish, speed,
-    pitch: as generate_audio (the stretch or the shift and the output stage see the concatenated waveform once)."""
+    pitch, denoise: as generate_audio (the noise suppression, the stretch or the shift and the output stage see the concatenated
+    waveform once)."""
     if model is None or vocos is None:
         raise RuntimeError("call preload_models() first")
     _check_pitch(pitch, speed)
+    _check_denoise(denoise)
     if prompt is None or prompt == "":
         prompt = None
         mode = "sliding-window"                                        # :162-163: overrides ANY mode, also an unknown one
@@ -485,6 +532,8 @@ def generate_audio_from_long_text(text, prompt=None, language="auto", accent="no
     samples = vocos.decode(features, bandwidth_id=np.array([2]))
     s = samples.squeeze()
     s = s.cpu().numpy() if torch is not None and isinstance(s, torch.Tensor) else np.asarray(s)
+    if denoise is not None:
+        s = _denoised([s.reshape(-1)], denoise)[0]
     if speed is not None or pitch is not None:
         return _finished(_to_rate(_at_speed([s.reshape(-1)], speed, pitch), sample_rate), finish, sample_rate)[0]
     if finish is not None:

@@ -132,12 +132,23 @@ def shift_pitch(wav: np.ndarray, pitch) -> np.ndarray:
     return np.array(G.model.engine.shift([wav.reshape(-1)], pitch)[0], np.float32)[None]
 
 
+def suppress_noise(wav: np.ndarray, denoise) -> np.ndarray:
+    """(1, L) mono fp32 -> the clip with its steady noise (hiss, a fan) suppressed, same length, on the loaded model's engine
+    (Engine.denoise: vx_denoise).  A zero-shot model clones the recording, not only the voice: the noise of an enrolment clip would be
+    in every utterance.  denoise: True for the defaults, or a utils.generation.Denoise (chosen values, or a stored noise profile -- what
+    a clip of continuous speech needs, which has no quiet frames to take one from)."""
+    if G.model is None:
+        raise RuntimeError("call preload_models() first: denoise runs on the loaded model's engine")
+    return np.array(G.model.engine._denoised([wav.reshape(-1)], denoise)[0], np.float32)[None]
+
+
 def tokenize_audio(tokenizer: AudioTokenizer, audio: Union[str, Tuple[np.ndarray, int]], trim_db: Optional[float] = None,
-                   lufs: Optional[float] = None, pitch=None):
+                   lufs: Optional[float] = None, pitch=None, denoise=None):
     """data/tokenizer.py:99-111: (path | (wav (C, L), sr)) -> `tokenizer.encode(wav[None])` = [(codes (1, 8, T), None)].
     trim_db (no reference counterpart; None = the clip as it is): `trim_silence` on the 24 kHz mono clip before the encoder sees it.
     lufs (no reference counterpart; None = the clip's own level): `level_loudness` on that clip, after the trim.
-    pitch (no reference counterpart; None = the clip's own pitch): `shift_pitch` on the 24 kHz mono clip, before the trim."""
+    pitch (no reference counterpart; None = the clip's own pitch): `shift_pitch` on the 24 kHz mono clip, before the trim.
+    denoise (no reference counterpart; None = the clip as recorded): `suppress_noise` on the mono clip, first of all."""
     wav, sr = _load_wav(audio) if isinstance(audio, str) else audio
     wav = np.asarray(wav.detach().cpu().numpy() if hasattr(wav, "detach") else wav, np.float32)
     if wav.ndim == 1:
@@ -146,6 +157,8 @@ def tokenize_audio(tokenizer: AudioTokenizer, audio: Union[str, Tuple[np.ndarray
         wav = wav.mean(0, keepdims=True)
     if sr != tokenizer.sample_rate:
         wav = np.asarray((resampler or _builtin_resampler())(wav, int(sr), tokenizer.sample_rate), np.float32)
+    if denoise is not None:
+        wav = suppress_noise(wav, denoise)
     if pitch is not None:
         if tokenizer.sample_rate != 24000:
             raise ValueError(f"pitch: Engine.shift works at 24 kHz, the tokenizer at {tokenizer.sample_rate}")
@@ -175,11 +188,13 @@ def make_transcript(name, wav, sr, transcript: Optional[str] = None):
 
 
 def make_prompt(name: str, audio_prompt_path: Union[str, Tuple[np.ndarray, int]], transcript: Optional[str] = None,
-                save_dir: Optional[str] = None, trim_db: Optional[float] = None, lufs: Optional[float] = None, pitch=None) -> str:
+                save_dir: Optional[str] = None, trim_db: Optional[float] = None, lufs: Optional[float] = None, pitch=None,
+                denoise=None) -> str:
     """utils/prompt_making.py:57-84.  `audio_prompt_path`: a WAV path or `(wav (C, L), sr)`.  Returns the path of the written .npz.
     trim_db: as `tokenize_audio` (leading and trailing silence of the clip is cut before it is encoded); lufs: as `tokenize_audio`
     (the clip is brought to that loudness, after the trim, before it is encoded); pitch: as `tokenize_audio` (the clip is shifted by
-    that many semitones, or that ratio, before the trim: the cloned voice follows its prompt)."""
+    that many semitones, or that ratio, before the trim: the cloned voice follows its prompt); denoise: as `tokenize_audio` (the
+    clip's steady noise is suppressed first of all, so that it is not cloned with the voice)."""
     global codec
     if G.model is None:
         raise RuntimeError("call preload_models() first (with EnCodec weights: model.load_encodec_state_dict)")
@@ -194,7 +209,7 @@ def make_prompt(name: str, audio_prompt_path: Union[str, Tuple[np.ndarray, int]]
     if wav_pr.shape[0] == 2:                                      # :62-63
         wav_pr = wav_pr.mean(0, keepdims=True)
     text_pr, lang_pr = make_transcript(name, wav_pr, sr, transcript)
-    encoded_frames = tokenize_audio(codec, (wav_pr, sr), trim_db=trim_db, lufs=lufs, pitch=pitch)          # :67
+    encoded_frames = tokenize_audio(codec, (wav_pr, sr), trim_db=trim_db, lufs=lufs, pitch=pitch, denoise=denoise)          # :67
     codes = encoded_frames[0][0]
     codes = codes.numpy() if hasattr(codes, "numpy") else np.asarray(codes)
     audio_tokens = np.transpose(codes, (0, 2, 1))                 # (1, T, 8)   (:68)
