@@ -561,15 +561,7 @@ class Engine:
         n = len(wavs)
         if n == 0:
             return []
-        ws = [np.ascontiguousarray(w, np.float32).reshape(-1) for w in wavs]
-        lens = np.array([len(w) for w in ws], np.int32)
-        stride = max(1, int(lens.max()))
-        if n == 1:
-            buf = ws[0] if len(ws[0]) else np.zeros(1, np.float32)        # no second copy of a single (long) row
-        else:
-            buf = np.zeros((n, stride), np.float32)
-            for i, w in enumerate(ws):
-                buf[i, : len(w)] = w
+        buf, lens, stride = self._packed(wavs)
         g = math.gcd(int(orig_rate), int(new_rate)) if int(orig_rate) > 0 and int(new_rate) > 0 else 1
         ostride = max(1, -(-(int(new_rate) // g) * stride // max(1, int(orig_rate) // g)))
         out = np.empty((n, ostride), np.float32)
@@ -593,7 +585,16 @@ class Engine:
     def dev_resample_window(self, input_samples: int = 0):
         """vx_dev_resample_window: input samples one launch of `resample` holds from now on (DEV_RESAMPLE_WINDOW_MIN ..
         RESAMPLE_WINDOW; 0 restores the default)"""
-        self._chk(self.lib.vx_dev_resample_window(self.ctx, int(input_samples)))
+        self._dev_window("resample", input_samples)
+
+    def _dev_window(self, name, value):
+        """vx_dev_<name>_window: the samples one launch of the stage holds from now on"""
+        self._chk(getattr(self.lib, f"vx_dev_{name}_window")(self.ctx, int(value)))
+
+    @staticmethod
+    def _dicts(struct_array):
+        """the structs of a ctypes array as dicts, field by field"""
+        return [{f[0]: getattr(w, f[0]) for f in w._fields_} for w in struct_array]
 
     def finish(self, wavs: Sequence[np.ndarray], frame: int, silence_db: float = -40.0, trim: int = 0, keep: int = 0, level_mode: int = 0,
                level_db: float = -1.0, max_gain_db: float = 20.0, fade_in: int = 0, fade_out: int = 0, pcm16: bool = False):
@@ -603,36 +604,48 @@ class Engine:
         peak / the RMS over the active frames to level_db dBFS with at most max_gain_db of gain; fade_in / fade_out samples of
         smoothstep; pcm16: int16 (round half to even, clamped) instead of float32.  Non-finite samples count as 0.  info: begin, end,
         active_frames, nonfinite, clipped, peak, gain, mean_square (include/vallex_hip.h: vx_wave_info)."""
-        return self._finish(wavs, frame, silence_db, trim, keep, level_mode, level_db, max_gain_db, fade_in, fade_out, pcm16, False)
+        return self._finish((frame, silence_db, trim, keep, level_mode, level_db, max_gain_db, fade_in, fade_out, pcm16), wavs)
 
     def measure(self, wavs: Sequence[np.ndarray], frame: int, silence_db: float = -40.0):
         """the info dicts of `finish` alone (vx_finish without an output: nothing is scaled or brought back): [begin, end) is the span
         from the first to the last active frame (trim = 3, keep = 0; 0, 0 for an all-silent row), peak the peak inside it; active_frames,
         nonfinite and mean_square say what the row holds; gain 1, clipped 0"""
-        return self._finish(wavs, frame, silence_db, 3, 0, 0, -1.0, 20.0, 0, 0, False, True)[1]
+        return self._finish((frame, silence_db, 3, 0, 0, -1.0, 20.0, 0, 0, False), wavs, measure_only=True)[1]
 
-    def _finish(self, wavs, frame, silence_db, trim, keep, level_mode, level_db, max_gain_db, fade_in, fade_out, pcm16, measure_only):
+    def _finish(self, fin, wavs, loud=None, lim=None, measure_only=False):
+        """the three entries of the output stage: fin = the fields of vx_finish_opts behind struct_size, the format as pcm16; loud =
+        (sample_rate, lufs, ceiling_db): vx_finish_loud; with lim = (lookahead, oversample): vx_finish_limited.  A frame / lookahead
+        of None is 10 ms / 5 ms at the sample rate.  -> (rows, info dicts); the loudness and limiter dicts go to last_loudness_info and
+        last_limit_info.  measure_only: no output, ([], infos)."""
         n = len(wavs)
         if n == 0:
+            if loud is not None:
+                self.last_loudness_info = []
+            if lim is not None:
+                self.last_limit_info = []
             return [], []
-        ws = [np.ascontiguousarray(w, np.float32).reshape(-1) for w in wavs]
-        lens = np.array([len(w) for w in ws], np.int32)
-        stride = max(1, int(lens.max()))
-        if n == 1:
-            buf = ws[0] if len(ws[0]) else np.zeros(1, np.float32)        # no second copy of a single (long) row
-        else:
-            buf = np.zeros((n, stride), np.float32)
-            for i, w in enumerate(ws):
-                buf[i, : len(w)] = w
-        o = vx_finish_opts(C.sizeof(vx_finish_opts), int(frame), float(silence_db), int(trim), int(keep), int(level_mode), float(level_db),
-                           float(max_gain_db), int(fade_in), int(fade_out), PCM_S16 if pcm16 else PCM_F32)
-        info = (vx_wave_info * n)()
+        buf, lens, stride = self._packed(wavs)
+        frame, silence_db, trim, keep, level_mode, level_db, max_gain_db, fade_in, fade_out, pcm16 = fin
+        opts = [vx_finish_opts(C.sizeof(vx_finish_opts), int(loud[0]) // 100 if frame is None else int(frame), float(silence_db), int(trim), int(keep),
+                               int(level_mode), float(level_db), float(max_gain_db), int(fade_in), int(fade_out), PCM_S16 if pcm16 else PCM_F32)]
+        infos, entry = [(vx_wave_info * n)()], self.lib.vx_finish
+        if loud is not None:
+            opts.append(vx_loudness_opts(C.sizeof(vx_loudness_opts), int(loud[0]), float(loud[1]), float(loud[2])))
+            infos.append((vx_loudness_info * n)())
+            entry = self.lib.vx_finish_loud
+        if lim is not None:
+            opts.append(vx_limit_opts(C.sizeof(vx_limit_opts), int(loud[0]) // 200 if lim[0] is None else int(lim[0]), int(lim[1])))
+            infos.append((vx_limit_info * n)())
+            entry = self.lib.vx_finish_limited
         out = None if measure_only else np.empty((n, stride), np.int16 if pcm16 else np.float32)
         out_lens = np.zeros(n, np.int32)
-        self._chk(self.lib.vx_finish(self.ctx, _ptr(buf, C.c_float), stride, _ptr(lens, C.c_int32), n, C.byref(o),
-                                     None if out is None else out.ctypes.data_as(C.c_void_p), stride, _ptr(out_lens, C.c_int32), info))
-        infos = [{f[0]: getattr(w, f[0]) for f in vx_wave_info._fields_} for w in info]
-        return ([] if out is None else [out[i, : out_lens[i]] for i in range(n)]), infos
+        self._chk(entry(self.ctx, _ptr(buf, C.c_float), stride, _ptr(lens, C.c_int32), n, *[C.byref(o) for o in opts],
+                        None if out is None else out.ctypes.data_as(C.c_void_p), stride, _ptr(out_lens, C.c_int32), *infos))
+        if loud is not None:
+            self.last_loudness_info = self._dicts(infos[1])
+        if lim is not None:
+            self.last_limit_info = self._dicts(infos[2])
+        return ([] if out is None else [out[i, : out_lens[i]] for i in range(n)]), self._dicts(infos[0])
 
     def dev_finish_frames(self, wav: np.ndarray, frame: int):
         """vx_dev_finish_frames: the frame table of one row as the measure kernel wrote it: (e float64, p float32, z int32)"""
@@ -647,7 +660,7 @@ class Engine:
     def dev_finish_window(self, input_samples: int = 0):
         """vx_dev_finish_window: input samples one launch of `finish` holds from now on (DEV_FINISH_WINDOW_MIN .. FINISH_WINDOW; 0
         restores the default)"""
-        self._chk(self.lib.vx_dev_finish_window(self.ctx, int(input_samples)))
+        self._dev_window("finish", input_samples)
 
     @staticmethod
     def _stretch_opts(speed, hop, search, sample_rate) -> vx_stretch_opts:
@@ -675,15 +688,7 @@ class Engine:
         if n == 0:
             return ([], []) if return_positions else []
         o = self._stretch_opts(speed, hop, search, sample_rate)
-        ws = [np.ascontiguousarray(w, np.float32).reshape(-1) for w in wavs]
-        lens = np.array([len(w) for w in ws], np.int32)
-        stride = max(1, int(lens.max()))
-        if n == 1:
-            buf = ws[0] if len(ws[0]) else np.zeros(1, np.float32)        # no second copy of a single (long) row
-        else:
-            buf = np.zeros((n, stride), np.float32)
-            for i, w in enumerate(ws):
-                buf[i, : len(w)] = w
+        buf, lens, stride = self._packed(wavs)
         num, den = max(1, o.speed_num), max(1, o.speed_den)
         ostride = max(1, -(-stride * den // num))
         pstride = max(1, -(-ostride // max(1, o.hop)))
@@ -715,7 +720,7 @@ class Engine:
     def dev_stretch_window(self, input_samples: int = 0):
         """vx_dev_stretch_window: input samples one launch of `stretch` holds from now on (DEV_STRETCH_WINDOW_MIN .. STRETCH_WINDOW; 0
         restores the default)"""
-        self._chk(self.lib.vx_dev_stretch_window(self.ctx, int(input_samples)))
+        self._dev_window("stretch", input_samples)
 
     @staticmethod
     def _packed(wavs):
@@ -751,7 +756,7 @@ class Engine:
         buf, lens, stride = self._packed(wavs)
         info = (vx_loudness_info * n)()
         self._chk(self.lib.vx_loudness(self.ctx, _ptr(buf, C.c_float), stride, _ptr(lens, C.c_int32), n, int(sample_rate), info))
-        return [{f[0]: getattr(w, f[0]) for f in vx_loudness_info._fields_} for w in info]
+        return self._dicts(info)
 
     def finish_loud(self, wavs: Sequence[np.ndarray], sample_rate: int, lufs: float, ceiling_db: float = -1.0, frame: Optional[int] = None,
                     silence_db: float = -40.0, trim: int = 0, keep: int = 0, max_gain_db: float = 20.0, fade_in: int = 0, fade_out: int = 0,
@@ -760,21 +765,8 @@ class Engine:
         LUFS (BS.1770, measured over that span at `sample_rate`) with at most max_gain_db of gain and a sample peak of at most
         ceiling_db dBFS.  frame None = 10 ms (sample_rate // 100); trim, keep, fades and pcm16 as in `finish`.  Returns (list of arrays,
         list of info dicts); the loudness dicts of the rows (as `loudness` on the kept spans) stay in `last_loudness_info`."""
-        n = len(wavs)
-        if n == 0:
-            self.last_loudness_info = []
-            return [], []
-        buf, lens, stride = self._packed(wavs)
-        o = vx_finish_opts(C.sizeof(vx_finish_opts), int(sample_rate) // 100 if frame is None else int(frame), float(silence_db), int(trim),
-                           int(keep), LEVEL_NONE, -1.0, float(max_gain_db), int(fade_in), int(fade_out), PCM_S16 if pcm16 else PCM_F32)
-        lo = vx_loudness_opts(C.sizeof(vx_loudness_opts), int(sample_rate), float(lufs), float(ceiling_db))
-        info, linfo = (vx_wave_info * n)(), (vx_loudness_info * n)()
-        out = np.empty((n, stride), np.int16 if pcm16 else np.float32)
-        out_lens = np.zeros(n, np.int32)
-        self._chk(self.lib.vx_finish_loud(self.ctx, _ptr(buf, C.c_float), stride, _ptr(lens, C.c_int32), n, C.byref(o), C.byref(lo),
-                                          out.ctypes.data_as(C.c_void_p), stride, _ptr(out_lens, C.c_int32), info, linfo))
-        self.last_loudness_info = [{f[0]: getattr(w, f[0]) for f in vx_loudness_info._fields_} for w in linfo]
-        return [out[i, : out_lens[i]] for i in range(n)], [{f[0]: getattr(w, f[0]) for f in vx_wave_info._fields_} for w in info]
+        return self._finish((frame, silence_db, trim, keep, LEVEL_NONE, -1.0, max_gain_db, fade_in, fade_out, pcm16), wavs,
+                            (sample_rate, lufs, ceiling_db))
 
     def dev_loudness_steps(self, wav: np.ndarray, sample_rate: int) -> np.ndarray:
         """vx_dev_loudness_steps: the step table of one row as the steps kernel wrote it (float64, one K-weighted energy per 100 ms)"""
@@ -789,7 +781,7 @@ class Engine:
     def dev_loudness_window(self, samples: int = 0):
         """vx_dev_loudness_window: samples one launch of the steps pass holds from now on (DEV_LOUDNESS_WINDOW_MIN .. LOUDNESS_WINDOW; 0
         restores the default); a call whose 3 S exceeds it is refused"""
-        self._chk(self.lib.vx_dev_loudness_window(self.ctx, int(samples)))
+        self._dev_window("loudness", samples)
 
     def limit_taps(self, oversample: int) -> np.ndarray:
         """vx_limit_taps: the taps the detector of `limit` interpolates with, (oversample, 15) float32 -- the resampler's table of the
@@ -801,10 +793,6 @@ class Engine:
         return t[: n if n > 1 else 0]
 
     last_limit_info = None           # the limiter dicts of the last `finish_limited` (also through a `finish=` LimitedFinish)
-
-    @staticmethod
-    def _limit_dicts(info):
-        return [{f[0]: getattr(w, f[0]) for f in vx_limit_info._fields_} for w in info]
 
     def limit(self, wavs: Sequence[np.ndarray], ceiling_db: float = -1.0, pre_gain: float = 1.0, lookahead: int = 120, oversample: int = 4):
         """vx_limit, a true-peak look-ahead limiter of mono fp32 waveforms (L_i,): every row times pre_gain, then held under ceiling_db
@@ -821,7 +809,7 @@ class Engine:
         out = np.empty((n, stride), np.float32)
         self._chk(self.lib.vx_limit(self.ctx, _ptr(buf, C.c_float), stride, _ptr(lens, C.c_int32), n, float(pre_gain), float(ceiling_db),
                                     C.byref(o), _ptr(out, C.c_float), stride, info))
-        return [out[i, : lens[i]] for i in range(n)], self._limit_dicts(info)
+        return [out[i, : lens[i]] for i in range(n)], self._dicts(info)
 
     def true_peak(self, wavs: Sequence[np.ndarray], oversample: int = 4):
         """the measure-only call of vx_limit: a list of dicts with peak = the `oversample`-times interpolated (true) peak of every row,
@@ -833,7 +821,7 @@ class Engine:
         o = vx_limit_opts(C.sizeof(vx_limit_opts), 1, int(oversample))
         info = (vx_limit_info * n)()
         self._chk(self.lib.vx_limit(self.ctx, _ptr(buf, C.c_float), stride, _ptr(lens, C.c_int32), n, 1.0, 0.0, C.byref(o), None, 0, info))
-        return self._limit_dicts(info)
+        return self._dicts(info)
 
     def finish_limited(self, wavs: Sequence[np.ndarray], sample_rate: int, lufs: float, ceiling_db: float = -1.0, lookahead: Optional[int] = None,
                        oversample: int = 4, frame: Optional[int] = None, silence_db: float = -40.0, trim: int = 0, keep: int = 0,
@@ -842,25 +830,8 @@ class Engine:
         row is brought to `lufs` LUFS with at most max_gain_db of gain, then held under ceiling_db dBTP by `limit` (lookahead None = 5 ms,
         sample_rate // 200), then faded and formatted.  Returns (list of arrays, list of info dicts; `gain` is the loudness gain); the
         loudness dicts stay in `last_loudness_info`, the limiter dicts in `last_limit_info`.  measure_only: no output, ([], infos)."""
-        n = len(wavs)
-        if n == 0:
-            self.last_loudness_info, self.last_limit_info = [], []
-            return [], []
-        buf, lens, stride = self._packed(wavs)
-        o = vx_finish_opts(C.sizeof(vx_finish_opts), int(sample_rate) // 100 if frame is None else int(frame), float(silence_db), int(trim),
-                           int(keep), LEVEL_NONE, -1.0, float(max_gain_db), int(fade_in), int(fade_out), PCM_S16 if pcm16 else PCM_F32)
-        lo = vx_loudness_opts(C.sizeof(vx_loudness_opts), int(sample_rate), float(lufs), float(ceiling_db))
-        lim = vx_limit_opts(C.sizeof(vx_limit_opts), int(sample_rate) // 200 if lookahead is None else int(lookahead), int(oversample))
-        info, linfo, minfo = (vx_wave_info * n)(), (vx_loudness_info * n)(), (vx_limit_info * n)()
-        out = None if measure_only else np.empty((n, stride), np.int16 if pcm16 else np.float32)
-        out_lens = np.zeros(n, np.int32)
-        self._chk(self.lib.vx_finish_limited(self.ctx, _ptr(buf, C.c_float), stride, _ptr(lens, C.c_int32), n, C.byref(o), C.byref(lo),
-                                             C.byref(lim), None if out is None else out.ctypes.data_as(C.c_void_p), stride,
-                                             _ptr(out_lens, C.c_int32), info, linfo, minfo))
-        self.last_loudness_info = [{f[0]: getattr(w, f[0]) for f in vx_loudness_info._fields_} for w in linfo]
-        self.last_limit_info = self._limit_dicts(minfo)
-        rows = [] if out is None else [out[i, : out_lens[i]] for i in range(n)]
-        return rows, [{f[0]: getattr(w, f[0]) for f in vx_wave_info._fields_} for w in info]
+        return self._finish((frame, silence_db, trim, keep, LEVEL_NONE, -1.0, max_gain_db, fade_in, fade_out, pcm16), wavs,
+                            (sample_rate, lufs, ceiling_db), (lookahead, oversample), measure_only)
 
     def dev_limit_gain(self, wav: np.ndarray, pre_gain: float = 1.0, ceiling_db: float = -1.0, lookahead: int = 120, oversample: int = 4):
         """vx_dev_limit_gain: (P, g) of one row as the limiter kernel wrote them (float32: the detector readings and the gains)"""
@@ -875,7 +846,7 @@ class Engine:
     def dev_limit_window(self, samples: int = 0):
         """vx_dev_limit_window: samples one launch of the limiter holds from now on (DEV_LIMIT_WINDOW_MIN .. LIMIT_WINDOW; 0 restores
         the default)"""
-        self._chk(self.lib.vx_dev_limit_window(self.ctx, int(samples)))
+        self._dev_window("limit", samples)
 
     @staticmethod
     def _f0_opts(sample_rate, hop, window, fmin, fmax, threshold) -> vx_f0_opts:
@@ -915,7 +886,7 @@ class Engine:
         self._chk(self.lib.vx_f0(self.ctx, _ptr(buf, C.c_float), stride, _ptr(lens, C.c_int32), n, C.byref(o), _ptr(f, C.c_float),
                                  _ptr(lag, C.c_int32), _ptr(ap, C.c_float), fstride, info))
         ms = [-(-int(L) // o.hop) for L in lens]
-        infos = [{fl[0]: getattr(w, fl[0]) for fl in vx_f0_info._fields_} for w in info]
+        infos = self._dicts(info)
         return [f[i, :m] for i, m in enumerate(ms)], [lag[i, :m] for i, m in enumerate(ms)], [ap[i, :m] for i, m in enumerate(ms)], infos
 
     def dev_f0_table(self, wav: np.ndarray, o: vx_f0_opts):
@@ -931,7 +902,7 @@ class Engine:
 
     def dev_f0_window(self, samples: int = 0):
         """vx_dev_f0_window: samples one launch of `f0` holds from now on (DEV_F0_WINDOW_MIN .. F0_WINDOW; 0 restores the default)"""
-        self._chk(self.lib.vx_dev_f0_window(self.ctx, int(samples)))
+        self._dev_window("f0", samples)
 
     @staticmethod
     def pitch_ratio(pitch) -> Fraction:
@@ -1029,7 +1000,7 @@ class Engine:
                                     None if rat is None else _ptr(rat, C.c_int32), C.byref(o), _ptr(out, C.c_float), stride,
                                     None if marks is None else _ptr(marks, C.c_int32), mstride, info))
         rows = [out[i, :L] for i, L in enumerate(lens)]
-        infos = [{fl[0]: getattr(w, fl[0]) for fl in vx_psola_info._fields_} for w in info]
+        infos = self._dicts(info)
         if return_marks:
             return rows, infos, [marks[i, : infos[i]["marks"] + 1] for i in range(n)]
         return rows, infos
@@ -1051,7 +1022,7 @@ class Engine:
     def dev_psola_window(self, samples: int = 0):
         """vx_dev_psola_window: samples one launch of `psola` holds from now on (DEV_PSOLA_WINDOW_MIN .. PSOLA_WINDOW; 0 restores the
         default)"""
-        self._chk(self.lib.vx_dev_psola_window(self.ctx, int(samples)))
+        self._dev_window("psola", samples)
 
     @staticmethod
     def denoise_tables() -> np.ndarray:
@@ -1120,7 +1091,7 @@ class Engine:
                                       None if psd is None else _ptr(psd, C.c_double), _ptr(out, C.c_float), stride, _ptr(prof, C.c_double),
                                       info))
         rows = [out[i, :L] for i, L in enumerate(lens)]
-        infos = [{fl[0]: getattr(w, fl[0]) for fl in vx_denoise_info._fields_} for w in info]
+        infos = self._dicts(info)
         self.last_denoise_info = infos
         return (rows, infos, [prof[i] for i in range(n)]) if return_profiles else (rows, infos)
 
@@ -1160,7 +1131,7 @@ class Engine:
     def dev_denoise_window(self, samples: int = 0):
         """vx_dev_denoise_window: samples one launch of `denoise` holds from now on (DEV_DENOISE_WINDOW_MIN .. DENOISE_WINDOW; 0
         restores the default)"""
-        self._chk(self.lib.vx_dev_denoise_window(self.ctx, int(samples)))
+        self._dev_window("denoise", samples)
 
     def dev_denoise_div(self, a: np.ndarray, b: np.ndarray) -> np.ndarray:
         """vx_dev_denoise_div: a / b element by element, float64, by a kernel compiled with the noise suppression's"""

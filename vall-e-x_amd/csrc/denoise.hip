@@ -25,7 +25,7 @@
 // broadcast -- the table c[q] itself would be read at a stride of 256 / h doubles (8-way at h = 32).
 // LDS: 4 x 4 KiB (re, im, the two twiddle tables) + 2 KiB (gains or powers) = 18.1 KiB a workgroup: 8 workgroups fit a CU's 160 KiB
 // and fill its 32 wave slots.
-#include "engine_ctx.h"
+#include "wave_stage.h"
 #include "denoise_host.h"
 
 #include "../../include/vallex_hip_dev.h"
@@ -246,18 +246,15 @@ static int dn_buffers(vx_ctx* c) {
 }
 
 // every check of vx_denoise behind the pointers: options, lengths, strides, the profile
-static int dn_check(vx_ctx* c, const char* who, int64_t wav_stride, const int32_t* lens, int batch, const vx_denoise_opts* o,
-                    const double* psd, int64_t out_stride) {
+static int dn_check(vx_ctx* c, const char* who, const int32_t* lens, int batch, const vx_denoise_opts* o, const double* psd, int64_t out_stride) {
   CHECK_STRUCT(*o, vx_denoise_opts);
   char why[160];
   if (dn_check_opts(*o, why, sizeof why)) FAIL(VX_EINVAL, "%s: %s", who, why);
-  const long win = c->dn_window ? c->dn_window : (long)VX_DENOISE_WINDOW;
-  for (int i = 0; i < batch; ++i) {
-    const long L = lens[i];
-    if (L < 0 || L > wav_stride) FAIL(VX_EINVAL, "%s: lens[%d] = %ld outside 0 .. wav_stride %ld", who, i, L, (long)wav_stride);
-    if (L > win) FAIL(VX_EINVAL, "%s: lens[%d] = %ld above the window of %ld samples (VX_DENOISE_WINDOW): a row is not cut", who, i, L, win);
-    if (L > out_stride) FAIL(VX_EINVAL, "%s: out_stride %ld below the %ld samples of row %d", who, (long)out_stride, L, i);
-  }
+  const long win = wave_window(c->dn_window, VX_DENOISE_WINDOW);
+  for (int i = 0; i < batch; ++i)
+    if (lens[i] > win)
+      FAIL(VX_EINVAL, "%s: lens[%d] = %ld above the window of %ld samples (VX_DENOISE_WINDOW): a row is not cut", who, i, (long)lens[i], win);
+  if (int e = wave_check_out_stride(c, who, lens, batch, out_stride, "")) return e;
   if (psd && !dn_psd_ok(psd)) FAIL(VX_EINVAL, "%s: noise_psd holds a word that is not finite or below 0", who);
   return VX_OK;
 }
@@ -267,7 +264,7 @@ static int dn_check(vx_ctx* c, const char* who, int64_t wav_stride, const int32_
 static int dn_run(vx_ctx* c, const char* who, const float* wav, int64_t wav_stride, const int32_t* lens, int batch, const vx_denoise_opts& o,
                   const double* psd, float* out, int64_t out_stride, double* psd_out, vx_denoise_info* info, double* tP, double* tE,
                   int32_t* tsel, long tsel_cap, int32_t* n_sel, double* tgain) {
-  const long win = c->dn_window ? c->dn_window : (long)VX_DENOISE_WINDOW;
+  const long win = wave_window(c->dn_window, VX_DENOISE_WINDOW);
   std::vector<DnJob> jobs;
   if (!dn_plan(lens, batch, win, dn_frame_cap(win), DN_MAX_JOBS, &jobs))
     FAIL(VX_EINVAL, "%s: a row in lens is above the window of %ld samples (vx_dev_denoise_window)", who, win);
@@ -355,13 +352,11 @@ int vx_denoise(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_t* l
                const double* noise_psd, float* out, int64_t out_stride, double* psd_out, vx_denoise_info* info) {
   using namespace vxe;
   if (!c) return VX_EINVAL;
-  if (!wav) FAIL(VX_EINVAL, "vx_denoise: wav is NULL");
-  if (!lens) FAIL(VX_EINVAL, "vx_denoise: lens is NULL");
+  if (int e = wave_check_rows(c, "vx_denoise", wav, wav_stride, lens, batch)) return e;
   if (!o) FAIL(VX_EINVAL, "vx_denoise: o is NULL");
   if (!out) FAIL(VX_EINVAL, "vx_denoise: out is NULL");
   if (!info) FAIL(VX_EINVAL, "vx_denoise: info is NULL");
-  if (batch <= 0) FAIL(VX_EINVAL, "vx_denoise: batch %d below 1", batch);
-  if (int e = dn_check(c, "vx_denoise", wav_stride, lens, batch, o, noise_psd, out_stride)) return e;
+  if (int e = dn_check(c, "vx_denoise", lens, batch, o, noise_psd, out_stride)) return e;
   return dn_run(c, "vx_denoise", wav, wav_stride, lens, batch, *o, noise_psd, out, out_stride, psd_out, info, nullptr, nullptr, nullptr, 0,
                 nullptr, nullptr);
 }
@@ -376,7 +371,7 @@ int vx_dev_denoise_table(vx_ctx* c, const float* wav, int32_t len, const vx_deno
   if (len < 0 || len > VX_DEV_DENOISE_TABLE_MAX) FAIL(VX_EINVAL, "vx_dev_denoise_table: len %d outside 0 .. %d", len, VX_DEV_DENOISE_TABLE_MAX);
   if (sel_cap < 0) FAIL(VX_EINVAL, "vx_dev_denoise_table: sel_cap %d below 0", sel_cap);
   const int64_t big = 0x7fffffffL;
-  if (int e = dn_check(c, "vx_dev_denoise_table", big, &len, 1, o, noise_psd, big)) return e;
+  if (int e = dn_check(c, "vx_dev_denoise_table", &len, 1, o, noise_psd, big)) return e;
   std::vector<float> y((size_t)len + 1);
   vx_denoise_info info;
   return dn_run(c, "vx_dev_denoise_table", wav, len, &len, 1, *o, noise_psd, y.data(), big, nullptr, &info, P, E, sel, sel_cap, n_sel, gain);
@@ -408,13 +403,7 @@ int vx_dev_denoise_fft(vx_ctx* c, const double* re, const double* im, int32_t nf
 }
 
 int vx_dev_denoise_window(vx_ctx* c, int32_t samples) {
-  using namespace vxe;
-  if (!c) return VX_EINVAL;
-  if (samples != 0 && (samples < VX_DEV_DENOISE_WINDOW_MIN || samples > VX_DENOISE_WINDOW))
-    FAIL(VX_EINVAL, "vx_dev_denoise_window: samples %d outside %d .. %d (0 restores the default)", samples, VX_DEV_DENOISE_WINDOW_MIN,
-         VX_DENOISE_WINDOW);
-  c->dn_window = samples;
-  return VX_OK;
+  return vxe::wave_set_window(c, &vx_ctx::dn_window, "vx_dev_denoise_window", "samples", samples, VX_DEV_DENOISE_WINDOW_MIN, VX_DENOISE_WINDOW);
 }
 
 int vx_dev_denoise_div(vx_ctx* c, const double* a, const double* b, int32_t n, double* q) {

@@ -512,13 +512,7 @@ inline void reset_call_stats(vx_ctx* c) {      // what vx_last_stats / vx_last_t
 // schedule.hip: entry points that overwrite the decode state refuse to run while a serving session owns it; vx_destroy frees an open one
 int serve_busy(vx_ctx* c, const char* what);
 void serve_free(vx_serve* v);
-// resample.hip: the launch buffers of the waveform entries, allocated by the first call that needs them and shared by vx_resample and
-// vx_finish (a context is single-threaded): rs_in RS_IN_CAP floats, rs_out RS_OUT_CAP floats, rs_meta RS_MAX_JOBS records of RS_TAB ints
-constexpr int RS_TAB = 8;                  // ints of a job record
-constexpr int RS_MAX_JOBS = 4096;          // jobs per launch (grid.y)
-constexpr long RS_IN_CAP = VX_RESAMPLE_WINDOW;          // input samples per launch, default
-constexpr long RS_OUT_CAP = 2 * RS_IN_CAP;              // output samples per launch
-int rs_buffers(vx_ctx* c);
+// (the launch buffers of the waveform entries and what else their translation units share: wave_stage.h)
 // score.hip: (log-probability, rank) of targets[r] in logits[r][0 .. ncols-1], one wavefront per row
 void launch_score_rows(const float* logits, int ld, int rows, int ncols, const int* targets, float* logp, int* rank, hipStream_t s);
 

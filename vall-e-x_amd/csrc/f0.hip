@@ -18,7 +18,7 @@
 // lane t of the frame reads y[j] as a broadcast and y[j + t] at stride 1 across the lanes (8-byte reads: no bank conflict).  d and d'
 // stay in LDS: lane 0 of the frame walks the prefix, all lanes divide, lane 0 picks.
 // LDS per frame: (W + lag_max + 2 (lag_max + 1)) doubles -- 40 976 bytes at the largest options, 11.2 KiB at W 600, lag_max 400.
-#include "engine_ctx.h"
+#include "wave_stage.h"
 #include "f0_host.h"
 
 #include "../../include/vallex_hip_dev.h"
@@ -115,15 +115,13 @@ __global__ __launch_bounds__(256) void f0_frames_kernel(const float* __restrict_
 }
 
 // every check of vx_f0 behind the pointers: options, lengths, the frame stride
-static int f0_check(vx_ctx* c, const char* who, int64_t wav_stride, const int32_t* lens, int batch, const vx_f0_opts* o, int64_t frame_stride,
-                    F0Geom* g) {
+static int f0_check(vx_ctx* c, const char* who, const int32_t* lens, int batch, const vx_f0_opts* o, int64_t frame_stride, F0Geom* g) {
   CHECK_STRUCT(*o, vx_f0_opts);
   char why[160];
   if (f0_check_opts(*o, why, sizeof why)) FAIL(VX_EINVAL, "%s: %s", who, why);
   *g = f0_geometry(*o);
   for (int i = 0; i < batch; ++i) {
     const long L = lens[i];
-    if (L < 0 || L > wav_stride) FAIL(VX_EINVAL, "%s: lens[%d] = %ld outside 0 .. wav_stride %ld", who, i, L, (long)wav_stride);
     if (f0_frames(*g, L) > frame_stride)
       FAIL(VX_EINVAL, "%s: frame_stride %ld below the %ld frames of row %d", who, (long)frame_stride, f0_frames(*g, L), i);
   }
@@ -133,7 +131,7 @@ static int f0_check(vx_ctx* c, const char* who, int64_t wav_stride, const int32_
 // plan, then one launch per group of jobs, everything of a launch behind one stream sync.  dtab / dptab: one row only.
 static int f0_run(vx_ctx* c, const char* who, const float* wav, int64_t wav_stride, const int32_t* lens, int batch, const F0Geom& g, float* f0,
                   int32_t* lag, float* ap, int64_t frame_stride, double* dtab, double* dptab) {
-  const long win = c->f0_window ? c->f0_window : (long)VX_F0_WINDOW;
+  const long win = wave_window(c->f0_window, VX_F0_WINDOW);
   const int R = g.W + g.T, T1 = g.T + 1;
   const long fcap = dtab ? std::min(F0_FRAME_CAP, F0_TABLE_CAP / T1) : F0_FRAME_CAP;
   std::vector<F0Job> jobs;
@@ -152,9 +150,7 @@ static int f0_run(vx_ctx* c, const char* who, const float* wav, int64_t wav_stri
   double* od = reinterpret_cast<double*>(c->rs_out + F0_TABLE_AT);
   double* odp = od + F0_TABLE_CAP;
   std::vector<int> tab;
-  for (size_t j0 = 0; j0 < jobs.size();) {
-    size_t j1 = j0;
-    while (j1 < jobs.size() && jobs[j1].launch == jobs[j0].launch) ++j1;
+  return wave_launches(c, jobs, [&](size_t j0, size_t j1) -> int {
     tab.clear();
     long blocks = 0;
     for (size_t k = j0; k < j1; ++k) {
@@ -179,11 +175,8 @@ static int f0_run(vx_ctx* c, const char* who, const float* wav, int64_t wav_stri
         D2H(dptab + j.k0 * T1, odp + j.f_off * T1, nf * T1 * sizeof(double));
       }
     }
-    SYNC();
-    HIPCHK(hipGetLastError());
-    j0 = j1;
-  }
-  return VX_OK;
+    return VX_OK;
+  });
 }
 
 }  // namespace vxe
@@ -194,15 +187,13 @@ int vx_f0(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_t* lens, 
           float* ap, int64_t frame_stride, vx_f0_info* info) {
   using namespace vxe;
   if (!c) return VX_EINVAL;
-  if (!wav) FAIL(VX_EINVAL, "vx_f0: wav is NULL");
-  if (!lens) FAIL(VX_EINVAL, "vx_f0: lens is NULL");
+  if (int e = wave_check_rows(c, "vx_f0", wav, wav_stride, lens, batch)) return e;
   if (!o) FAIL(VX_EINVAL, "vx_f0: o is NULL");
   if (!f0) FAIL(VX_EINVAL, "vx_f0: f0 is NULL");
   if (!lag) FAIL(VX_EINVAL, "vx_f0: lag is NULL");
   if (!info) FAIL(VX_EINVAL, "vx_f0: info is NULL");
-  if (batch <= 0) FAIL(VX_EINVAL, "vx_f0: batch %d below 1", batch);
   F0Geom g;
-  if (int e = f0_check(c, "vx_f0", wav_stride, lens, batch, o, frame_stride, &g)) return e;
+  if (int e = f0_check(c, "vx_f0", lens, batch, o, frame_stride, &g)) return e;
   if (int e = f0_run(c, "vx_f0", wav, wav_stride, lens, batch, g, f0, lag, ap, frame_stride, nullptr, nullptr)) return e;
   for (int i = 0; i < batch; ++i) {
     const float* x = wav + (long)i * wav_stride;
@@ -220,7 +211,7 @@ int vx_dev_f0_table(vx_ctx* c, const float* wav, int32_t len, const vx_f0_opts* 
   if (len < 0) FAIL(VX_EINVAL, "vx_dev_f0_table: len %d below 0", len);
   F0Geom g;
   const int64_t big = 0x7fffffffL;
-  if (int e = f0_check(c, "vx_dev_f0_table", len, &len, 1, o, big, &g)) return e;
+  if (int e = f0_check(c, "vx_dev_f0_table", &len, 1, o, big, &g)) return e;
   const size_t M = (size_t)f0_frames(g, len);
   std::vector<float> f(M + 1), a(M + 1);
   std::vector<int32_t> l(M + 1);
@@ -228,12 +219,7 @@ int vx_dev_f0_table(vx_ctx* c, const float* wav, int32_t len, const vx_f0_opts* 
 }
 
 int vx_dev_f0_window(vx_ctx* c, int32_t samples) {
-  using namespace vxe;
-  if (!c) return VX_EINVAL;
-  if (samples != 0 && (samples < VX_DEV_F0_WINDOW_MIN || samples > VX_F0_WINDOW))
-    FAIL(VX_EINVAL, "vx_dev_f0_window: samples %d outside %d .. %d (0 restores the default)", samples, VX_DEV_F0_WINDOW_MIN, VX_F0_WINDOW);
-  c->f0_window = samples;
-  return VX_OK;
+  return vxe::wave_set_window(c, &vx_ctx::f0_window, "vx_dev_f0_window", "samples", samples, VX_DEV_F0_WINDOW_MIN, VX_F0_WINDOW);
 }
 
 }  // extern "C"

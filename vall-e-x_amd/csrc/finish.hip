@@ -17,8 +17,12 @@
 // grid (tile, job).  A measure tile stages `fpt` whole frames into LDS with coalesced loads at a frame stride of F | 1 floats -- odd,
 // so the lanes of a 32-lane LDS group, which read consecutive FRAMES at the same offset, fall on 32 different banks -- and lane t then
 // walks frame t.  An apply tile is FN_TILE consecutive elements, lane-contiguous loads and stores.
-#include "engine_ctx.h"
-#include "finish_host.h"
+//
+// The three entries of the output stage -- vx_finish here, vx_finish_loud (loudness.hip), vx_finish_limited (limit.hip) -- check their
+// pointers and run ONE pipeline, fn_pipeline below: frames -> spans -> [steps -> gain] -> [limiter] -> apply -> infos.
+#include "wave_stage.h"
+#include "loudness_host.h"
+#include "limit_host.h"
 
 #include "../../include/vallex_hip_dev.h"
 
@@ -108,12 +112,11 @@ __global__ __launch_bounds__(256) void wave_apply_kernel(const float* __restrict
   if (tid == 0 && clip_s) atomicAdd(tb + 6, clip_s);
 }
 
-static long fn_win(const vx_ctx* c, int F) { return std::max<long>(c->fn_window ? c->fn_window : (long)VX_FINISH_WINDOW, F); }
+static long fn_win(const vx_ctx* c, int F) { return std::max<long>(wave_window(c->fn_window, VX_FINISH_WINDOW), F); }
 
-// the measure pass: the frame table of every row, row i at table[f0[i] ..).  resident: the whole batch went through ONE launch, and
-// row i's samples still lie at rs_in + base[i].  (fn_measure and fn_apply are shared with vx_finish_loud, loudness.hip, and vx_finish_limited, limit.hip.)
+// the measure pass (wave_stage.h)
 int fn_measure(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_t* lens, int batch, int F, std::vector<FnFrame>& table,
-                      std::vector<long>& f0, bool* resident, std::vector<long>& base) {
+               std::vector<long>& f0, bool* resident, std::vector<long>& base) {
   std::vector<long> lo(batch, 0), hi(batch);
   f0.assign(batch + 1, 0);
   base.assign(batch, 0);
@@ -128,9 +131,7 @@ int fn_measure(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_t* l
   const int stride = F | 1, fpt = std::max(1, std::min(256, FN_LDS / stride));
   FnFrame* ft = reinterpret_cast<FnFrame*>(c->rs_out);
   std::vector<int> tab;
-  for (size_t j0 = 0; j0 < jobs.size();) {
-    size_t j1 = j0;
-    while (j1 < jobs.size() && jobs[j1].launch == jobs[j0].launch) ++j1;
+  return wave_launches(c, jobs, [&](size_t j0, size_t j1) -> int {
     tab.clear();
     long max_f = 0;
     for (size_t k = j0; k < j1; ++k) {
@@ -147,11 +148,8 @@ int fn_measure(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_t* l
       const FnJob& j = jobs[k];
       D2H(table.data() + f0[j.row] + j.s_lo / F, ft + j.f_off, (size_t)fn_nframes(j.cnt, F) * sizeof(FnFrame));
     }
-    SYNC();
-    HIPCHK(hipGetLastError());
-    j0 = j1;
-  }
-  return VX_OK;
+    return VX_OK;
+  });
 }
 
 // the two device fade tables, rebuilt when a length changes
@@ -170,9 +168,9 @@ static int fn_fades(vx_ctx* c, int fade_in, int fade_out) {
   return VX_OK;
 }
 
-// src (with resident): the device buffer the rows lie in, row i's sample 0 at src + base[i]; nullptr: rs_in
-int fn_apply(vx_ctx* c, const float* wav, int64_t wav_stride, int batch, const vx_finish_opts& o, bool resident,
-                    const std::vector<long>& base, void* out, int64_t out_stride, vx_wave_info* info, const float* src) {
+// the apply pass (wave_stage.h)
+int fn_apply(vx_ctx* c, const float* wav, int64_t wav_stride, int batch, const vx_finish_opts& o, bool resident, const std::vector<long>& base,
+             void* out, int64_t out_stride, vx_wave_info* info, const float* src) {
   if (int e = fn_fades(c, o.fade_in, o.fade_out)) return e;
   const float* in = resident && src ? src : c->rs_in;
   const bool s16 = o.format == VX_PCM_S16;
@@ -184,9 +182,7 @@ int fn_apply(vx_ctx* c, const float* wav, int64_t wav_stride, int batch, const v
   const float* tab_in = c->fn_fade;
   const float* tab_out = c->fn_fade ? c->fn_fade + FN_FADE_CAP : nullptr;
   std::vector<int> tab, back;
-  for (size_t j0 = 0; j0 < jobs.size();) {
-    size_t j1 = j0;
-    while (j1 < jobs.size() && jobs[j1].launch == jobs[j0].launch) ++j1;
+  return wave_launches(c, jobs, [&](size_t j0, size_t j1) -> int {
     tab.clear();
     long max_cnt = 0;
     for (size_t k = j0; k < j1; ++k) {
@@ -214,10 +210,122 @@ int fn_apply(vx_ctx* c, const float* wav, int64_t wav_stride, int batch, const v
     }
     back.resize(tab.size());
     D2H(back.data(), c->rs_meta, back.size() * sizeof(int));
-    SYNC();
-    HIPCHK(hipGetLastError());
+    return VX_OK;
+  }, [&](size_t j0, size_t j1) -> int {
     for (size_t k = j0; k < j1; ++k) info[jobs[k].row].clipped += back[(k - j0) * RS_TAB + 6];
-    j0 = j1;
+    return VX_OK;
+  });
+}
+
+// The limiter over every kept span [w.begin, w.end) as a row of its own at the gain w.gain, then -- with an output -- the apply pass at
+// gain 1 over the limited samples (fades and format); w.clipped is that pass's.  Resident rows stay on the device in between: the
+// limited samples lie in the upper half of rs_out.  Without an output the detector alone runs.
+static int fn_limited(vx_ctx* c, const char* who, const float* wav, int64_t wav_stride, int batch, const vx_finish_opts& o, float ceiling_db,
+                      const vx_limit_opts& lim, bool resident, const std::vector<long>& base, void* out, int64_t out_stride,
+                      std::vector<vx_wave_info>& w, vx_limit_info* lw) {
+  const size_t n = (size_t)batch;
+  if (c->lm_window) resident = false;
+  std::vector<long> kept, len(n), sbase(n, 0);
+  std::vector<float> gs(n);
+  std::vector<const float*> src(n);
+  std::vector<float*> dst(n, nullptr);
+  long stride = 1;
+  for (size_t i = 0; i < n; ++i) stride = std::max<long>(stride, w[i].end - w[i].begin);
+  std::vector<float> limited;                                      // the limited spans on the host when the call does not fit one launch
+  if (out && !resident) limited.resize(n * (size_t)stride);
+  for (size_t i = 0; i < n; ++i) {
+    src[i] = wav + (long)i * wav_stride + w[i].begin;
+    if (!limited.empty()) dst[i] = limited.data() + i * (size_t)stride;
+    len[i] = w[i].end - w[i].begin;
+    gs[i] = w[i].gain;
+    if (resident) sbase[i] = base[i] + w[i].begin;
+  }
+  if (int e = lm_run(c, who, src.data(), len.data(), batch, gs.data(), lm_ceiling(ceiling_db), lim.lookahead, lim.oversample, resident, sbase,
+                     out && !resident ? dst.data() : nullptr, nullptr, nullptr, out && resident, &kept, lw))
+    return e;
+  if (!out) return VX_OK;
+  std::vector<vx_wave_info> a(w);
+  for (size_t i = 0; i < n; ++i) a[i].gain = 1.f;
+  if (resident) {
+    for (size_t i = 0; i < n; ++i) kept[i] -= w[i].begin;          // row i's limited sample `begin` lies at rs_out + kept[i]
+    if (int e = fn_apply(c, wav, wav_stride, batch, o, true, kept, out, out_stride, a.data(), c->rs_out)) return e;
+  } else {
+    for (size_t i = 0; i < n; ++i) { a[i].end -= a[i].begin; a[i].begin = 0; }
+    if (int e = fn_apply(c, limited.data(), stride, batch, o, false, kept, out, out_stride, a.data(), nullptr)) return e;
+  }
+  for (size_t i = 0; i < n; ++i) w[i].clipped = a[i].clipped;
+  return VX_OK;
+}
+
+// The output stage behind the entries' pointer checks (wave_stage.h).  What the three entries differ in is decided by lo and lim alone:
+//   checks      vx_finish names a struct of the wrong size without its own name in front and checks its rows behind its options (the
+//               two others have checked theirs in front of their pointers); a loudness target refuses a level_mode
+//   allocation  rs_buffers; with lo the step tables (ln_buffers), with lim the limiter's (lm_buffers)
+//   gain        fn_reduce's level; with lo ln_gain under the sample peak; with lim lm_gain, the limiter, and the apply pass at gain 1
+//   residency   rows that went through ONE frames launch stay in rs_in for the later passes, unless a pass has a development window set
+int fn_pipeline(vx_ctx* c, const char* who, const float* wav, int64_t wav_stride, const int32_t* lens, int batch, const vx_finish_opts& o,
+                const vx_loudness_opts* lo, const vx_limit_opts* lim, void* out, int64_t out_stride, int32_t* out_lens, vx_wave_info* info,
+                vx_loudness_info* linfo, vx_limit_info* liminfo) {
+  if (!lo) CHECK_STRUCT(o, vx_finish_opts);
+  else {
+    CHECK_STRUCT_OF(who, o, vx_finish_opts);
+    CHECK_STRUCT_OF(who, *lo, vx_loudness_opts);
+  }
+  char why[160];
+  if (fn_check_opts(o, why, sizeof why)) FAIL(VX_EINVAL, "%s: %s", who, why);
+  if (lo) {
+    if (o.level_mode != VX_LEVEL_NONE) FAIL(VX_EINVAL, "%s: level_mode %d is not VX_LEVEL_NONE: the loudness target sets the level", who, o.level_mode);
+    if (ln_check_opts(*lo, why, sizeof why)) FAIL(VX_EINVAL, "%s: %s", who, why);
+  }
+  if (lim)
+    if (int e = lm_check(c, who, lim, 1.f, lo->ceiling_db)) return e;
+  if (!lo)
+    if (int e = wave_check_rows(c, who, wav, wav_stride, lens, batch)) return e;
+  if (out)
+    if (int e = wave_check_out_stride(c, who, lens, batch, out_stride, " (its untrimmed length)")) return e;
+  const int S = lo ? ln_step(lo->sample_rate) : 0;
+  if (lo && c->ln_window && c->ln_window < 3L * S)
+    FAIL(VX_EINVAL, "%s: the launch window of %ld samples (vx_dev_loudness_window) is below 3 S = %d at sample_rate %d", who, c->ln_window, 3 * S,
+         lo->sample_rate);
+  HIPCHK(hipSetDevice(c->dev));
+  if (int e = lo ? ln_buffers(c) : rs_buffers(c)) return e;
+  if (lim)
+    if (int e = lm_buffers(c, lim->oversample)) return e;
+  const size_t n = (size_t)batch;
+  // frames pass -> span, peak and the level gain
+  std::vector<FnFrame> table;
+  std::vector<long> f0, base;
+  bool resident = false;
+  if (int e = fn_measure(c, wav, wav_stride, lens, batch, o.frame, table, f0, &resident, base)) return e;
+  const double thr2 = fn_thr2(o.silence_db);
+  std::vector<vx_wave_info> w(n);
+  for (size_t i = 0; i < n; ++i) fn_reduce(table.data() + f0[i], lens[i], o, thr2, &w[i]);
+  std::vector<vx_loudness_info> li(lo ? n : 0);
+  std::vector<vx_limit_info> lw(lim ? n : 0);
+  if (lo) {
+    // steps pass over the kept spans -> gain; the limiter takes the ceiling's place in it
+    std::vector<long> b(n), e(n), z0;
+    for (size_t i = 0; i < n; ++i) { b[i] = w[i].begin; e[i] = w[i].end; }
+    if (c->ln_window) resident = false;
+    std::vector<double> z;
+    std::vector<int> nonf;
+    if (int err = ln_steps(c, who, wav, wav_stride, b.data(), e.data(), batch, lo->sample_rate, resident, base, z, z0, nonf)) return err;
+    for (size_t i = 0; i < n; ++i) {
+      ln_reduce(z.data() + z0[i], e[i] - b[i], S, nonf[i], &li[i]);
+      w[i].gain = lim ? lm_gain(li[i].loudness, lo->target_lufs, o.max_gain_db)
+                      : ln_gain(li[i].loudness, lo->target_lufs, lo->ceiling_db, o.max_gain_db, w[i].peak);
+    }
+  }
+  if (lim) {
+    if (int e = fn_limited(c, who, wav, wav_stride, batch, o, lo->ceiling_db, *lim, resident, base, out, out_stride, w, lw.data())) return e;
+  } else if (out) {
+    if (int e = fn_apply(c, wav, wav_stride, batch, o, resident, base, out, out_stride, w.data(), nullptr)) return e;
+  }
+  for (size_t i = 0; i < n; ++i) {
+    info[i] = w[i];
+    if (lo) linfo[i] = li[i];
+    if (lim) liminfo[i] = lw[i];
+    if (out_lens) out_lens[i] = w[i].end - w[i].begin;
   }
   return VX_OK;
 }
@@ -236,30 +344,7 @@ int vx_finish(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_t* le
   if (!info) FAIL(VX_EINVAL, "vx_finish: info is NULL");
   if (out && !out_lens) FAIL(VX_EINVAL, "vx_finish: out is given without out_lens");
   if (batch <= 0) FAIL(VX_EINVAL, "vx_finish: batch %d below 1", batch);
-  CHECK_STRUCT(*o, vx_finish_opts);
-  char why[160];
-  if (fn_check_opts(*o, why, sizeof why)) FAIL(VX_EINVAL, "vx_finish: %s", why);
-  for (int i = 0; i < batch; ++i) {
-    const long L = lens[i];
-    if (L < 0 || L > wav_stride) FAIL(VX_EINVAL, "vx_finish: lens[%d] = %ld outside 0 .. wav_stride %ld", i, L, (long)wav_stride);
-    if (out && L > out_stride) FAIL(VX_EINVAL, "vx_finish: out_stride %ld below the %ld samples of row %d (its untrimmed length)", (long)out_stride, L, i);
-  }
-  HIPCHK(hipSetDevice(c->dev));
-  if (int e = rs_buffers(c)) return e;
-  std::vector<FnFrame> table;
-  std::vector<long> f0, base;
-  bool resident = false;
-  if (int e = fn_measure(c, wav, wav_stride, lens, batch, o->frame, table, f0, &resident, base)) return e;
-  const double thr2 = fn_thr2(o->silence_db);
-  std::vector<vx_wave_info> w((size_t)batch);
-  for (int i = 0; i < batch; ++i) fn_reduce(table.data() + f0[i], lens[i], *o, thr2, &w[(size_t)i]);
-  if (out)
-    if (int e = fn_apply(c, wav, wav_stride, batch, *o, resident, base, out, out_stride, w.data(), nullptr)) return e;
-  for (int i = 0; i < batch; ++i) {
-    info[i] = w[(size_t)i];
-    if (out_lens) out_lens[i] = w[(size_t)i].end - w[(size_t)i].begin;
-  }
-  return VX_OK;
+  return fn_pipeline(c, "vx_finish", wav, wav_stride, lens, batch, *o, nullptr, nullptr, out, out_stride, out_lens, info, nullptr, nullptr);
 }
 
 int vx_dev_finish_frames(vx_ctx* c, const float* wav, int32_t len, int32_t frame, double* e, float* p, int32_t* z) {
@@ -280,13 +365,8 @@ int vx_dev_finish_frames(vx_ctx* c, const float* wav, int32_t len, int32_t frame
 }
 
 int vx_dev_finish_window(vx_ctx* c, int32_t input_samples) {
-  using namespace vxe;
-  if (!c) return VX_EINVAL;
-  if (input_samples != 0 && (input_samples < VX_DEV_FINISH_WINDOW_MIN || input_samples > VX_FINISH_WINDOW))
-    FAIL(VX_EINVAL, "vx_dev_finish_window: input_samples %d outside %d .. %d (0 restores the default)", input_samples,
-         VX_DEV_FINISH_WINDOW_MIN, VX_FINISH_WINDOW);
-  c->fn_window = input_samples;
-  return VX_OK;
+  return vxe::wave_set_window(c, &vx_ctx::fn_window, "vx_dev_finish_window", "input_samples", input_samples, VX_DEV_FINISH_WINDOW_MIN,
+                              VX_FINISH_WINDOW);
 }
 
 }  // extern "C"

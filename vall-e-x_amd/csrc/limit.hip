@@ -15,9 +15,7 @@
 // Work decomposition: a launch covers a ragged list of PARTS (outputs [s, s + cnt) of one row with up to 2 Wn + 7 real samples on
 // either side: limit_host.h, lm_plan), grid (tile, part), 256 threads.  Loads and stores are lane-contiguous.  Two instances: Wn up to
 // 128 (50 KiB of LDS, three workgroups per CU) and up to 1024 (106 KiB, one); static LDS, so neither needs a launch attribute.
-#include "engine_ctx.h"
-#include "finish_host.h"
-#include "loudness_host.h"
+#include "wave_stage.h"
 #include "limit_host.h"
 
 #include "../../include/vallex_hip_dev.h"
@@ -34,16 +32,6 @@ static_assert(VX_DEV_LIMIT_WINDOW_MIN >= 2 * (2 * LM_LOOKAHEAD_MAX + LM_WIDTH) +
 
 struct LmRec { float peak, min_gain; int reduced, nonfinite; };
 static_assert(sizeof(LmRec) == 16, "the kernel writes 16-byte tile records");
-
-// the frames pass and the apply pass of vx_finish (finish.hip), the steps pass of vx_loudness (loudness.hip)
-int fn_measure(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_t* lens, int batch, int F, std::vector<FnFrame>& table,
-               std::vector<long>& f0, bool* resident, std::vector<long>& base);
-int fn_apply(vx_ctx* c, const float* wav, int64_t wav_stride, int batch, const vx_finish_opts& o, bool resident, const std::vector<long>& base,
-             void* out, int64_t out_stride, vx_wave_info* info, const float* src);
-int ln_buffers(vx_ctx* c);
-int ln_steps(vx_ctx* c, const char* who, const float* wav, int64_t wav_stride, const long* lo, const long* hi, int batch, int rate,
-             bool resident, const std::vector<long>& base, std::vector<double>& z, std::vector<long>& z0, std::vector<int>& nonf);
-int ln_check_rows(vx_ctx* c, const char* who, const float* wav, int64_t wav_stride, const int32_t* lens, int batch);
 
 // tab [nparts][RS_TAB]: {in_off, hl, cnt, hr, out_off, rec_off, pre_gain bits}: the part's outputs are the samples in[in_off + hl .. in_off + hl + cnt),
 // the hl samples in front and the hr behind are real samples of the row; whatever lies outside in[in_off .. in_off + hl + cnt + hr) and
@@ -178,9 +166,8 @@ __global__ __launch_bounds__(256) void limit_rows_kernel(const float* __restrict
   }
 }
 
-static long lm_win(const vx_ctx* c) { return c->lm_window ? c->lm_window : (long)VX_LIMIT_WINDOW; }
-
-static int lm_buffers(vx_ctx* c, int n) {
+// (lm_buffers, lm_run and lm_check: wave_stage.h)
+int lm_buffers(vx_ctx* c, int n) {
   if (int e = rs_buffers(c)) return e;
   if (!c->lm_rec) {
     if (int e = dev_alloc(c, &c->lm_rec, (size_t)LM_REC_CAP * 4, false)) return e;
@@ -200,13 +187,13 @@ static int lm_buffers(vx_ctx* c, int n) {
 // rs_in + base[i], nothing is uploaded and one launch takes all of them.  dst / dP / dG (each may be NULL): host rows that receive out,
 // P and g.  keep (with resident): the limited samples stay on the device, row i's at rs_out + kept[i].  Neither dst, keep nor dG: the
 // detector alone runs (peak, nonfinite).
-static int lm_run(vx_ctx* c, const char* who, const float* const* src, const long* len, int batch, const float* gs, float cc, int Wn, int n, bool resident,
-                  const std::vector<long>& base, float* const* dst, float* const* dP, float* const* dG, bool keep, std::vector<long>* kept,
-                  vx_limit_info* info) {
+int lm_run(vx_ctx* c, const char* who, const float* const* src, const long* len, int batch, const float* gs, float cc, int Wn, int n, bool resident,
+           const std::vector<long>& base, float* const* dst, float* const* dP, float* const* dG, bool keep, std::vector<long>* kept,
+           vx_limit_info* info) {
   for (int i = 0; i < batch; ++i) info[i] = {0.f, 1.f, cc, 0, 0};
   if (kept) kept->assign((size_t)batch, 0);
   std::vector<LmJob> jobs;
-  const long win = resident ? (long)RS_IN_CAP : lm_win(c);
+  const long win = resident ? (long)RS_IN_CAP : wave_window(c->lm_window, VX_LIMIT_WINDOW);
   if (!lm_plan(len, batch, Wn, win, RS_MAX_JOBS, LM_T, &jobs))
     FAIL(VX_EINVAL, "%s: the launch window of %ld samples (vx_dev_limit_window) cannot hold two halos of 2 lookahead + 7 = %ld samples plus one sample",
          who, win, lm_halo(Wn));
@@ -218,9 +205,7 @@ static int lm_run(vx_ctx* c, const char* who, const float* const* src, const lon
   LmRec* d_rec = reinterpret_cast<LmRec*>(c->lm_rec);
   std::vector<int> tab;
   std::vector<LmRec> recs;
-  for (size_t j0 = 0; j0 < jobs.size();) {
-    size_t j1 = j0;
-    while (j1 < jobs.size() && jobs[j1].launch == jobs[j0].launch) ++j1;
+  return wave_launches(c, jobs, [&](size_t j0, size_t j1) -> int {
     tab.clear();
     long max_cnt = 0, nrec = 0;
     for (size_t q = j0; q < j1; ++q) {
@@ -251,8 +236,8 @@ static int lm_run(vx_ctx* c, const char* who, const float* const* src, const lon
     }
     recs.resize((size_t)nrec);
     D2H(recs.data(), d_rec, (size_t)nrec * sizeof(LmRec));
-    SYNC();
-    HIPCHK(hipGetLastError());
+    return VX_OK;
+  }, [&](size_t j0, size_t j1) -> int {
     for (size_t q = j0; q < j1; ++q) {
       const LmJob& j = jobs[q];
       vx_limit_info& w = info[j.row];
@@ -264,16 +249,13 @@ static int lm_run(vx_ctx* c, const char* who, const float* const* src, const lon
         w.nonfinite += r.nonfinite;
       }
     }
-    j0 = j1;
-  }
-  return VX_OK;
+    return VX_OK;
+  });
 }
 
-static int lm_check(vx_ctx* c, const char* who, const vx_limit_opts* o, float pre_gain, float ceiling_db) {
+int lm_check(vx_ctx* c, const char* who, const vx_limit_opts* o, float pre_gain, float ceiling_db) {
   if (!o) FAIL(VX_EINVAL, "%s: the vx_limit_opts pointer is NULL", who);
-  if (o->struct_size != sizeof(vx_limit_opts))
-    FAIL(VX_EINVAL, "%s: vx_limit_opts.struct_size is %u, this library expects %zu (ABI version %d)", who, o->struct_size, sizeof(vx_limit_opts),
-         VX_ABI_VERSION);
+  CHECK_STRUCT_OF(who, *o, vx_limit_opts);
   char why[160];
   if (lm_check_opts(*o, pre_gain, ceiling_db, why, sizeof why)) FAIL(VX_EINVAL, "%s: %s", who, why);
   return VX_OK;
@@ -295,12 +277,12 @@ int vx_limit(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_t* len
              const vx_limit_opts* o, float* out, int64_t out_stride, vx_limit_info* info) {
   using namespace vxe;
   if (!c) return VX_EINVAL;
-  if (int e = ln_check_rows(c, "vx_limit", wav, wav_stride, lens, batch)) return e;
+  if (int e = wave_check_rows(c, "vx_limit", wav, wav_stride, lens, batch)) return e;
   if (!o) FAIL(VX_EINVAL, "vx_limit: o is NULL");
   if (!info) FAIL(VX_EINVAL, "vx_limit: info is NULL");
   if (int e = lm_check(c, "vx_limit", o, pre_gain, ceiling_db)) return e;
-  for (int i = 0; i < batch; ++i)
-    if (out && lens[i] > out_stride) FAIL(VX_EINVAL, "vx_limit: out_stride %ld below the %ld samples of row %d", (long)out_stride, (long)lens[i], i);
+  if (out)
+    if (int e = wave_check_out_stride(c, "vx_limit", lens, batch, out_stride, "")) return e;
   HIPCHK(hipSetDevice(c->dev));
   if (int e = lm_buffers(c, o->oversample)) return e;
   std::vector<const float*> src((size_t)batch);
@@ -325,8 +307,7 @@ int vx_finish_limited(vx_ctx* c, const float* wav, int64_t wav_stride, const int
                       vx_wave_info* info, vx_loudness_info* linfo, vx_limit_info* liminfo) {
   using namespace vxe;
   if (!c) return VX_EINVAL;
-  const char* who = "vx_finish_limited";
-  if (int e = ln_check_rows(c, who, wav, wav_stride, lens, batch)) return e;
+  if (int e = wave_check_rows(c, "vx_finish_limited", wav, wav_stride, lens, batch)) return e;
   if (!o) FAIL(VX_EINVAL, "vx_finish_limited: o is NULL");
   if (!lo_) FAIL(VX_EINVAL, "vx_finish_limited: lo is NULL");
   if (!lim) FAIL(VX_EINVAL, "vx_finish_limited: lim is NULL");
@@ -334,91 +315,7 @@ int vx_finish_limited(vx_ctx* c, const float* wav, int64_t wav_stride, const int
   if (!linfo) FAIL(VX_EINVAL, "vx_finish_limited: linfo is NULL");
   if (!liminfo) FAIL(VX_EINVAL, "vx_finish_limited: liminfo is NULL");
   if (out && !out_lens) FAIL(VX_EINVAL, "vx_finish_limited: out is given without out_lens");
-  if (o->struct_size != sizeof(vx_finish_opts))
-    FAIL(VX_EINVAL, "vx_finish_limited: vx_finish_opts.struct_size is %u, this library expects %zu (ABI version %d)", o->struct_size,
-         sizeof(vx_finish_opts), VX_ABI_VERSION);
-  if (lo_->struct_size != sizeof(vx_loudness_opts))
-    FAIL(VX_EINVAL, "vx_finish_limited: vx_loudness_opts.struct_size is %u, this library expects %zu (ABI version %d)", lo_->struct_size,
-         sizeof(vx_loudness_opts), VX_ABI_VERSION);
-  char why[160];
-  if (fn_check_opts(*o, why, sizeof why)) FAIL(VX_EINVAL, "vx_finish_limited: %s", why);
-  if (o->level_mode != VX_LEVEL_NONE)
-    FAIL(VX_EINVAL, "vx_finish_limited: level_mode %d is not VX_LEVEL_NONE: the loudness target sets the level", o->level_mode);
-  if (ln_check_opts(*lo_, why, sizeof why)) FAIL(VX_EINVAL, "vx_finish_limited: %s", why);
-  if (int e = lm_check(c, who, lim, 1.f, lo_->ceiling_db)) return e;
-  for (int i = 0; i < batch; ++i)
-    if (out && lens[i] > out_stride)
-      FAIL(VX_EINVAL, "vx_finish_limited: out_stride %ld below the %ld samples of row %d (its untrimmed length)", (long)out_stride, (long)lens[i], i);
-  const int S = ln_step(lo_->sample_rate);
-  if (c->ln_window && c->ln_window < 3L * S)
-    FAIL(VX_EINVAL, "vx_finish_limited: the launch window of %ld samples (vx_dev_loudness_window) is below 3 S = %d at sample_rate %d", c->ln_window,
-         3 * S, lo_->sample_rate);
-  HIPCHK(hipSetDevice(c->dev));
-  if (int e = ln_buffers(c)) return e;
-  if (int e = lm_buffers(c, lim->oversample)) return e;
-  // frames pass -> span
-  std::vector<FnFrame> table;
-  std::vector<long> f0, base;
-  bool resident = false;
-  if (int e = fn_measure(c, wav, wav_stride, lens, batch, o->frame, table, f0, &resident, base)) return e;
-  const double thr2 = fn_thr2(o->silence_db);
-  std::vector<vx_wave_info> w((size_t)batch);
-  std::vector<long> lo((size_t)batch), hi((size_t)batch), z0;
-  for (int i = 0; i < batch; ++i) {
-    fn_reduce(table.data() + f0[(size_t)i], lens[i], *o, thr2, &w[(size_t)i]);
-    lo[(size_t)i] = w[(size_t)i].begin; hi[(size_t)i] = w[(size_t)i].end;
-  }
-  // steps pass over the kept spans -> gain, without the ceiling term
-  if (c->ln_window) resident = false;
-  std::vector<double> z;
-  std::vector<int> nonf;
-  if (int e = ln_steps(c, who, wav, wav_stride, lo.data(), hi.data(), batch, lo_->sample_rate, resident, base, z, z0, nonf)) return e;
-  std::vector<vx_loudness_info> li((size_t)batch);
-  for (int i = 0; i < batch; ++i) {
-    ln_reduce(z.data() + z0[(size_t)i], hi[(size_t)i] - lo[(size_t)i], S, nonf[(size_t)i], &li[(size_t)i]);
-    w[(size_t)i].gain = lm_gain(li[(size_t)i].loudness, lo_->target_lufs, o->max_gain_db);
-  }
-  // the limiter over every kept span as a row of its own
-  if (c->lm_window) resident = false;
-  std::vector<vx_limit_info> lw((size_t)batch);
-  std::vector<long> kept, len((size_t)batch), sbase((size_t)batch, 0);
-  std::vector<float> gs((size_t)batch);
-  std::vector<const float*> src((size_t)batch);
-  std::vector<float*> dst((size_t)batch, nullptr);
-  long stride = 1;
-  for (int i = 0; i < batch; ++i) stride = std::max(stride, hi[(size_t)i] - lo[(size_t)i]);
-  std::vector<float> limited;                                      // the limited spans on the host when the call does not fit one launch
-  if (out && !resident) limited.resize((size_t)batch * (size_t)stride);
-  for (int i = 0; i < batch; ++i) {
-    src[(size_t)i] = wav + (long)i * wav_stride + lo[(size_t)i];
-    if (!limited.empty()) dst[(size_t)i] = limited.data() + (size_t)i * (size_t)stride;
-    len[(size_t)i] = hi[(size_t)i] - lo[(size_t)i];
-    gs[(size_t)i] = w[(size_t)i].gain;
-    if (resident) sbase[(size_t)i] = base[(size_t)i] + lo[(size_t)i];
-  }
-  if (int e = lm_run(c, who, src.data(), len.data(), batch, gs.data(), lm_ceiling(lo_->ceiling_db), lim->lookahead, lim->oversample, resident, sbase,
-                     out && !resident ? dst.data() : nullptr, nullptr, nullptr, out && resident, &kept, lw.data()))
-    return e;
-  if (out) {
-    std::vector<vx_wave_info> a(w);                               // the apply pass at gain 1 over the limited samples: fades and format
-    for (int i = 0; i < batch; ++i) a[(size_t)i].gain = 1.f;
-    if (resident) {
-      // row i's limited sample `begin` lies at rs_out + kept[i]
-      for (int i = 0; i < batch; ++i) kept[(size_t)i] -= lo[(size_t)i];
-      if (int e = fn_apply(c, wav, wav_stride, batch, *o, true, kept, out, out_stride, a.data(), c->rs_out)) return e;
-    } else {
-      for (int i = 0; i < batch; ++i) { a[(size_t)i].end -= a[(size_t)i].begin; a[(size_t)i].begin = 0; }
-      if (int e = fn_apply(c, limited.data(), stride, batch, *o, false, kept, out, out_stride, a.data(), nullptr)) return e;
-    }
-    for (int i = 0; i < batch; ++i) w[(size_t)i].clipped = a[(size_t)i].clipped;
-  }
-  for (int i = 0; i < batch; ++i) {
-    info[i] = w[(size_t)i];
-    linfo[i] = li[(size_t)i];
-    liminfo[i] = lw[(size_t)i];
-    if (out_lens) out_lens[i] = w[(size_t)i].end - w[(size_t)i].begin;
-  }
-  return VX_OK;
+  return fn_pipeline(c, "vx_finish_limited", wav, wav_stride, lens, batch, *o, lo_, lim, out, out_stride, out_lens, info, linfo, liminfo);
 }
 
 int vx_dev_limit_gain(vx_ctx* c, const float* wav, int32_t len, float pre_gain, float ceiling_db, const vx_limit_opts* o, float* P, float* g) {
@@ -438,12 +335,7 @@ int vx_dev_limit_gain(vx_ctx* c, const float* wav, int32_t len, float pre_gain, 
 }
 
 int vx_dev_limit_window(vx_ctx* c, int32_t samples) {
-  using namespace vxe;
-  if (!c) return VX_EINVAL;
-  if (samples != 0 && (samples < VX_DEV_LIMIT_WINDOW_MIN || samples > VX_LIMIT_WINDOW))
-    FAIL(VX_EINVAL, "vx_dev_limit_window: samples %d outside %d .. %d (0 restores the default)", samples, VX_DEV_LIMIT_WINDOW_MIN, VX_LIMIT_WINDOW);
-  c->lm_window = samples;
-  return VX_OK;
+  return vxe::wave_set_window(c, &vx_ctx::lm_window, "vx_dev_limit_window", "samples", samples, VX_DEV_LIMIT_WINDOW_MIN, VX_LIMIT_WINDOW);
 }
 
 }  // extern "C"

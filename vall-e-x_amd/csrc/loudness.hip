@@ -17,8 +17,7 @@
 // which read the same offset of consecutive streams, fall on different banks -- and then each lane runs its recursion over its row of
 // the tile.  LDS use does not depend on S.  The loads of chunk q + 1 are in flight while the recursion runs over chunk q (two tiles).
 // The recursion is a dependent chain of fp64 operations: the kernel is latency-bound by construction.
-#include "engine_ctx.h"
-#include "finish_host.h"
+#include "wave_stage.h"
 #include "loudness_host.h"
 
 #include "../../include/vallex_hip_dev.h"
@@ -34,12 +33,6 @@ static_assert(VX_DEV_LOUDNESS_WINDOW_MIN >= 3 * LN_STEP_MIN && VX_DEV_LOUDNESS_W
 static_assert(LN_LANES * LN_C % 64 == 0 && LN_STRIDE % 2 == 1, "tile shape");
 
 struct LnCoef { double c[10]; };
-
-// the frames pass and the apply pass of vx_finish (finish.hip), unchanged
-int fn_measure(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_t* lens, int batch, int F, std::vector<FnFrame>& table,
-               std::vector<long>& f0, bool* resident, std::vector<long>& base);
-int fn_apply(vx_ctx* c, const float* wav, int64_t wav_stride, int batch, const vx_finish_opts& o, bool resident, const std::vector<long>& base,
-             void* out, int64_t out_stride, vx_wave_info* info, const float* src);
 
 // tab [njobs][RS_TAB]: {in_off, pre, cnt, z_off}: the job's steps cover in[in_off + pre .. in_off + pre + cnt), the `pre` samples in
 // front are its warm-up (what a lane would read in front of in_off lies before the span: 0).  Step t of the job -> z[z_off + t],
@@ -110,9 +103,7 @@ __global__ __launch_bounds__(LN_LANES) void loudness_steps_kernel(const float* _
   }
 }
 
-static long ln_win(const vx_ctx* c) { return c->ln_window ? c->ln_window : (long)VX_LOUDNESS_WINDOW; }
-
-// (ln_buffers, ln_steps and ln_check_rows are shared with vx_finish_limited, limit.hip)
+// (ln_buffers and ln_steps: wave_stage.h)
 int ln_buffers(vx_ctx* c) {
   if (int e = rs_buffers(c)) return e;
   if (!c->ln_z) {
@@ -125,7 +116,7 @@ int ln_buffers(vx_ctx* c) {
 // the steps pass over the spans [lo[i], hi[i]) of the rows: the step table of row i at z[z0[i] ..), its non-finite samples in nonf[i].
 // resident: the rows already lie in rs_in, row i's sample 0 at rs_in + base[i]; nothing is uploaded and one launch takes all of them.
 int ln_steps(vx_ctx* c, const char* who, const float* wav, int64_t wav_stride, const long* lo, const long* hi, int batch, int rate,
-                    bool resident, const std::vector<long>& base, std::vector<double>& z, std::vector<long>& z0, std::vector<int>& nonf) {
+             bool resident, const std::vector<long>& base, std::vector<double>& z, std::vector<long>& z0, std::vector<int>& nonf) {
   const int S = ln_step(rate);
   LnCoef k;
   ln_coeffs(rate, k.c);
@@ -136,13 +127,11 @@ int ln_steps(vx_ctx* c, const char* who, const float* wav, int64_t wav_stride, c
   std::vector<LnJob> jobs;
   // resident rows are not moved: a window that holds every span whole, so that a job is a row (batch <= RS_MAX_JOBS then: the frames
   // pass had a job per row)
-  const long win = resident ? std::max<long>(RS_IN_CAP, 3L * S) : ln_win(c);
+  const long win = resident ? std::max<long>(RS_IN_CAP, 3L * S) : wave_window(c->ln_window, VX_LOUDNESS_WINDOW);
   if (!ln_plan(lo, hi, batch, S, win, RS_MAX_JOBS, &jobs))
     FAIL(VX_EINVAL, "%s: the launch window of %ld samples (vx_dev_loudness_window) is below 3 S = %d at sample_rate %d", who, win, 3 * S, rate);
   std::vector<int> tab, cnts;
-  for (size_t j0 = 0; j0 < jobs.size();) {
-    size_t j1 = j0;
-    while (j1 < jobs.size() && jobs[j1].launch == jobs[j0].launch) ++j1;
+  return wave_launches(c, jobs, [&](size_t j0, size_t j1) -> int {
     tab.clear();
     long max_st = 0, nz = 0;
     for (size_t q = j0; q < j1; ++q) {
@@ -164,24 +153,14 @@ int ln_steps(vx_ctx* c, const char* who, const float* wav, int64_t wav_stride, c
       D2H(z.data() + z0[j.row] + j.j0, c->ln_z + j.z_off, (size_t)ln_nsteps(j.cnt, S) * sizeof(double));
     }
     D2H(cnts.data(), c->ln_nonf, (size_t)nz * sizeof(int));
-    SYNC();
-    HIPCHK(hipGetLastError());
+    return VX_OK;
+  }, [&](size_t j0, size_t j1) -> int {
     for (size_t q = j0; q < j1; ++q) {
       const LnJob& j = jobs[q];
       for (long t = 0; t < ln_nsteps(j.cnt, S); ++t) nonf[j.row] += cnts[(size_t)(j.z_off + t)];
     }
-    j0 = j1;
-  }
-  return VX_OK;
-}
-
-int ln_check_rows(vx_ctx* c, const char* who, const float* wav, int64_t wav_stride, const int32_t* lens, int batch) {
-  if (!wav) FAIL(VX_EINVAL, "%s: wav is NULL", who);
-  if (!lens) FAIL(VX_EINVAL, "%s: lens is NULL", who);
-  if (batch <= 0) FAIL(VX_EINVAL, "%s: batch %d below 1", who, batch);
-  for (int i = 0; i < batch; ++i)
-    if (lens[i] < 0 || lens[i] > wav_stride) FAIL(VX_EINVAL, "%s: lens[%d] = %ld outside 0 .. wav_stride %ld", who, i, (long)lens[i], (long)wav_stride);
-  return VX_OK;
+    return VX_OK;
+  });
 }
 
 }  // namespace vxe
@@ -199,7 +178,7 @@ int vx_loudness(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_t* 
                 vx_loudness_info* info) {
   using namespace vxe;
   if (!c) return VX_EINVAL;
-  if (int e = ln_check_rows(c, "vx_loudness", wav, wav_stride, lens, batch)) return e;
+  if (int e = wave_check_rows(c, "vx_loudness", wav, wav_stride, lens, batch)) return e;
   if (!info) FAIL(VX_EINVAL, "vx_loudness: info is NULL");
   char why[160];
   if (ln_check_rate(sample_rate, why, sizeof why)) FAIL(VX_EINVAL, "vx_loudness: %s", why);
@@ -218,61 +197,13 @@ int vx_finish_loud(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_
                    const vx_loudness_opts* lo_, void* out, int64_t out_stride, int32_t* out_lens, vx_wave_info* info, vx_loudness_info* linfo) {
   using namespace vxe;
   if (!c) return VX_EINVAL;
-  if (int e = ln_check_rows(c, "vx_finish_loud", wav, wav_stride, lens, batch)) return e;
+  if (int e = wave_check_rows(c, "vx_finish_loud", wav, wav_stride, lens, batch)) return e;
   if (!o) FAIL(VX_EINVAL, "vx_finish_loud: o is NULL");
   if (!lo_) FAIL(VX_EINVAL, "vx_finish_loud: lo is NULL");
   if (!info) FAIL(VX_EINVAL, "vx_finish_loud: info is NULL");
   if (!linfo) FAIL(VX_EINVAL, "vx_finish_loud: linfo is NULL");
   if (out && !out_lens) FAIL(VX_EINVAL, "vx_finish_loud: out is given without out_lens");
-  if (o->struct_size != sizeof(vx_finish_opts))
-    FAIL(VX_EINVAL, "vx_finish_loud: vx_finish_opts.struct_size is %u, this library expects %zu (ABI version %d)", o->struct_size,
-         sizeof(vx_finish_opts), VX_ABI_VERSION);
-  if (lo_->struct_size != sizeof(vx_loudness_opts))
-    FAIL(VX_EINVAL, "vx_finish_loud: vx_loudness_opts.struct_size is %u, this library expects %zu (ABI version %d)", lo_->struct_size,
-         sizeof(vx_loudness_opts), VX_ABI_VERSION);
-  char why[160];
-  if (fn_check_opts(*o, why, sizeof why)) FAIL(VX_EINVAL, "vx_finish_loud: %s", why);
-  if (o->level_mode != VX_LEVEL_NONE) FAIL(VX_EINVAL, "vx_finish_loud: level_mode %d is not VX_LEVEL_NONE: the loudness target sets the level", o->level_mode);
-  if (ln_check_opts(*lo_, why, sizeof why)) FAIL(VX_EINVAL, "vx_finish_loud: %s", why);
-  for (int i = 0; i < batch; ++i)
-    if (out && lens[i] > out_stride)
-      FAIL(VX_EINVAL, "vx_finish_loud: out_stride %ld below the %ld samples of row %d (its untrimmed length)", (long)out_stride, (long)lens[i], i);
-  const int S = ln_step(lo_->sample_rate);
-  if (c->ln_window && c->ln_window < 3L * S)
-    FAIL(VX_EINVAL, "vx_finish_loud: the launch window of %ld samples (vx_dev_loudness_window) is below 3 S = %d at sample_rate %d", c->ln_window, 3 * S,
-         lo_->sample_rate);
-  HIPCHK(hipSetDevice(c->dev));
-  if (int e = ln_buffers(c)) return e;
-  // frames pass -> span and peak
-  std::vector<FnFrame> table;
-  std::vector<long> f0, base;
-  bool resident = false;
-  if (int e = fn_measure(c, wav, wav_stride, lens, batch, o->frame, table, f0, &resident, base)) return e;
-  const double thr2 = fn_thr2(o->silence_db);
-  std::vector<vx_wave_info> w((size_t)batch);
-  std::vector<long> lo((size_t)batch), hi((size_t)batch), z0;
-  for (int i = 0; i < batch; ++i) {
-    fn_reduce(table.data() + f0[(size_t)i], lens[i], *o, thr2, &w[(size_t)i]);
-    lo[(size_t)i] = w[(size_t)i].begin; hi[(size_t)i] = w[(size_t)i].end;
-  }
-  // steps pass over the kept spans (a development window sends it through launches of its own: the rows are uploaded again)
-  if (c->ln_window) resident = false;
-  std::vector<double> z;
-  std::vector<int> nonf;
-  if (int e = ln_steps(c, "vx_finish_loud", wav, wav_stride, lo.data(), hi.data(), batch, lo_->sample_rate, resident, base, z, z0, nonf)) return e;
-  std::vector<vx_loudness_info> li((size_t)batch);
-  for (int i = 0; i < batch; ++i) {
-    ln_reduce(z.data() + z0[(size_t)i], hi[(size_t)i] - lo[(size_t)i], S, nonf[(size_t)i], &li[(size_t)i]);
-    w[(size_t)i].gain = ln_gain(li[(size_t)i].loudness, lo_->target_lufs, lo_->ceiling_db, o->max_gain_db, w[(size_t)i].peak);
-  }
-  if (out)
-    if (int e = fn_apply(c, wav, wav_stride, batch, *o, resident, base, out, out_stride, w.data(), nullptr)) return e;
-  for (int i = 0; i < batch; ++i) {
-    info[i] = w[(size_t)i];
-    linfo[i] = li[(size_t)i];
-    if (out_lens) out_lens[i] = w[(size_t)i].end - w[(size_t)i].begin;
-  }
-  return VX_OK;
+  return fn_pipeline(c, "vx_finish_loud", wav, wav_stride, lens, batch, *o, lo_, nullptr, out, out_stride, out_lens, info, linfo, nullptr);
 }
 
 int vx_dev_loudness_steps(vx_ctx* c, const float* wav, int32_t n, int32_t sample_rate, double* z) {
@@ -295,13 +226,7 @@ int vx_dev_loudness_steps(vx_ctx* c, const float* wav, int32_t n, int32_t sample
 }
 
 int vx_dev_loudness_window(vx_ctx* c, int32_t samples) {
-  using namespace vxe;
-  if (!c) return VX_EINVAL;
-  if (samples != 0 && (samples < VX_DEV_LOUDNESS_WINDOW_MIN || samples > VX_LOUDNESS_WINDOW))
-    FAIL(VX_EINVAL, "vx_dev_loudness_window: samples %d outside %d .. %d (0 restores the default)", samples, VX_DEV_LOUDNESS_WINDOW_MIN,
-         VX_LOUDNESS_WINDOW);
-  c->ln_window = samples;
-  return VX_OK;
+  return vxe::wave_set_window(c, &vx_ctx::ln_window, "vx_dev_loudness_window", "samples", samples, VX_DEV_LOUDNESS_WINDOW_MIN, VX_LOUDNESS_WINDOW);
 }
 
 }  // extern "C"

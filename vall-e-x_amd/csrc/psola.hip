@@ -22,7 +22,7 @@
 // (n0 - Wmax, n1 - 1 + Wmax], found by two bisections; they pass through LDS in chunks of 256 records and every lane walks them in
 // order.  The source samples are read through L2 (a grain's source lies within 2 Wmax of the tile: the reads of a tile stay in a
 // window of a few KiB).
-#include "engine_ctx.h"
+#include "wave_stage.h"
 #include "psola_host.h"
 
 #include "../../include/vallex_hip_dev.h"
@@ -173,20 +173,18 @@ __global__ __launch_bounds__(256) void psola_synth_kernel(const float* __restric
 }
 
 // every check of vx_psola behind the pointers and before the walk: options, lengths, strides, ratios
-static int ps_check(vx_ctx* c, const char* who, int64_t wav_stride, const int32_t* lens, int batch, int64_t lag_stride, const int32_t* ratio,
+static int ps_check(vx_ctx* c, const char* who, const int32_t* lens, int batch, int64_t lag_stride, const int32_t* ratio,
                     const vx_psola_opts* o, int64_t out_stride, PsGeom* g) {
   CHECK_STRUCT(*o, vx_psola_opts);
   char why[160];
   if (ps_check_opts(*o, why, sizeof why)) FAIL(VX_EINVAL, "%s: %s", who, why);
   *g = ps_geometry(*o);
-  const long win = c->ps_window ? c->ps_window : (long)VX_PSOLA_WINDOW;
+  const long win = wave_window(c->ps_window, VX_PSOLA_WINDOW);
   for (int i = 0; i < batch; ++i) {
     const long L = lens[i];
-    if (L < 0 || L > wav_stride) FAIL(VX_EINVAL, "%s: lens[%d] = %ld outside 0 .. wav_stride %ld", who, i, L, (long)wav_stride);
     if (L > win) FAIL(VX_EINVAL, "%s: lens[%d] = %ld above the window of %ld samples (VX_PSOLA_WINDOW): a row is not cut", who, i, L, win);
     const long Mf = ps_frames(*g, L);
     if (Mf > lag_stride) FAIL(VX_EINVAL, "%s: lag_stride %ld below the %ld frames of row %d", who, (long)lag_stride, Mf, i);
-    if (L > out_stride) FAIL(VX_EINVAL, "%s: out_stride %ld below the %ld samples of row %d", who, (long)out_stride, L, i);
     if (ratio)
       for (long k = 0; k < Mf; ++k) {
         const int r = ratio[(long)i * lag_stride + k];
@@ -194,7 +192,7 @@ static int ps_check(vx_ctx* c, const char* who, int64_t wav_stride, const int32_
           FAIL(VX_EINVAL, "%s: ratio[%d][%ld] = %d outside %d .. %d", who, i, k, r, PS_RATIO_MIN, PS_RATIO_MAX);
       }
   }
-  return VX_OK;
+  return wave_check_out_stride(c, who, lens, batch, out_stride, "");
 }
 
 // The general path.  First every launch's mark walk, so that N of every row is known before anything reaches the caller; then the
@@ -203,7 +201,7 @@ static int ps_check(vx_ctx* c, const char* who, int64_t wav_stride, const int32_
 static int ps_run(vx_ctx* c, const char* who, const float* wav, int64_t wav_stride, const int32_t* lens, int batch, const int32_t* lag,
                   int64_t lag_stride, const int32_t* ratio, const PsGeom& g, float* out, int64_t out_stride, int32_t* marks,
                   int64_t marks_stride, vx_psola_info* info, double* cost, long cost_cap, int32_t* gtab, long gtab_cap) {
-  const long win = c->ps_window ? c->ps_window : (long)VX_PSOLA_WINDOW;
+  const long win = wave_window(c->ps_window, VX_PSOLA_WINDOW);
   std::vector<PsJob> jobs;
   if (!ps_plan(g, lens, batch, win, PS_MARK_CAP, PS_GRAIN_CAP, PS_LAG_CAP, PS_MAX_JOBS, &jobs))
     FAIL(VX_EINVAL, "%s: a row in lens is above the window of %ld samples (vx_dev_psola_window)", who, win);
@@ -226,9 +224,7 @@ static int ps_run(vx_ctx* c, const char* who, const float* wav, int64_t wav_stri
     }
     return VX_OK;
   };
-  for (size_t j0 = 0; j0 < jobs.size();) {                       // the mark walks
-    size_t j1 = j0;
-    while (j1 < jobs.size() && jobs[j1].launch == jobs[j0].launch) ++j1;
+  const int err = wave_launches(c, jobs, [&](size_t j0, size_t j1) -> int {      // the mark walks
     tab.clear();
     cnt.assign(j1 - j0, 0);
     if (int e = stage(j0, j1)) return e;
@@ -242,8 +238,8 @@ static int ps_run(vx_ctx* c, const char* who, const float* wav, int64_t wav_stri
     hipLaunchKernelGGL(psola_marks_kernel, dim3((unsigned)(j1 - j0)), dim3(256), lds, c->stream, c->rs_in, c->rs_meta, dlag, dmark, dcost,
                        dcnt, g);
     D2H(cnt.data(), dcnt, (j1 - j0) * sizeof(int));
-    SYNC();
-    HIPCHK(hipGetLastError());
+    return VX_OK;
+  }, [&](size_t j0, size_t j1) -> int {                            // N marks of every row, then the marks themselves
     for (size_t k = j0; k < j1; ++k) {
       const PsJob& j = jobs[k];
       const long N = cnt[k - j0];
@@ -256,8 +252,9 @@ static int ps_run(vx_ctx* c, const char* who, const float* wav, int64_t wav_stri
       }
     }
     SYNC();
-    j0 = j1;
-  }
+    return VX_OK;
+  });
+  if (err) return err;
   std::vector<std::vector<PsGrain>> rgrains((size_t)batch);
   std::vector<vx_psola_info> rinfo((size_t)batch);
   for (int i = 0; i < batch; ++i) {                              // the synthesis marks; every refusal that needs N
@@ -275,9 +272,9 @@ static int ps_run(vx_ctx* c, const char* who, const float* wav, int64_t wav_stri
     rinfo[(size_t)i] = {(int32_t)N, nv, (int32_t)J, ps_gaps(rgrains[(size_t)i], lens[i]), ps_nonfinite(x, lens[i])};
   }
   std::vector<PsGrain> gall;
-  for (size_t j0 = 0; j0 < jobs.size();) {                       // the synthesis
-    size_t j1 = j0;
-    while (j1 < jobs.size() && jobs[j1].launch == jobs[j0].launch) ++j1;
+  // the synthesis: its own loop, not wave_launches -- a launch group of empty rows alone launches nothing and syncs nothing
+  for (size_t j0 = 0, j1; j0 < jobs.size(); j0 = j1) {
+    for (j1 = j0 + 1; j1 < jobs.size() && jobs[j1].launch == jobs[j0].launch;) ++j1;
     tab.clear();
     gall.clear();
     long blocks = 0;
@@ -291,20 +288,18 @@ static int ps_run(vx_ctx* c, const char* who, const float* wav, int64_t wav_stri
       gall.insert(gall.end(), gr.begin(), gr.end());
       blocks += (L + PS_TILE - 1) / PS_TILE;
     }
-    if (blocks > 0) {
-      H2D(c->rs_meta, tab.data(), tab.size() * sizeof(int));
-      if (!gall.empty()) H2D(dgrain, gall.data(), gall.size() * sizeof(PsGrain));
-      hipLaunchKernelGGL(psola_synth_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, c->rs_in, c->rs_meta, (int)(j1 - j0), dgrain,
-                         c->rs_out, ps_wmax(g));
-      for (size_t k = j0; k < j1; ++k) {
-        const PsJob& j = jobs[k];
-        if (lens[j.row] > 0) D2H(out + (long)j.row * out_stride, c->rs_out + j.in_off, (size_t)lens[j.row] * sizeof(float));
-      }
-      if (gtab && !gall.empty()) D2H(gtab, dgrain, gall.size() * sizeof(PsGrain));
-      SYNC();
-      HIPCHK(hipGetLastError());
+    if (blocks == 0) continue;
+    H2D(c->rs_meta, tab.data(), tab.size() * sizeof(int));
+    if (!gall.empty()) H2D(dgrain, gall.data(), gall.size() * sizeof(PsGrain));
+    hipLaunchKernelGGL(psola_synth_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, c->rs_in, c->rs_meta, (int)(j1 - j0), dgrain,
+                       c->rs_out, ps_wmax(g));
+    for (size_t k = j0; k < j1; ++k) {
+      const PsJob& j = jobs[k];
+      if (lens[j.row] > 0) D2H(out + (long)j.row * out_stride, c->rs_out + j.in_off, (size_t)lens[j.row] * sizeof(float));
     }
-    j0 = j1;
+    if (gtab && !gall.empty()) D2H(gtab, dgrain, gall.size() * sizeof(PsGrain));
+    SYNC();
+    HIPCHK(hipGetLastError());
   }
   for (int i = 0; i < batch; ++i) {
     if (marks) memcpy(marks + (long)i * marks_stride, rmarks[(size_t)i].data(), rmarks[(size_t)i].size() * sizeof(int32_t));
@@ -323,15 +318,13 @@ int vx_psola(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_t* len
              vx_psola_info* info) {
   using namespace vxe;
   if (!c) return VX_EINVAL;
-  if (!wav) FAIL(VX_EINVAL, "vx_psola: wav is NULL");
-  if (!lens) FAIL(VX_EINVAL, "vx_psola: lens is NULL");
+  if (int e = wave_check_rows(c, "vx_psola", wav, wav_stride, lens, batch)) return e;
   if (!lag) FAIL(VX_EINVAL, "vx_psola: lag is NULL");
   if (!o) FAIL(VX_EINVAL, "vx_psola: o is NULL");
   if (!out) FAIL(VX_EINVAL, "vx_psola: out is NULL");
   if (!info) FAIL(VX_EINVAL, "vx_psola: info is NULL");
-  if (batch <= 0) FAIL(VX_EINVAL, "vx_psola: batch %d below 1", batch);
   PsGeom g;
-  if (int e = ps_check(c, "vx_psola", wav_stride, lens, batch, lag_stride, ratio, o, out_stride, &g)) return e;
+  if (int e = ps_check(c, "vx_psola", lens, batch, lag_stride, ratio, o, out_stride, &g)) return e;
   return ps_run(c, "vx_psola", wav, wav_stride, lens, batch, lag, lag_stride, ratio, g, out, out_stride, marks, marks_stride, info, nullptr, 0,
                 nullptr, 0);
 }
@@ -347,7 +340,7 @@ int vx_dev_psola_table(vx_ctx* c, const float* wav, int32_t len, const int32_t* 
   if (len < 0) FAIL(VX_EINVAL, "vx_dev_psola_table: len %d below 0", len);
   PsGeom g;
   const int64_t big = 0x7fffffffL;
-  if (int e = ps_check(c, "vx_dev_psola_table", len, &len, 1, big, ratio, o, big, &g)) return e;
+  if (int e = ps_check(c, "vx_dev_psola_table", &len, 1, big, ratio, o, big, &g)) return e;
   std::vector<float> y((size_t)len + 1);
   vx_psola_info info;
   if (int e = ps_run(c, "vx_dev_psola_table", wav, len, &len, 1, lag, big, ratio, g, y.data(), big, nullptr, 0, &info, cost, cost_cap, grains,
@@ -359,13 +352,7 @@ int vx_dev_psola_table(vx_ctx* c, const float* wav, int32_t len, const int32_t* 
 }
 
 int vx_dev_psola_window(vx_ctx* c, int32_t samples) {
-  using namespace vxe;
-  if (!c) return VX_EINVAL;
-  if (samples != 0 && (samples < VX_DEV_PSOLA_WINDOW_MIN || samples > VX_PSOLA_WINDOW))
-    FAIL(VX_EINVAL, "vx_dev_psola_window: samples %d outside %d .. %d (0 restores the default)", samples, VX_DEV_PSOLA_WINDOW_MIN,
-         VX_PSOLA_WINDOW);
-  c->ps_window = samples;
-  return VX_OK;
+  return vxe::wave_set_window(c, &vx_ctx::ps_window, "vx_dev_psola_window", "samples", samples, VX_DEV_PSOLA_WINDOW_MIN, VX_PSOLA_WINDOW);
 }
 
 }  // extern "C"

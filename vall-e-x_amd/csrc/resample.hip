@@ -22,14 +22,14 @@
 // No atomics, no inline assembly.
 #include <utility>
 
-#include "engine_ctx.h"
+#include "wave_stage.h"
 #include "resample_host.h"
 
 #include "../../include/vallex_hip_dev.h"
 
 namespace vxe {
 
-// job record (RS_TAB ints, engine_ctx.h): {in_off, s_lo, in_cnt, L, blk0, nblk, out_off, out_cnt}
+// job record (RS_TAB ints, wave_stage.h): {in_off, s_lo, in_cnt, L, blk0, nblk, out_off, out_cnt}
 constexpr int RS_LDS = 8192;               // floats of input span a workgroup stages
 constexpr int RS_TILE_OUT = 2048;          // outputs a workgroup aims at
 static_assert(VX_DEV_RESAMPLE_WINDOW_MIN >= 256 && VX_DEV_RESAMPLE_WINDOW_MIN <= RS_IN_CAP, "window bounds of the dev header");
@@ -108,6 +108,28 @@ int rs_buffers(vx_ctx* c) {
   return dev_alloc(c, &c->rs_in, (size_t)RS_IN_CAP, false);
 }
 
+int wave_check_rows(vx_ctx* c, const char* who, const float* wav, int64_t wav_stride, const int32_t* lens, int batch) {
+  if (!wav) FAIL(VX_EINVAL, "%s: wav is NULL", who);
+  if (!lens) FAIL(VX_EINVAL, "%s: lens is NULL", who);
+  if (batch <= 0) FAIL(VX_EINVAL, "%s: batch %d below 1", who, batch);
+  for (int i = 0; i < batch; ++i)
+    if (lens[i] < 0 || lens[i] > wav_stride) FAIL(VX_EINVAL, "%s: lens[%d] = %ld outside 0 .. wav_stride %ld", who, i, (long)lens[i], (long)wav_stride);
+  return VX_OK;
+}
+
+int wave_check_out_stride(vx_ctx* c, const char* who, const int32_t* lens, int batch, int64_t out_stride, const char* note) {
+  for (int i = 0; i < batch; ++i)
+    if (lens[i] > out_stride) FAIL(VX_EINVAL, "%s: out_stride %ld below the %ld samples of row %d%s", who, (long)out_stride, (long)lens[i], i, note);
+  return VX_OK;
+}
+
+int wave_set_window(vx_ctx* c, long vx_ctx::*field, const char* who, const char* arg, int32_t samples, long lo, long hi) {
+  if (!c) return VX_EINVAL;
+  if (samples != 0 && (samples < lo || samples > hi)) FAIL(VX_EINVAL, "%s: %s %d outside %ld .. %ld (0 restores the default)", who, arg, samples, lo, hi);
+  c->*field = samples;
+  return VX_OK;
+}
+
 static int rs_blocks_per_tile(const RsGeom& g) {
   const long b_out = (RS_TILE_OUT + g.n - 1) / g.n;
   const long b_lds = g.K <= RS_LDS ? (RS_LDS - g.K) / g.o + 1 : 1;
@@ -122,11 +144,9 @@ int vx_resample(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_t* 
                 int32_t new_rate, float* out, int64_t out_stride, int32_t* out_lens) {
   using namespace vxe;
   if (!c) return VX_EINVAL;
-  if (!wav) FAIL(VX_EINVAL, "vx_resample: wav is NULL");
-  if (!lens) FAIL(VX_EINVAL, "vx_resample: lens is NULL");
+  if (int e = wave_check_rows(c, "vx_resample", wav, wav_stride, lens, batch)) return e;
   if (!out) FAIL(VX_EINVAL, "vx_resample: out is NULL");
   if (!out_lens) FAIL(VX_EINVAL, "vx_resample: out_lens is NULL");
-  if (batch <= 0) FAIL(VX_EINVAL, "vx_resample: batch %d below 1", batch);
   if (orig_rate <= 0) FAIL(VX_EINVAL, "vx_resample: orig_rate %d below 1", orig_rate);
   if (new_rate <= 0) FAIL(VX_EINVAL, "vx_resample: new_rate %d below 1", new_rate);
   RsGeom g;
@@ -138,7 +158,6 @@ int vx_resample(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_t* 
   std::vector<long> olen(batch);
   for (int i = 0; i < batch; ++i) {
     const long L = lens[i];
-    if (L < 0 || L > wav_stride) FAIL(VX_EINVAL, "vx_resample: lens[%d] = %ld outside 0 .. wav_stride %ld", i, L, (long)wav_stride);
     olen[i] = same ? L : rs_out_len(g, L);
     if (olen[i] > 0x7fffffffL) FAIL(VX_EINVAL, "vx_resample: lens[%d] = %ld gives %ld output samples, more than out_lens holds", i, L, olen[i]);
     if (olen[i] > out_stride) FAIL(VX_EINVAL, "vx_resample: out_stride %ld below the %ld output samples of row %d", (long)out_stride, olen[i], i);
@@ -150,7 +169,7 @@ int vx_resample(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_t* 
     }
     return VX_OK;
   }
-  const long win = c->rs_window ? c->rs_window : RS_IN_CAP;
+  const long win = wave_window(c->rs_window, RS_IN_CAP);
   if (g.K > win) FAIL(VX_EINVAL, "vx_resample: the window of %ld input samples (vx_dev_resample_window) is below the %ld taps of %d -> %d", win, g.K, orig_rate, new_rate);
   HIPCHK(hipSetDevice(c->dev));
   if (int e = rs_buffers(c)) return e;
@@ -163,9 +182,7 @@ int vx_resample(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_t* 
   std::vector<RsJob> jobs;
   if (!rs_plan(g, lens, batch, win, RS_OUT_CAP, RS_MAX_JOBS, &jobs)) FAIL(VX_EINVAL, "vx_resample: no block fits an empty launch (window %ld)", win);   // K <= win rules it out
   std::vector<int> tab;
-  for (size_t j0 = 0; j0 < jobs.size();) {
-    size_t j1 = j0;
-    while (j1 < jobs.size() && jobs[j1].launch == jobs[j0].launch) ++j1;
+  const int err = wave_launches(c, jobs, [&](size_t j0, size_t j1) -> int {
     tab.clear();
     long max_blk = 0;
     for (size_t k = j0; k < j1; ++k) {
@@ -187,10 +204,9 @@ int vx_resample(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_t* 
       const RsJob& j = jobs[k];
       D2H(out + (long)j.row * out_stride + j.a * g.n, c->rs_out + j.out_off, (size_t)j.out_cnt * sizeof(float));
     }
-    SYNC();
-    HIPCHK(hipGetLastError());
-    j0 = j1;
-  }
+    return VX_OK;
+  });
+  if (err) return err;
   for (int i = 0; i < batch; ++i) out_lens[i] = (int32_t)olen[i];
   return VX_OK;
 }
@@ -216,13 +232,8 @@ int vx_dev_resample_taps(vx_ctx* c, int32_t orig_rate, int32_t new_rate, float* 
 }
 
 int vx_dev_resample_window(vx_ctx* c, int32_t input_samples) {
-  using namespace vxe;
-  if (!c) return VX_EINVAL;
-  if (input_samples != 0 && (input_samples < VX_DEV_RESAMPLE_WINDOW_MIN || input_samples > RS_IN_CAP))
-    FAIL(VX_EINVAL, "vx_dev_resample_window: input_samples %d outside %d .. %ld (0 restores the default)", input_samples,
-         VX_DEV_RESAMPLE_WINDOW_MIN, RS_IN_CAP);
-  c->rs_window = input_samples;
-  return VX_OK;
+  return vxe::wave_set_window(c, &vx_ctx::rs_window, "vx_dev_resample_window", "input_samples", input_samples, VX_DEV_RESAMPLE_WINDOW_MIN,
+                              vxe::RS_IN_CAP);
 }
 
 }  // extern "C"

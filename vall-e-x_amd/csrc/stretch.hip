@@ -19,8 +19,7 @@
 // lanes of a wavefront read reg[c + j] at stride 1 (conflict-free) and t[j] as a broadcast.  Each lane keeps its best (D, d); six
 // shuffle steps reduce a wavefront, one LDS step the four of them.
 // LDS: 2 (2D + 2H) + H floats and 48 bytes -- 57 392 bytes at the largest options, 6.7 KiB at hop 240, search 150.
-#include "engine_ctx.h"
-#include "finish_host.h"
+#include "wave_stage.h"
 #include "stretch_host.h"
 
 #include "../../include/vallex_hip_dev.h"
@@ -157,7 +156,7 @@ static int st_tables(vx_ctx* c, int H) {
 }
 
 // every check of vx_stretch behind the pointers: options, lengths, strides.  olen [batch] = Lout of every row.
-static int st_check(vx_ctx* c, const char* who, int64_t wav_stride, const int32_t* lens, int batch, const vx_stretch_opts* o,
+static int st_check(vx_ctx* c, const char* who, const int32_t* lens, int batch, const vx_stretch_opts* o,
                     int64_t out_stride, bool has_pos, int64_t pos_stride, StGeom* g, std::vector<long>* olen) {
   CHECK_STRUCT(*o, vx_stretch_opts);
   char why[160];
@@ -166,7 +165,6 @@ static int st_check(vx_ctx* c, const char* who, int64_t wav_stride, const int32_
   olen->resize((size_t)batch);
   for (int i = 0; i < batch; ++i) {
     const long L = lens[i];
-    if (L < 0 || L > wav_stride) FAIL(VX_EINVAL, "%s: lens[%d] = %ld outside 0 .. wav_stride %ld", who, i, L, (long)wav_stride);
     const long n = st_out_len(*g, L), M = st_frames(*g, L);
     if (n > 0x7fffffffL || (M > 0 && st_nominal(*g, M - 1) + g->D > 0x7fffffffL))
       FAIL(VX_EINVAL, "%s: lens[%d] = %ld gives %ld output samples or a position above what out_lens / pos hold", who, i, L, n);
@@ -180,7 +178,7 @@ static int st_check(vx_ctx* c, const char* who, int64_t wav_stride, const int32_
 // the general path: plan, then one launch per group of jobs, everything of a launch behind one stream sync.  cost: one row only.
 static int st_run(vx_ctx* c, const char* who, const float* wav, int64_t wav_stride, const int32_t* lens, int batch, const StGeom& g,
                   float* out, int64_t out_stride, int32_t* pos, int64_t pos_stride, double* cost) {
-  const long win = c->st_window ? c->st_window : (long)VX_STRETCH_WINDOW;
+  const long win = wave_window(c->st_window, VX_STRETCH_WINDOW);
   std::vector<StJob> jobs;
   if (!st_plan(g, lens, batch, win, RS_OUT_CAP, ST_FRAME_CAP, ST_MAX_JOBS, &jobs))
     FAIL(VX_EINVAL, "%s: the window of %ld input samples (vx_dev_stretch_window) is below one frame's span at hop %d, search %d", who, win, g.H, g.D);
@@ -192,9 +190,7 @@ static int st_run(vx_ctx* c, const char* who, const float* wav, int64_t wav_stri
   const size_t lds = 48 + (size_t)(2 * S + g.H) * sizeof(float);
   std::vector<long> p_last((size_t)batch, 0);                    // p of the last frame a launch has walked, per row
   std::vector<int> tab, last;
-  for (size_t j0 = 0; j0 < jobs.size();) {
-    size_t j1 = j0;
-    while (j1 < jobs.size() && jobs[j1].launch == jobs[j0].launch) ++j1;
+  return wave_launches(c, jobs, [&](size_t j0, size_t j1) -> int {
     tab.clear();
     last.assign(j1 - j0, 0);
     for (size_t k = j0; k < j1; ++k) {
@@ -221,12 +217,11 @@ static int st_run(vx_ctx* c, const char* who, const float* wav, int64_t wav_stri
       if (cost) D2H(cost + j.k0, c->st_cost + j.f_off, (size_t)nf * sizeof(double));
       D2H(&last[k - j0], c->st_pos + j.f_off + nf - 1, sizeof(int));
     }
-    SYNC();
-    HIPCHK(hipGetLastError());
+    return VX_OK;
+  }, [&](size_t j0, size_t j1) -> int {
     for (size_t k = j0; k < j1; ++k) p_last[(size_t)jobs[k].row] = last[k - j0];
-    j0 = j1;
-  }
-  return VX_OK;
+    return VX_OK;
+  });
 }
 
 }  // namespace vxe
@@ -237,15 +232,13 @@ int vx_stretch(vx_ctx* c, const float* wav, int64_t wav_stride, const int32_t* l
                int64_t out_stride, int32_t* out_lens, int32_t* pos, int64_t pos_stride) {
   using namespace vxe;
   if (!c) return VX_EINVAL;
-  if (!wav) FAIL(VX_EINVAL, "vx_stretch: wav is NULL");
-  if (!lens) FAIL(VX_EINVAL, "vx_stretch: lens is NULL");
+  if (int e = wave_check_rows(c, "vx_stretch", wav, wav_stride, lens, batch)) return e;
   if (!o) FAIL(VX_EINVAL, "vx_stretch: o is NULL");
   if (!out) FAIL(VX_EINVAL, "vx_stretch: out is NULL");
   if (!out_lens) FAIL(VX_EINVAL, "vx_stretch: out_lens is NULL");
-  if (batch <= 0) FAIL(VX_EINVAL, "vx_stretch: batch %d below 1", batch);
   StGeom g;
   std::vector<long> olen;
-  if (int e = st_check(c, "vx_stretch", wav_stride, lens, batch, o, out_stride, pos != nullptr, pos_stride, &g, &olen)) return e;
+  if (int e = st_check(c, "vx_stretch", lens, batch, o, out_stride, pos != nullptr, pos_stride, &g, &olen)) return e;
   if (g.num == g.den) {                                          // nothing to stretch: the input bits
     for (int i = 0; i < batch; ++i) {
       if (olen[(size_t)i]) memmove(out + (long)i * out_stride, wav + (long)i * wav_stride, (size_t)olen[(size_t)i] * sizeof(float));
@@ -270,18 +263,13 @@ int vx_dev_stretch_costs(vx_ctx* c, const float* wav, int32_t len, const vx_stre
   StGeom g;
   std::vector<long> olen;
   const int64_t big = 0x7fffffffL;
-  if (int e = st_check(c, "vx_dev_stretch_costs", len, &len, 1, o, big, true, big, &g, &olen)) return e;
+  if (int e = st_check(c, "vx_dev_stretch_costs", &len, 1, o, big, true, big, &g, &olen)) return e;
   return st_run(c, "vx_dev_stretch_costs", wav, len, &len, 1, g, out, big, pos, big, cost);
 }
 
 int vx_dev_stretch_window(vx_ctx* c, int32_t input_samples) {
-  using namespace vxe;
-  if (!c) return VX_EINVAL;
-  if (input_samples != 0 && (input_samples < VX_DEV_STRETCH_WINDOW_MIN || input_samples > VX_STRETCH_WINDOW))
-    FAIL(VX_EINVAL, "vx_dev_stretch_window: input_samples %d outside %d .. %d (0 restores the default)", input_samples,
-         VX_DEV_STRETCH_WINDOW_MIN, VX_STRETCH_WINDOW);
-  c->st_window = input_samples;
-  return VX_OK;
+  return vxe::wave_set_window(c, &vx_ctx::st_window, "vx_dev_stretch_window", "input_samples", input_samples, VX_DEV_STRETCH_WINDOW_MIN,
+                              VX_STRETCH_WINDOW);
 }
 
 }  // extern "C"
