@@ -394,6 +394,89 @@ typedef struct vx_stretch_opts {
 int vx_stretch(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t* lens, int32_t batch, const vx_stretch_opts* o,
                float* out, int64_t out_stride, int32_t* out_lens, int32_t* pos /* may be NULL */, int64_t pos_stride);
 
+/* Where the pauses of a row are: the frames pass of vx_finish (frames of o->frame = F samples, the same kernel and the same frame
+ * table) reduced on the host to the quiet stretches INSIDE the speech.  No reference counterpart.
+ *
+ * - Frames.  Frame f covers the samples [f F, min((f + 1) F, L)), n_f of them; e_f is the double sum of the exact squares of y in
+ *   sample order, y[i] = isfinite(x[i]) ? x[i] : 0, as vx_finish states it.
+ * - Quiet.  Frame f is quiet iff e_f <= 10^(silence_db / 10) * n_f -- the negation of vx_finish's active rule with the same
+ *   operands, so the detector and `trim` agree to the bit on every frame.
+ * - Pauses.  Let f_first and f_last be the first and the last frame that is not quiet.  A pause is a maximal run [f_a, f_b) of quiet
+ *   frames with f_first < f_a and f_b <= f_last, of at least min_frames frames.  Leading and trailing silence are no pauses (they
+ *   are vx_finish's trim); a row without an active frame has none.
+ * - Spans.  A pause is reported as the sample span [f_a F + keep, f_b F - keep) and dropped when that span is empty.  Spans come in
+ *   order: spans[b][2 i], spans[b][2 i + 1] = begin, end of pause i; counts[b] = the number reported.
+ * - Refusals.  VX_EINVAL, nothing launched or written behind the frames pass, the message names the field: a wrong struct_size; NULL
+ *   wav / lens / o / spans / counts; batch <= 0; a length negative or above wav_stride; frame outside 16 .. 4096; silence_db not
+ *   finite or above 0; min_frames below 1; keep below 0; a span_stride below 2 * counts[b] -- the message names the row and the
+ *   count needed, and no row's spans are written.
+ * - Limits.  The detector assumes a steady noise floor, as `trim` does: one threshold for the whole row.
+ * - State.  As vx_finish: no weights, no decode state, the resampler's launch buffers; the launch window of the frames pass is
+ *   vx_finish's. */
+typedef struct vx_pause_opts {
+  uint32_t struct_size;   /* = sizeof(vx_pause_opts) */
+  int32_t frame;          /* F, 16 .. 4096 samples (10 ms = rate / 100) */
+  float silence_db;       /* finite, <= 0: a frame at or below this mean square (dBFS) is quiet */
+  int32_t min_frames;     /* >= 1: the shortest run of quiet frames that is a pause */
+  int32_t keep;           /* >= 0: samples of a pause left out of its span at either end */
+} vx_pause_opts;
+int vx_pauses(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t* lens, int32_t batch, const vx_pause_opts* o,
+              int32_t* spans, int64_t span_stride /* in int32 elements */, int32_t* counts);
+
+/* A piecewise time map applied by WSOLA: where vx_stretch has one speed for the row, vx_retime takes anchors (input sample, output
+ * sample) and maps every segment between two anchors at its own rate.  Segments of equal input and output length are copied, the
+ * others are walked by WSOLA under vx_stretch's arithmetic with both ends pinned, so that every segment starts and ends at a known
+ * input sample and the segments of a row do not depend on each other.  No reference counterpart.  Inputs are a row x of length L,
+ * its anchors and the options hop (H) and search (D).
+ *
+ * - Anchors.  Row b has n_anchors[b] = m + 1 anchors (a_i, b_i), i = 0 .. m, at anchors[b][2 i], anchors[b][2 i + 1]; both
+ *   coordinates strictly increase, (a_0, b_0) = (0, 0) and a_m = L.  Lout = b_m.  A row of length 0 has the single anchor (0, 0)
+ *   and writes nothing.
+ * - Segments.  Segment i maps the input [a_i, a_{i+1}), la samples, onto the output [b_i, b_{i+1}), lb samples.
+ * - Samples.  y[i] = isfinite(x[i]) ? x[i] : 0.  Outside [0, L), y = 0.
+ * - Copy segment, la == lb.  out[b_i + j] has the bits of x[a_i + j], non-finite values included, as vx_stretch at speed 1.
+ * - Walked segment, la != lb.  It needs la >= 2H, lb >= 2H and 1/4 <= la / lb <= 4.  It has M = floor(lb / H) frames and rem =
+ *   lb - M H; frame k writes the output samples [b_i + k H, b_i + (k + 1) H), the last one rem more.
+ *   - Start pin.  p_0 = a_i and out[b_i + j] = y[a_i + j] for j in [0, H); cost 0.  The segment before ended at a_i exactly.
+ *   - Nominal positions, 1 <= k <= M - 1.  n_k = a_i + floor(k * (la - lb + (M - 1) H) / (M - 1)) in 64-bit integers: the straight
+ *     line from p_0 to the end pin.
+ *   - Template.  t[j] = y[p_{k-1} + H + j], j in [0, H).  It may read past a_{i+1}: the row's own samples, 0 past its end.
+ *   - Search, 1 <= k <= M - 2.  d in [-D, D] with a_i <= n_k + d <= a_{i+1} - H; d = 0 always qualifies.  For every such d ONE LANE
+ *     computes two double sums from 0.0 in order j = 0 .. H-1: c_d = sum (double)y[n_k + d + j] * (double)t[j] and e_d = sum
+ *     (double)y[n_k + d + j]^2; D_d = e_d - 2.0 * c_d.  p_k = n_k + d* with the smallest D_d, ties to the smallest |d|, then to the
+ *     negative d.  Every product is exact in double: contraction changes no bit.
+ *   - End pin, k = M - 1.  p_{M-1} = n_{M-1} = a_{i+1} - (H + rem) without a search; its cost is D_0, the D of that one offset.
+ *   - Crossfade, 1 <= k <= M - 1.  out[b_i + k H + j] = (float)((double)y[p_k + j] * (double)w[j] + (double)t[j] * (double)w[H-1-j])
+ *     with the smoothstep table w of H entries (vx_stretch's).  Frame M - 1 then continues plainly: out[b_i + M H + j] =
+ *     y[p_{M-1} + H + j] for j in [0, rem).  The segment therefore ends with y[a_{i+1} - 1] and the next one goes on from a_{i+1}.
+ * - Tables.  pos[b] and cost[b] (either may be NULL) hold p_k and the winning D_d of the frames of the row's walked segments, in
+ *   segment order, frame order inside a segment; their count is the sum of M over the walked segments.
+ * - Exactness.  A sample's bits depend on its row, its anchors and the options only: not on the batch, the launch windows or the
+ *   workgroup a segment lands on.  No atomics.  Two calls give the same bits.
+ * - Windows.  One launch holds VX_RETIME_WINDOW input samples.  A walked segment is one job and is never cut: it needs its samples
+ *   [a_i - D, a_{i+1} + D + H), cut to the row, inside one launch.  Copy segments are cut anywhere.
+ * - Refusals.  VX_EINVAL, nothing launched, nothing written, the message names the field: a wrong struct_size; NULL wav / lens /
+ *   anchors / n_anchors / o / out / out_lens; batch <= 0; a length negative or above wav_stride; hop outside 16 .. 2048; search
+ *   outside 0 .. 1024; n_anchors[b] below 1 or 2 n_anchors[b] above anchor_stride; anchors that do not start at (0, 0), do not
+ *   increase or do not end at a_m = L; a walked segment with la or lb below 2H, or la / lb outside 1/4 .. 4; a walked segment longer
+ *   than a launch window; out_stride below a row's Lout; pos_stride below a row's frame count when pos or cost is given.
+ * - Limits.  The end pin is a forced offset: an anchor in the middle of voiced speech can cost a phase step across one hop, and
+ *   `cost` shows it -- put anchors into pauses and between words.  A walked segment is not cut across launches.
+ * - State.  As vx_stretch.
+ *
+ *   wav [batch][wav_stride] fp32; anchors [batch][anchor_stride] int32; out [batch][out_stride] fp32, out_lens [batch] = Lout; pos
+ *   [batch][pos_stride] int32, cost [batch][pos_stride] double.  Elements behind out_lens[b] and behind the last record are not
+ *   written. */
+#define VX_RETIME_WINDOW (1 << 23)
+typedef struct vx_retime_opts {
+  uint32_t struct_size;   /* = sizeof(vx_retime_opts) */
+  int32_t hop;            /* H, 16 .. 2048 samples */
+  int32_t search;         /* D, 0 .. 1024 samples on either side of the nominal position */
+} vx_retime_opts;
+int vx_retime(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t* lens, int32_t batch, const int32_t* anchors,
+              int64_t anchor_stride /* in int32 elements */, const int32_t* n_anchors, const vx_retime_opts* o, float* out,
+              int64_t out_stride, int32_t* out_lens, int32_t* pos /* may be NULL */, double* cost /* may be NULL */, int64_t pos_stride);
+
 /* Programme loudness after ITU-R BS.1770 (the quantity of EBU R 128 and of every delivery specification in LUFS) of mono fp32 rows on
  * the device, and vx_finish with its level step replaced by a loudness target.  No reference counterpart.  All arithmetic is double
  * unless stated.  Every operation named is separately rounded.  A plain numpy restatement reproduces every quantity bit for bit, given

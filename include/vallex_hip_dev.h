@@ -414,6 +414,13 @@ int vx_dev_stretch_window(vx_ctx* ctx, int32_t input_samples);
  * arithmetic, not by a shortcut.  VX_EINVAL, nothing written: a NULL pointer, len < 0, options out of range. */
 int vx_dev_stretch_costs(vx_ctx* ctx, const float* wav, int32_t len, const vx_stretch_opts* o, float* out, int32_t* pos, double* cost);
 
+/* Input samples one launch of vx_retime holds, for later calls on this context: VX_DEV_RETIME_WINDOW_MIN .. VX_RETIME_WINDOW, or 0 for
+ * the default (VX_RETIME_WINDOW).  A small window puts the segments of one row into different launches -- what the window tests need;
+ * the device buffers keep their size.  A walked segment is never cut: while a window below its span (la + 2 search + hop, cut to the
+ * row) is set, vx_retime refuses that segment (VX_EINVAL).  VX_EINVAL, nothing changed, for any other value. */
+#define VX_DEV_RETIME_WINDOW_MIN 2048
+int vx_dev_retime_window(vx_ctx* ctx, int32_t input_samples);
+
 /* The step table of ONE row as loudness_steps_kernel (csrc/loudness.hip, the steps pass of vx_loudness and vx_finish_loud) writes it:
  * z [ceil(n / S)], S = sample_rate / 10, z_j = the K-weighted energy of samples [j S, min((j + 1) S, n)) as include/vallex_hip.h
  * defines it.  The row goes through the same planner and windows as vx_loudness.  VX_EINVAL, nothing written: a NULL pointer, n < 0,

@@ -87,6 +87,16 @@ class vx_stretch_opts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("speed_num", C.c_int32), ("speed_den", C.c_int32), ("hop", C.c_int32), ("search", C.c_int32)]
 
 
+class vx_pause_opts(C.Structure):
+    """options of vx_pauses (the pause detector: the frame and threshold of vx_finish, the shortest run, the margin kept)"""
+    _fields_ = [("struct_size", C.c_uint32), ("frame", C.c_int32), ("silence_db", C.c_float), ("min_frames", C.c_int32), ("keep", C.c_int32)]
+
+
+class vx_retime_opts(C.Structure):
+    """options of vx_retime (the time map: hop and search radius of the WSOLA frames of its walked segments)"""
+    _fields_ = [("struct_size", C.c_uint32), ("hop", C.c_int32), ("search", C.c_int32)]
+
+
 class vx_wave_info(C.Structure):
     """what vx_finish measured of one row"""
     _fields_ = [("begin", C.c_int32), ("end", C.c_int32), ("active_frames", C.c_int32), ("nonfinite", C.c_int32), ("clipped", C.c_int32),
@@ -156,7 +166,7 @@ SYMBOLS = ["vx_abi_version", "vx_create", "vx_destroy", "vx_last_error", "vx_syn
            "vx_fallback_reset", "vx_arith_mode", "vx_infer_continuous", "vx_serve_open", "vx_serve_submit", "vx_serve_run",
            "vx_serve_close", "vx_serve_submit_ex", "vx_serve_cancel", "vx_serve_submit_filtered", "vx_score", "vx_align", "vx_resample",
            "vx_finish", "vx_stretch", "vx_loudness_coeffs", "vx_loudness", "vx_finish_loud", "vx_limit_taps", "vx_limit",
-           "vx_finish_limited", "vx_psola", "vx_denoise_tables", "vx_denoise"]
+           "vx_finish_limited", "vx_psola", "vx_denoise_tables", "vx_denoise", "vx_pauses", "vx_retime"]
 # ... and include/vallex_hip_dev.h: measurement / kernel development, never called by the mirrors of the reference API
 DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kernel", "vx_bench_gemm", "vx_bench_attn",
                "vx_bench_gemm_clock", "vx_bench_gemm_epilogue", "vx_dev_sample", "vx_dev_attn", "vx_dev_sample_filtered",
@@ -164,7 +174,7 @@ DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kerne
                "vx_dev_seam_op", "vx_dev_resample_taps", "vx_dev_resample_window", "vx_dev_finish_frames", "vx_dev_finish_window",
                "vx_dev_stretch_window", "vx_dev_stretch_costs", "vx_dev_loudness_steps", "vx_dev_loudness_window",
                "vx_dev_limit_gain", "vx_dev_limit_window", "vx_dev_psola_table", "vx_dev_psola_window", "vx_dev_switches",
-               "vx_dev_denoise_fft", "vx_dev_denoise_table", "vx_dev_denoise_window", "vx_dev_denoise_div"]
+               "vx_dev_denoise_fft", "vx_dev_denoise_table", "vx_dev_denoise_window", "vx_dev_denoise_div", "vx_dev_retime_window"]
 # the pitch tracker's entries, one of vallex_hip.h and two of vallex_hip_dev.h, in a list of their own: the header scan of
 # tests/test_abi.py matches names of letters and underscores, and these carry a digit (tests/test_f0_refs.py checks them)
 F0_SYMBOLS = ["vx_f0"]
@@ -202,6 +212,7 @@ DEV_ALIGN_ROW_TILE, DEV_ALIGN_KEY_TILE = 32, 32      # VX_DEV_ALIGN_* of include
 RESAMPLE_WINDOW, DEV_RESAMPLE_WINDOW_MIN = 1 << 23, 512     # VX_RESAMPLE_WINDOW / VX_DEV_RESAMPLE_WINDOW_MIN: input samples per launch
 FINISH_WINDOW, DEV_FINISH_WINDOW_MIN = 1 << 23, 512         # VX_FINISH_WINDOW / VX_DEV_FINISH_WINDOW_MIN: input samples per launch
 STRETCH_WINDOW, DEV_STRETCH_WINDOW_MIN = 1 << 23, 2048      # VX_STRETCH_WINDOW / VX_DEV_STRETCH_WINDOW_MIN: input samples per launch
+RETIME_WINDOW, DEV_RETIME_WINDOW_MIN = 1 << 23, 2048        # VX_RETIME_WINDOW / VX_DEV_RETIME_WINDOW_MIN: input samples per launch
 LOUDNESS_WINDOW, DEV_LOUDNESS_WINDOW_MIN = 1 << 23, 4096    # VX_LOUDNESS_WINDOW / VX_DEV_LOUDNESS_WINDOW_MIN: samples per launch
 LIMIT_WINDOW, DEV_LIMIT_WINDOW_MIN = 1 << 23, 8192          # VX_LIMIT_WINDOW / VX_DEV_LIMIT_WINDOW_MIN: samples per launch
 F0_WINDOW, DEV_F0_WINDOW_MIN = 1 << 23, 3072                # VX_F0_WINDOW / VX_DEV_F0_WINDOW_MIN: samples per launch
@@ -358,6 +369,10 @@ def load_library() -> C.CDLL:
                                          P(C.c_int32), C.c_int32, P(C.c_int32), P(C.c_double)]
     lib.vx_dev_denoise_window.argtypes = [ctx, C.c_int32]
     lib.vx_dev_denoise_div.argtypes = [ctx, P(C.c_double), P(C.c_double), C.c_int32, P(C.c_double)]
+    lib.vx_pauses.argtypes = [ctx, P(C.c_float), C.c_int64, P(C.c_int32), C.c_int32, P(vx_pause_opts), P(C.c_int32), C.c_int64, P(C.c_int32)]
+    lib.vx_retime.argtypes = [ctx, P(C.c_float), C.c_int64, P(C.c_int32), C.c_int32, P(C.c_int32), C.c_int64, P(C.c_int32), P(vx_retime_opts),
+                              P(C.c_float), C.c_int64, P(C.c_int32), P(C.c_int32), P(C.c_double), C.c_int64]
+    lib.vx_dev_retime_window.argtypes = [ctx, C.c_int32]
     lib.vx_dev_stretch_costs.argtypes = [ctx, P(C.c_float), C.c_int32, P(vx_stretch_opts), P(C.c_float), P(C.c_int32), P(C.c_double)]
     lib.vx_last_stats.argtypes = [ctx, P(C.c_int64), P(C.c_int64), P(C.c_double), P(C.c_double)]
     lib.vx_last_truncated.argtypes = [ctx, P(C.c_int32)]
@@ -721,6 +736,79 @@ class Engine:
         """vx_dev_stretch_window: input samples one launch of `stretch` holds from now on (DEV_STRETCH_WINDOW_MIN .. STRETCH_WINDOW; 0
         restores the default)"""
         self._dev_window("stretch", input_samples)
+
+    def pauses(self, wavs: Sequence[np.ndarray], rate: int, silence_db: float = -50.0, min_ms: float = 150.0, keep_ms: float = 20.0):
+        """vx_pauses, where the pauses are: mono fp32 waveforms (L_i,) at `rate` -> a list of int32 arrays (n_i, 2) of sample spans
+        [begin, end).  The rows are measured in 10 ms frames (rate // 100) by the frames pass of `finish`; a frame whose mean square
+        is at or below 10^(silence_db / 10) is quiet -- the negation of `trim`'s rule -- and a pause is a run of at least min_ms of
+        quiet frames between the first and the last active frame, reported without keep_ms at either end.  Leading and trailing
+        silence are no pauses (Finish(trim=...) cuts those)."""
+        n = len(wavs)
+        if n == 0:
+            return []
+        frame = int(rate) // 100
+        o = vx_pause_opts(C.sizeof(vx_pause_opts), frame, float(silence_db), max(1, -(-int(round(float(min_ms) * int(rate) / 1000.0)) // max(1, frame))),
+                          int(round(float(keep_ms) * int(rate) / 1000.0)))
+        buf, lens, stride = self._packed(wavs)
+        sstride = 2 * max(1, -(-stride // max(1, frame)) // 2 + 1)
+        spans = np.zeros((n, sstride), np.int32)
+        counts = np.zeros(n, np.int32)
+        self._chk(self.lib.vx_pauses(self.ctx, _ptr(buf, C.c_float), stride, _ptr(lens, C.c_int32), n, C.byref(o), _ptr(spans, C.c_int32),
+                                     sstride, _ptr(counts, C.c_int32)))
+        return [spans[i, : 2 * counts[i]].reshape(-1, 2).copy() for i in range(n)]
+
+    last_retime_info = None          # per row of the last `retime`: dict(segments, walked, frames, out_len)
+
+    def retime(self, wavs: Sequence[np.ndarray], maps, hop: Optional[int] = None, search: Optional[int] = None, sample_rate: int = 24000,
+               positions: bool = False):
+        """vx_retime, a piecewise time map: mono fp32 waveforms (L_i,) and, per row, anchors (k_i, 2) of (input sample, output sample)
+        from (0, 0) to (L_i, Lout_i), strictly increasing (utils.alignment.pause_map / pace_map build them) -> a list of float32
+        arrays of Lout_i samples.  A segment between two anchors that keeps its length is copied bit for bit; any other is walked by
+        WSOLA (the arithmetic of `stretch`) from its first to its last input sample exactly, at 1/4 .. 4 times the pace, and needs 2
+        hops on either side.  hop None = 10 ms, search None = 6.25 ms at sample_rate.  positions: (waveforms, positions, costs) --
+        per row the input sample and the match cost of every frame of its walked segments, in order.  Sets last_retime_info."""
+        n = len(wavs)
+        if n != len(maps):
+            raise ValueError(f"{n} waveforms and {len(maps)} maps")
+        if n == 0:
+            self.last_retime_info = []
+            return ([], [], []) if positions else []
+        o = vx_retime_opts(C.sizeof(vx_retime_opts), int(sample_rate) // 100 if hop is None else int(hop),
+                           int(sample_rate) // 160 if search is None else int(search))
+        ans = [np.ascontiguousarray(m, np.int64).reshape(-1, 2) for m in maps]
+        for a in ans:
+            if len(a) and (np.abs(a) >= 2 ** 31).any():
+                raise ValueError("an anchor does not fit int32")
+        buf, lens, stride = self._packed(wavs)
+        astride = 2 * max(1, max(len(a) for a in ans))
+        anc = np.zeros((n, astride), np.int32)
+        na = np.array([len(a) for a in ans], np.int32)
+        info = []
+        for i, a in enumerate(ans):
+            anc[i, : 2 * len(a)] = a.reshape(-1)
+            d = np.diff(a, axis=0)
+            wk = d[d[:, 0] != d[:, 1]] if len(d) else d
+            info.append(dict(segments=int(len(d)), walked=int(len(wk)), frames=int((wk[:, 1] // max(1, o.hop)).sum()) if len(wk) else 0,
+                             out_len=int(a[-1, 1]) if len(a) else 0))
+        ostride = max(1, max(min(max(r["out_len"], 0), 2 ** 31 - 1) for r in info))
+        pstride = max(1, max(max(r["frames"], 0) for r in info))
+        out = np.empty((n, ostride), np.float32)
+        out_lens = np.zeros(n, np.int32)
+        pos = np.zeros((n, pstride), np.int32) if positions else None
+        cost = np.zeros((n, pstride), np.float64) if positions else None
+        self._chk(self.lib.vx_retime(self.ctx, _ptr(buf, C.c_float), stride, _ptr(lens, C.c_int32), n, _ptr(anc, C.c_int32), astride,
+                                     _ptr(na, C.c_int32), C.byref(o), _ptr(out, C.c_float), ostride, _ptr(out_lens, C.c_int32),
+                                     None if pos is None else _ptr(pos, C.c_int32), None if cost is None else _ptr(cost, C.c_double), pstride))
+        self.last_retime_info = info
+        rows = [out[i, : out_lens[i]] for i in range(n)]
+        if not positions:
+            return rows
+        return rows, [pos[i, : info[i]["frames"]] for i in range(n)], [cost[i, : info[i]["frames"]] for i in range(n)]
+
+    def dev_retime_window(self, input_samples: int = 0):
+        """vx_dev_retime_window: input samples one launch of `retime` holds from now on (DEV_RETIME_WINDOW_MIN .. RETIME_WINDOW; 0
+        restores the default)"""
+        self._dev_window("retime", input_samples)
 
     @staticmethod
     def _packed(wavs):
@@ -1214,6 +1302,20 @@ class Engine:
             return self.shift(rows, pitch, speed)
         return rows if speed is None else self.stretch(rows, speed)
 
+    def _paused(self, rows, pauses, rate: int = 24000):
+        """the rows of a vocoder call (or an enrolment clip) through `pauses` (an object with the fields of utils.generation.Pauses; None:
+        as they are) at `rate`: `pauses` finds the spans, utils.alignment.pause_map turns them into anchors, `retime` applies them"""
+        if pauses is None:
+            return rows
+        from .utils.alignment import pause_map
+        rate = int(rate)
+        ms = lambda v: None if v is None else int(round(float(v) * rate / 1000.0))
+        rows = [np.ascontiguousarray(r, np.float32).reshape(-1) for r in rows]
+        spans = self.pauses(rows, rate, pauses.silence_db, pauses.at_least_ms, pauses.keep_ms)
+        maps = [pause_map(len(r), sp, max_len=ms(pauses.max_ms), min_len=ms(pauses.min_ms), scale=pauses.scale, hop=rate // 100)
+                for r, sp in zip(rows, spans)]
+        return self.retime(rows, maps, sample_rate=rate)
+
     last_finish_info = None          # the info dicts of the last call that went through a `finish=` argument
 
     def _finished(self, rows, finish, rate: int):
@@ -1238,9 +1340,10 @@ class Engine:
         return out
 
     def vocos_decode(self, codes: Sequence[np.ndarray], bandwidth_id: int = 2, sample_rate: int = 24000, finish=None, speed=None, pitch=None,
-                     denoise=None):
+                     denoise=None, pauses=None):
         """denoise (None: nothing runs; True or a utils.generation.Denoise): the decoded rows go through `denoise` first of all, directly
-        behind the vocoder.  speed (None: nothing runs): the decoded rows go through `stretch` at 24 kHz first; pitch (None: nothing runs): through `shift`
+        behind the vocoder.  pauses (None: nothing runs; a utils.generation.Pauses): then through `pauses` and `retime` at 24 kHz, which
+        shorten, lengthen or scale the pauses inside the speech, behind `denoise` and in front of speed and pitch.  speed (None: nothing runs): the decoded rows go through `stretch` at 24 kHz first; pitch (None: nothing runs): through `shift`
         instead, which takes the speed along; sample_rate other than 24000: then through `resample` (24000 -> sample_rate), one more
         launch; finish (a utils.generation.Finish): then through `finish` at that rate"""
         if pitch is not None:
@@ -1258,11 +1361,13 @@ class Engine:
         audio = np.empty((n, stride * 320), np.float32)
         self._chk(self.lib.vx_vocos_decode(self.ctx, _ptr(buf, C.c_int64), stride, _ptr(lens, C.c_int32), n,
                                            int(bandwidth_id), _ptr(audio, C.c_float), stride * 320))
-        rows = self._stretched(self._denoised([audio[i, : lens[i] * 320] for i in range(n)], denoise), speed, pitch)
+        rows = self._stretched(self._paused(self._denoised([audio[i, : lens[i] * 320] for i in range(n)], denoise), pauses), speed, pitch)
         return self._finished(rows if int(sample_rate) == 24000 else self.resample(rows, 24000, int(sample_rate)), finish, sample_rate)
 
-    def encodec_decode(self, codes: Sequence[np.ndarray], sample_rate: int = 24000, finish=None, speed=None, pitch=None, denoise=None):
-        """speed, pitch, sample_rate, finish, denoise: as vocos_decode (denoise, stretch or shift at 24 kHz, then resample, then finish)"""
+    def encodec_decode(self, codes: Sequence[np.ndarray], sample_rate: int = 24000, finish=None, speed=None, pitch=None, denoise=None,
+                       pauses=None):
+        """speed, pitch, sample_rate, finish, denoise, pauses: as vocos_decode (denoise, pauses, stretch or shift at 24 kHz, then resample,
+        then finish)"""
         if pitch is not None:
             self._shift_plan(pitch, speed)                                # a ValueError comes before the vocoder runs
         if denoise is not None:
@@ -1276,8 +1381,8 @@ class Engine:
         audio = np.zeros((n, stride * 320), np.float32)
         self._chk(self.lib.vx_encodec_decode(self.ctx, _ptr(buf, C.c_int64), stride, _ptr(lens, C.c_int32), n,
                                              _ptr(audio, C.c_float), stride * 320))
-        if speed is not None or pitch is not None or denoise is not None:
-            rows = self._stretched(self._denoised([audio[i, : lens[i] * 320] for i in range(n)], denoise), speed, pitch)
+        if speed is not None or pitch is not None or denoise is not None or pauses is not None:
+            rows = self._stretched(self._paused(self._denoised([audio[i, : lens[i] * 320] for i in range(n)], denoise), pauses), speed, pitch)
             return self._finished(rows if int(sample_rate) == 24000 else self.resample(rows, 24000, int(sample_rate)), finish, sample_rate)
         if int(sample_rate) != 24000:
             return self._finished(self.resample([audio[i, : lens[i] * 320] for i in range(n)], 24000, int(sample_rate)), finish, sample_rate)

@@ -232,6 +232,14 @@ struct vx_ctx {
   float *vfeat = nullptr, *vcol = nullptr, *vx0 = nullptr, *vx1 = nullptr, *vhid = nullptr, *vo = nullptr,
         *vreim = nullptr, *vframes = nullptr, *vaudio = nullptr;
   long v_rows_cap = 0;
+
+  // time map (vx_retime, retime.hip): runs in the resampler's launch buffers (rs_buffers); needs no weights.  Behind everything
+  // else: the fields in front of it keep the places they had
+  float* rt_fade = nullptr;        // [2048] the crossfade table of the hop it was last built for (rt_fade_n)
+  int rt_fade_n = 0;
+  int* rt_pos = nullptr;           // [RT_FRAME_CAP] positions of one launch's frames
+  double* rt_cost = nullptr;       // [RT_FRAME_CAP] winning costs of one launch's frames
+  long rt_window = 0;              // input samples per launch set by vx_dev_retime_window (0: the default, VX_RETIME_WINDOW)
 };
 
 #define HIPCHK(expr)                                                                                   \

@@ -115,3 +115,92 @@ def range_contour(f0, lag, ratio, scale) -> np.ndarray:
         med = vals[(vals.size - 1) // 2]
         out[v] = ratio * (f[v] / med) ** (scale - 1.0)
     return np.clip(np.rint(out * 65536.0), 43691, 131072).astype(np.int32)
+
+
+# ---- time maps for Engine.retime (vx_retime): anchors (input sample, output sample), integers throughout ---------------------------
+def _walkable(la: int, new: int, hop: int) -> int:
+    """the output length a segment of la input samples gets when `new` is asked for: la itself (a copy) where it is too short to walk
+    (below 2 hop), else `new` clamped to what vx_retime walks: at least 2 hop, and la / new inside 1/4 .. 4"""
+    if la < 2 * hop:
+        return la
+    return min(max(new, 2 * hop, -(-la // 4)), 4 * la)
+
+
+def _anchors(length: int, spans, new_lens) -> np.ndarray:
+    """(0, 0), then the two ends of every span with its new length, then (length, Lout); everything between the spans keeps its
+    length.  An anchor that repeats the one before it is dropped."""
+    out, shift, prev = [(0, 0)], 0, 0
+    for (s, e), n in zip(spans, new_lens):
+        s, e, n = int(s), int(e), int(n)
+        if not prev <= s < e <= length:
+            raise ValueError(f"span ({s}, {e}) is empty, out of order or outside 0 .. {length}")
+        for a, b in ((s, s + shift), (e, s + shift + n)):
+            if (a, b) != out[-1]:
+                out.append((a, b))
+        shift += n - (e - s)
+        prev = e
+    if (length, length + shift) != out[-1]:
+        out.append((int(length), int(length) + shift))
+    return np.array(out, np.int32).reshape(-1, 2)
+
+
+def pause_map(length: int, pauses, max_len=None, min_len=None, scale=None, hop: int = 240) -> np.ndarray:
+    """Anchors for `Engine.retime` that change the pauses of a row of `length` samples and nothing else: `pauses` (n, 2) are sample
+    spans as `Engine.pauses` returns them.  A pause of P samples becomes a walked segment of clamp(round_half_even(P * scale), min_len,
+    max_len) samples (scale None: P; a bound of None: none), then clamped to what vx_retime walks at `hop`: at least 2 hop and within
+    1/4 .. 4 of P.  A pause below 2 hop stays as it is, and everything between the pauses is copied bit for bit.  Returns (k, 2)
+    int32 from (0, 0) to (length, Lout).  Integers and Fractions only: the same anchors on every machine."""
+    from fractions import Fraction
+    length, hop = int(length), int(hop)
+    sp = np.asarray(pauses, np.int64).reshape(-1, 2)
+    new = []
+    for s, e in sp:
+        P = int(e - s)
+        n = P if scale is None else int(round(P * Fraction(scale)))          # round(Fraction) rounds half to even
+        if min_len is not None:
+            n = max(n, int(min_len))
+        if max_len is not None:
+            n = min(n, int(max_len))
+        new.append(_walkable(P, n, hop))
+    return _anchors(length, sp, new)
+
+
+def pace_map(length: int, segments, rates, hop: int = 240) -> np.ndarray:
+    """Anchors for `Engine.retime` that speak every token at its own pace: `segments` (n, 2) are the sample spans [first, end) of the
+    tokens, in order and not overlapping (the frames of `monotonic_segments` times 320: first * 320, (last + 1) * 320), `rates` (n,)
+    the pace of each (a number or Fraction; 2 = twice as fast, half as long).  A token of P samples gets round_half_even(P / rate)
+    samples, clamped as `pause_map` clamps; a token below 2 hop, and everything outside the tokens, keeps its length."""
+    from fractions import Fraction
+    length, hop = int(length), int(hop)
+    sp = np.asarray(segments, np.int64).reshape(-1, 2)
+    if len(sp) != len(rates):
+        raise ValueError(f"{len(sp)} segments and {len(rates)} rates")
+    new = []
+    for (s, e), r in zip(sp, rates):
+        r = Fraction(r)
+        if r <= 0:
+            raise ValueError(f"rate {r} is not positive")
+        P = int(e - s)
+        new.append(_walkable(P, int(round(P / r)), hop))
+    return _anchors(length, sp, new)
+
+
+def retimed_sample(anchors, t, inverse: bool = False):
+    """Where input sample `t` is heard after `Engine.retime` under `anchors` (k, 2) -- or, with inverse=True, which input sample is
+    heard at output sample `t`.  Exact at every anchor and linear in between: b_i + floor((t - a_i) lb / la) inside segment i.
+    Inside a copy segment that is exact.  Inside a walked segment of la input and lb output samples the sample truly heard at an
+    output time lies within D + 2 H |la / lb - 1| input samples of the line (search D, hop H): a frame is searched within D of its
+    nominal position, plays H input samples at the input's own pace while the line moves H la / lb, and the nominal positions aim at
+    the end pin, up to 2 H in front of the anchor -- D + 2 H at half or double pace.  Pass positions=True to `Engine.retime` for the
+    exact positions.  `t` is clamped to the map's range; it may be an array (int64 out)."""
+    an = np.asarray(anchors, np.int64).reshape(-1, 2)
+    if len(an) < 1:
+        raise ValueError("no anchors")
+    src, dst = (an[:, 1], an[:, 0]) if inverse else (an[:, 0], an[:, 1])
+    ta = np.clip(np.asarray(t, np.int64), src[0], src[-1])
+    if len(an) == 1:
+        out = np.full(ta.shape, dst[0], np.int64)
+    else:
+        i = np.clip(np.searchsorted(src, ta, side="right") - 1, 0, len(an) - 2)
+        out = dst[i] + (ta - src[i]) * (dst[i + 1] - dst[i]) // (src[i + 1] - src[i])
+    return int(out) if np.ndim(t) == 0 else out

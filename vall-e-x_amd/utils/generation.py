@@ -271,6 +271,40 @@ class Denoise:
         Engine._denoise_opts(self.strength_db, self.floor_db, self.frac, self.kmin, self.profile)
 
 
+@dataclass(frozen=True)
+class Pauses:
+    """A request to change the pauses inside the speech, accepted wherever `pauses=` is: a pause is a stretch of at least at_least_ms
+    at or below silence_db (the rule of Finish(trim=...), Engine.pauses) between the first and the last sound; keep_ms of it stay
+    untouched at either end.  Each pause is scaled by `scale` (None: kept), then held to min_ms .. max_ms (None: no bound), and walked
+    to that length by WSOLA (Engine.retime, vx_retime); everything else keeps its bits.  A pause can change by a factor of 4 at the
+    most and never falls below two hops (20 ms).  Leading and trailing silence are Finish's."""
+    max_ms: Optional[float] = None
+    min_ms: Optional[float] = None
+    scale: Optional[float] = None
+    silence_db: float = -50.0
+    at_least_ms: float = 150.0
+    keep_ms: float = 20.0
+
+    def __post_init__(self):
+        for name in ("max_ms", "min_ms", "scale"):
+            v = getattr(self, name)
+            if v is not None and not (np.isfinite(v) and v > 0):
+                raise ValueError(f"Pauses: {name} {v!r} is not a positive number")
+        if self.max_ms is not None and self.min_ms is not None and self.min_ms > self.max_ms:
+            raise ValueError(f"Pauses: min_ms {self.min_ms} above max_ms {self.max_ms}")
+        if not (np.isfinite(self.silence_db) and self.silence_db <= 0):
+            raise ValueError(f"Pauses: silence_db {self.silence_db!r} is not a finite value <= 0")
+        if not (np.isfinite(self.at_least_ms) and self.at_least_ms > 0 and np.isfinite(self.keep_ms) and self.keep_ms >= 0):
+            raise ValueError(f"Pauses: at_least_ms {self.at_least_ms!r} must be positive and keep_ms {self.keep_ms!r} not negative")
+
+
+def _paused(wavs, pauses):
+    """the 24 kHz waveforms of a vocoder call through `pauses` (None: as they are), behind `denoise` and in front of speed and pitch"""
+    if pauses is None:
+        return wavs
+    return model.engine._paused(wavs, pauses, SAMPLE_RATE)
+
+
 def _denoised(wavs, denoise):
     """the 24 kHz waveforms of a vocoder call through `denoise` (None: as they are), directly behind the vocoder"""
     if denoise is None:
@@ -328,7 +362,7 @@ def _infer_one(text, audio_prompts, text_prompts, lang_pr, language, accent, **k
 
 
 def generate_audio(text, prompt=None, language="auto", accent="no-accent", sample_rate=None, finish=None, speed=None, pitch=None,
-                   denoise=None, **kw):
+                   denoise=None, pauses=None, **kw):
     """utils/generation.py:92-152.  sample_rate (no reference counterpart; None = 24 kHz, the reference's): the waveform is resampled
     on the device (Engine.resample, vx_resample) to that rate.  finish (a `Finish`; None = the raw fp32 of the reference): the output
     stage behind it -- trim, level, fades, int16 with pcm16=True.  speed (a float, a Fraction or a (num, den) pair in 1/2 .. 2; None =
@@ -339,7 +373,10 @@ def generate_audio(text, prompt=None, language="auto", accent="no-accent", sampl
     `Pitch` (pitch, formants=True, range=None) keeps the formants instead (the pitch tracker, then the PSOLA shift: vx_f0, vx_psola)
     and can scale the intonation's range; it is accepted wherever `pitch=` is.  denoise (None = the waveform as the vocoder gave it;
     True or a `Denoise`): spectral noise suppression on the device (Engine.denoise, vx_denoise) directly behind the vocoder, before
-    speed, pitch, resample and finish -- for a preset that was enrolled from a noisy clip."""
+    speed, pitch, resample and finish -- for a preset that was enrolled from a noisy clip.  pauses (None = the pauses the model
+    sampled; a `Pauses`): the pauses inside the speech are found (Engine.pauses, vx_pauses) and shortened, lengthened or scaled by a
+    piecewise time map (Engine.retime, vx_retime) at 24 kHz, behind denoise and in front of speed and pitch; the speech between them
+    keeps its bits."""
     if model is None or vocos is None:
         raise RuntimeError("call preload_models() first")
     _check_pitch(pitch, speed)
@@ -363,6 +400,8 @@ def generate_audio(text, prompt=None, language="auto", accent="no-accent", sampl
     s = s.cpu().numpy() if torch is not None and isinstance(s, torch.Tensor) else np.asarray(s)
     if denoise is not None:
         s = _denoised([s.reshape(-1)], denoise)[0]
+    if pauses is not None:
+        s = _paused([s.reshape(-1)], pauses)[0]
     if speed is not None or pitch is not None:
         return _finished(_to_rate(_at_speed([s.reshape(-1)], speed, pitch), sample_rate), finish, sample_rate)[0]
     if finish is not None:
@@ -371,7 +410,7 @@ def generate_audio(text, prompt=None, language="auto", accent="no-accent", sampl
 
 
 def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent", text_languages=None, sample_rate=None, finish=None,
-                         speed=None, pitch=None, denoise=None, **kw):
+                         speed=None, pitch=None, denoise=None, pauses=None, **kw):
     """Batch form of `generate_audio` (no reference equivalent: the reference synthesises one utterance per call,
     utils/generation.py:92-152): utterance i of the batch equals `generate_audio(texts[i], prompts[i], language[i], accent)`.
     `texts`: strings (need the tokenizer hook) or phoneme-id arrays; `prompts`: one preset name / path / None per utterance (or
@@ -383,7 +422,8 @@ def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent
     `Finish`): the output stage behind it, one more call for the list.  `speed` (None = as produced): the speaking rate, one vx_stretch
     call for the list before both.  `pitch` (None = as produced): the pitch shift of `generate_audio`, Engine.shift for the list in
     place of the stretch.  `denoise` (None = as produced): the noise suppression of `generate_audio`, one Engine.denoise call for the
-    list directly behind Vocos.  Returns a list of float32 waveforms (int16 with pcm16=True)."""
+    list directly behind Vocos.  `pauses` (None = as produced): the pause control of `generate_audio`, one Engine.pauses and one
+    Engine.retime call for the list behind that.  Returns a list of float32 waveforms (int16 with pcm16=True)."""
     if model is None or vocos is None:
         raise RuntimeError("call preload_models() first")
     _check_pitch(pitch, speed)
@@ -396,7 +436,7 @@ def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent
             for text, prompt, lang_in, tl in zip(texts, prompts, langs_in, text_languages)]
     codes = model.inference_batch(rows, top_k=-100, temperature=1, **kw)
     return model.engine.vocos_decode(codes, 2, sample_rate=SAMPLE_RATE if sample_rate is None else int(sample_rate), finish=finish,
-                                     speed=speed, pitch=pitch, denoise=denoise)
+                                     speed=speed, pitch=pitch, denoise=denoise, pauses=pauses)
 
 
 def _utterance_row(text, prompt, lang_in, accent, tl=None) -> dict:
@@ -436,9 +476,10 @@ class AudioServer:
     applied behind that (vx_finish is allowed as well).  `speed` (None = as produced): ONE speaking rate for the server, applied to
     every delivered waveform between Vocos and the resampler (vx_stretch is allowed as well).  `pitch` (None = as produced): ONE pitch
     shift for the server (generate_audio's `pitch`), applied there in place of the stretch.  `denoise` (None = as produced): ONE noise
-    suppression for the server (generate_audio's `denoise`), applied directly behind Vocos (vx_denoise is allowed as well)."""
+    suppression for the server (generate_audio's `denoise`), applied directly behind Vocos (vx_denoise is allowed as well).  `pauses` (None = as produced): ONE pause
+    control for the server (generate_audio's `pauses`), applied behind that (vx_pauses and vx_retime are allowed as well)."""
 
-    def __init__(self, sample_rate=None, finish=None, speed=None, pitch=None, denoise=None, **serve_kw):
+    def __init__(self, sample_rate=None, finish=None, speed=None, pitch=None, denoise=None, pauses=None, **serve_kw):
         if model is None or vocos is None:
             raise RuntimeError("call preload_models() first")
         rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
@@ -451,9 +492,10 @@ class AudioServer:
         self.pitch = pitch
         _check_denoise(denoise)
         self.denoise = denoise
+        self.pauses = pauses
         self._server = model.serve(top_k=-100, temperature=1.0,
                                    post=lambda codes: model.engine.vocos_decode(codes, 2, sample_rate=rate, finish=finish, speed=speed,
-                                                                                pitch=pitch, denoise=denoise),
+                                                                                pitch=pitch, denoise=denoise, pauses=pauses),
                                    **serve_kw)
 
     def submit(self, text, prompt=None, language="auto", accent="no-accent", best_of=1, seed=None, uniforms=None,
@@ -478,10 +520,10 @@ class AudioServer:
 
 
 def generate_audio_from_long_text(text, prompt=None, language="auto", accent="no-accent", mode="sliding-window", sample_rate=None,
-                                  finish=None, speed=None, pitch=None, denoise=None, **kw):
+                                  finish=None, speed=None, pitch=None, denoise=None, pauses=None, **kw):
     """utils/generation.py:155-276.  `text` may also be a list of sentences / id arrays (pre-split).  sample_rate, finish, speed,
-    pitch, denoise: as generate_audio (the noise suppression, the stretch or the shift and the output stage see the concatenated
-    waveform once)."""
+    pitch, denoise, pauses: as generate_audio (the noise suppression, the pause control, the stretch or the shift and the output
+    stage see the concatenated waveform once)."""
     if model is None or vocos is None:
         raise RuntimeError("call preload_models() first")
     _check_pitch(pitch, speed)
@@ -534,6 +576,8 @@ def generate_audio_from_long_text(text, prompt=None, language="auto", accent="no
     s = s.cpu().numpy() if torch is not None and isinstance(s, torch.Tensor) else np.asarray(s)
     if denoise is not None:
         s = _denoised([s.reshape(-1)], denoise)[0]
+    if pauses is not None:
+        s = _paused([s.reshape(-1)], pauses)[0]
     if speed is not None or pitch is not None:
         return _finished(_to_rate(_at_speed([s.reshape(-1)], speed, pitch), sample_rate), finish, sample_rate)[0]
     if finish is not None:

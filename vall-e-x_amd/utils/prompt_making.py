@@ -142,13 +142,25 @@ def suppress_noise(wav: np.ndarray, denoise) -> np.ndarray:
     return np.array(G.model.engine._denoised([wav.reshape(-1)], denoise)[0], np.float32)[None]
 
 
+def shorten_pauses(wav: np.ndarray, max_pause_ms: float, sample_rate: int) -> np.ndarray:
+    """(1, L) mono fp32 at sample_rate -> the clip with every pause inside the speech held to max_pause_ms, on the loaded model's
+    engine (Engine.pauses and Engine.retime: vx_pauses, vx_retime; utils.generation.Pauses' defaults otherwise).  The speech keeps
+    its bits.  A long gap in an enrolment clip costs prompt frames of the KV arena on every request that uses it, as silence in
+    front of it does."""
+    if G.model is None:
+        raise RuntimeError("call preload_models() first: max_pause_ms runs on the loaded model's engine")
+    return np.array(G.model.engine._paused([wav.reshape(-1)], G.Pauses(max_ms=float(max_pause_ms)), int(sample_rate))[0], np.float32)[None]
+
+
 def tokenize_audio(tokenizer: AudioTokenizer, audio: Union[str, Tuple[np.ndarray, int]], trim_db: Optional[float] = None,
-                   lufs: Optional[float] = None, pitch=None, denoise=None):
+                   lufs: Optional[float] = None, pitch=None, denoise=None, max_pause_ms: Optional[float] = None):
     """data/tokenizer.py:99-111: (path | (wav (C, L), sr)) -> `tokenizer.encode(wav[None])` = [(codes (1, 8, T), None)].
     trim_db (no reference counterpart; None = the clip as it is): `trim_silence` on the 24 kHz mono clip before the encoder sees it.
     lufs (no reference counterpart; None = the clip's own level): `level_loudness` on that clip, after the trim.
     pitch (no reference counterpart; None = the clip's own pitch): `shift_pitch` on the 24 kHz mono clip, before the trim.
-    denoise (no reference counterpart; None = the clip as recorded): `suppress_noise` on the mono clip, first of all."""
+    denoise (no reference counterpart; None = the clip as recorded): `suppress_noise` on the mono clip, first of all.
+    max_pause_ms (no reference counterpart; None = the clip's own pauses): `shorten_pauses` on the mono clip, behind denoise and
+    pitch and in front of the trim."""
     wav, sr = _load_wav(audio) if isinstance(audio, str) else audio
     wav = np.asarray(wav.detach().cpu().numpy() if hasattr(wav, "detach") else wav, np.float32)
     if wav.ndim == 1:
@@ -163,6 +175,8 @@ def tokenize_audio(tokenizer: AudioTokenizer, audio: Union[str, Tuple[np.ndarray
         if tokenizer.sample_rate != 24000:
             raise ValueError(f"pitch: Engine.shift works at 24 kHz, the tokenizer at {tokenizer.sample_rate}")
         wav = shift_pitch(wav, pitch)
+    if max_pause_ms is not None:
+        wav = shorten_pauses(wav, max_pause_ms, tokenizer.sample_rate)
     if trim_db is not None:
         wav = trim_silence(wav, trim_db)
     if lufs is not None:
@@ -189,12 +203,13 @@ def make_transcript(name, wav, sr, transcript: Optional[str] = None):
 
 def make_prompt(name: str, audio_prompt_path: Union[str, Tuple[np.ndarray, int]], transcript: Optional[str] = None,
                 save_dir: Optional[str] = None, trim_db: Optional[float] = None, lufs: Optional[float] = None, pitch=None,
-                denoise=None) -> str:
+                denoise=None, max_pause_ms: Optional[float] = None) -> str:
     """utils/prompt_making.py:57-84.  `audio_prompt_path`: a WAV path or `(wav (C, L), sr)`.  Returns the path of the written .npz.
     trim_db: as `tokenize_audio` (leading and trailing silence of the clip is cut before it is encoded); lufs: as `tokenize_audio`
     (the clip is brought to that loudness, after the trim, before it is encoded); pitch: as `tokenize_audio` (the clip is shifted by
     that many semitones, or that ratio, before the trim: the cloned voice follows its prompt); denoise: as `tokenize_audio` (the
-    clip's steady noise is suppressed first of all, so that it is not cloned with the voice)."""
+    clip's steady noise is suppressed first of all, so that it is not cloned with the voice); max_pause_ms: as `tokenize_audio`
+    (every pause inside the speech is held to that length, behind denoise and pitch and in front of the trim)."""
     global codec
     if G.model is None:
         raise RuntimeError("call preload_models() first (with EnCodec weights: model.load_encodec_state_dict)")
@@ -209,7 +224,8 @@ def make_prompt(name: str, audio_prompt_path: Union[str, Tuple[np.ndarray, int]]
     if wav_pr.shape[0] == 2:                                      # :62-63
         wav_pr = wav_pr.mean(0, keepdims=True)
     text_pr, lang_pr = make_transcript(name, wav_pr, sr, transcript)
-    encoded_frames = tokenize_audio(codec, (wav_pr, sr), trim_db=trim_db, lufs=lufs, pitch=pitch, denoise=denoise)          # :67
+    encoded_frames = tokenize_audio(codec, (wav_pr, sr), trim_db=trim_db, lufs=lufs, pitch=pitch, denoise=denoise,
+                                    max_pause_ms=max_pause_ms)    # :67
     codes = encoded_frames[0][0]
     codes = codes.numpy() if hasattr(codes, "numpy") else np.asarray(codes)
     audio_tokens = np.transpose(codes, (0, 2, 1))                 # (1, T, 8)   (:68)
