@@ -11,6 +11,7 @@ import pytest
 
 from tests import _finish_refs as FR
 from tests import _retime_refs as R
+from tests import _stretch_refs as S
 from vallex_amd import _capi
 from vallex_amd._capi import VX_EINVAL, Engine, VallexHipError, _ptr
 from vallex_amd.utils.alignment import pause_map
@@ -186,6 +187,31 @@ def test_engine_retime_and_other_hops(eng, ref):
         _same(go[0], wo, (hop, D))
         _same(gp[0], wp.astype(np.int32), (hop, D))
         _same(gc[0], wc, (hop, D))
+
+
+def test_stretch_and_retime_share_their_tables(eng):
+    """vx_stretch and vx_retime keep one crossfade table (rebuilt when the hop changes) and one pair of position / cost tables in a
+    context.  One row through both, the hops alternating: a table left over from the other stage or the other hop would show in the
+    words.  The map has a copy, a walked segment with a searched frame and a pinned end with a tail at both hops, and another copy."""
+    x = S.rows(240)[6][:2000]
+    an = np.array([(0, 0), (300, 300), (1500, 1200), (2000, 1700)], np.int32)
+    assert [(900 // h, 900 % h) for h in (160, 240)] == [(5, 100), (3, 180)]      # frames and tail of the walked segment
+
+    def stretched(costs, hop, D):
+        want = S.stretch(x, 4, 5, hop, D)
+        if costs:
+            out, pos, cost = eng.dev_stretch_costs(x, (4, 5), hop, D)
+            _same(cost, want[2], ("stretch", hop, "cost"))
+        else:
+            (out,), (pos,) = eng.stretch([x], (4, 5), hop, D, return_positions=True)
+        _same(out, want[0], ("stretch", hop, "out"))
+        _same(pos, want[1].astype(np.int32), ("stretch", hop, "pos"))
+
+    stretched(False, 240, 150)
+    _check_rows(_raw(eng, [x], [an], 160, 100), [R.retime(x, an, 160, 100)], "retime 160 behind stretch 240")
+    stretched(False, 240, 150)
+    _check_rows(_raw(eng, [x], [an], 240, 150), [R.retime(x, an, 240, 150)], "retime 240 behind stretch 240")
+    stretched(True, 160, 100)
 
 
 def test_refusals(eng, ref):

@@ -6,8 +6,9 @@ its contract (tests/_stretch_refs.py) on the same host:
 A row is a serial walk over its frames (frame k starts from the position frame k - 1 found), so the 60 s row shows the cost per frame
 and the 32-row batch what running rows side by side on different CUs buys.  Best of --reps (default 3) after one warm-up call (the
 first call allocates the buffers and builds the crossfade table); the host clock stops behind the call's last stream
-synchronisation.  The bytes that cross the host boundary each way are counted from the shapes.
-   python tools/stretch_bench.py [--reps 3] [--out profiles/r23_stretch.json]
+synchronisation.  The bytes that cross the host boundary each way are counted from the shapes.  --largest adds 1 row x 8 s at the
+largest options (hop 2048, search 1024: the 24-register prefetch and the largest LDS layout of the walk).
+   python tools/stretch_bench.py [--reps 3] [--largest] [--out profiles/r23_stretch.json]
 The context is created without weights: the entry needs none.  No threshold, the numbers are a record."""
 import argparse
 import json
@@ -53,23 +54,24 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default="")
+    ap.add_argument("--largest", action="store_true", help="add 1 row x 8 s at hop 2048, search 1024")
     ap.add_argument("--no-ref", action="store_true", help="skip the numpy restatement (minutes of host time on the large cases)")
     a = ap.parse_args()
     eng = Engine(num_layers=2, max_batch=1, max_text=8, max_prompt=8, max_new=8, with_vocos=False)
     rng = np.random.default_rng(0)
     res = dict(reps=a.reps, hop=HOP, search=SEARCH, cases=[])
-    for rows, seconds in ((32, 8), (1, 60)):
+    for rows, seconds, hop, search in ((32, 8, HOP, SEARCH), (1, 60, HOP, SEARCH)) + (((1, 8, 2048, 1024),) if a.largest else ()):
         x = speech_like(rows, seconds, rng)
         for num, den in ((4, 5), (5, 4)):
-            dev_ms, (dev, pos) = best(lambda: eng.stretch(list(x), (num, den), HOP, SEARCH, RATE, return_positions=True), a.reps)
+            dev_ms, (dev, pos) = best(lambda: eng.stretch(list(x), (num, den), hop, search, RATE, return_positions=True), a.reps)
             frames = int(sum(len(p) for p in pos))
-            case = dict(rows=rows, seconds=seconds, speed=f"{num}/{den}", in_samples=int(x.size), out_samples=int(sum(len(d) for d in dev)),
+            case = dict(rows=rows, seconds=seconds, hop=hop, search=search, speed=f"{num}/{den}", in_samples=int(x.size), out_samples=int(sum(len(d) for d in dev)),
                         frames=frames, frames_of_the_longest_row=int(max(len(p) for p in pos)),
                         bytes_to_device=int(x.size) * 4 + rows * 64, bytes_to_host=int(sum(len(d) for d in dev)) * 4 + frames * 4 + rows * 4,
                         vx_stretch_wall_ms=dev_ms, wall_us_per_frame_of_the_longest_row=dev_ms * 1e3 / max(1, max(len(p) for p in pos)))
             if not a.no_ref:
                 t0 = time.perf_counter()
-                ref = [R.stretch(r, num, den, HOP, SEARCH) for r in x]          # once: it is slow and it is not what is measured
+                ref = [R.stretch(r, num, den, hop, search) for r in x]          # once: it is slow and it is not what is measured
                 case["numpy_restatement_wall_ms"] = (time.perf_counter() - t0) * 1e3
                 case["numpy_over_device"] = case["numpy_restatement_wall_ms"] / dev_ms
                 case["outputs_equal_the_restatement"] = bool(all(np.array_equal(d.view(np.uint32), w[0].view(np.uint32)) for d, w in zip(dev, ref)))

@@ -176,7 +176,8 @@ struct vx_ctx {
   float* fn_fade = nullptr;        // [2][2^20] the fade-in / fade-out tables, allocated by the first call with a fade
   int fn_fade_n[2] = {0, 0};       // the lengths the two device tables were last built for
   long fn_window = 0;              // input samples per launch set by vx_dev_finish_window (0: the default, VX_FINISH_WINDOW)
-  // time-stretch (vx_stretch, stretch.hip): runs in the resampler's launch buffers (rs_buffers); needs no weights
+  // time-stretch (vx_stretch, stretch.hip): runs in the resampler's launch buffers (rs_buffers); needs no weights.  The three tables
+  // are the time map's too (vx_retime: ws_tables, wave_stage.h)
   float* st_fade = nullptr;        // [2048] the crossfade table of the hop it was last built for (st_fade_n)
   int st_fade_n = 0;
   int* st_pos = nullptr;           // [ST_FRAME_CAP] positions of one launch's frames
@@ -233,12 +234,8 @@ struct vx_ctx {
         *vreim = nullptr, *vframes = nullptr, *vaudio = nullptr;
   long v_rows_cap = 0;
 
-  // time map (vx_retime, retime.hip): runs in the resampler's launch buffers (rs_buffers); needs no weights.  Behind everything
-  // else: the fields in front of it keep the places they had
-  float* rt_fade = nullptr;        // [2048] the crossfade table of the hop it was last built for (rt_fade_n)
-  int rt_fade_n = 0;
-  int* rt_pos = nullptr;           // [RT_FRAME_CAP] positions of one launch's frames
-  double* rt_cost = nullptr;       // [RT_FRAME_CAP] winning costs of one launch's frames
+  // time map (vx_retime, retime.hip): runs in the resampler's launch buffers (rs_buffers) and the stretch's tables; needs no weights.
+  // Behind everything else: the fields in front of it keep the places they had
   long rt_window = 0;              // input samples per launch set by vx_dev_retime_window (0: the default, VX_RETIME_WINDOW)
 };
 

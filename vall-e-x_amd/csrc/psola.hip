@@ -15,8 +15,8 @@
 // Work decomposition.  Marks: mark i + 1 needs mark i, so a row is a serial walk: one 256-thread workgroup per row, the rows of a
 // launch side by side on different CUs.  The template and the search region y[a + P - D, a + 2P + D) are widened once to double in
 // LDS (zeros outside the row and in place of non-finite samples); candidate c = d + D belongs to lane c mod 256 (at most 257
-// candidates), the lanes read reg[c + j] at stride 1 and t[j] as a broadcast; six shuffle steps reduce a wavefront, one LDS step the
-// four of them.  LDS: 8 + 2 period_max + 2 (period_max / 8) doubles -- 18 496 bytes at the largest options, 7.1 KiB at period_max 400.
+// candidates), the lanes read reg[c + j] at stride 1 and t[j] as a broadcast; the order and the reduction of the lanes' winners are
+// ws_walk.h's.  LDS: 8 + 2 period_max + 2 (period_max / 8) doubles -- 18 496 bytes at the largest options, 7.1 KiB at period_max 400.
 // Synthesis: a workgroup writes one tile of PS_TILE outputs of one row, four per lane.  The grains are sorted by s_j and none is
 // wider than Wmax = period_max + period_max / 8 on either side, so the tile's grains are the run with s_j in
 // (n0 - Wmax, n1 - 1 + Wmax], found by two bisections; they pass through LDS in chunks of 256 records and every lane walks them in
@@ -24,6 +24,7 @@
 // window of a few KiB).
 #include "wave_stage.h"
 #include "psola_host.h"
+#include "ws_walk.h"
 
 #include "../../include/vallex_hip_dev.h"
 
@@ -35,7 +36,6 @@ constexpr int PS_TAB = 16;                                   // ints of a job re
 constexpr int PS_MAX_JOBS = RS_MAX_JOBS * RS_TAB / PS_TAB;   // the records of a launch fill rs_meta
 constexpr int PS_TILE = 1024;                                // outputs of a synthesis workgroup
 constexpr int PS_CHUNK = 256;                                // grain records in LDS at a time
-constexpr int PS_NONE = 0x3fffffff;                          // the offset of a lane that saw no candidate: loses every tie
 // rs_out, in words: [0, RS_IN_CAP) the output samples, then the lags, the marks, the mark costs (doubles), the mark counts of the
 // jobs and the grain table (four ints a record)
 constexpr long PS_LAG_AT = RS_IN_CAP, PS_LAG_CAP = RS_IN_CAP / PS_HOP_MIN + PS_MAX_JOBS;
@@ -50,8 +50,6 @@ static_assert(PS_GRAIN_AT + 4 * PS_GRAIN_CAP <= RS_OUT_CAP, "the tables fit behi
 static_assert(PS_STEP_MIN == 14 && PS_GRAIN_STEP_MIN == 7, "the bounds the dev header promises");
 static_assert((8 + 2 * PS_PERIOD_MAX + 2 * (PS_PERIOD_MAX / 8)) * sizeof(double) <= 65536, "LDS of the largest options");
 static_assert(sizeof(PsGrain) == 16, "a grain record is four ints");
-
-__device__ __forceinline__ float ps_clean(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u ? x : 0.f; }
 
 // tab [njobs][PS_TAB]:
 //   0 in_off   first float of the row in `in` (and of its outputs in `out`);  1 L  samples of the row
@@ -69,7 +67,7 @@ __global__ __launch_bounds__(256) void psola_marks_kernel(const float* __restric
   const long in_off = tb[0], L = tb[1], Mf = tb[3], m_off = tb[4];
   const int m_cap = tb[5], tid = threadIdx.x;
   const int* lg = lag + tb[2];
-  auto y_at = [&](long s) -> double { return s >= 0 && s < L ? (double)ps_clean(in[in_off + s]) : 0.0; };
+  auto y_at = [&](long s) -> double { return s >= 0 && s < L ? (double)ws_clean(in[in_off + s]) : 0.0; };
   long a = 0;
   int i = 0;
   for (;;) {                                                     // a and i are the same in every lane
@@ -89,7 +87,7 @@ __global__ __launch_bounds__(256) void psola_marks_kernel(const float* __restric
     for (int j = tid; j < R; j += 256) reg[j] = y_at(a + P - D + j);
     __syncthreads();
     double bC = __builtin_inf();
-    int bd = PS_NONE;
+    int bd = WS_NONE;
     for (int cd = tid; cd < ncand; cd += 256) {
       const double* rp = reg + cd;
       double cs = 0.0, es = 0.0;
@@ -100,21 +98,11 @@ __global__ __launch_bounds__(256) void psola_marks_kernel(const float* __restric
         es = es + p * p;
       }
       const double Cd = es - 2.0 * cs;                           // 2 c is exact
-      if (ps_better(Cd, cd - D, bC, bd)) { bC = Cd; bd = cd - D; }
+      if (ws_better(Cd, cd - D, bC, bd)) { bC = Cd; bd = cd - D; }
     }
-    for (int off = 32; off; off >>= 1) {
-      const double oC = __shfl_xor(bC, off, 64);
-      const int od = __shfl_xor(bd, off, 64);
-      if (ps_better(oC, od, bC, bd)) { bC = oC; bd = od; }
-    }
-    if ((tid & 63) == 0) { redC[tid >> 6] = bC; redd[tid >> 6] = bd; }
-    __syncthreads();
-    bC = redC[0]; bd = redd[0];
-#pragma unroll
-    for (int v = 1; v < 4; ++v)
-      if (ps_better(redC[v], redd[v], bC, bd)) { bC = redC[v]; bd = redd[v]; }
-    if (tid == 0) cost[m_off + i] = bC;
-    a += P + bd;
+    const WsWin win = ws_reduce(bC, bd, redC, redd, [] {});
+    if (tid == 0) cost[m_off + i] = win.D;
+    a += P + win.d;
     ++i;
   }
   if (tid == 0) { cost[m_off + i] = 0.0; cnt[blockIdx.x] = i; }
@@ -158,7 +146,7 @@ __global__ __launch_bounds__(256) void psola_synth_kernel(const float* __restric
         if (n < n1 && rr >= -(long)G.Wl && rr < G.Wr) {
           const float w = ps_weight((int)rr, G.Wl, G.Wr);
           const long src = G.a + rr;
-          const float yv = src >= 0 && src < L ? ps_clean(in[in_off + src]) : 0.f;
+          const float yv = src >= 0 && src < L ? ws_clean(in[in_off + src]) : 0.f;
           num[u] = num[u] + (double)yv * (double)w;
           den[u] = den[u] + (double)w;
         }

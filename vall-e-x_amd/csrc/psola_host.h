@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/vallex_hip.h"
+#include "ws_walk.h"
 
 namespace vxe {
 
@@ -65,12 +66,8 @@ VX_PS_HD inline int ps_period(const PsGeom& g, const int32_t* lag, long Mf, long
   return *voiced ? t : g.U;
 }
 
-// the total order of the search: smaller cost, then smaller |d|, then the negative d
-VX_PS_HD inline bool ps_better(double Ca, int da, double Cb, int db) {
-  if (Ca != Cb) return Ca < Cb;
-  const int aa = da < 0 ? -da : da, ab = db < 0 ? -db : db;
-  return aa != ab ? aa < ab : da < db;
-}
+// the total order of the search (ws_walk.h): smaller cost, then smaller |d|, then the negative d
+VX_PS_HD inline bool ps_better(double Ca, int da, double Cb, int db) { return ws_better(Ca, da, Cb, db); }
 
 struct PsGrain { int32_t s, a, Wl, Wr; };                       // centre, source centre, left and right width
 

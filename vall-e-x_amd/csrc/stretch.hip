@@ -1,26 +1,15 @@
 // The speaking rate (vx_stretch, include/vallex_hip.h): a pitch-preserving time-stretch of mono fp32 rows by WSOLA.
 //
-// Frame k of a row writes the output hop [k H, (k + 1) H): a crossfade between the continuation of the previous input segment (the
-// template t[j] = y[p_{k-1} + H + j]) and a new segment y[p_k + j], where p_k = n_k + d* is searched in [n_k - D, n_k + D] around the
-// nominal position n_k = floor(k H num / den) for the smallest D_d = e_d - 2 c_d (the squared distance to the template minus the
-// template's energy).  The contract -- sums, tie rule, crossfade, every rounding -- is in the header; stretch_host.h has the integers.
+// Frame k of a row writes the output hop [k H, (k + 1) H) from a segment at p_k = n_k + d*, searched over all of [n_k - D, n_k + D]
+// around the nominal position n_k = floor(k H num / den); frame 0 is the input itself.  The frame, its arithmetic contract and its
+// LDS are ws_walk.h's; the header states every rounding; stretch_host.h has the integers.
 //
-// Arithmetic (the contract the tests rest on): candidate d is summed by ONE lane in double in sample order from 0.0, every product
-// of two fp32 values is exact in double, the winner is a total order on (D, |d|, d), an output is two exact products, one double
-// addition and one rounding.  The bits therefore depend neither on the lane, the wave, the job, the window nor the launch a frame
-// lands in.  No atomics, no inline assembly.
-//
-// Work decomposition: frame k needs p_{k-1}, so a row is a serial walk.  A launch covers a ragged list of JOBS (the frames [k0, k1)
-// of one row: a whole row, or one window of a long one), grid (job): one 256-thread workgroup walks its job's frames in order, the
-// rows of a batch run side by side on different CUs.  Everything frame k reads -- the search region, the new segment and the NEXT
-// frame's template -- lies in y[n_k - D, n_k + D + 2H), which is staged into LDS as fp32 with zeros outside the row (the padding
-// never exists in HBM).  That span depends on n_k alone, not on p_{k-1}: the region of frame k + 1 is loaded into registers before
-// frame k is searched and stored into the other LDS buffer behind the search.  Candidate c = d + D belongs to lane c mod 256; the
-// lanes of a wavefront read reg[c + j] at stride 1 (conflict-free) and t[j] as a broadcast.  Each lane keeps its best (D, d); six
-// shuffle steps reduce a wavefront, one LDS step the four of them.
-// LDS: 2 (2D + 2H) + H floats and 48 bytes -- 57 392 bytes at the largest options, 6.7 KiB at hop 240, search 150.
+// Work decomposition: a launch covers a ragged list of JOBS (the frames [k0, k1) of one row: a whole row, or one window of a long
+// one, which starts from the position the previous launch found for frame k0 - 1), grid (job): one 256-thread workgroup walks its
+// job's frames in order, the rows of a batch run side by side on different CUs.
 #include "wave_stage.h"
 #include "stretch_host.h"
+#include "ws_walk.h"
 
 #include "../../include/vallex_hip_dev.h"
 
@@ -28,20 +17,9 @@ namespace vxe {
 
 constexpr int ST_TAB = 16;                                   // ints of a job record
 constexpr int ST_MAX_JOBS = RS_MAX_JOBS * RS_TAB / ST_TAB;   // the records of a launch fill rs_meta
-constexpr long ST_FRAME_CAP = 1L << 18;                      // frames of a launch: the position / cost tables
-constexpr int ST_NONE = 0x3fffffff;                          // the offset of a lane that saw no candidate: loses every tie
 static_assert(VX_STRETCH_WINDOW == RS_IN_CAP, "vx_stretch runs in the resampler's launch buffers");
 static_assert(VX_DEV_STRETCH_WINDOW_MIN >= 2 * 300 + 3 * 441 && VX_DEV_STRETCH_WINDOW_MIN <= VX_STRETCH_WINDOW, "window bounds of the dev header");
 static_assert(2 * ST_SEARCH_MAX + 3 * ST_HOP_MAX <= VX_STRETCH_WINDOW, "one frame fits the default window");
-static_assert((2 * ST_SEARCH_MAX + 2 * ST_HOP_MAX + 255) / 256 <= 24, "the prefetch registers hold the largest region");
-static_assert(48 + (2 * (2 * ST_SEARCH_MAX + 2 * ST_HOP_MAX) + ST_HOP_MAX) * sizeof(float) <= 65536, "LDS of the largest options");
-
-// the total order of the search: smaller D, then smaller |d|, then the negative d
-__device__ __forceinline__ bool st_better(double Da, int da, double Db, int db) {
-  if (Da != Db) return Da < Db;
-  const int aa = da < 0 ? -da : da, ab = db < 0 ? -db : db;
-  return aa != ab ? aa < ab : da < db;
-}
 
 // tab [njobs][ST_TAB]:
 //   0 in_off   first float of the job's staged samples in `in`
@@ -49,28 +27,16 @@ __device__ __forceinline__ bool st_better(double Da, int da, double Db, int db) 
 //   3 k0, 4 k1 frames of the job;  5 p_prev  p_{k0-1} (k0 >= 1)
 //   6 out_off  first float of the job's outputs in `out` (output sample k0 H of the row);  7 Lout  output samples of the ROW
 //   8 f_off    first record of the job in `pos` / `cost`
-// NPRE: registers of the prefetch, 256 NPRE >= 2D + 2H
 template <int NPRE>
 __global__ __launch_bounds__(256) void stretch_rows_kernel(const float* __restrict__ in, const int* __restrict__ tab,
                                                            const float* __restrict__ w, float* __restrict__ out, int* __restrict__ pos,
                                                            double* __restrict__ cost, int H, int D, int num, int den) {
   extern __shared__ double st_lds[];
-  double* redD = st_lds;                                         // [4] the wavefronts' winners
-  int* redd = reinterpret_cast<int*>(st_lds + 4);                // [4]
-  float* reg = reinterpret_cast<float*>(st_lds + 6);             // [2][S] the regions of this frame and the next
-  const int S = 2 * D + 2 * H, ncand = 2 * D + 1;
-  float* t = reg + 2 * S;                                        // [H] the template
+  const WsLds l(st_lds, H, D);
   const int* tb = tab + blockIdx.x * ST_TAB;
-  const long in_off = tb[0], s_lo = tb[1], in_cnt = tb[2], out_off = tb[6], Lout = tb[7], f_off = tb[8];
+  const long out_off = tb[6], Lout = tb[7], f_off = tb[8];
   const int k0 = tb[3], k1 = tb[4], tid = threadIdx.x;
-  // sample s of the row: 0 outside the row and where it is not finite; the job holds every sample of the row its frames can read
-  // (stretch_host.h: st_span) -- the range test keeps a wrong table inside the buffer
-  auto y_at = [&](long s) -> float {
-    const long r = s - s_lo;
-    if (r < 0 || r >= in_cnt) return 0.f;
-    const float x = in[in_off + r];
-    return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u ? x : 0.f;
-  };
+  const WsRow y_at{in + tb[0], tb[1], tb[2]};
   long p_prev = tb[5];
   int ks = k0;
   if (k0 == 0) {                                                 // frame 0: p_0 = 0, the input itself
@@ -80,67 +46,22 @@ __global__ __launch_bounds__(256) void stretch_rows_kernel(const float* __restri
     ks = 1;
   }
   if (ks >= k1) return;                                          // block-uniform
-  for (int j = tid; j < H; j += 256) t[j] = y_at(p_prev + H + j);
+  for (int j = tid; j < H; j += 256) l.t[j] = y_at(p_prev + H + j);
   {
     const long base = (long)ks * H * num / den - D;
-    for (int i = tid; i < S; i += 256) reg[i] = y_at(base + i);
+    for (int i = tid; i < l.S; i += 256) l.reg[i] = y_at(base + i);
   }
   for (int k = ks; k < k1; ++k) {
-    float* cur = reg + ((k - ks) & 1) * S;
-    float* oth = reg + (((k - ks) & 1) ^ 1) * S;
-    const long nk = (long)k * H * num / den;                     // cur holds y[n_k - D, n_k - D + S)
-    __syncthreads();                                             // cur and t are written; nobody reads oth or red* any more
-    const bool more = k + 1 < k1;
-    float pre[NPRE];
-    if (more) {
-      const long nbase = (long)(k + 1) * H * num / den - D;
-#pragma unroll
-      for (int i = 0; i < NPRE; ++i) pre[i] = tid + 256 * i < S ? y_at(nbase + tid + 256 * i) : 0.f;
-    }
-    double bD = __builtin_inf();
-    int bd = ST_NONE;
-    for (int cd = tid; cd < ncand; cd += 256) {
-      const float* rp = cur + cd;
-      double cs = 0.0, es = 0.0;
-#pragma unroll 16
-      for (int j = 0; j < H; ++j) {
-        const double a = (double)rp[j], b = (double)t[j];
-        cs += a * b;                                             // both products are exact in double: an fma gives the same bits
-        es += a * a;
-      }
-      const double Dd = es - 2.0 * cs;                           // 2 c is exact
-      if (st_better(Dd, cd - D, bD, bd)) { bD = Dd; bd = cd - D; }
-    }
-    for (int off = 32; off; off >>= 1) {
-      const double oD = __shfl_xor(bD, off, 64);
-      const int od = __shfl_xor(bd, off, 64);
-      if (st_better(oD, od, bD, bd)) { bD = oD; bd = od; }
-    }
-    if ((tid & 63) == 0) { redD[tid >> 6] = bD; redd[tid >> 6] = bd; }
-    if (more) {
-#pragma unroll
-      for (int i = 0; i < NPRE; ++i)
-        if (tid + 256 * i < S) oth[tid + 256 * i] = pre[i];
-    }
-    __syncthreads();
-    bD = redD[0]; bd = redd[0];
-#pragma unroll
-    for (int v = 1; v < 4; ++v)
-      if (st_better(redD[v], redd[v], bD, bd)) { bD = redD[v]; bd = redd[v]; }
-    const int r0 = bd + D;                                       // p_k - base, 0 .. 2D
-    const long o0 = (long)k * H;
-    for (int j = tid; j < H; j += 256) {
-      const float a = cur[r0 + j], tt = t[j];
-      const float v = (float)((double)a * (double)w[j] + (double)tt * (double)w[H - 1 - j]);
-      if (o0 + j < Lout) out[out_off + (o0 - (long)k0 * H) + j] = v;
-      t[j] = cur[r0 + H + j];                                    // the next frame's template; lane j alone touches t[j] here
-    }
-    if (tid == 0) { pos[f_off + (k - k0)] = (int)(nk + bd); cost[f_off + (k - k0)] = bD; }
+    const long nk = (long)k * H * num / den, o0 = (long)k * H;
+    const long left = Lout - o0;                                 // the last frame of a row may end in front of its hop
+    const WsWin b = ws_frame<NPRE>(l, (k - ks) & 1, y_at, k + 1 < k1, (long)(k + 1) * H * num / den - D, 0, 2 * D, H, D, w,
+                                   out + out_off + (o0 - (long)k0 * H), left < H ? (int)left : H);
+    if (tid == 0) { pos[f_off + (k - k0)] = (int)(nk + b.d); cost[f_off + (k - k0)] = b.D; }
   }
 }
 
-// the crossfade table, rebuilt when the hop changes, and the position / cost tables of a launch
-static int st_tables(vx_ctx* c, int H) {
+// the crossfade table, rebuilt when the hop changes, and the position / cost tables of a launch (wave_stage.h)
+int ws_tables(vx_ctx* c, int H) {
   if (!c->st_fade) {
     if (int e = dev_alloc(c, &c->st_fade, (size_t)ST_HOP_MAX, false)) return e;
     if (int e = dev_alloc(c, &c->st_pos, (size_t)ST_FRAME_CAP, false)) return e;
@@ -185,9 +106,9 @@ static int st_run(vx_ctx* c, const char* who, const float* wav, int64_t wav_stri
   if (jobs.empty()) return VX_OK;
   HIPCHK(hipSetDevice(c->dev));
   if (int e = rs_buffers(c)) return e;
-  if (int e = st_tables(c, g.H)) return e;
+  if (int e = ws_tables(c, g.H)) return e;
   const int S = 2 * g.D + 2 * g.H;
-  const size_t lds = 48 + (size_t)(2 * S + g.H) * sizeof(float);
+  const size_t lds = ws_lds_bytes(g.H, g.D);
   std::vector<long> p_last((size_t)batch, 0);                    // p of the last frame a launch has walked, per row
   std::vector<int> tab, last;
   return wave_launches(c, jobs, [&](size_t j0, size_t j1) -> int {
@@ -203,12 +124,8 @@ static int st_run(vx_ctx* c, const char* who, const float* wav, int64_t wav_stri
     }
     H2D(c->rs_meta, tab.data(), tab.size() * sizeof(int));
     const dim3 grid((unsigned)(j1 - j0));
-    if (S <= 8 * 256)
-      hipLaunchKernelGGL(stretch_rows_kernel<8>, grid, dim3(256), lds, c->stream, c->rs_in, c->rs_meta, c->st_fade, c->rs_out, c->st_pos,
-                         c->st_cost, g.H, g.D, (int)g.num, (int)g.den);
-    else
-      hipLaunchKernelGGL(stretch_rows_kernel<24>, grid, dim3(256), lds, c->stream, c->rs_in, c->rs_meta, c->st_fade, c->rs_out, c->st_pos,
-                         c->st_cost, g.H, g.D, (int)g.num, (int)g.den);
+    WS_LAUNCH(stretch_rows_kernel, S, grid, dim3(256), lds, c->stream, c->rs_in, c->rs_meta, c->st_fade, c->rs_out, c->st_pos, c->st_cost,
+              g.H, g.D, (int)g.num, (int)g.den);
     for (size_t k = j0; k < j1; ++k) {
       const StJob& j = jobs[k];
       const long nf = j.k1 - j.k0;

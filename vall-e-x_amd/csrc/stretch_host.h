@@ -21,6 +21,10 @@ constexpr int ST_SPEED_MAX = 32767;
 
 struct StGeom { long num, den; int H, D; };      // the speed over its gcd, the hop, the search radius
 
+// LDS of a workgroup that walks frames of hop H, search D (ws_walk.h: WsLds): four winners, two regions of 2D + 2H floats, the template
+constexpr size_t ws_lds_bytes(int H, int D) { return 48 + (size_t)(2 * (2 * D + 2 * H) + H) * sizeof(float); }
+static_assert(ws_lds_bytes(ST_HOP_MAX, ST_SEARCH_MAX) <= 65536, "LDS of the largest options");
+
 // nullptr: the options are in range; else the message (in buf), naming the field
 inline const char* st_check_opts(const vx_stretch_opts& o, char* buf, size_t nbuf) {
   if (o.hop < ST_HOP_MIN || o.hop > ST_HOP_MAX) snprintf(buf, nbuf, "hop %d outside %d .. %d", o.hop, ST_HOP_MIN, ST_HOP_MAX);

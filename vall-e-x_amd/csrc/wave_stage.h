@@ -1,5 +1,5 @@
 // What the waveform translation units share (resample.hip, finish.hip, stretch.hip, loudness.hip, limit.hip, f0.hip, psola.hip,
-// denoise.hip): the launch buffers, the checks of a ragged batch of rows, the development windows, the launch-group driver, and the
+// denoise.hip, retime.hip): the launch buffers, the checks of a ragged batch of rows, the development windows, the launch-group driver, and the
 // passes of the output stage that vx_finish, vx_finish_loud and vx_finish_limited run in turn.  Not part of the public C ABI.
 #pragma once
 
@@ -15,6 +15,10 @@ constexpr int RS_MAX_JOBS = 4096;          // jobs per launch (grid.y)
 constexpr long RS_IN_CAP = VX_RESAMPLE_WINDOW;          // input samples per launch, default
 constexpr long RS_OUT_CAP = 2 * RS_IN_CAP;              // output samples per launch
 int rs_buffers(vx_ctx* c);
+// stretch.hip: the tables of a WSOLA walk (vx_stretch, vx_retime: ws_walk.h), shared like the launch buffers: st_fade, the crossfade
+// table of hop H, rebuilt when the hop changes, and st_pos / st_cost, the positions and winning costs of one launch's frames
+constexpr long ST_FRAME_CAP = 1L << 18;    // frames per launch
+int ws_tables(vx_ctx* c, int H);
 
 // resample.hip: wav, lens and batch of an entry (NULL, batch below 1), then every lens[i] against 0 .. wav_stride
 int wave_check_rows(vx_ctx* c, const char* who, const float* wav, int64_t wav_stride, const int32_t* lens, int batch);
