@@ -798,6 +798,71 @@ int vx_denoise(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t*
                const double* noise_psd /* may be NULL */, float* out, int64_t out_stride, double* psd_out /* may be NULL */,
                vx_denoise_info* info);
 
+/* A biquad equaliser of mono fp32 rows on the device: the one stage that changes the spectrum on purpose -- a high-pass in front of an
+ * enrolment clip's noise estimate, a telephone band in front of the 8 kHz resample, a presence lift.  No reference counterpart.
+ *
+ * - Sections.  A filter is 1 .. VX_EQ_MAX_SECTIONS (8) second-order sections in series, each five doubles b0 b1 b2 a1 a2 with a0
+ *   normalised to 1: sections [nsections][5].  vx_eq_design(kind, sample_rate, f0, q, gain_db, c) is a pure host function that writes
+ *   the audio-EQ-cookbook section of a kind (VX_EQ_HIGHPASS .. VX_EQ_HIGHSHELF; the band-pass has a 0 dB peak; gain_db is read by the
+ *   peak and the two shelves), divided by a0, in double, with w0 = 2 pi f0 / sample_rate, alpha = sin w0 / (2 q), A = 10^(gain_db / 40),
+ *   1 - cos w0 = 2 sin^2(w0 / 2) and 1 + cos w0 = 2 cos^2(w0 / 2).  Any stable section of the caller's own is as good.
+ * - Per-sample arithmetic.  Section after section, each in transposed direct form II, all in IEEE double with contraction off and
+ *   every operation rounded on its own (the recursion of vx_loudness):
+ *       u  = b0 * x + s1
+ *       s1 = (b1 * x - a1 * u) + s2
+ *       s2 = b2 * x - a2 * u          x of the next section = u
+ *   The input is widened from fp32; a non-finite input sample is 0 and is counted (nonfinite).  The output is ONE rounding of the last
+ *   u to fp32; a result that is not finite after that rounding is written as 0 and counted (nonfinite_out), so a NaN or an Inf never
+ *   reaches an output.  (The identity section 1 0 0 0 0 returns the input bits; a -0 comes back as +0.)
+ * - Bounded memory.  Output sample n of a row belongs to step j = n / S, S = VX_EQ_STEP.  Its value is the recursion above started
+ *   from rest (every s1, s2 = +0) at sample j S - W and run to n; samples before the row are 0.  An output is therefore a function of
+ *   at most W + S input samples and the coefficients: its bits do not depend on the row, the batch, the job, the tile, the window or
+ *   the launch.  No atomics, no inline assembly.
+ * - W is a function of the filter alone, computed on the host in double: a unit impulse runs through the cascade with the recursion
+ *   above for 2 VX_EQ_WARM_MAX samples, h[k]; T(k) = |h[k]| + T(k + 1), summed from the far end with one addition per sample; W is the
+ *   smallest multiple of 32 with T(W) <= 2^-24.  vx_eq_plan(sections, n, &warm, &step) is a pure host function that reports W and S.
+ *   Starting from rest at p is filtering the row with everything before p zeroed, so the distance to the unbounded recursion at any
+ *   sample is at most peak(x) T(W) <= 2^-24 peak(x): below half an fp32 ulp of a full-scale output.
+ * - The limit.  A filter whose T does not fall to 2^-24 within VX_EQ_WARM_MAX samples is refused: narrow hum notches (50 Hz, Q 100 at
+ *   24 kHz) need a carried state, which this stage does not have.
+ * - info [batch]: warm = W; nonfinite, nonfinite_out as above; peak = the largest |out| of the row (a maximum: order-free, exact).
+ * - State.  As vx_denoise: it needs no weights, works while a serving session is open and touches no decode state.  Samples go
+ *   through the resampler's launch buffers and the pinned ring.
+ * - Windows.  One launch holds VX_EQ_WINDOW (2^23) staged samples, warm-ups included.  Rows are packed into launches in order.  A
+ *   longer row is cut at step multiples, and a later part carries the W samples in front of its first step.  By the rules above no
+ *   cut changes a bit.
+ * - Refusals.  These return VX_EINVAL, launch nothing and write nothing, and the message names the section or the field: NULL wav /
+ *   lens / sections / out / info (vx_eq_design: c; vx_eq_plan: sections, warm or step); batch <= 0; a length negative, above wav_stride
+ *   or above out_stride; nsections outside 1 .. 8; a coefficient that is not finite; an unstable section (|a2| >= 1 or
+ *   |a1| >= 1 + a2); no W up to VX_EQ_WARM_MAX.  vx_eq_design: kind out of range, sample_rate outside 8000 .. 192000, f0 outside
+ *   (0, sample_rate / 2), q not above 0, |gain_db| above 24.  The two host functions have no context: vx_eq_last_error() returns the
+ *   message of the last one of them that refused on the calling thread ("" before the first).
+ *
+ *   wav [batch][wav_stride] fp32, lens [batch] (a row of length 0 is legal and writes nothing); out [batch][out_stride] fp32, L samples
+ *   per row.  Elements behind a row's end are not written. */
+#define VX_EQ_MAX_SECTIONS 8
+#define VX_EQ_WARM_MAX 65536
+#ifndef VX_EQ_STEP        /* a constant of the contract; tools/eq_bench.py builds the library at others to measure them */
+#define VX_EQ_STEP 128
+#endif
+#define VX_EQ_WINDOW (1 << 23)
+#define VX_EQ_HIGHPASS 0
+#define VX_EQ_LOWPASS 1
+#define VX_EQ_BANDPASS 2
+#define VX_EQ_NOTCH 3
+#define VX_EQ_PEAK 4
+#define VX_EQ_LOWSHELF 5
+#define VX_EQ_HIGHSHELF 6
+typedef struct vx_eq_info {
+  int32_t warm, nonfinite, nonfinite_out;
+  float peak;
+} vx_eq_info;
+int vx_eq_design(int32_t kind, int32_t sample_rate, double f0, double q, double gain_db, double c[5]);
+int vx_eq_plan(const double* sections, int32_t nsections, int32_t* warm, int32_t* step);
+const char* vx_eq_last_error(void);
+int vx_eq(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t* lens, int32_t batch, const double* sections,
+          int32_t nsections, float* out, int64_t out_stride, vx_eq_info* info);
+
 /* ---- step-level entries (kernel-level parity tests; same kernels as vx_infer) ---------------------------- */
 /* first ar_decoder.infer call (models/vallex.py:528-562): embeds, runs the prefix-LM prefill, fills the KV arena,
  * leaves the logits of the last row available.  batch <= 32. */

@@ -499,6 +499,14 @@ int vx_dev_denoise_window(vx_ctx* ctx, int32_t samples);
  * that double division on the device is correctly rounded.  VX_EINVAL: a NULL pointer, n outside 1 .. 65536. */
 int vx_dev_denoise_div(vx_ctx* ctx, const double* a, const double* b, int32_t n, double* q);
 
+/* Staged samples one launch of vx_eq holds (warm-ups included), for later calls on this context: VX_DEV_EQ_WINDOW_MIN .. VX_EQ_WINDOW,
+ * or 0 for the default (VX_EQ_WINDOW).  A small window sends short rows through several jobs and launches -- what the window tests
+ * need; the device buffers keep their size.  A launch must hold a warm-up and one step: while a window below W + VX_EQ_STEP of a
+ * call's filter is set, that call is refused (VX_EINVAL), not run with a larger window.  VX_EINVAL, nothing changed, for any other
+ * value. */
+#define VX_DEV_EQ_WINDOW_MIN 4096
+int vx_dev_eq_window(vx_ctx* ctx, int32_t samples);
+
 #ifdef __cplusplus
 }
 #endif

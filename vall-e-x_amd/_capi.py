@@ -97,6 +97,11 @@ class vx_retime_opts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("hop", C.c_int32), ("search", C.c_int32)]
 
 
+class vx_eq_info(C.Structure):
+    """what vx_eq did to one row: the warm-up W of the filter, the non-finite inputs and results it zeroed, the largest |out|"""
+    _fields_ = [("warm", C.c_int32), ("nonfinite", C.c_int32), ("nonfinite_out", C.c_int32), ("peak", C.c_float)]
+
+
 class vx_wave_info(C.Structure):
     """what vx_finish measured of one row"""
     _fields_ = [("begin", C.c_int32), ("end", C.c_int32), ("active_frames", C.c_int32), ("nonfinite", C.c_int32), ("clipped", C.c_int32),
@@ -166,7 +171,8 @@ SYMBOLS = ["vx_abi_version", "vx_create", "vx_destroy", "vx_last_error", "vx_syn
            "vx_fallback_reset", "vx_arith_mode", "vx_infer_continuous", "vx_serve_open", "vx_serve_submit", "vx_serve_run",
            "vx_serve_close", "vx_serve_submit_ex", "vx_serve_cancel", "vx_serve_submit_filtered", "vx_score", "vx_align", "vx_resample",
            "vx_finish", "vx_stretch", "vx_loudness_coeffs", "vx_loudness", "vx_finish_loud", "vx_limit_taps", "vx_limit",
-           "vx_finish_limited", "vx_psola", "vx_denoise_tables", "vx_denoise", "vx_pauses", "vx_retime"]
+           "vx_finish_limited", "vx_psola", "vx_denoise_tables", "vx_denoise", "vx_pauses", "vx_retime", "vx_eq_design",
+           "vx_eq_plan", "vx_eq_last_error", "vx_eq"]
 # ... and include/vallex_hip_dev.h: measurement / kernel development, never called by the mirrors of the reference API
 DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kernel", "vx_bench_gemm", "vx_bench_attn",
                "vx_bench_gemm_clock", "vx_bench_gemm_epilogue", "vx_dev_sample", "vx_dev_attn", "vx_dev_sample_filtered",
@@ -174,7 +180,8 @@ DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kerne
                "vx_dev_seam_op", "vx_dev_resample_taps", "vx_dev_resample_window", "vx_dev_finish_frames", "vx_dev_finish_window",
                "vx_dev_stretch_window", "vx_dev_stretch_costs", "vx_dev_loudness_steps", "vx_dev_loudness_window",
                "vx_dev_limit_gain", "vx_dev_limit_window", "vx_dev_psola_table", "vx_dev_psola_window", "vx_dev_switches",
-               "vx_dev_denoise_fft", "vx_dev_denoise_table", "vx_dev_denoise_window", "vx_dev_denoise_div", "vx_dev_retime_window"]
+               "vx_dev_denoise_fft", "vx_dev_denoise_table", "vx_dev_denoise_window", "vx_dev_denoise_div", "vx_dev_retime_window",
+               "vx_dev_eq_window"]
 # the pitch tracker's entries, one of vallex_hip.h and two of vallex_hip_dev.h, in a list of their own: the header scan of
 # tests/test_abi.py matches names of letters and underscores, and these carry a digit (tests/test_f0_refs.py checks them)
 F0_SYMBOLS = ["vx_f0"]
@@ -213,6 +220,9 @@ RESAMPLE_WINDOW, DEV_RESAMPLE_WINDOW_MIN = 1 << 23, 512     # VX_RESAMPLE_WINDOW
 FINISH_WINDOW, DEV_FINISH_WINDOW_MIN = 1 << 23, 512         # VX_FINISH_WINDOW / VX_DEV_FINISH_WINDOW_MIN: input samples per launch
 STRETCH_WINDOW, DEV_STRETCH_WINDOW_MIN = 1 << 23, 2048      # VX_STRETCH_WINDOW / VX_DEV_STRETCH_WINDOW_MIN: input samples per launch
 RETIME_WINDOW, DEV_RETIME_WINDOW_MIN = 1 << 23, 2048        # VX_RETIME_WINDOW / VX_DEV_RETIME_WINDOW_MIN: input samples per launch
+EQ_WINDOW, DEV_EQ_WINDOW_MIN = 1 << 23, 4096                # VX_EQ_WINDOW / VX_DEV_EQ_WINDOW_MIN: staged samples per launch
+EQ_MAX_SECTIONS, EQ_WARM_MAX = 8, 65536                     # VX_EQ_MAX_SECTIONS / VX_EQ_WARM_MAX
+EQ_KINDS = {"highpass": 0, "lowpass": 1, "bandpass": 2, "notch": 3, "peak": 4, "low_shelf": 5, "high_shelf": 6}      # VX_EQ_*
 LOUDNESS_WINDOW, DEV_LOUDNESS_WINDOW_MIN = 1 << 23, 4096    # VX_LOUDNESS_WINDOW / VX_DEV_LOUDNESS_WINDOW_MIN: samples per launch
 LIMIT_WINDOW, DEV_LIMIT_WINDOW_MIN = 1 << 23, 8192          # VX_LIMIT_WINDOW / VX_DEV_LIMIT_WINDOW_MIN: samples per launch
 F0_WINDOW, DEV_F0_WINDOW_MIN = 1 << 23, 3072                # VX_F0_WINDOW / VX_DEV_F0_WINDOW_MIN: samples per launch
@@ -373,6 +383,13 @@ def load_library() -> C.CDLL:
     lib.vx_retime.argtypes = [ctx, P(C.c_float), C.c_int64, P(C.c_int32), C.c_int32, P(C.c_int32), C.c_int64, P(C.c_int32), P(vx_retime_opts),
                               P(C.c_float), C.c_int64, P(C.c_int32), P(C.c_int32), P(C.c_double), C.c_int64]
     lib.vx_dev_retime_window.argtypes = [ctx, C.c_int32]
+    lib.vx_eq_design.argtypes = [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, P(C.c_double)]
+    lib.vx_eq_plan.argtypes = [P(C.c_double), C.c_int32, P(C.c_int32), P(C.c_int32)]
+    lib.vx_eq_last_error.argtypes = []
+    lib.vx_eq_last_error.restype = C.c_char_p
+    lib.vx_eq.argtypes = [ctx, P(C.c_float), C.c_int64, P(C.c_int32), C.c_int32, P(C.c_double), C.c_int32, P(C.c_float), C.c_int64,
+                          P(vx_eq_info)]
+    lib.vx_dev_eq_window.argtypes = [ctx, C.c_int32]
     lib.vx_dev_stretch_costs.argtypes = [ctx, P(C.c_float), C.c_int32, P(vx_stretch_opts), P(C.c_float), P(C.c_int32), P(C.c_double)]
     lib.vx_last_stats.argtypes = [ctx, P(C.c_int64), P(C.c_int64), P(C.c_double), P(C.c_double)]
     lib.vx_last_truncated.argtypes = [ctx, P(C.c_int32)]
@@ -382,7 +399,7 @@ def load_library() -> C.CDLL:
     lib.vx_arith_mode.argtypes = [ctx, P(C.c_int32), P(C.c_int32)]
     for name in SYMBOLS + DEV_SYMBOLS + F0_SYMBOLS + F0_DEV_SYMBOLS:
         fn = getattr(lib, name)
-        if name not in ("vx_destroy", "vx_last_error", "vx_read_tap", "vx_abi_version"):
+        if name not in ("vx_destroy", "vx_last_error", "vx_read_tap", "vx_abi_version", "vx_eq_last_error"):
             fn.restype = C.c_int
     _lib = lib
     return lib
@@ -809,6 +826,85 @@ class Engine:
         """vx_dev_retime_window: input samples one launch of `retime` holds from now on (DEV_RETIME_WINDOW_MIN .. RETIME_WINDOW; 0
         restores the default)"""
         self._dev_window("retime", input_samples)
+
+    @staticmethod
+    def eq_design(kind, f0: float, q: float = 0.7071067811865476, gain_db: float = 0.0, sample_rate: int = 24000) -> np.ndarray:
+        """vx_eq_design: the cookbook section of `kind` (a name of EQ_KINDS or its number) at f0 Hz, float64 (5,): b0 b1 b2 a1 a2 with
+        a0 = 1.  gain_db is read by the peak and the two shelves.  ValueError: what the library refuses, in its words."""
+        lib = load_library()
+        c = np.zeros(5, np.float64)
+        k = EQ_KINDS.get(kind, kind) if isinstance(kind, str) else kind
+        if isinstance(k, str):
+            raise ValueError(f"eq_design: kind {kind!r} is none of {sorted(EQ_KINDS)}")
+        if lib.vx_eq_design(int(k), int(sample_rate), float(f0), float(q), float(gain_db), _ptr(c, C.c_double)) != 0:
+            raise ValueError(lib.vx_eq_last_error().decode())
+        return c
+
+    @staticmethod
+    def _eq_sections(sections, sample_rate: int = 24000) -> np.ndarray:
+        """(n, 5) float64 of a `sections` argument: an array of sections, or an object with `sections(sample_rate)` (a
+        utils.generation.Eq, resolved at the rate of the call)"""
+        if hasattr(sections, "sections"):
+            sections = sections.sections(int(sample_rate))
+        s = np.ascontiguousarray(sections, np.float64)
+        if s.ndim == 1 and s.size == 5:
+            s = s.reshape(1, 5)
+        if s.ndim != 2 or s.shape[1] != 5:
+            raise ValueError(f"eq: sections of shape {s.shape}, not (n, 5): b0 b1 b2 a1 a2 per section")
+        return s
+
+    @classmethod
+    def eq_plan(cls, sections, sample_rate: int = 24000):
+        """vx_eq_plan: (W, S) of a filter -- the warm-up in samples the library runs in front of every step of S samples.  ValueError:
+        a filter the library refuses (an unstable or non-finite section, none or more than 8, a memory above EQ_WARM_MAX samples)."""
+        lib = load_library()
+        s = cls._eq_sections(sections, sample_rate)
+        key = s.tobytes()
+        if key in cls._eq_plans:                                          # the walk over the impulse response costs a millisecond or more
+            return cls._eq_plans[key]
+        w, st = C.c_int32(0), C.c_int32(0)
+        if lib.vx_eq_plan(_ptr(s if len(s) else np.zeros((1, 5)), C.c_double), len(s), C.byref(w), C.byref(st)) != 0:
+            raise ValueError(lib.vx_eq_last_error().decode())
+        if len(cls._eq_plans) >= 64:
+            cls._eq_plans.clear()
+        cls._eq_plans[key] = (w.value, st.value)
+        return w.value, st.value
+
+    _eq_plans = {}                   # sections (their bytes) -> (W, S) of the filters `eq_plan` accepted
+
+    last_eq_info = None              # the info dicts of the last `eq` (also through an `eq=` argument)
+
+    def eq(self, wavs: Sequence[np.ndarray], sections, sample_rate: int = 24000, return_info: bool = False):
+        """vx_eq, a cascade of 1 .. 8 biquads over mono fp32 waveforms (L_i,) -> float32 rows of L_i samples.  sections: (n, 5) float64
+        (b0 b1 b2 a1 a2 per section: `eq_design`), or a utils.generation.Eq, whose specs are resolved at sample_rate.  Every output is
+        the double recursion started from rest W samples in front of its step (`eq_plan`), rounded once; a non-finite input is 0, a
+        non-finite result is written as 0.  return_info: (rows, infos), dicts with warm, nonfinite, nonfinite_out and peak
+        (include/vallex_hip.h: vx_eq_info).  Sets last_eq_info."""
+        s = self._eq_sections(sections, sample_rate)
+        self.eq_plan(s)                                                   # a ValueError comes before any launch
+        n = len(wavs)
+        if n == 0:
+            self.last_eq_info = []
+            return ([], []) if return_info else []
+        buf, lens, stride = self._packed(wavs)
+        out = np.empty((n, stride), np.float32)
+        info = (vx_eq_info * n)()
+        self._chk(self.lib.vx_eq(self.ctx, _ptr(buf, C.c_float), stride, _ptr(lens, C.c_int32), n, _ptr(s, C.c_double), len(s),
+                                 _ptr(out, C.c_float), stride, info))
+        rows = [out[i, :L] for i, L in enumerate(lens)]
+        self.last_eq_info = self._dicts(info)
+        return (rows, self.last_eq_info) if return_info else rows
+
+    def _equalised(self, rows, eq, rate: int = 24000):
+        """the rows of an `eq=` argument (None: as they are) at `rate`"""
+        if eq is None:
+            return rows
+        return self.eq(rows, eq, sample_rate=rate)
+
+    def dev_eq_window(self, samples: int = 0):
+        """vx_dev_eq_window: staged samples one launch of `eq` holds from now on (DEV_EQ_WINDOW_MIN .. EQ_WINDOW; 0 restores the
+        default)"""
+        self._dev_window("eq", samples)
 
     @staticmethod
     def _packed(wavs):
@@ -1340,16 +1436,20 @@ class Engine:
         return out
 
     def vocos_decode(self, codes: Sequence[np.ndarray], bandwidth_id: int = 2, sample_rate: int = 24000, finish=None, speed=None, pitch=None,
-                     denoise=None, pauses=None):
+                     denoise=None, pauses=None, eq=None):
         """denoise (None: nothing runs; True or a utils.generation.Denoise): the decoded rows go through `denoise` first of all, directly
         behind the vocoder.  pauses (None: nothing runs; a utils.generation.Pauses): then through `pauses` and `retime` at 24 kHz, which
         shorten, lengthen or scale the pauses inside the speech, behind `denoise` and in front of speed and pitch.  speed (None: nothing runs): the decoded rows go through `stretch` at 24 kHz first; pitch (None: nothing runs): through `shift`
         instead, which takes the speed along; sample_rate other than 24000: then through `resample` (24000 -> sample_rate), one more
-        launch; finish (a utils.generation.Finish): then through `finish` at that rate"""
+        launch; finish (a utils.generation.Finish): then through `finish` at that rate.  eq (None: nothing runs; a utils.generation.Eq
+        or (n, 5) sections): the rows go through `eq` at 24 kHz behind denoise, pauses and speed / pitch and directly in front of the
+        resample, so that a telephone band precedes the decimation and `finish` measures what is delivered"""
         if pitch is not None:
             self._shift_plan(pitch, speed)                                # a ValueError comes before the vocoder runs
         if denoise is not None:
             self._denoise_opts(**self._denoise_parts(denoise))
+        if eq is not None:
+            self.eq_plan(eq, 24000)
         n = len(codes)
         lens = np.array([c.shape[0] for c in codes], np.int32)
         stride = max(1, int(lens.max()))
@@ -1362,16 +1462,19 @@ class Engine:
         self._chk(self.lib.vx_vocos_decode(self.ctx, _ptr(buf, C.c_int64), stride, _ptr(lens, C.c_int32), n,
                                            int(bandwidth_id), _ptr(audio, C.c_float), stride * 320))
         rows = self._stretched(self._paused(self._denoised([audio[i, : lens[i] * 320] for i in range(n)], denoise), pauses), speed, pitch)
+        rows = self._equalised(rows, eq, 24000)
         return self._finished(rows if int(sample_rate) == 24000 else self.resample(rows, 24000, int(sample_rate)), finish, sample_rate)
 
     def encodec_decode(self, codes: Sequence[np.ndarray], sample_rate: int = 24000, finish=None, speed=None, pitch=None, denoise=None,
-                       pauses=None):
-        """speed, pitch, sample_rate, finish, denoise, pauses: as vocos_decode (denoise, pauses, stretch or shift at 24 kHz, then resample,
-        then finish)"""
+                       pauses=None, eq=None):
+        """speed, pitch, sample_rate, finish, denoise, pauses, eq: as vocos_decode (denoise, pauses, stretch or shift and eq at 24 kHz,
+        then resample, then finish)"""
         if pitch is not None:
             self._shift_plan(pitch, speed)                                # a ValueError comes before the vocoder runs
         if denoise is not None:
             self._denoise_opts(**self._denoise_parts(denoise))
+        if eq is not None:
+            self.eq_plan(eq, 24000)
         n = len(codes)
         lens = np.array([c.shape[0] for c in codes], np.int32)
         stride = max(1, int(lens.max()))
@@ -1381,8 +1484,9 @@ class Engine:
         audio = np.zeros((n, stride * 320), np.float32)
         self._chk(self.lib.vx_encodec_decode(self.ctx, _ptr(buf, C.c_int64), stride, _ptr(lens, C.c_int32), n,
                                              _ptr(audio, C.c_float), stride * 320))
-        if speed is not None or pitch is not None or denoise is not None or pauses is not None:
+        if speed is not None or pitch is not None or denoise is not None or pauses is not None or eq is not None:
             rows = self._stretched(self._paused(self._denoised([audio[i, : lens[i] * 320] for i in range(n)], denoise), pauses), speed, pitch)
+            rows = self._equalised(rows, eq, 24000)
             return self._finished(rows if int(sample_rate) == 24000 else self.resample(rows, 24000, int(sample_rate)), finish, sample_rate)
         if int(sample_rate) != 24000:
             return self._finished(self.resample([audio[i, : lens[i] * 320] for i in range(n)], 24000, int(sample_rate)), finish, sample_rate)

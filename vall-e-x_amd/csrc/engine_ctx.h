@@ -237,6 +237,8 @@ struct vx_ctx {
   // time map (vx_retime, retime.hip): runs in the resampler's launch buffers (rs_buffers) and the stretch's tables; needs no weights.
   // Behind everything else: the fields in front of it keep the places they had
   long rt_window = 0;              // input samples per launch set by vx_dev_retime_window (0: the default, VX_RETIME_WINDOW)
+  // equaliser (vx_eq, eq.hip): runs in the resampler's launch buffers (rs_buffers) alone; needs no weights.  Behind everything else too
+  long eq_window = 0;              // staged samples per launch set by vx_dev_eq_window (0: the default, VX_EQ_WINDOW)
 };
 
 #define HIPCHK(expr)                                                                                   \

@@ -298,6 +298,117 @@ class Pauses:
             raise ValueError(f"Pauses: at_least_ms {self.at_least_ms!r} must be positive and keep_ms {self.keep_ms!r} not negative")
 
 
+class Eq(tuple):
+    """An equaliser request, accepted wherever `eq=` is: an immutable tuple of specs (kind, f0_hz, q, gain_db), at most 8, one biquad
+    each (Engine.eq, vx_eq).  The specs are resolved to coefficients at the sample rate of the call (`sections`), so one object serves
+    the enrolment end (at the tokenizer's rate) and the output end (at 24 kHz).  `a + b` is the cascade of both.  Narrow hum notches
+    (50 Hz at Q 100) have a longer memory than the stage carries and are refused by the call that would run them."""
+
+    __slots__ = ()
+    KINDS = ("highpass", "lowpass", "bandpass", "notch", "peak", "low_shelf", "high_shelf")
+    MAX_SECTIONS = 8
+
+    def __new__(cls, specs=()):
+        out = []
+        for sp in specs:
+            if len(sp) != 4:
+                raise ValueError(f"Eq: a spec is (kind, f0_hz, q, gain_db), got {sp!r}")
+            kind, f0, q, gain = sp[0], float(sp[1]), float(sp[2]), float(sp[3])
+            if kind not in cls.KINDS:
+                raise ValueError(f"Eq: kind {kind!r} is none of {cls.KINDS}")
+            if not (np.isfinite(f0) and f0 > 0):
+                raise ValueError(f"Eq: f0 {sp[1]!r} is not a positive frequency")
+            if not (np.isfinite(q) and q > 0):
+                raise ValueError(f"Eq: q {sp[2]!r} is not a finite value above 0")
+            if not abs(gain) <= 24.0:
+                raise ValueError(f"Eq: gain_db {sp[3]!r} outside -24 .. 24")
+            out.append((kind, f0, q, gain))
+        if len(out) > cls.MAX_SECTIONS:
+            raise ValueError(f"Eq: {len(out)} sections, at most {cls.MAX_SECTIONS}")
+        return super().__new__(cls, out)
+
+    def __add__(self, other):
+        if not isinstance(other, Eq):
+            return NotImplemented
+        return Eq(tuple(self) + tuple(other))
+
+    def __repr__(self):
+        return f"Eq({list(self)!r})"
+
+    @classmethod
+    def highpass(cls, f, q=0.7071):
+        return cls([("highpass", f, q, 0.0)])
+
+    @classmethod
+    def lowpass(cls, f, q=0.7071):
+        return cls([("lowpass", f, q, 0.0)])
+
+    @classmethod
+    def bandpass(cls, f, q=0.7071):
+        return cls([("bandpass", f, q, 0.0)])
+
+    @classmethod
+    def notch(cls, f, q=0.7071):
+        return cls([("notch", f, q, 0.0)])
+
+    @classmethod
+    def peak(cls, f, gain_db, q=1.0):
+        return cls([("peak", f, q, gain_db)])
+
+    @classmethod
+    def low_shelf(cls, f, gain_db, q=0.7071):
+        return cls([("low_shelf", f, q, gain_db)])
+
+    @classmethod
+    def high_shelf(cls, f, gain_db, q=0.7071):
+        return cls([("high_shelf", f, q, gain_db)])
+
+    @classmethod
+    def rumble(cls):
+        """a high-pass at 80 Hz, Q 0.7071: DC offset, desk rumble and the boom of a close microphone"""
+        return cls.highpass(80.0, 0.7071)
+
+    @classmethod
+    def telephone(cls):
+        """the telephone band, fourth-order Butterworth 300 .. 3400 Hz: in front of an 8 kHz delivery"""
+        return cls.highpass(300.0, 0.5412) + cls.highpass(300.0, 1.3066) + cls.lowpass(3400.0, 0.5412) + cls.lowpass(3400.0, 1.3066)
+
+    @classmethod
+    def presence(cls):
+        """a peak at 3 kHz, +4 dB, Q 1 and a high shelf at 8 kHz, +3 dB: for small speakers"""
+        return cls.peak(3000.0, 4.0, 1.0) + cls.high_shelf(8000.0, 3.0)
+
+    def sections(self, sample_rate=SAMPLE_RATE) -> np.ndarray:
+        """(n, 5) float64, b0 b1 b2 a1 a2 per section at sample_rate (vx_eq_design).  ValueError: no section, or a spec the rate does
+        not allow (f0 at or above sample_rate / 2)."""
+        from .._capi import Engine
+        if not len(self):
+            raise ValueError("Eq: no section")
+        return np.stack([Engine.eq_design(kind, f0, q, gain, int(sample_rate)) for kind, f0, q, gain in self])
+
+    def response(self, freqs, sample_rate=SAMPLE_RATE) -> np.ndarray:
+        """|H| of the cascade at freqs (Hz), from the designed coefficients"""
+        z = np.exp(-2j * np.pi * np.asarray(freqs, np.float64) / float(sample_rate))
+        h = np.ones(z.shape, np.complex128)
+        for b0, b1, b2, a1, a2 in self.sections(sample_rate):
+            h = h * (b0 + b1 * z + b2 * z * z) / (1.0 + a1 * z + a2 * z * z)
+        return np.abs(h)
+
+
+def _equalised(wavs, eq):
+    """the 24 kHz waveforms of a vocoder call through `eq` (None: as they are), behind denoise, pauses and speed / pitch and directly
+    in front of the resampler"""
+    if eq is None:
+        return wavs
+    return model.engine._equalised(wavs, eq, SAMPLE_RATE)
+
+
+def _check_eq(eq):
+    """the ValueError of an `eq` argument that Engine.eq would refuse at 24 kHz, before anything is synthesised"""
+    if eq is not None:
+        model.engine.eq_plan(eq, SAMPLE_RATE)
+
+
 def _paused(wavs, pauses):
     """the 24 kHz waveforms of a vocoder call through `pauses` (None: as they are), behind `denoise` and in front of speed and pitch"""
     if pauses is None:
@@ -362,7 +473,7 @@ def _infer_one(text, audio_prompts, text_prompts, lang_pr, language, accent, **k
 
 
 def generate_audio(text, prompt=None, language="auto", accent="no-accent", sample_rate=None, finish=None, speed=None, pitch=None,
-                   denoise=None, pauses=None, **kw):
+                   denoise=None, pauses=None, eq=None, **kw):
     """utils/generation.py:92-152.  sample_rate (no reference counterpart; None = 24 kHz, the reference's): the waveform is resampled
     on the device (Engine.resample, vx_resample) to that rate.  finish (a `Finish`; None = the raw fp32 of the reference): the output
     stage behind it -- trim, level, fades, int16 with pcm16=True.  speed (a float, a Fraction or a (num, den) pair in 1/2 .. 2; None =
@@ -376,9 +487,12 @@ def generate_audio(text, prompt=None, language="auto", accent="no-accent", sampl
     speed, pitch, resample and finish -- for a preset that was enrolled from a noisy clip.  pauses (None = the pauses the model
     sampled; a `Pauses`): the pauses inside the speech are found (Engine.pauses, vx_pauses) and shortened, lengthened or scaled by a
     piecewise time map (Engine.retime, vx_retime) at 24 kHz, behind denoise and in front of speed and pitch; the speech between them
-    keeps its bits."""
+    keeps its bits.  eq (None = the spectrum the vocoder gave; an `Eq`): a cascade of biquads on the device (Engine.eq, vx_eq) at
+    24 kHz, behind denoise, pauses and speed / pitch and directly in front of the resample -- a telephone band precedes the decimation,
+    and loudness, limiter and trim of `finish` measure what is delivered."""
     if model is None or vocos is None:
         raise RuntimeError("call preload_models() first")
+    _check_eq(eq)
     _check_pitch(pitch, speed)
     _check_denoise(denoise)
     if isinstance(text, str):
@@ -402,15 +516,15 @@ def generate_audio(text, prompt=None, language="auto", accent="no-accent", sampl
         s = _denoised([s.reshape(-1)], denoise)[0]
     if pauses is not None:
         s = _paused([s.reshape(-1)], pauses)[0]
-    if speed is not None or pitch is not None:
-        return _finished(_to_rate(_at_speed([s.reshape(-1)], speed, pitch), sample_rate), finish, sample_rate)[0]
+    if speed is not None or pitch is not None or eq is not None:
+        return _finished(_to_rate(_equalised(_at_speed([s.reshape(-1)], speed, pitch), eq), sample_rate), finish, sample_rate)[0]
     if finish is not None:
         return _finished(_to_rate([s.reshape(-1)], sample_rate), finish, sample_rate)[0]
     return s if sample_rate is None else _to_rate([s.reshape(-1)], sample_rate)[0]
 
 
 def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent", text_languages=None, sample_rate=None, finish=None,
-                         speed=None, pitch=None, denoise=None, pauses=None, **kw):
+                         speed=None, pitch=None, denoise=None, pauses=None, eq=None, **kw):
     """Batch form of `generate_audio` (no reference equivalent: the reference synthesises one utterance per call,
     utils/generation.py:92-152): utterance i of the batch equals `generate_audio(texts[i], prompts[i], language[i], accent)`.
     `texts`: strings (need the tokenizer hook) or phoneme-id arrays; `prompts`: one preset name / path / None per utterance (or
@@ -423,9 +537,11 @@ def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent
     call for the list before both.  `pitch` (None = as produced): the pitch shift of `generate_audio`, Engine.shift for the list in
     place of the stretch.  `denoise` (None = as produced): the noise suppression of `generate_audio`, one Engine.denoise call for the
     list directly behind Vocos.  `pauses` (None = as produced): the pause control of `generate_audio`, one Engine.pauses and one
-    Engine.retime call for the list behind that.  Returns a list of float32 waveforms (int16 with pcm16=True)."""
+    Engine.retime call for the list behind that.  `eq` (None = as produced): the equaliser of `generate_audio`, one Engine.eq call for
+    the list directly in front of the resample.  Returns a list of float32 waveforms (int16 with pcm16=True)."""
     if model is None or vocos is None:
         raise RuntimeError("call preload_models() first")
+    _check_eq(eq)
     _check_pitch(pitch, speed)
     _check_denoise(denoise)
     n = len(texts)
@@ -436,7 +552,7 @@ def generate_audio_batch(texts, prompts=None, language="auto", accent="no-accent
             for text, prompt, lang_in, tl in zip(texts, prompts, langs_in, text_languages)]
     codes = model.inference_batch(rows, top_k=-100, temperature=1, **kw)
     return model.engine.vocos_decode(codes, 2, sample_rate=SAMPLE_RATE if sample_rate is None else int(sample_rate), finish=finish,
-                                     speed=speed, pitch=pitch, denoise=denoise, pauses=pauses)
+                                     speed=speed, pitch=pitch, denoise=denoise, pauses=pauses, eq=eq)
 
 
 def _utterance_row(text, prompt, lang_in, accent, tl=None) -> dict:
@@ -477,9 +593,11 @@ class AudioServer:
     every delivered waveform between Vocos and the resampler (vx_stretch is allowed as well).  `pitch` (None = as produced): ONE pitch
     shift for the server (generate_audio's `pitch`), applied there in place of the stretch.  `denoise` (None = as produced): ONE noise
     suppression for the server (generate_audio's `denoise`), applied directly behind Vocos (vx_denoise is allowed as well).  `pauses` (None = as produced): ONE pause
-    control for the server (generate_audio's `pauses`), applied behind that (vx_pauses and vx_retime are allowed as well)."""
+    control for the server (generate_audio's `pauses`), applied behind that (vx_pauses and vx_retime are allowed as well).
+    `eq` (None = as produced): ONE equaliser for the server (generate_audio's `eq`), applied directly in front of the resampler (vx_eq
+    is allowed as well)."""
 
-    def __init__(self, sample_rate=None, finish=None, speed=None, pitch=None, denoise=None, pauses=None, **serve_kw):
+    def __init__(self, sample_rate=None, finish=None, speed=None, pitch=None, denoise=None, pauses=None, eq=None, **serve_kw):
         if model is None or vocos is None:
             raise RuntimeError("call preload_models() first")
         rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
@@ -493,9 +611,11 @@ class AudioServer:
         _check_denoise(denoise)
         self.denoise = denoise
         self.pauses = pauses
+        _check_eq(eq)
+        self.eq = eq
         self._server = model.serve(top_k=-100, temperature=1.0,
                                    post=lambda codes: model.engine.vocos_decode(codes, 2, sample_rate=rate, finish=finish, speed=speed,
-                                                                                pitch=pitch, denoise=denoise, pauses=pauses),
+                                                                                pitch=pitch, denoise=denoise, pauses=pauses, eq=eq),
                                    **serve_kw)
 
     def submit(self, text, prompt=None, language="auto", accent="no-accent", best_of=1, seed=None, uniforms=None,
@@ -520,12 +640,13 @@ class AudioServer:
 
 
 def generate_audio_from_long_text(text, prompt=None, language="auto", accent="no-accent", mode="sliding-window", sample_rate=None,
-                                  finish=None, speed=None, pitch=None, denoise=None, pauses=None, **kw):
+                                  finish=None, speed=None, pitch=None, denoise=None, pauses=None, eq=None, **kw):
     """utils/generation.py:155-276.  `text` may also be a list of sentences / id arrays (pre-split).  sample_rate, finish, speed,
-    pitch, denoise, pauses: as generate_audio (the noise suppression, the pause control, the stretch or the shift and the output
-    stage see the concatenated waveform once)."""
+    pitch, denoise, pauses, eq: as generate_audio (the noise suppression, the pause control, the stretch or the shift, the equaliser
+    and the output stage see the concatenated waveform once)."""
     if model is None or vocos is None:
         raise RuntimeError("call preload_models() first")
+    _check_eq(eq)
     _check_pitch(pitch, speed)
     _check_denoise(denoise)
     if prompt is None or prompt == "":
@@ -578,8 +699,8 @@ def generate_audio_from_long_text(text, prompt=None, language="auto", accent="no
         s = _denoised([s.reshape(-1)], denoise)[0]
     if pauses is not None:
         s = _paused([s.reshape(-1)], pauses)[0]
-    if speed is not None or pitch is not None:
-        return _finished(_to_rate(_at_speed([s.reshape(-1)], speed, pitch), sample_rate), finish, sample_rate)[0]
+    if speed is not None or pitch is not None or eq is not None:
+        return _finished(_to_rate(_equalised(_at_speed([s.reshape(-1)], speed, pitch), eq), sample_rate), finish, sample_rate)[0]
     if finish is not None:
         return _finished(_to_rate([s.reshape(-1)], sample_rate), finish, sample_rate)[0]
     return s if sample_rate is None else _to_rate([s.reshape(-1)], sample_rate)[0]

@@ -142,6 +142,16 @@ def suppress_noise(wav: np.ndarray, denoise) -> np.ndarray:
     return np.array(G.model.engine._denoised([wav.reshape(-1)], denoise)[0], np.float32)[None]
 
 
+def equalise(wav: np.ndarray, eq, sample_rate: int) -> np.ndarray:
+    """(1, L) mono fp32 at sample_rate -> the clip through `eq` (a utils.generation.Eq, resolved at sample_rate, or (n, 5) sections),
+    same length, on the loaded model's engine (Engine.eq: vx_eq).  A zero-shot model clones the recording: a DC offset, desk rumble
+    or the boom of a close microphone would be in every utterance, and would decide which frames `suppress_noise` takes for noise --
+    Eq.rumble() in front of it is what a studio chain does first."""
+    if G.model is None:
+        raise RuntimeError("call preload_models() first: eq runs on the loaded model's engine")
+    return np.array(G.model.engine._equalised([wav.reshape(-1)], eq, int(sample_rate))[0], np.float32)[None]
+
+
 def shorten_pauses(wav: np.ndarray, max_pause_ms: float, sample_rate: int) -> np.ndarray:
     """(1, L) mono fp32 at sample_rate -> the clip with every pause inside the speech held to max_pause_ms, on the loaded model's
     engine (Engine.pauses and Engine.retime: vx_pauses, vx_retime; utils.generation.Pauses' defaults otherwise).  The speech keeps
@@ -153,12 +163,15 @@ def shorten_pauses(wav: np.ndarray, max_pause_ms: float, sample_rate: int) -> np
 
 
 def tokenize_audio(tokenizer: AudioTokenizer, audio: Union[str, Tuple[np.ndarray, int]], trim_db: Optional[float] = None,
-                   lufs: Optional[float] = None, pitch=None, denoise=None, max_pause_ms: Optional[float] = None):
+                   lufs: Optional[float] = None, pitch=None, denoise=None, max_pause_ms: Optional[float] = None, eq=None):
     """data/tokenizer.py:99-111: (path | (wav (C, L), sr)) -> `tokenizer.encode(wav[None])` = [(codes (1, 8, T), None)].
     trim_db (no reference counterpart; None = the clip as it is): `trim_silence` on the 24 kHz mono clip before the encoder sees it.
     lufs (no reference counterpart; None = the clip's own level): `level_loudness` on that clip, after the trim.
     pitch (no reference counterpart; None = the clip's own pitch): `shift_pitch` on the 24 kHz mono clip, before the trim.
-    denoise (no reference counterpart; None = the clip as recorded): `suppress_noise` on the mono clip, first of all.
+    eq (no reference counterpart; None = the clip's own spectrum): `equalise` on the mono clip at the tokenizer's rate, first of all,
+    so that a DC offset or rumble does not choose the noise frames of `denoise`.
+    denoise (no reference counterpart; None = the clip as recorded): `suppress_noise` on the mono clip, behind eq and in front of
+    everything else.
     max_pause_ms (no reference counterpart; None = the clip's own pauses): `shorten_pauses` on the mono clip, behind denoise and
     pitch and in front of the trim."""
     wav, sr = _load_wav(audio) if isinstance(audio, str) else audio
@@ -169,6 +182,8 @@ def tokenize_audio(tokenizer: AudioTokenizer, audio: Union[str, Tuple[np.ndarray
         wav = wav.mean(0, keepdims=True)
     if sr != tokenizer.sample_rate:
         wav = np.asarray((resampler or _builtin_resampler())(wav, int(sr), tokenizer.sample_rate), np.float32)
+    if eq is not None:
+        wav = equalise(wav, eq, tokenizer.sample_rate)
     if denoise is not None:
         wav = suppress_noise(wav, denoise)
     if pitch is not None:
@@ -203,13 +218,15 @@ def make_transcript(name, wav, sr, transcript: Optional[str] = None):
 
 def make_prompt(name: str, audio_prompt_path: Union[str, Tuple[np.ndarray, int]], transcript: Optional[str] = None,
                 save_dir: Optional[str] = None, trim_db: Optional[float] = None, lufs: Optional[float] = None, pitch=None,
-                denoise=None, max_pause_ms: Optional[float] = None) -> str:
+                denoise=None, max_pause_ms: Optional[float] = None, eq=None) -> str:
     """utils/prompt_making.py:57-84.  `audio_prompt_path`: a WAV path or `(wav (C, L), sr)`.  Returns the path of the written .npz.
     trim_db: as `tokenize_audio` (leading and trailing silence of the clip is cut before it is encoded); lufs: as `tokenize_audio`
     (the clip is brought to that loudness, after the trim, before it is encoded); pitch: as `tokenize_audio` (the clip is shifted by
     that many semitones, or that ratio, before the trim: the cloned voice follows its prompt); denoise: as `tokenize_audio` (the
-    clip's steady noise is suppressed first of all, so that it is not cloned with the voice); max_pause_ms: as `tokenize_audio`
-    (every pause inside the speech is held to that length, behind denoise and pitch and in front of the trim)."""
+    clip's steady noise is suppressed in front of everything but eq, so that it is not cloned with the voice); max_pause_ms: as
+    `tokenize_audio` (every pause inside the speech is held to that length, behind denoise and pitch and in front of the trim); eq: as
+    `tokenize_audio` (the clip goes through the equaliser first of all: Eq.rumble() takes a DC offset and rumble out before the noise
+    estimate sees them)."""
     global codec
     if G.model is None:
         raise RuntimeError("call preload_models() first (with EnCodec weights: model.load_encodec_state_dict)")
@@ -225,7 +242,7 @@ def make_prompt(name: str, audio_prompt_path: Union[str, Tuple[np.ndarray, int]]
         wav_pr = wav_pr.mean(0, keepdims=True)
     text_pr, lang_pr = make_transcript(name, wav_pr, sr, transcript)
     encoded_frames = tokenize_audio(codec, (wav_pr, sr), trim_db=trim_db, lufs=lufs, pitch=pitch, denoise=denoise,
-                                    max_pause_ms=max_pause_ms)    # :67
+                                    max_pause_ms=max_pause_ms, eq=eq)    # :67
     codes = encoded_frames[0][0]
     codes = codes.numpy() if hasattr(codes, "numpy") else np.asarray(codes)
     audio_tokens = np.transpose(codes, (0, 2, 1))                 # (1, T, 8)   (:68)
