@@ -863,6 +863,50 @@ const char* vx_eq_last_error(void);
 int vx_eq(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t* lens, int32_t batch, const double* sections,
           int32_t nsections, float* out, int64_t out_stride, vx_eq_info* info);
 
+/* The equaliser with a carried state: the same cascade as vx_eq without its bounded memory, for the filters vx_eq refuses or pays a
+ * long warm-up for (mains-hum notches, a 5 Hz high-pass), and with a state input and output, which gives a caller chunked filtering
+ * and a start from something other than rest.  No reference counterpart.
+ *
+ * - Sections, per-sample arithmetic, the sanitising of the input, the single rounding of the output, nonfinite, nonfinite_out and
+ *   peak are exactly vx_eq's (above).
+ * - State and step.  The state of a cascade of ns sections is z = (s1[0], s2[0], .., s1[ns - 1], s2[ns - 1]), D = 2 ns doubles.  A row
+ *   is walked in steps of Sc = VX_EQ_CARRY_STEP samples.
+ * - M [D][D], row-major: column k is the state the cascade reaches from the unit state e_k (every other component +0) over Sc zero
+ *   inputs, run by the recursion above.  vx_eq_carry_plan(sections, nsections, m, &step) is a pure host function that reports M and
+ *   Sc; it refuses what vx_eq's section checks refuse and an M with an entry that is not finite.
+ * - A row of n samples has J = ceil(n / Sc) steps; the last one is padded with zeros.  Three passes:
+ *     ends   f_j = the state after the Sc samples of step j, started from rest.
+ *     chain  z_0 = state_in of the row (rest when state_in is NULL), then for every component i
+ *                acc = M[i][0] * z_j[0];   acc = acc + M[i][k] * z_j[k]  for k = 1 .. D - 1 in this order;   z_{j+1}[i] = f_j[i] + acc
+ *            in double, every operation rounded on its own (no fma).  Structural zeros of M are multiplied and added like any other
+ *            entry: the rule has no cases.
+ *     rows   step j runs the cascade from z_j over its own samples; each value of the last section is rounded once to fp32.
+ *   The cascade is linear in (state, input), so this is mathematically the unbounded recursion from state_in; the distance to it is
+ *   rounding in double alone.  There is no W and no limit on a filter's memory.
+ * - Consequence.  The bits of a row are a function of the row, the coefficients and its state_in.  They do not depend on the batch,
+ *   the job, the tile, the window or the launch.  No atomics, no inline assembly.
+ * - state_in [batch][D] (may be NULL: every row from rest); state_out [batch][D] (may be NULL): the state the rows pass holds behind
+ *   the row's last sample; for a row of length 0 it is the row's state_in.  A row filtered in two calls, state_out of the first as
+ *   state_in of the second, equals the one call within rounding in double (far below half an fp32 ulp of the peak), but not bit for
+ *   bit: at a cut the second call starts from the state the rows pass ran to, the one call from f + M z, and the two differ in
+ *   rounding.  Cut at multiples of Sc if the second call's steps are to be the one call's.
+ * - info [batch]: a vx_eq_info with warm = 0.
+ * - Windows.  As vx_eq, on the same field (vx_dev_eq_window): rows are packed into launches of VX_EQ_WINDOW staged samples in order;
+ *   a longer row is cut at step multiples and the chain's z is carried into the next launch on the device.  No cut changes a bit.
+ *   Every window runs three launches (ends, chain, rows) on the context's stream; the step tables lie in the launch buffers.
+ * - Refusals.  VX_EINVAL, nothing launched, nothing written, the message names the section or the field: NULL wav / lens / sections /
+ *   out / info (vx_eq_carry_plan: sections, m or step); batch <= 0; a length negative, above
+ *   wav_stride or above out_stride; nsections outside 1 .. 8; a coefficient that is not finite; an unstable section; a state_in
+ *   entry that is not finite.  vx_eq_carry_plan has no context: its message is vx_eq_last_error()'s, and it is vx_eq_plan's own text
+ *   for the same sections -- it starts "vx_eq_plan:", and a NULL m or step reads "sections, warm or step is NULL". */
+#ifndef VX_EQ_CARRY_STEP  /* a constant of the contract; tools/eq_carry_bench.py builds the library at others to measure them */
+#define VX_EQ_CARRY_STEP 512
+#endif
+int vx_eq_carry_plan(const double* sections, int32_t nsections, double* m /* [2 ns][2 ns] */, int32_t* step);
+int vx_eq_carry(vx_ctx* ctx, const float* wav, int64_t wav_stride, const int32_t* lens, int32_t batch, const double* sections,
+                int32_t nsections, const double* state_in /* [batch][2 ns] or NULL */, float* out, int64_t out_stride,
+                double* state_out /* [batch][2 ns] or NULL */, vx_eq_info* info);
+
 /* ---- step-level entries (kernel-level parity tests; same kernels as vx_infer) ---------------------------- */
 /* first ar_decoder.infer call (models/vallex.py:528-562): embeds, runs the prefix-LM prefill, fills the KV arena,
  * leaves the logits of the last row available.  batch <= 32. */

@@ -10,11 +10,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libvallex_hip.so")
 PREFLIGHT = os.path.join(CSRC, "vx_preflight.bin")      # library-free box check (csrc/preflight.hip, vall-e-x_amd/_preflight.py)
-SOURCES = ["gemm_f32.hip", "gemm_f16x2.hip", "gemm_bf16x3.hip", "gemm_bf16x3_dma.hip", "rows.hip", "attn_full.hip", "attn_full_x3.hip", "attn_full_h2.hip", "decode.hip", "beams.hip", "admit.hip", "serve.hip", "serve_sample.hip", "vocos.hip", "encodec.hip", "engine.hip", "schedule.hip", "weights.hip", "vocoders.hip", "bench_harness.hip", "score.hip", "align.hip", "dev_wave.hip", "dev_seam.hip", "resample.hip", "finish.hip", "stretch.hip", "loudness.hip", "limit.hip", "f0.hip", "psola.hip", "denoise.hip", "retime.hip", "eq.hip"]
+SOURCES = ["gemm_f32.hip", "gemm_f16x2.hip", "gemm_bf16x3.hip", "gemm_bf16x3_dma.hip", "rows.hip", "attn_full.hip", "attn_full_x3.hip", "attn_full_h2.hip", "decode.hip", "beams.hip", "admit.hip", "serve.hip", "serve_sample.hip", "vocos.hip", "encodec.hip", "engine.hip", "schedule.hip", "weights.hip", "vocoders.hip", "bench_harness.hip", "score.hip", "align.hip", "dev_wave.hip", "dev_seam.hip", "resample.hip", "finish.hip", "stretch.hip", "loudness.hip", "limit.hip", "f0.hip", "psola.hip", "denoise.hip", "retime.hip", "eq.hip", "eq_carry.hip"]
 HEADERS = ["vx_common.h"]                    # every translation unit
 # the engine's translation units (host code: context, drivers, C ABI) also see the internal context header and the public ABI
-ENGINE_TUS = ("engine.hip", "schedule.hip", "beams.hip", "admit.hip", "serve.hip", "serve_sample.hip", "weights.hip", "vocoders.hip", "bench_harness.hip", "score.hip", "align.hip", "dev_wave.hip", "dev_seam.hip", "resample.hip", "finish.hip", "stretch.hip", "loudness.hip", "limit.hip", "f0.hip", "psola.hip", "denoise.hip", "retime.hip", "eq.hip")
-ENGINE_HEADERS = ["engine_ctx.h", "wave_stage.h", "ws_walk.h", "resample_host.h", "finish_host.h", "stretch_host.h", "loudness_host.h", "limit_host.h", "f0_host.h", "psola_host.h", "denoise_host.h", "retime_host.h", "eq_host.h", os.path.join("..", "..", "include", "vallex_hip.h"),
+ENGINE_TUS = ("engine.hip", "schedule.hip", "beams.hip", "admit.hip", "serve.hip", "serve_sample.hip", "weights.hip", "vocoders.hip", "bench_harness.hip", "score.hip", "align.hip", "dev_wave.hip", "dev_seam.hip", "resample.hip", "finish.hip", "stretch.hip", "loudness.hip", "limit.hip", "f0.hip", "psola.hip", "denoise.hip", "retime.hip", "eq.hip", "eq_carry.hip")
+ENGINE_HEADERS = ["engine_ctx.h", "wave_stage.h", "ws_walk.h", "resample_host.h", "finish_host.h", "stretch_host.h", "loudness_host.h", "limit_host.h", "f0_host.h", "psola_host.h", "denoise_host.h", "retime_host.h", "eq_host.h", "eq_carry_host.h", os.path.join("..", "..", "include", "vallex_hip.h"),
                   os.path.join("..", "..", "include", "vallex_hip_dev.h")]
 # kernarg preload: the first kernel arguments arrive in SGPRs with the wave instead of through an s_load round trip at the
 # head of every launch (the compiler keeps a compatibility prologue for firmware without the feature)

@@ -172,7 +172,7 @@ SYMBOLS = ["vx_abi_version", "vx_create", "vx_destroy", "vx_last_error", "vx_syn
            "vx_serve_close", "vx_serve_submit_ex", "vx_serve_cancel", "vx_serve_submit_filtered", "vx_score", "vx_align", "vx_resample",
            "vx_finish", "vx_stretch", "vx_loudness_coeffs", "vx_loudness", "vx_finish_loud", "vx_limit_taps", "vx_limit",
            "vx_finish_limited", "vx_psola", "vx_denoise_tables", "vx_denoise", "vx_pauses", "vx_retime", "vx_eq_design",
-           "vx_eq_plan", "vx_eq_last_error", "vx_eq"]
+           "vx_eq_plan", "vx_eq_last_error", "vx_eq", "vx_eq_carry_plan", "vx_eq_carry"]
 # ... and include/vallex_hip_dev.h: measurement / kernel development, never called by the mirrors of the reference API
 DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kernel", "vx_bench_gemm", "vx_bench_attn",
                "vx_bench_gemm_clock", "vx_bench_gemm_epilogue", "vx_dev_sample", "vx_dev_attn", "vx_dev_sample_filtered",
@@ -389,6 +389,9 @@ def load_library() -> C.CDLL:
     lib.vx_eq_last_error.restype = C.c_char_p
     lib.vx_eq.argtypes = [ctx, P(C.c_float), C.c_int64, P(C.c_int32), C.c_int32, P(C.c_double), C.c_int32, P(C.c_float), C.c_int64,
                           P(vx_eq_info)]
+    lib.vx_eq_carry_plan.argtypes = [P(C.c_double), C.c_int32, P(C.c_double), P(C.c_int32)]
+    lib.vx_eq_carry.argtypes = [ctx, P(C.c_float), C.c_int64, P(C.c_int32), C.c_int32, P(C.c_double), C.c_int32, P(C.c_double), P(C.c_float),
+                                C.c_int64, P(C.c_double), P(vx_eq_info)]
     lib.vx_dev_eq_window.argtypes = [ctx, C.c_int32]
     lib.vx_dev_stretch_costs.argtypes = [ctx, P(C.c_float), C.c_int32, P(vx_stretch_opts), P(C.c_float), P(C.c_int32), P(C.c_double)]
     lib.vx_last_stats.argtypes = [ctx, P(C.c_int64), P(C.c_int64), P(C.c_double), P(C.c_double)]
@@ -872,7 +875,7 @@ class Engine:
 
     _eq_plans = {}                   # sections (their bytes) -> (W, S) of the filters `eq_plan` accepted
 
-    last_eq_info = None              # the info dicts of the last `eq` (also through an `eq=` argument)
+    last_eq_info = None              # the info dicts of the last `eq` or `eq_carry` (also through an `eq=` argument)
 
     def eq(self, wavs: Sequence[np.ndarray], sections, sample_rate: int = 24000, return_info: bool = False):
         """vx_eq, a cascade of 1 .. 8 biquads over mono fp32 waveforms (L_i,) -> float32 rows of L_i samples.  sections: (n, 5) float64
@@ -895,10 +898,70 @@ class Engine:
         self.last_eq_info = self._dicts(info)
         return (rows, self.last_eq_info) if return_info else rows
 
+    @classmethod
+    def eq_carry_plan(cls, sections, sample_rate: int = 24000):
+        """vx_eq_carry_plan: (M, Sc) of a filter -- the (2 n, 2 n) float64 matrix that takes the cascade's state over a step of Sc zero
+        inputs, and the step.  ValueError: a filter the library refuses (an unstable or non-finite section, none or more than 8).
+        There is no limit on a filter's memory."""
+        lib = load_library()
+        s = cls._eq_sections(sections, sample_rate)
+        key = s.tobytes()
+        if key not in cls._eq_carry_plans:                                # 2 n runs of the cascade over a step: remembered like `eq_plan`'s W
+            m = np.zeros((2 * max(1, len(s)), 2 * max(1, len(s))), np.float64)
+            st = C.c_int32(0)
+            if lib.vx_eq_carry_plan(_ptr(s if len(s) else np.zeros((1, 5)), C.c_double), len(s), _ptr(m, C.c_double), C.byref(st)) != 0:
+                raise ValueError("eq_carry_plan: " + lib.vx_eq_last_error().decode().split(": ", 1)[-1])
+            if len(cls._eq_carry_plans) >= 64:
+                cls._eq_carry_plans.clear()
+            cls._eq_carry_plans[key] = (m, st.value)
+        m, step = cls._eq_carry_plans[key]
+        return m.copy(), step
+
+    _eq_carry_plans = {}             # sections (their bytes) -> (M, Sc) of the filters `eq_carry_plan` accepted
+
+    def eq_carry(self, wavs: Sequence[np.ndarray], eq, sample_rate: int = 24000, state=None, return_state: bool = False):
+        """vx_eq_carry, the equaliser with a carried state: the cascade of `eq` over mono fp32 waveforms (L_i,) -> float32 rows of L_i
+        samples, every row the unbounded recursion from its start state (to rounding in double), whatever the filter's memory.  eq:
+        (n, 5) float64 sections or a utils.generation.Eq / CarriedEq, resolved at sample_rate.  state (None: from rest -- unless eq
+        carries prime_hz, then every row of at least ten periods starts from the steady state of its own periodic component:
+        CarriedEq.prime): (rows, 2 n) float64, s1 s2 per section.  return_state: (rows, states), states (rows, 2 n) float64 behind
+        each row's last sample -- the `state` of a call that continues the rows.  Sets last_eq_info (warm = 0)."""
+        s = self._eq_sections(eq, sample_rate)
+        self.eq_carry_plan(s)                                             # a ValueError comes before any launch
+        n, D = len(wavs), 2 * len(s)
+        if n == 0:
+            self.last_eq_info = []
+            return ([], np.zeros((0, D))) if return_state else []
+        if state is None and getattr(eq, "prime_hz", None) is not None:
+            state = eq.prime(self, wavs, s, sample_rate)
+        if state is not None:
+            state = np.ascontiguousarray(state, np.float64)
+            if state.shape != (n, D):
+                raise ValueError(f"eq_carry: state of shape {state.shape}, not (rows, 2 sections) = ({n}, {D})")
+        buf, lens, stride = self._packed(wavs)
+        out = np.empty((n, stride), np.float32)
+        sout = np.zeros((n, D), np.float64)
+        info = (vx_eq_info * n)()
+        self._chk(self.lib.vx_eq_carry(self.ctx, _ptr(buf, C.c_float), stride, _ptr(lens, C.c_int32), n, _ptr(s, C.c_double), len(s),
+                                       None if state is None else _ptr(state, C.c_double), _ptr(out, C.c_float), stride,
+                                       _ptr(sout, C.c_double), info))
+        rows = [out[i, :L] for i, L in enumerate(lens)]
+        self.last_eq_info = self._dicts(info)
+        return (rows, sout) if return_state else rows
+
+    def _eq_check(self, eq, rate: int = 24000):
+        """the ValueError of an `eq=` argument its stage would refuse at `rate`: `eq_carry_plan` for a carried eq, else `eq_plan`"""
+        if getattr(eq, "is_carried", False):
+            self.eq_carry_plan(eq, rate)
+        else:
+            self.eq_plan(eq, rate)
+
     def _equalised(self, rows, eq, rate: int = 24000):
-        """the rows of an `eq=` argument (None: as they are) at `rate`"""
+        """the rows of an `eq=` argument (None: as they are) at `rate`: through `eq_carry` for a carried eq, else through `eq`"""
         if eq is None:
             return rows
+        if getattr(eq, "is_carried", False):
+            return self.eq_carry(rows, eq, sample_rate=rate)
         return self.eq(rows, eq, sample_rate=rate)
 
     def dev_eq_window(self, samples: int = 0):
@@ -1449,7 +1512,7 @@ class Engine:
         if denoise is not None:
             self._denoise_opts(**self._denoise_parts(denoise))
         if eq is not None:
-            self.eq_plan(eq, 24000)
+            self._eq_check(eq, 24000)
         n = len(codes)
         lens = np.array([c.shape[0] for c in codes], np.int32)
         stride = max(1, int(lens.max()))
@@ -1474,7 +1537,7 @@ class Engine:
         if denoise is not None:
             self._denoise_opts(**self._denoise_parts(denoise))
         if eq is not None:
-            self.eq_plan(eq, 24000)
+            self._eq_check(eq, 24000)
         n = len(codes)
         lens = np.array([c.shape[0] for c in codes], np.int32)
         stride = max(1, int(lens.max()))

@@ -13,6 +13,7 @@ globals, and already-tokenised phoneme ids may be passed in place of `text`.
 from __future__ import annotations
 
 import logging
+import math
 import os
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence, Tuple, Union
@@ -301,8 +302,9 @@ class Pauses:
 class Eq(tuple):
     """An equaliser request, accepted wherever `eq=` is: an immutable tuple of specs (kind, f0_hz, q, gain_db), at most 8, one biquad
     each (Engine.eq, vx_eq).  The specs are resolved to coefficients at the sample rate of the call (`sections`), so one object serves
-    the enrolment end (at the tokenizer's rate) and the output end (at 24 kHz).  `a + b` is the cascade of both.  Narrow hum notches
-    (50 Hz at Q 100) have a longer memory than the stage carries and are refused by the call that would run them."""
+    the enrolment end (at the tokenizer's rate) and the output end (at 24 kHz).  `a + b` is the cascade of both.  A filter whose
+    memory is longer than vx_eq's warm-up carries (a narrow hum notch: 50 Hz at Q 100) is refused by the call that would run a plain
+    Eq; the same specs as a `CarriedEq` (`carried()`, `Eq.hum()`) run on the stage that carries its state and has no such limit."""
 
     __slots__ = ()
     KINDS = ("highpass", "lowpass", "bandpass", "notch", "peak", "low_shelf", "high_shelf")
@@ -330,7 +332,24 @@ class Eq(tuple):
     def __add__(self, other):
         if not isinstance(other, Eq):
             return NotImplemented
+        if isinstance(self, CarriedEq) or isinstance(other, CarriedEq):   # either side carried: carried, primed as the first that is
+            hz = [e.prime_hz for e in (self, other) if getattr(e, "prime_hz", None) is not None]
+            opt = tuple(getattr(self, "optional", (False,) * len(self))) + tuple(getattr(other, "optional", (False,) * len(other)))
+            return CarriedEq(tuple(self) + tuple(other), prime_hz=hz[0] if hz else None, optional=opt)
         return Eq(tuple(self) + tuple(other))
+
+    def carried(self, prime_hz=None):
+        """the same specs on the stage that carries its state (Engine.eq_carry): no limit on the filter's memory"""
+        return CarriedEq(tuple(self), prime_hz=prime_hz)
+
+    @classmethod
+    def hum(cls, f0=50.0, harmonics=6, q=35.0):
+        """mains hum: notches at f0 k, k = 1 .. harmonics (those at or above the Nyquist of the call's rate are dropped when the specs
+        are resolved), carried, and primed at f0 so that the notches do not ring in over the start of the clip (`CarriedEq`)"""
+        if not (isinstance(harmonics, (int, np.integer)) and 1 <= harmonics <= cls.MAX_SECTIONS):
+            raise ValueError(f"Eq.hum: harmonics {harmonics!r} outside 1 .. {cls.MAX_SECTIONS}")
+        return CarriedEq([("notch", float(f0) * k, q, 0.0) for k in range(1, int(harmonics) + 1)], prime_hz=float(f0),
+                         optional=(True,) * int(harmonics))
 
     def __repr__(self):
         return f"Eq({list(self)!r})"
@@ -395,6 +414,72 @@ class Eq(tuple):
         return np.abs(h)
 
 
+PRIME_PERIODS, PRIME_CAP_S = 10, 10
+
+
+def hum_lead(x, sections, sample_rate, prime_hz):
+    """the lead a primed filter runs in front of a row (integers and numpy; None: the row starts from rest): the mean of the row's
+    first 10 periods of P = round(sample_rate / prime_hz) samples -- the row's own periodic component, everything else averaged down
+    -- tiled to the smallest multiple of P that is at least ln(1000) / -ln(r) samples (r = max sqrt(a2) over the sections with
+    a2 > 0, the slowest pole radius: the ring-in has fallen by 60 dB), at most 10 s.  A non-finite sample counts as 0, as in the
+    stage.  A row below 10 periods has no lead."""
+    x = np.asarray(x, np.float32).reshape(-1)
+    P = int(round(float(sample_rate) / float(prime_hz)))
+    a2 = [float(c[4]) for c in np.asarray(sections, np.float64).reshape(-1, 5) if c[4] > 0]
+    if P < 1 or len(x) < PRIME_PERIODS * P or not a2:
+        return None
+    need = math.log(1000.0) / -math.log(max(math.sqrt(v) for v in a2))
+    reps = max(1, min(int(math.ceil(need / P)), PRIME_CAP_S * int(sample_rate) // P))
+    head = x[: PRIME_PERIODS * P]
+    head = np.where(np.isfinite(head), head, np.float32(0)).astype(np.float64)
+    return np.tile(head.reshape(PRIME_PERIODS, P).mean(axis=0).astype(np.float32), reps)
+
+
+class CarriedEq(Eq):
+    """An `Eq` that runs on the carried-state stage (Engine.eq_carry, vx_eq_carry) wherever `eq=` is accepted: the same specs and
+    limits, no limit on the filter's memory.  `a + b` with either side carried is carried.  prime_hz (None: every row starts from
+    rest): the rows start from the state the filter is in after a lead built from the row's own component of that period
+    (`hum_lead`), so a hum notch takes the hum out from the first sample instead of ringing in over the first second.  optional:
+    one flag per spec; a flagged spec at or above the Nyquist of the call's rate is dropped by `sections` (Eq.hum's harmonics)."""
+
+    is_carried = True
+
+    def __new__(cls, specs=(), prime_hz=None, optional=None):
+        self = super().__new__(cls, specs)
+        if prime_hz is not None and not (np.isfinite(float(prime_hz)) and float(prime_hz) > 0):
+            raise ValueError(f"CarriedEq: prime_hz {prime_hz!r} is not a positive frequency")
+        opt = (False,) * len(self) if optional is None else tuple(bool(v) for v in optional)
+        if len(opt) != len(self):
+            raise ValueError(f"CarriedEq: {len(opt)} optional flags for {len(self)} specs")
+        self.__dict__.update(prime_hz=None if prime_hz is None else float(prime_hz), optional=opt)
+        return self
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a CarriedEq is immutable")
+
+    def __repr__(self):
+        opt = f", optional={self.optional!r}" if any(self.optional) else ""
+        return f"CarriedEq({list(self)!r}, prime_hz={self.prime_hz!r}{opt})"
+
+    def carried(self, prime_hz=None):
+        return self if prime_hz is None else CarriedEq(tuple(self), prime_hz=prime_hz, optional=self.optional)
+
+    def sections(self, sample_rate=SAMPLE_RATE) -> np.ndarray:
+        kept = Eq([sp for sp, opt in zip(self, self.optional) if not (opt and sp[1] >= 0.5 * float(sample_rate))])
+        return kept.sections(sample_rate)
+
+    def prime(self, engine, wavs, sections, sample_rate):
+        """the start states (rows, 2 n) float64 of `wavs` under this filter: every lead through one Engine.eq_carry call of its own,
+        from rest; a row without a lead starts from rest.  None: no row has one."""
+        leads = [hum_lead(w, sections, sample_rate, self.prime_hz) for w in wavs]
+        have = [i for i, ld in enumerate(leads) if ld is not None]
+        if not have:
+            return None
+        state = np.zeros((len(wavs), 2 * len(sections)), np.float64)
+        state[have] = engine.eq_carry([leads[i] for i in have], np.asarray(sections, np.float64), sample_rate, return_state=True)[1]
+        return state
+
+
 def _equalised(wavs, eq):
     """the 24 kHz waveforms of a vocoder call through `eq` (None: as they are), behind denoise, pauses and speed / pitch and directly
     in front of the resampler"""
@@ -404,8 +489,11 @@ def _equalised(wavs, eq):
 
 
 def _check_eq(eq):
-    """the ValueError of an `eq` argument that Engine.eq would refuse at 24 kHz, before anything is synthesised"""
-    if eq is not None:
+    """the ValueError of an `eq` argument that Engine.eq (a CarriedEq: Engine.eq_carry) would refuse at 24 kHz, before anything is
+    synthesised"""
+    if eq is not None and getattr(eq, "is_carried", False):
+        model.engine.eq_carry_plan(eq, SAMPLE_RATE)
+    elif eq is not None:
         model.engine.eq_plan(eq, SAMPLE_RATE)
 
 
