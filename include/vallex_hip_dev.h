@@ -98,6 +98,14 @@ int vx_dev_attn(vx_ctx* ctx, int32_t variant, int32_t planes, int32_t batch, con
  * VX_EINVAL for a null out or n < 14 (VX_DEV_SWITCHES), VX_ESTATE before vx_finalize_weights. */
 #define VX_DEV_SWITCHES 14
 int vx_dev_switches(vx_ctx* ctx, int32_t* out, int32_t n);
+/* The switches of the decode step's weight-streaming GEMMs (round 35), read like the fields above and reported apart from them
+ * (the word count of vx_dev_switches is fixed).  Both choose WHERE a workgroup runs or in which order it requests its operands,
+ * never what it computes: every output word is the same under either value.  out[0 .. 1]:
+ *    0 l2_kmap        VX_L2_KMAP (1: linear2 of the 5 .. 32-row chain cuts its block id with the K slice fastest, one slice per XCD)
+ *    1 l1_interleave  VX_L1_INTERLEAVE (1: linear1 requests w, x0, x1 per k-block; 0: all of x, then the weights)
+ * VX_EINVAL for a null out or n < 2 (VX_DEV_GEMM_LEVERS), VX_ESTATE before vx_finalize_weights. */
+#define VX_DEV_GEMM_LEVERS 2
+int vx_dev_gemm_levers(vx_ctx* ctx, int32_t* out, int32_t n);
 /* The attention block of ONE decode step on nrows (1 .. 32) chosen rows: the launches of the engine's step from the attention launch
  * to the launch behind which the out_proj result exists, with the chain and the context splits the engine's own rule picks for nrows
  * rows under the context's switches (reported in geom[4] = {nsplit, sb_qkv, split_fused, sb_chain}).  With the default switches:

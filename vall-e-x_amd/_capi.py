@@ -180,7 +180,7 @@ DEV_SYMBOLS = ["vx_prof_enable", "vx_prof_get", "vx_prof_reset", "vx_bench_kerne
                "vx_dev_seam_op", "vx_dev_resample_taps", "vx_dev_resample_window", "vx_dev_finish_frames", "vx_dev_finish_window",
                "vx_dev_stretch_window", "vx_dev_stretch_costs", "vx_dev_loudness_steps", "vx_dev_loudness_window",
                "vx_dev_limit_gain", "vx_dev_limit_window", "vx_dev_psola_table", "vx_dev_psola_window", "vx_dev_switches",
-               "vx_dev_denoise_fft", "vx_dev_denoise_table", "vx_dev_denoise_window", "vx_dev_denoise_div", "vx_dev_retime_window",
+               "vx_dev_gemm_levers", "vx_dev_denoise_fft", "vx_dev_denoise_table", "vx_dev_denoise_window", "vx_dev_denoise_div", "vx_dev_retime_window",
                "vx_dev_eq_window"]
 # the pitch tracker's entries, one of vallex_hip.h and two of vallex_hip_dev.h, in a list of their own: the header scan of
 # tests/test_abi.py matches names of letters and underscores, and these carry a digit (tests/test_f0_refs.py checks them)
@@ -319,6 +319,7 @@ def load_library() -> C.CDLL:
                                     P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
                                     P(C.c_int32)]
     lib.vx_dev_switches.argtypes = [ctx, P(C.c_int32), C.c_int32]
+    lib.vx_dev_gemm_levers.argtypes = [ctx, P(C.c_int32), C.c_int32]
     lib.vx_dev_dec_op.argtypes = [ctx, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_int32), P(C.c_int32), P(C.c_float), P(C.c_float),
                                   P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float)]
     lib.vx_dev_gemm.argtypes = [ctx, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), C.c_int32, C.c_int32, P(C.c_int32),
@@ -1808,6 +1809,12 @@ class Engine:
         out = np.full(max(n, 1), DEV_SENTINEL_I, np.int32)
         self._chk(self.lib.vx_dev_switches(self.ctx, _ptr(out, C.c_int32), n))
         return {k: int(v) for k, v in zip(DEV_SWITCHES, out)}
+
+    def dev_gemm_levers(self):
+        """vx_dev_gemm_levers: {l2_kmap, l1_interleave} as the context read them (include/vallex_hip_dev.h)"""
+        out = np.full(2, DEV_SENTINEL_I, np.int32)
+        self._chk(self.lib.vx_dev_gemm_levers(self.ctx, _ptr(out, C.c_int32), 2))
+        return {"l2_kmap": int(out[0]), "l1_interleave": int(out[1])}
 
     def dev_dec_attn(self, ctx_len, k_rows, v_rows, tmax: int, qkv=None, x_in=None, resid=None, active=None, slot_order=None,
                      qkv_balanced: bool = False, skp: int = 0, k_fill=0.0, v_fill=0.0):

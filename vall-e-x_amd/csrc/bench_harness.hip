@@ -104,8 +104,8 @@ int vx_bench_kernel(vx_ctx* c, int32_t which, int32_t reps, int32_t gen_offset, 
       // (write-through result stores, as in the 32-row step: decode.hip store_result)
       else launch_skinny_gemm(L.in_wp, c->xp, c->p_qkv, 3 * D_MODEL, D_MODEL, SK_QKV, c->stream, true);
       launch_skinny_gemm(L.out_wp, c->xp_att, c->p_o, D_MODEL, D_MODEL, SK_OUT, c->stream, true);
-      launch_skinny16_relu_pack(L.l1_wp, c->xp, L.l1_b, c->xp4, D_FF, D_MODEL, c->stream);
-      launch_skinny_gemm(L.l2_wp, c->xp4, c->p_o, D_MODEL, D_FF, SK_L2, c->stream, true);
+      launch_linear1(c, L.l1_wp, c->xp, L.l1_b, c->xp4, c->stream);
+      launch_skinny_gemm_kmap(L.l2_wp, c->xp4, c->p_o, D_MODEL, D_FF, SK_L2, c->stream, true, c->l2_kmap);
     };
     seq();
     HIPCHK(hipEventRecord(e0, c->stream));
@@ -125,15 +125,16 @@ int vx_bench_kernel(vx_ctx* c, int32_t which, int32_t reps, int32_t gen_offset, 
     launches = reps;
     bytes = 3.0 * D_MODEL * D_MODEL * 4.0;
 #ifdef VX_DEV_PROBES
-  } else if (which == 3) {
-    // development timeline (tools/step_timeline.py): `reps` graph replays of a ONE-layer decode step (QKV | attention |
+  } else if (which == 3 || which == 4) {
+    // development timeline (tools/step_timeline.py): `reps` graph replays of a ONE-layer (which 3) or the whole (which 4) decode step (QKV | attention |
     // reduce+LN | linear1 | linear2 | reduce+LN | predict | sampler) on the live state; the kernels stamp the wall clock
     // (decode.hip) and the caller fetches the stamps of the last replay with vx_dev_stamps.
     vx_sampling sp{};
     sp.struct_size = sizeof(vx_sampling); sp.top_k = 10; sp.temperature = 1.0f; sp.seed = 1; sp.force_eos_at = -1; sp.best_of = 1;
     SampleArgs sa = make_sample_args(c, &sp, 1, nullptr);
     const int nl_keep = c->NL;
-    c->NL = 1;
+    if (which == 3) c->NL = 1;      // which 4: the whole step; the stamps that remain are the LAST layer's, whose weights the other
+                                    // layers' 500 MB have pushed out of every cache since the previous replay
     hipGraph_t g = nullptr;
     hipGraphExec_t ge = nullptr;
     HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
@@ -169,6 +170,7 @@ int vx_bench_kernel(vx_ctx* c, int32_t which, int32_t reps, int32_t gen_offset, 
 
 #ifdef VX_DEV_PROBES
 extern "C" int vx_dev_stamps(unsigned long long* out) { dev_read_stamps(out); return VX_OK; }
+extern "C" int vx_dev_wave_stamps(unsigned long long* out) { vx::dev_read_wave_stamps(out); return VX_OK; }
 extern "C" int vx_dev_gemm_stamps(unsigned long long* out) { dev_read_gemm_stamps(out); return VX_OK; }
 #endif
 
@@ -773,6 +775,16 @@ int vx_dev_attn(vx_ctx* c, int32_t variant, int32_t planes, int32_t batch, const
   return VX_OK;
 }
 
+// vx_dev_gemm_levers: the request-order / block-mapping switches of the decode GEMMs (weights.hip), in the header's order
+int vx_dev_gemm_levers(vx_ctx* c, int32_t* out, int32_t n) {
+  if (!c) return VX_EINVAL;
+  if (!out || n < VX_DEV_GEMM_LEVERS) FAIL(VX_EINVAL, "vx_dev_gemm_levers: out must hold %d words", VX_DEV_GEMM_LEVERS);
+  if (!c->finalized) FAIL(VX_ESTATE, "vx_dev_gemm_levers: weights not finalized");
+  out[0] = c->l2_kmap;
+  out[1] = c->l1_interleave;
+  return VX_OK;
+}
+
 // vx_dev_switches: the kernel-selection fields finalize_weights read (weights.hip), in the order include/vallex_hip_dev.h documents
 int vx_dev_switches(vx_ctx* c, int32_t* out, int32_t n) {
   if (!c) return VX_EINVAL;
@@ -1033,13 +1045,14 @@ int vx_dev_dec_op(vx_ctx* c, int32_t op, int32_t variant, int32_t layer, int32_t
       launch_dec_embed_ln_pack(di, di + MB, emb_tab, emb_alpha, c->pe, dh, c->ar[0].n1_w, c->ar[0].n1_b, dxp, nrows, st);
       break;
     case VX_DEV_OP_GEMM:
-      launch_skinny_gemm(wp, dx, dout, Npad, K, sk, st, nrows > SB_ROWS);
+      // as the engine launches it: linear2 of the 5 .. 32-row chain takes the context's block mapping
+      launch_skinny_gemm_kmap(wp, dx, dout, Npad, K, sk, st, nrows > SB_ROWS, nrows > SB_ROWS && variant == VX_DEV_W_L2 && c->l2_kmap);
       break;
     case VX_DEV_OP_QKV_BAL:
       launch_skinny_qkv_balanced(wp, dx, dout, st);
       break;
     case VX_DEV_OP_LINEAR1:
-      launch_skinny16_relu_pack(wp, dx, L.l1_b, dout, D_FF, D_MODEL, st);
+      launch_linear1(c, wp, dx, L.l1_b, dout, st);
       break;
     case VX_DEV_OP_REDUCE_LN:
       // the engine's four uses: behind out_proj (4 slabs, or 16 head slabs of the fused dec_attn) with norm2, behind linear2 with the

@@ -71,8 +71,19 @@ void dev_clear_stamps() {
   static std::vector<unsigned long long> z(8 * 512 * 8, 0ull);
   (void)hipMemcpyToSymbol(HIP_SYMBOL(vx_stamps), z.data(), z.size() * sizeof(unsigned long long));
 }
+// ... and lane 0 of EVERY wave of linear1 (round 35: is the wave that ends last the one whose loads were issued last?):
+// vx_wave_stamps[workgroup < 256][wave < 8][slot < 4]; slots: 0 start, 1 requests issued, 2 last MFMA, 3 behind the barrier
+__device__ unsigned long long vx_wave_stamps[256 * 8 * 4];
+#define VX_WAVE_STAMP(SLOT)                                                                                             \
+  do {                                                                                                                  \
+    if ((threadIdx.x & 63) == 0 && blockIdx.x < 256) vx_wave_stamps[(blockIdx.x * 8 + (threadIdx.x >> 6)) * 4 + (SLOT)] = wall_clock64(); \
+  } while (0)
+void dev_read_wave_stamps(unsigned long long* out) {      // declared in engine_ctx.h
+  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(vx_wave_stamps), sizeof(unsigned long long) * 256 * 8 * 4);
+}
 #else
 #define VX_STAMP(TYPE, SLOT)
+#define VX_WAVE_STAMP(SLOT)
 #endif
 
 // Results of the kernels of the 5 .. 32-row decode chain are stored WRITE-THROUGH at agent scope (`sc1`).  The step is a chain of
@@ -97,15 +108,29 @@ __device__ __forceinline__ void store_result(float* p, float v, bool wt = true) 
 }
 
 // output: raw split-K partial slab [ks][b][n] (row-major per batch row; consumers: dec_attn, dec_reduce_ln_pack, dec_sample)
+//
+// Block mapping (round 35).  The grid is (column tiles, K slices), column tile fastest, and the hardware deals workgroups to the 8 XCDs
+// round-robin in that order: with kslog < 0 (column tile = blockIdx.x, K slice = blockIdx.y) every XCD ends up with ALL the K slices
+// and its L2 pulls the whole x image.  linear2 of the 5 .. 32-row chain runs with kslog = log2(splitk) instead: the linear block id
+// is cut as  K slice = id & (splitk - 1), column tile = id >> kslog,  so an XCD holds the workgroups of ONE K slice (8 slices) and
+// fetches that 64 KB slice of linear1's write-through image once for its 32 workgroups -- 0.5 MB of x traffic chip-wide instead
+// of 4 MB, all of it requested ahead of the weight stream.  A bijection of (column tile, K slice) for any power-of-two slice
+// count, and a placement hint only: which XCD runs a block changes nothing the block computes or where it stores (same bits).
+// Measured alone on the cold 12-layer step (docs/log_r35.md): last MFMA 5.15 -> 4.72 us, end of the launch 5.93 -> 5.44 us behind
+// its first workgroup; AR -6.4 ms per batch of 32.  The other roles (in_proj, out_proj, predict, the vocoders' recurrences) keep
+// the plain mapping: not measured.
+// Request order: x first, then the weights (below).  Weights first and w[u], x[u] interleaved were both measured on the 12-layer
+// step in round 35 and lost (+1 .. +2 ms AR per batch): left as it was.
 __global__ __launch_bounds__(256) void skinny_gemm_kernel(const float* __restrict__ Wp, const float* __restrict__ xp,
-                                                          float* __restrict__ out, int Npad, int K, int splitk, int wt) {
+                                                          float* __restrict__ out, int Npad, int K, int splitk, int wt, int kslog) {
   __shared__ __attribute__((aligned(16))) float red[4 * 16 * 64];
   const int stype_ = Npad == 3 * D_MODEL ? 0 : (Npad == D_MODEL ? 1 : 2);
   (void)stype_;
   VX_STAMP(stype_, 0);
   // (no "every row has finished" early exit here: reading that flag -- written by the previous step's sampler -- costs a
   // memory round trip before the first weight load of EVERY launch; steps after the last EOS are bounded by sync_every)
-  const int nt = blockIdx.x, ks = blockIdx.y;
+  const int id = blockIdx.x + gridDim.x * blockIdx.y;            // the order in which the workgroups are dealt to the XCDs
+  const int nt = kslog < 0 ? (int)blockIdx.x : id >> kslog, ks = kslog < 0 ? (int)blockIdx.y : id & (splitk - 1);
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int KB = K / 8;
   const int kb_per_wave = KB / (splitk * 4);
@@ -161,9 +186,19 @@ __global__ __launch_bounds__(256) void skinny_gemm_kernel(const float* __restric
 }
 
 // wt: write-through result stores (store_result above) -- the 5 .. 32-row decode chain only
+// kmap: K slice fastest in the block id (the kernel's header); power-of-two slice counts only, any other count keeps the plain mapping
+// (declared in engine_ctx.h: linear2 of the engine's 5 .. 32-row chain is its one caller)
+void launch_skinny_gemm_kmap(const float* Wp, const float* xp, float* partial, int Npad, int K, int splitk,
+                             hipStream_t s, bool wt, bool kmap) {
+  int kslog = -1;
+  if (kmap && splitk > 0 && (splitk & (splitk - 1)) == 0)
+    for (kslog = 0; (1 << kslog) < splitk;) ++kslog;
+  hipLaunchKernelGGL(skinny_gemm_kernel, dim3(Npad / 32, splitk), dim3(256), 0, s, Wp, xp, partial, Npad, K, splitk, wt ? 1 : 0, kslog);
+}
+
 void launch_skinny_gemm(const float* Wp, const float* xp, float* partial, int Npad, int K, int splitk,
                         hipStream_t s, bool wt) {
-  hipLaunchKernelGGL(skinny_gemm_kernel, dim3(Npad / 32, splitk), dim3(256), 0, s, Wp, xp, partial, Npad, K, splitk, wt ? 1 : 0);
+  launch_skinny_gemm_kmap(Wp, xp, partial, Npad, K, splitk, s, wt, false);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -177,6 +212,8 @@ void launch_skinny_gemm(const float* Wp, const float* xp, float* partial, int Np
 // k and v: the arithmetic of skinny_gemm_kernel with splitk = 4, operation for operation (same slabs).  q: eight slabs instead of four
 // (a different summation order: dec_attn_kernel<*, SK_QKV_BALANCED> sums them, and the goldens decide).  Slab layout unchanged,
 // out[(ks * MB + b) * 3072 + n]; the k / v columns of slabs 4..7 are never written or read.
+// Request order: x first, then the weights.  Weights first and w[u], x[u] interleaved were measured on the 12-layer step in round 35
+// and lost (+3 .. +4 ms AR per batch, docs/log_r35.md): left as it was.
 __global__ __launch_bounds__(256, 2) void skinny_qkv_bal_kernel(const float* __restrict__ Wp, const float* __restrict__ xp,
                                                              float* __restrict__ out) {
   __shared__ __attribute__((aligned(16))) float red[4 * 16 * 64];
@@ -193,12 +230,14 @@ __global__ __launch_bounds__(256, 2) void skinny_qkv_bal_kernel(const float* __r
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   f32x4 w[8], x[8];
+  VX_STAMP(0, 0);
   if (isq) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) x[u] = xq[(long)u * 64];
 #pragma unroll
     for (int u = 0; u < 4; ++u) w[u] = __builtin_nontemporal_load(wp + (long)u * 64);
     __builtin_amdgcn_sched_barrier(0);      // every request before the first MFMA (left alone the scheduler sinks the loads to their uses)
+    VX_STAMP(0, 1);
 #pragma unroll
     for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -209,11 +248,13 @@ __global__ __launch_bounds__(256, 2) void skinny_qkv_bal_kernel(const float* __r
 #pragma unroll
     for (int u = 0; u < 8; ++u) w[u] = __builtin_nontemporal_load(wp + (long)u * 64);
     __builtin_amdgcn_sched_barrier(0);
+    VX_STAMP(0, 1);
 #pragma unroll
     for (int u = 0; u < 8; ++u)
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[u][j], x[u][j], acc, 0, 0, 0);
   }
+  VX_STAMP(0, 2);
   // the four waves' partial sums, combined exactly as in skinny_gemm_kernel (ascending wave order)
 #pragma unroll
   for (int r = 0; r < 16; ++r) red[((wid * 16 + r) * 64) + lane] = acc[r];
@@ -226,6 +267,7 @@ __global__ __launch_bounds__(256, 2) void skinny_qkv_bal_kernel(const float* __r
   }
   float* dst = out + ((long)ks * MB + (lane & 31)) * Npad + nt * 32 + 4 * (lane >> 5);
   store_result(dst + wid * 8, t);
+  VX_STAMP(0, 4);
 }
 
 void launch_skinny_qkv_balanced(const float* Wp, const float* xp, float* partial, hipStream_t s) {
@@ -239,6 +281,18 @@ void launch_skinny_qkv_balanced(const float* Wp, const float* xp, float* partial
 // (modules/transformer.py:371-373).
 //   weight image: W16[((nt*KB16 + kb)*64 + lane)*4 + j] = W[16nt + (lane&15)][16kb + 4(lane>>4) + j]   (KB16 = K/16)
 //   x fragment  : read from the 32-row packed image: x[b = 16half + (lane&15)][16kb + 4(lane>>4) + j]
+//
+// Request order (round 35).  A workgroup requests 128 KB of x (all of it: there is no K split) and 64 KB of weights, 24 loads per
+// lane, and a CU's vector memory path takes 64 B per clock: with the x loads of every wave in front, most of a microsecond of L2
+// traffic passed before the first HBM request of the CU left.  Now every k-block is requested as  w[u], x0[u], x1[u]:  the weight
+// stream starts with the first instruction, an MFMA group still waits for nothing but its own three loads (loads return in
+// order), and all 24 requests are still out before the first MFMA.  Same MFMA sequence, same sums, same stores: bit-identical.
+// Measured on the cold 12-layer step (docs/log_r35.md): last MFMA 3.85 -> 3.41 us, end of the launch 6.18 -> 5.55 us behind
+// its first workgroup, AR -3.4 ms per batch of 32.  Weights first (8 w, then 16 x) lost: every MFMA then waits for the whole
+// weight tile.  skinny16_relu_pack_xfirst_kernel keeps the order of rounds 2 .. 34 (VX_L1_INTERLEAVE=0).
+// The tail: 1.6 us between wave 0's last MFMA and the end of the workgroup.  The -DVX_DEV_PROBES build stamps lane 0 of every wave
+// (VX_WAVE_STAMP) so that the wait at the barrier and the sum behind it can be told apart; docs/log_r35.md has the figures and
+// what they say about sharing the final sum among the eight waves (not built in round 35).
 // ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void pack_weight16_kernel(const float* __restrict__ W, int N, int K,
                                                             float* __restrict__ Wp) {
@@ -260,10 +314,9 @@ void launch_pack_weight16(const float* W, int N, int K, float* Wp, hipStream_t s
 
 constexpr int S16_WAVES = 8;
 
-__global__ __launch_bounds__(S16_WAVES * 64) void skinny16_relu_pack_kernel(const float* __restrict__ W16,
-                                                                            const float* __restrict__ xp,
-                                                                            const float* __restrict__ bias,
-                                                                            float* __restrict__ xp_out, int K) {
+template <bool INTERLEAVE>
+__device__ __forceinline__ void skinny16_relu_pack_body(const float* __restrict__ W16, const float* __restrict__ xp, const float* __restrict__ bias,
+                                                        float* __restrict__ xp_out, int K) {
   __shared__ __attribute__((aligned(16))) float red[S16_WAVES * 8 * 64];
   const int nt = blockIdx.x;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -278,12 +331,26 @@ __global__ __launch_bounds__(S16_WAVES * 64) void skinny16_relu_pack_kernel(cons
   f32x4 w[8], x0[8], x1[8];
   // requested with the first weights: a load in the epilogue would put one more memory round trip behind the MFMAs
   const f32x4 bi = *reinterpret_cast<const f32x4*>(bias + nt * 16 + 4 * kg);
+  // (the scheduling fences pin the order written here.  Left alone the scheduler groups the loads by base address and sinks x
+  // loads to their uses: through round 34 the compiled kernel requested 8 x blocks, the 8 weight blocks and the bias before its
+  // first MFMA and the other 8 x blocks between the MFMAs, each behind a wait -- tests/test_isa.py asked for no more than that)
 #define VX_S16_LOAD(I)                                                                                                   \
-  _Pragma("unroll") for (int u = 0; u < 8; ++u) { x0[u] = xq[(long)((I) + u) * 128]; x1[u] = xq[(long)((I) + u) * 128 + 16]; } \
-  _Pragma("unroll") for (int u = 0; u < 8; ++u) w[u] = __builtin_nontemporal_load(wp + (long)((I) + u) * 64);
+  if constexpr (INTERLEAVE) {                                                                                            \
+    _Pragma("unroll") for (int u = 0; u < 8; ++u) {                                                                       \
+      w[u] = __builtin_nontemporal_load(wp + (long)((I) + u) * 64);                                                      \
+      x0[u] = xq[(long)((I) + u) * 128]; x1[u] = xq[(long)((I) + u) * 128 + 16];                                         \
+      __builtin_amdgcn_sched_barrier(0);                                                                                 \
+    }                                                                                                                    \
+  } else {                                                                                                               \
+    _Pragma("unroll") for (int u = 0; u < 8; ++u) { x0[u] = xq[(long)((I) + u) * 128]; x1[u] = xq[(long)((I) + u) * 128 + 16]; } \
+    _Pragma("unroll") for (int u = 0; u < 8; ++u) w[u] = __builtin_nontemporal_load(wp + (long)((I) + u) * 64);           \
+    __builtin_amdgcn_sched_barrier(0);                                                                                   \
+  }
   VX_STAMP(3, 0);
+  VX_WAVE_STAMP(0);
   VX_S16_LOAD(0)
   VX_STAMP(3, 1);
+  VX_WAVE_STAMP(1);
   for (int i = 0;;) {
 #pragma unroll
     for (int u = 0; u < 8; ++u)
@@ -298,6 +365,7 @@ __global__ __launch_bounds__(S16_WAVES * 64) void skinny16_relu_pack_kernel(cons
   }
 #undef VX_S16_LOAD
   VX_STAMP(3, 2);
+  VX_WAVE_STAMP(2);
   // acc{h}[r] = out[b = 16h + (lane&15)][n = 16nt + 4(lane>>4) + r].  Wave 0 finishes acc0 and wave 1 acc1 (each sums the
   // eight waves' partials in ascending order, adds the bias, applies ReLU and stores its half of the packed image).
 #pragma unroll
@@ -306,6 +374,7 @@ __global__ __launch_bounds__(S16_WAVES * 64) void skinny16_relu_pack_kernel(cons
     red[(wid * 8 + 4 + r) * 64 + lane] = acc1[r];
   }
   __syncthreads();
+  VX_WAVE_STAMP(3);
   if (wid < 2) {
     f32x4 a4;
 #pragma unroll
@@ -324,9 +393,28 @@ __global__ __launch_bounds__(S16_WAVES * 64) void skinny16_relu_pack_kernel(cons
   VX_STAMP(3, 4);
 }
 
+__global__ __launch_bounds__(S16_WAVES * 64) void skinny16_relu_pack_kernel(const float* __restrict__ W16,
+                                                                            const float* __restrict__ xp,
+                                                                            const float* __restrict__ bias,
+                                                                            float* __restrict__ xp_out, int K) {
+  skinny16_relu_pack_body<true>(W16, xp, bias, xp_out, K);
+}
+__global__ __launch_bounds__(S16_WAVES * 64) void skinny16_relu_pack_xfirst_kernel(const float* __restrict__ W16,
+                                                                                   const float* __restrict__ xp,
+                                                                                   const float* __restrict__ bias,
+                                                                                   float* __restrict__ xp_out, int K) {
+  skinny16_relu_pack_body<false>(W16, xp, bias, xp_out, K);
+}
+
 void launch_skinny16_relu_pack(const float* W16, const float* xp, const float* bias, float* xp_out, int N, int K,
                                hipStream_t s) {
   hipLaunchKernelGGL(skinny16_relu_pack_kernel, dim3(N / 16), dim3(S16_WAVES * 64), 0, s, W16, xp, bias, xp_out, K);
+}
+
+// the request order of rounds 2 .. 34 (VX_L1_INTERLEAVE=0; declared in engine_ctx.h)
+void launch_skinny16_relu_pack_xfirst(const float* W16, const float* xp, const float* bias, float* xp_out, int N, int K,
+                                      hipStream_t s) {
+  hipLaunchKernelGGL(skinny16_relu_pack_xfirst_kernel, dim3(N / 16), dim3(S16_WAVES * 64), 0, s, W16, xp, bias, xp_out, K);
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -647,8 +647,8 @@ void ar_step_launches(vx_ctx* c, const SampleArgs* sa, const ServeSampleArgs* rs
       { ProfScope ps(c, 1); launch_skinny_gemm(L.out_wp, c->xp_att, c->p_o, D_MODEL, D_MODEL, SK_OUT, st, true); }
       launch_dec_reduce_ln_pack(c->p_o, SK_OUT, D_MODEL, L.out_b, c->dh, c->dh, L.n2_w, L.n2_b, c->xp, nb, st);
     }
-    { ProfScope ps(c, 1); launch_skinny16_relu_pack(L.l1_wp, c->xp, L.l1_b, c->xp4, D_FF, D_MODEL, st); }
-    { ProfScope ps(c, 1); launch_skinny_gemm(L.l2_wp, c->xp4, c->p_o, D_MODEL, D_FF, SK_L2, st, true); }
+    { ProfScope ps(c, 1); launch_linear1(c, L.l1_wp, c->xp, L.l1_b, c->xp4, st); }
+    { ProfScope ps(c, 1); launch_skinny_gemm_kmap(L.l2_wp, c->xp4, c->p_o, D_MODEL, D_FF, SK_L2, st, true, c->l2_kmap); }
     const float* ng = (l + 1 < NL) ? c->ar[l + 1].n1_w : W(c, "ar_decoder.norm.weight");
     const float* nbp = (l + 1 < NL) ? c->ar[l + 1].n1_b : W(c, "ar_decoder.norm.bias");
     launch_dec_reduce_ln_pack(c->p_o, SK_L2, D_MODEL, L.l2_b, c->dh, c->dh, ng, nbp, c->xp, nb, st);
@@ -656,6 +656,15 @@ void ar_step_launches(vx_ctx* c, const SampleArgs* sa, const ServeSampleArgs* rs
   { ProfScope ps(c, 1); launch_skinny_gemm(c->pred_wp, c->xp, c->p_logits, PRED_NPAD, D_MODEL, SK_PRED, st, true); }
   if (rsa) LAUNCH(launch_serve_sample(*rsa, st));
   else if (sa) LAUNCH(launch_dec_sample(*sa, st));
+}
+
+// The placement / request-order switches of the decode step's GEMMs (round 35), read with the other per-context switches at finalize
+// (weights.hip).  They pick where a workgroup runs and in which order it requests its operands, never a kernel's arithmetic or a
+// launch sequence: every output word is the same under either value (tests/test_gpu_kernel_dec_gemm_levers.py runs both sides bit for
+// bit), so they are reported by vx_dev_gemm_levers and not among the kernel-SELECTION words of vx_dev_switches.
+void read_dec_gemm_levers(vx_ctx* c) {
+  if (const char* ev = getenv("VX_L2_KMAP")) c->l2_kmap = !(ev[0] == '0');
+  if (const char* ev = getenv("VX_L1_INTERLEAVE")) c->l1_interleave = !(ev[0] == '0');
 }
 
 // the decode kernels compile these split counts in (decode.hip); retuning one without instantiating it must not reach a GPU

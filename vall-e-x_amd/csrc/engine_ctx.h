@@ -138,6 +138,8 @@ struct vx_ctx {
   bool sb_chain = false;           // the current micro-batch decodes on the small-batch chain (set by ar_prefill)
   bool sb_fuse = true;             // <= SB_ROWS rows: reduce+LN / combine folded into the consuming GEMM (VX_SB_FUSE=0: the general chain)
   bool qkv_bal = true;             // the decode in_proj GEMM on 512 workgroups (8 K slices of q, 4 of k / v; VX_QKV_BALANCED=0: 384 x 4 slices)
+  bool l2_kmap = true;             // linear2 of the 5 .. 32-row chain: one K slice per XCD (decode.hip skinny_gemm_kernel; VX_L2_KMAP=0: column tile fastest)
+  bool l1_interleave = true;       // linear1 requests w[u], x0[u], x1[u] per k-block (VX_L1_INTERLEAVE=0: all of x, then the weights)
   float* qk_new = nullptr;         // [MB][16][2][64]: q / 8 and k_new of the step's new token (dec_attn_qkv_kernel -> out_proj prologue)
   float *p_qkv = nullptr, *p_o = nullptr, *p_oh = nullptr, *p_logits = nullptr, *part_o = nullptr, *part_ml = nullptr;
   std::map<const unsigned short*, int> w_shift;   // f16x2: power-of-two scale exponent of every weight's planes
@@ -381,6 +383,22 @@ SampleArgs make_sample_args(vx_ctx* c, const vx_sampling* s, int commit, float* 
 struct ServeSampleArgs;
 // rsa != null (serving session): the step ends in the per-row sampler (serve_sample.hip) instead of dec_sample
 void ar_step_launches(vx_ctx* c, const SampleArgs* sa, const ServeSampleArgs* rsa = nullptr);
+void read_dec_gemm_levers(vx_ctx* c);      // VX_L2_KMAP / VX_L1_INTERLEAVE -> c->l2_kmap / c->l1_interleave (engine.hip; called at finalize)
+// the switched launchers of the decode step's GEMMs (decode.hip, round 35): linear2 with the K slice fastest in the block id, linear1
+// with the request order of rounds 2 .. 34
+}  // namespace vxe
+namespace vx {
+void launch_skinny_gemm_kmap(const float* Wp, const float* xp, float* partial, int Npad, int K, int splitk, hipStream_t s, bool wt, bool kmap);
+void launch_skinny16_relu_pack_xfirst(const float* W16, const float* xp, const float* bias, float* xp_out, int N, int K, hipStream_t s);
+#ifdef VX_DEV_PROBES
+void dev_read_wave_stamps(unsigned long long* out);      // decode.hip: lane 0 of every wave of linear1 (tools/step_timeline.py --step)
+#endif
+}  // namespace vx
+namespace vxe {
+inline void launch_linear1(const vx_ctx* c, const float* W16, const float* xp, const float* bias, float* xp_out, hipStream_t s) {
+  if (c->l1_interleave) launch_skinny16_relu_pack(W16, xp, bias, xp_out, D_FF, D_MODEL, s);
+  else launch_skinny16_relu_pack_xfirst(W16, xp, bias, xp_out, D_FF, D_MODEL, s);
+}
 int launch_status(vx_ctx* c);      // VX_EINVAL (+ message) if a launcher refused since the last check
 // decode geometry of a decode batch of nrows rows (engine.hip): sets c->nsplit, c->split_fused, c->sb_chain, c->sb_qkv; `identity`: the
 // launch slot order is the identity.  Also called by vx_dev_dec_attn (bench_harness.hip), which restores the four fields.

@@ -150,6 +150,7 @@ int vx_finalize_weights(vx_ctx* c) {
   if ((e = dev_alloc(c, &c->xp_att, (size_t)MB * d))) return e;
   if ((e = dev_alloc(c, &c->xp4, (size_t)2 * MB * f))) return e;   // linear1's two split-K slabs, packed image
   if (const char* ev = getenv("VX_QKV_BALANCED")) c->qkv_bal = !(ev[0] == '0');
+  read_dec_gemm_levers(c);         // VX_L2_KMAP, VX_L1_INTERLEAVE (engine.hip)
   static_assert(SK_QKV_BAL_Q == 8 && SK_QKV_BAL_KV == SK_QKV, "skinny_qkv_bal_kernel writes 8 q slabs and SK_QKV k / v slabs into p_qkv");
   if ((e = dev_alloc(c, &c->p_qkv, (size_t)std::max(SK_QKV, SK_QKV_BAL_Q) * MB * 3 * d))) return e;
   if ((e = dev_alloc(c, &c->p_o, (size_t)std::max(SK_OUT, SK_L2) * MB * d))) return e;
